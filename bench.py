@@ -7,7 +7,10 @@ encode, BLAKE3 Merkle-Damgard leaf chain over the K chunks, Merkle tree) followe
 test_PC(2^28, 4, 32) -- all on the GPU through the C ABI (libhobbit_hip.so), with the polynomial already resident in HBM when the
 timed region starts.  --phase commit times the commit alone.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 28] [--chunks 32] [--mode replicas|sharded]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 28] [--chunks 32] [--mode replicas|sharded] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step returned to its caller (the commitment's root and Merkle levels, the opening's
+arrays) as DIR/<name>.npy, so that two builds can be compared output for output; the inputs depend only on the arguments.
 
 N > 1: launched by torch.distributed.run, one rank per GPU.  Default mode for N > 1 is `sharded`: ONE commitment and ONE opening
 of the same 2^logn polynomial, chunks sharded over the ranks (parallel.py: by default the chain relay -- contiguous chunks per rank, the leaf
@@ -20,6 +23,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -170,6 +175,62 @@ def algorithmic_bytes(N, K, world=1, sharded=False, nz=1.0):
     }
 
 
+DUMP_BUDGET = 64 << 20        # --dump-outputs: bytes written in all
+DUMP_ARRAY_CAP = 16 << 20     # an array larger than this (as float64) is written as a seeded sample of its rows plus a digest of the whole
+
+
+def as_float(a):
+    """exact float64 image of an output array: 64-bit words and byte strings (digests) as their little-endian 32-bit words"""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        return a.astype(np.float64)
+    if a.dtype.kind == "b":
+        a = a.astype(np.uint8)
+    if a.ndim == 0:
+        a = a.reshape(1)
+    if a.dtype.itemsize == 8 or (a.dtype.itemsize == 1 and a.shape[-1] % 4 == 0):
+        a = a.astype(a.dtype.newbyteorder("<")).view("<u4")
+    return a.astype(np.float64)
+
+
+def flatten_outputs(obj, prefix="", out=None):
+    """numpy arrays of a (nested) result dict, keyed "<key>.<key>..."; anything else (handles, ints, device objects) is left out"""
+    out = {} if out is None else out
+    if isinstance(obj, dict):
+        for k in sorted(obj, key=str):
+            flatten_outputs(obj[k], "%s.%s" % (prefix, k) if prefix else str(k), out)
+    elif isinstance(obj, np.ndarray):
+        out[prefix] = obj
+    return out
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy for every array, at most DUMP_BUDGET bytes in all.  An array over DUMP_ARRAY_CAP (or over what is left) is written
+    as the rows <name>.sample_idx picks with a fixed seed, next to <name>.sha256, the digest of the whole array's raw bytes."""
+    import hashlib
+    files, left = {}, DUMP_BUDGET
+    for name in sorted(arrays):
+        raw = np.ascontiguousarray(arrays[name])
+        a = as_float(raw)
+        cap = min(DUMP_ARRAY_CAP, left - (1 << 20))       # 1 MiB held back for the sample's index and digest
+        if a.nbytes > cap:
+            rows = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+            k = int(max(1, min(rows.shape[0], cap // (rows[0].nbytes + 8))))
+            idx = np.sort(np.random.default_rng(12345).choice(rows.shape[0], k, replace=False))
+            files[name + ".sample_idx"] = idx.astype(np.float64)
+            files[name + ".sha256"] = as_float(np.frombuffer(hashlib.sha256(raw.tobytes()).digest(), np.uint8))
+            left -= files[name + ".sample_idx"].nbytes + files[name + ".sha256"].nbytes
+            a = a[idx]
+        files[name] = a
+        left -= a.nbytes
+        if left < 0:
+            raise RuntimeError("--dump-outputs: the outputs do not fit in %d bytes" % DUMP_BUDGET)
+    os.makedirs(path, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": len(files), "bytes": int(sum(a.nbytes for a in files.values()))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -191,7 +252,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropin", action="store_true", help="skip the reference-shaped driver leg (host/test_pc <logN> 4 <K>: host vector in, PCIe inclusive)")
     ap.add_argument("--cpu-logn", type=int, default=24, help="size of the CPU-baseline sample (2^24: about 17 s of single-thread reference time)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (commitment root and Merkle levels, opening) as DIR/<name>.npy, float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.mode is None:
         args.mode = "sharded" if args.gpus > 1 else "replicas"
 
@@ -241,12 +306,12 @@ def main():
 
     do_open = args.phase != "commit"
     full_open = args.phase == "commit+open" or sharded            # the sharded open is always the full prover side
-    import numpy as np
     x_open = np.stack([np.arange(1, args.logn + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15 % ((1 << 61) - 1)) % np.uint64((1 << 61) - 1),
                        np.arange(7, args.logn + 7, dtype=np.uint64) * np.uint64(1234567891011) % np.uint64((1 << 61) - 1)], axis=1)
     open_last = {}
+    kept = {}
 
-    def step():
+    def step(keep=False):
         if sharded:
             commit_fn = mod.parallel.sharded_commit_relay if relay else mod.parallel.sharded_commit
             last["res"] = commit_fn(ops_, dist, plan, rank, (d_local.ptr, len(own)))
@@ -257,7 +322,10 @@ def main():
         c = hb.commit_standard((d_poly, N), K, trs, 1, sync=not do_open)        # with an opening behind it: queued, not waited for
         if do_open:
             open_last["res"] = hb.open_core((d_poly, N), c, x_open, args.queries, full=full_open)
-        c.free()                          # parks the 16.5 GiB of buffers for the next step
+        if keep:
+            kept["c"] = c                 # --dump-outputs: read back after the timed region, then freed
+        else:
+            c.free()                      # parks the 16.5 GiB of buffers for the next step
 
     # Setup, not warm-up: the first call allocates every workspace (16.5 GiB tensor, 12 GiB of scratch), and on this driver the
     # SECOND open of a process carries a one-time ~25 ms GPU-idle gap in front of its first kernel (seen in the rocprofv3 kernel
@@ -291,15 +359,26 @@ def main():
     t0 = time.perf_counter()
     hb.timer_begin()
     step_ms = []
-    for _ in range(args.steps):
+    for i in range(args.steps):
         ts = time.perf_counter()
-        step()
+        step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         step_ms.append(1e3 * (time.perf_counter() - ts))
     ev_ms = hb.timer_end_ms()
     barrier()
     wall = time.perf_counter() - t0
     if gc_off:
         gc.enable()
+    # what the last timed step handed back, taken before the profiled step below overwrites it
+    outputs = None
+    if args.dump_outputs:
+        if "c" in kept:
+            c = kept.pop("c")
+            outputs = {"commit": {"root": c.root(), "levels": c.levels()}} if rank == 0 else None
+            c.free()
+        elif sharded:
+            outputs = {"commit": last["res"]}
+        if rank == 0 and do_open:
+            outputs["open"] = open_last["res"]
     prof = hb.profile_report()
     prof.pop("k_fill_splitmix", None)          # the untimed filler in front of the barrier
     hb.profile(1); hb.profile_reset()
@@ -393,6 +472,8 @@ def main():
                 out["cpu_baseline_open_port"] = cpu_open_port(args.cpu_logn, K, args.queries, full_open)
         if not args.no_dropin and world == 1 and do_open and full_open:
             out["dropin"] = dropin_leg(args.logn, K)
+        if outputs is not None:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, flatten_outputs(outputs))
         print(json.dumps(out))
     hb.close()
     if dist is not None:

@@ -3,7 +3,7 @@
 Generates tests/golden/<case>.npz by running tests/golden_cases.py against the REAL reference
 (oracle/_ref/libhobbit_ref.so, built from /root/reference by `make -C oracle ref`).  Run here
 (where /root/reference exists); the fixtures are committed because the reference cannot travel
-to the GPU box.  Usage:  python oracle/gen_golden.py [case ...]
+to the GPU box.  Usage:  python oracle/gen_golden.py [case ... | oracle_vs_ref]
 """
 import os
 import sys
@@ -34,6 +34,14 @@ def main():
         out = golden_cases.case_codeproofs_matrix(ref, claim)
         np.savez_compressed(os.path.join(ROOT, "tests", "golden", "codeproofs_matrix.npz"), **out)
         print("codeproofs_matrix %d arrays" % len(out))
+    if not sys.argv[1:] or "oracle_vs_ref" in sys.argv[1:]:
+        # the reference's answers on tests/test_oracle_vs_ref.py's inputs, one file, keys "<case>__<key>"
+        out = {}
+        for name, fn in golden_cases.VS_REF_CASES.items():
+            out.update(("%s__%s" % (name, k), v) for k, v in fn(ref).items())
+        path = os.path.join(ROOT, "tests", "golden", "oracle_vs_ref.npz")
+        np.savez_compressed(path, **out)
+        print("oracle_vs_ref  %3d arrays  %7.1f KB" % (len(out), os.path.getsize(path) / 1024.0))
 
 
 if __name__ == "__main__":

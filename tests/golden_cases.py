@@ -536,3 +536,39 @@ def case_gate(lib):
 
 CASES = dict(streamdrv=case_streamdrv, elastic_open=case_elastic_open, elastic_open2=case_elastic_open2, field=case_field, mimc=case_mimc, blake=case_blake, merkle=case_merkle, graph_encode=case_graph_encode,
              fft=case_fft, tensorcode=case_tensorcode, commit=case_commit, commit_rs=case_commit_rs, sumcheck=case_sumcheck, elastic=case_elastic, codeproofs=case_codeproofs, streamfold=case_streamfold, lkpfold=case_lkpfold, multree=case_multree, innerpcs=case_innerpcs, gate=case_gate)
+
+
+# Cross-checks of the restatement against the real reference on inputs beyond CASES (tests/test_oracle_vs_ref.py), recorded once from
+# oracle/_ref by oracle/gen_golden.py into tests/golden/oracle_vs_ref.npz as "<case>__<key>" so that the check needs no reference build.
+VS_REF_GRAPH_SIZES = (14, 20, 50, 128, 333, 512, 2048)
+
+
+def vs_ref_graph_encode(lib, n):
+    # the libraries draw from the one process-wide libc generator: reset before EACH draw
+    lib.rng_reset()
+    levels = lib.expander_init_store(n)
+    if hasattr(lib, "encode_reset_scratch"):
+        lib.encode_reset_scratch()
+    d, ln = lib.encode_monolithic(splitmix_field(n, n))
+    return dict(levels=np.array(levels, np.int64), len=np.array(ln, np.int64), code=dg(d), code_samp=samp(d[:ln]))
+
+
+def vs_ref_commit_2e18(lib):
+    poly, trs = test_pc_inputs(lib, 1 << 18, 32)
+    lv, t = lib.commit_standard(poly, 32, trs, 1, want_tensor=True)
+    if hasattr(lib, "release_commit"):
+        lib.release_commit()
+    return dict(poly=dg(poly), levels_shape=np.array(lv.shape, np.int64), levels=dg(lv), root=lv[-1].copy(), levels_samp=samp(lv),
+                tensor_shape=np.array(t.shape, np.int64), tensor=dg(t), tensor_samp=samp(t))
+
+
+def vs_ref_elastic_shape(lib):
+    """aggregate / compute_aggregation_reply of Elastic_PC::open (option 1) at a shape outside the fixtures"""
+    N, B = 1 << 17, 1 << 13
+    aggr, root = lib.elastic_aggregate(N, B, splitmix_field(N // B, 5))
+    reply = lib.elastic_reply(N, B, elastic_open_queries(B, 333, 7))
+    return dict(aggr=dg(aggr), aggr_samp=samp(aggr), root=root, reply_shape=np.array(reply.shape, np.int64), reply=dg(reply), reply_samp=samp(reply))
+
+
+VS_REF_CASES = dict([("graph_encode_n%d" % n, (lambda lib, n=n: vs_ref_graph_encode(lib, n))) for n in VS_REF_GRAPH_SIZES] +
+                    [("commit_2e18", vs_ref_commit_2e18), ("elastic_shape", vs_ref_elastic_shape)])
