@@ -145,6 +145,7 @@ static void free_code(DeviceCode &c) {
     if (c.d_pm_rowptr) hipFree(c.d_pm_rowptr);
     if (c.d_pm_idx) hipFree(c.d_pm_idx);
     if (c.d_pm_w) hipFree(c.d_pm_w);
+    for (void *q : {(void *)c.d_tile_ptr, (void *)c.d_tile_width, (void *)c.d_tile_out, (void *)c.d_tile_e32, (void *)c.d_tile_eidx, (void *)c.d_tile_ew}) if (q) hipFree(q);
     c = DeviceCode();
 }
 
@@ -646,7 +647,7 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
     if (c.small_weights) HB_TRY(up((void **)&c.d_edges32, e32.data(), e32.size() * sizeof(uint2)));
     else { HB_TRY(up((void **)&c.d_eidx, eidx.data(), eidx.size() * 4)); HB_TRY(up((void **)&c.d_ew, ew.data(), ew.size() * sizeof(F))); }
     // deep codes (n = 4096: the codeword does not leave room for two workgroups per CU): first and last step also in fat form
-    if (c.small_weights && c.steps.size() >= 4 && (size_t)c.len * 16 > 80 * 1024) {
+    if (c.small_weights && c.steps.size() >= 4 && (size_t)c.len * 16 > 80 * 1024 && (size_t)c.len * 16 <= 160 * 1024) {
         const uint32_t capA[3] = {FAT_A_CAP0, FAT_A_CAP1, 0}, capD[3] = {FAT_D_CAP0, FAT_D_CAP1, FAT_D_CAP2};
         build_fat_step(*plan.front().g, (uint32_t)plan.front().in_off, (uint32_t)plan.front().out_off, FAT_A_NOUT, FAT_A_CONS, capA, c.fatA);
         build_fat_step(*plan.back().g, (uint32_t)plan.back().in_off, (uint32_t)plan.back().out_off, FAT_D_NOUT, FAT_D_CONS, capD, c.fatD);
@@ -655,6 +656,59 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
         std::vector<MidPlanStep> ms;
         for (size_t i = 1; i + 1 < plan.size(); i++) ms.push_back({plan[i].g, plan[i].in_off, plan[i].out_off});
         build_mid(ms, (uint32_t)plan[1].in_off, (uint32_t)plan[1].g->L, c.mid);
+    }
+    // long codes: the outer steps whose windows do not fit in LDS, in tiled form (hobbit_ctx.hpp TiledStep)
+    if ((size_t)c.len * 16 > 160 * 1024) {
+        uint32_t d = 0;
+        while (d < (uint32_t)D && cwlen[d] > TILE_MID_MAX) d++;
+        c.tiled_depth = d;
+        std::vector<uint32_t> tptr, twid, tout, teidx; std::vector<uint2> te32; std::vector<F> tew;
+        for (size_t si = 0; si < plan.size(); si++) {
+            if (si >= d && si < plan.size() - d) continue;
+            const HostGraph &g = *plan[si].g;
+            TiledStep t;
+            t.in_off = (uint32_t)plan[si].in_off; t.in_len = (uint32_t)g.L; t.out_off = (uint32_t)plan[si].out_off; t.out_len = (uint32_t)g.R;
+            t.ntiles = (t.in_len + TILE_ELEMS - 1) / TILE_ELEMS;
+            t.n_slices = (t.out_len + 63) / 64;
+            t.groups = (t.n_slices + TILE_WAVES * TILE_MAXS - 1) / (TILE_WAVES * TILE_MAXS);
+            t.tile_base = (uint32_t)tptr.size(); t.out_base = (uint32_t)tout.size();
+            // in-edges of every output in input order, so that those of one tile are a contiguous run: tile k of output o is [beg(o, k), beg(o, k + 1))
+            std::vector<std::vector<std::pair<uint32_t, F>>> rows(g.R);
+            for (long long i = 0; i < g.L; i++)
+                for (int j = 0; j < g.degree; j++) rows[g.nbr[i * g.degree + j]].push_back({(uint32_t)i, g.w[i * g.degree + j]});
+            auto beg = [&](uint32_t o, uint32_t k) {
+                return (size_t)(std::lower_bound(rows[o].begin(), rows[o].end(), k * TILE_ELEMS, [](const std::pair<uint32_t, F> &e, uint32_t v) { return e.first < v; }) - rows[o].begin());
+            };
+            std::vector<uint32_t> order((size_t)g.R);
+            for (size_t q = 0; q < order.size(); q++) order[q] = (uint32_t)q;
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].size() > rows[b].size(); });
+            for (uint32_t sl = 0; sl < t.n_slices; sl++) {
+                for (uint32_t l = 0; l < 64; l++) { const size_t q = (size_t)sl * 64 + l; tout.push_back(q < order.size() ? order[q] : 0xFFFFFFFFu); }
+                for (uint32_t k = 0; k < t.ntiles; k++) {
+                    size_t lo[64], hi[64], width = 0;
+                    for (uint32_t l = 0; l < 64; l++) {
+                        const size_t q = (size_t)sl * 64 + l;
+                        lo[l] = hi[l] = 0;
+                        if (q < order.size()) { lo[l] = beg(order[q], k); hi[l] = beg(order[q], k + 1); width = std::max(width, hi[l] - lo[l]); }
+                    }
+                    width = (width + ENC_UNROLL - 1) / ENC_UNROLL * ENC_UNROLL;
+                    tptr.push_back((uint32_t)c.tile_records); twid.push_back((uint32_t)width);
+                    for (size_t e = 0; e < width; e++)
+                        for (uint32_t l = 0; l < 64; l++) {
+                            uint32_t id = 0; F w = fmake(0);
+                            if (lo[l] + e < hi[l]) { const auto &r = rows[order[(size_t)sl * 64 + l]][lo[l] + e]; id = r.first - k * TILE_ELEMS; w = r.second; }
+                            if (c.small_weights) te32.push_back(make_uint2(id, (uint32_t)w.re)); else { teidx.push_back(id); tew.push_back(w); }
+                        }
+                    c.tile_records += width * 64;
+                }
+            }
+            c.tsteps.push_back(t);
+        }
+        HB_TRY(up((void **)&c.d_tile_ptr, tptr.data(), tptr.size() * 4));
+        HB_TRY(up((void **)&c.d_tile_width, twid.data(), twid.size() * 4));
+        HB_TRY(up((void **)&c.d_tile_out, tout.data(), tout.size() * 4));
+        if (c.small_weights) HB_TRY(up((void **)&c.d_tile_e32, te32.data(), te32.size() * sizeof(uint2)));
+        else { HB_TRY(up((void **)&c.d_tile_eidx, teidx.data(), teidx.size() * 4)); HB_TRY(up((void **)&c.d_tile_ew, tew.data(), tew.size() * sizeof(F))); }
     }
     if (len_out) *len_out = c.len;
     return 0;

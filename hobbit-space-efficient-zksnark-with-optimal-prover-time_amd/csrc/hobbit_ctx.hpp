@@ -73,6 +73,22 @@ struct MidCode {
     uint32_t *d_wt = nullptr, *d_ot = nullptr, *d_oidx = nullptr, *d_w = nullptr;
 };
 
+// Long codes (codeword over 160 KB: n >= ~6000, tensor_row_size 8192 / 16384 of Our_PC): the outer steps C_0 .. C_{d-1} and D_{d-1} .. D_0,
+// whose input windows are too long for one workgroup's LDS, run one launch each through k_enc_tiled (hobbit_kernels.hip); the sub-codeword of
+// depth d (the first that fits TILE_MID_MAX) is encoded by one k_encode pass on its own window.  A tiled step cuts its input window into tiles
+// of TILE_ELEMS elements (64 KB); its outputs keep one order (by in-degree) and 64-wide slices across tiles, and every (slice, tile) pair owns
+// a k-major block of edge records whose input lies in that tile -- index relative to the tile start, padded with zero-weight records to a
+// multiple of ENC_UNROLL -- so a lane carries its outputs' 96-bit sums in registers from tile to tile and folds once at the end.
+static constexpr uint32_t TILE_ELEMS = 4096;            // 64 KB of LDS: two workgroups per CU
+static constexpr uint32_t TILE_WAVES = 8, TILE_MAXS = 4; // waves per workgroup, slices per wave: a workgroup owns TILE_WAVES*TILE_MAXS*64 outputs
+static constexpr uint32_t TILE_MID_MAX = 4096;          // longest sub-codeword left to the one-pass k_encode
+struct TiledStep {
+    uint32_t in_off, in_len, out_off, out_len;
+    uint32_t ntiles, n_slices, groups;      // groups: workgroups per column (blockIdx.y), each TILE_WAVES*TILE_MAXS slices
+    uint32_t tile_base;                     // index of (slice 0, tile 0) in tile_ptr / tile_width (slice-major, ntiles per slice)
+    uint32_t out_base;                      // index of this step's first entry in tile_out (64 per slice)
+};
+
 struct DeviceCode {         // finalized code for one message length n
     long long n = 0, len = 0;
     bool small_weights = true;               // all weights real and < 2^32
@@ -84,6 +100,13 @@ struct DeviceCode {         // finalized code for one message length n
     size_t n_edges_padded = 0, n_edges = 0;
     FatStep fatA, fatC1, fatD;               // first, second and last step in fat form (deep codes only: n = 4096)
     MidCode mid;                             // the steps between them
+    // long codes: steps [0, tiled_depth) and [nsteps - tiled_depth, nsteps) in tiled form (tiled_depth = 0: the codeword fits in LDS)
+    uint32_t tiled_depth = 0;
+    std::vector<TiledStep> tsteps;           // C_0 .. C_{d-1}, then D_{d-1} .. D_0 (the order of `steps`)
+    uint32_t *d_tile_ptr = nullptr, *d_tile_width = nullptr, *d_tile_out = nullptr;
+    uint2 *d_tile_e32 = nullptr;             // {index in the tile, w32}   (small_weights)
+    uint32_t *d_tile_eidx = nullptr; F *d_tile_ew = nullptr;   // general weights
+    size_t tile_records = 0;
     // H^T in CSR (evaluate_parity_matrix), built on first use
     uint32_t *d_pm_rowptr = nullptr, *d_pm_idx = nullptr; F *d_pm_w = nullptr; size_t pm_rows = 0;
 };

@@ -3,7 +3,8 @@
 // All kernels are integer (F_{p^2}, p = 2^61-1) or hash work: no MFMA.  The streaming kernels
 // (fold, aggregate, leaf chain, tree levels) are HBM-bound and use 16-byte-per-lane coalesced
 // accesses; the FFT and the expander encode keep a whole row / codeword in LDS (64 KB / <=110 KB
-// of the CU's 160 KB) and are bound by the v_mad_u64_u32 rate.
+// of the CU's 160 KB; longer codewords stream their outer steps through 64 KB tiles, k_enc_tiled)
+// and are bound by the v_mad_u64_u32 rate.
 #include "hobbit_kernels.hpp"
 #include <atomic>
 #include "hobbit_blake3.hpp"
@@ -1171,11 +1172,128 @@ static int launch_enc_mid(hobbit_ctx *ctx, const MidCode &m, F *tensor, size_t l
     return 0;
 }
 
+// ============================================================================================
+// Long codes (hobbit_ctx.hpp TiledStep): one SpMV step whose input window is longer than LDS, one workgroup per (column, output group).
+// The window streams through LDS one 64 KB tile at a time; a wave owns up to TILE_MAXS slices of 64 outputs (one output per lane) and keeps
+// their four unreduced 96-bit sums per output in registers across the tiles -- the same acc96_mad4 / acc_fold arithmetic as k_encode, one
+// Mersenne fold per output -- and stores the outputs to the column at the end.  copy_in (out-of-place C_0): the workgroup of output group 0
+// also writes the window to the destination column; [z_lo, z_hi): zeros it writes behind the codeword (D_0).
+// ============================================================================================
+template <bool SMALLW>
+__global__ void __launch_bounds__(TILE_WAVES * 64)
+k_enc_tiled(const F *__restrict__ src, size_t ld_src, F *__restrict__ dst, size_t ld_dst, TiledStep ts, const uint32_t *__restrict__ tile_ptr,
+            const uint32_t *__restrict__ tile_width, const uint32_t *__restrict__ tile_out, const uint2 *__restrict__ e32,
+            const uint32_t *__restrict__ eidx, const F *__restrict__ ew, uint32_t copy_in, uint32_t z_lo, uint32_t z_hi) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    F *tile = reinterpret_cast<F *>(lds_raw);
+    const F *in = src + (size_t)blockIdx.x * ld_src + ts.in_off;
+    F *out = dst + (size_t)blockIdx.x * ld_dst;
+    const uint32_t grp = blockIdx.y, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool copy = copy_in && grp == 0;
+    Acc96 acc[TILE_MAXS][4];
+    F accf[TILE_MAXS];
+#pragma unroll
+    for (uint32_t m = 0; m < TILE_MAXS; m++) {
+        accf[m] = fmake(0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[m][q] = {0, 0};
+    }
+    for (uint32_t k = 0; k < ts.ntiles; k++) {
+        const uint32_t lo = k * TILE_ELEMS, cnt = min(TILE_ELEMS, ts.in_len - lo);
+        if (k) __syncthreads();                                  // every wave is done with the previous tile
+        for (uint32_t b0 = 0; b0 < cnt; b0 += 4 * blockDim.x) {  // four global loads per thread in flight
+            F v[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) { const uint32_t i = b0 + u * blockDim.x + threadIdx.x; if (i < cnt) v[u] = ldF(in + lo + i); }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const uint32_t i = b0 + u * blockDim.x + threadIdx.x;
+                if (i < cnt) { stF(&tile[i], v[u]); if (copy) stF(out + ts.in_off + lo + i, v[u]); }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t m = 0; m < TILE_MAXS; m++) {
+            const uint32_t sl = (grp * TILE_MAXS + m) * TILE_WAVES + wave;        // wave-uniform
+            if (sl >= ts.n_slices) continue;
+            const uint32_t ti = ts.tile_base + sl * ts.ntiles + k;
+            const uint32_t base = tile_ptr[ti] + lane, width = tile_width[ti];   // width: a multiple of ENC_UNROLL
+            if (SMALLW) {
+                for (uint32_t j = 0; j < width; j += ENC_UNROLL) {
+                    uint2 e[ENC_UNROLL]; uint4 x[ENC_UNROLL];
+#pragma unroll
+                    for (int u = 0; u < ENC_UNROLL; u++) e[u] = e32[base + (j + u) * 64];
+#pragma unroll
+                    for (int u = 0; u < ENC_UNROLL; u++) x[u] = *reinterpret_cast<const uint4 *>(tile + e[u].x);
+#pragma unroll
+                    for (int u = 0; u < ENC_UNROLL; u++) acc96_mad4(acc[m][0], acc[m][1], acc[m][2], acc[m][3], e[u].y, x[u]);
+                }
+            } else {
+                for (uint32_t j = 0; j < width; j++) accf[m] = fadd(accf[m], fmul(ldF(tile + eidx[base + j * 64]), ldF(ew + base + j * 64)));
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t m = 0; m < TILE_MAXS; m++) {
+        const uint32_t sl = (grp * TILE_MAXS + m) * TILE_WAVES + wave;
+        if (sl >= ts.n_slices) continue;
+        const uint32_t t = tile_out[ts.out_base + sl * 64 + lane];
+        if (t != 0xFFFFFFFFu) stF(out + ts.out_off + t, SMALLW ? fmake(acc_fold(acc[m][0], acc[m][1]), acc_fold(acc[m][2], acc[m][3])) : accf[m]);
+    }
+    if (grp == 0)
+        for (uint32_t i = z_lo + threadIdx.x; i < z_hi; i += blockDim.x) stF(out + i, fmake(0));
+}
+
+template <bool SMALLW>
+static int launch_enc_tiled(hobbit_ctx *ctx, const char *name, const F *src, size_t ld_src, F *dst, size_t ld_dst, size_t batch, const TiledStep &ts,
+                            uint32_t copy_in, uint32_t z_lo, uint32_t z_hi) {
+    const DeviceCode &c = ctx->code;
+    const uint32_t lds = std::min(ts.in_len, TILE_ELEMS) * 16;
+    hipFuncSetAttribute((const void *)k_enc_tiled<SMALLW>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    // grid.x: columns, at most 2^31 - 1 per launch
+    for (size_t b0 = 0; b0 < batch; b0 += 0x7FFFFFFFu) {
+        const size_t nb = std::min<size_t>(batch - b0, 0x7FFFFFFFu);
+        HB_LAUNCH(ctx, name, (k_enc_tiled<SMALLW>), dim3((unsigned)nb, ts.groups), dim3(TILE_WAVES * 64), lds, src + b0 * ld_src, ld_src, dst + b0 * ld_dst, ld_dst, ts,
+                  c.d_tile_ptr, c.d_tile_width, c.d_tile_out, c.d_tile_e32, c.d_tile_eidx, c.d_tile_ew, copy_in, z_lo, z_hi);
+    }
+    return 0;
+}
+
+// Long codes: C_0 .. C_{d-1} tiled (C_0 reads the source; out of place it also copies the message), the sub-codeword of depth d as one k_encode
+// pass on its window, D_{d-1} .. D_0 tiled (D_0 writes the zero tail).  Every launch reads what the one before it wrote to the destination.
+static int launch_encode_long(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t ld_dst, size_t batch, int write_msg) {
+    const DeviceCode &c = ctx->code;
+    const uint32_t d = c.tiled_depth, nsteps = (uint32_t)c.steps.size(), nn = (uint32_t)c.n;
+    uint32_t z_hi = 2 * nn;
+    if (ctx->enc_skip_tail) { z_hi = std::min<uint32_t>(2 * nn, ((uint32_t)c.len + 3) & ~3u); ctx->enc_tail_skipped = true; }
+    for (uint32_t j = 0; j < d; j++) {
+        const F *s = j ? dst : src; const size_t ls = j ? ld_dst : ld_src;
+        HB_TRY(c.small_weights ? launch_enc_tiled<true>(ctx, "k_enc_tiled_C", s, ls, dst, ld_dst, batch, c.tsteps[j], j == 0 && write_msg, 0, 0)
+                               : launch_enc_tiled<false>(ctx, "k_enc_tiled_fullw_C", s, ls, dst, ld_dst, batch, c.tsteps[j], j == 0 && write_msg, 0, 0));
+    }
+    if (d < nsteps - d) {
+        const EncStep &first = c.steps[d], &last = c.steps[nsteps - d - 1];
+        const uint32_t w_lo = first.in_off, x_end = first.out_off, w_end = last.out_off + last.out_len;     // x_d = [w_lo, x_end), sub-codeword [w_lo, w_end)
+        EncPass pm = {w_lo, w_lo, x_end, d, nsteps - d, x_end, w_end, 0};
+        HB_TRY(c.small_weights ? launch_encode_pass<true>(ctx, "k_encode_long_M", dst, ld_dst, dst, ld_dst, batch, pm, w_end - w_lo, block_for(c, d, nsteps - d, 8))
+                               : launch_encode_pass<false>(ctx, "k_encode_fullw_long_M", dst, ld_dst, dst, ld_dst, batch, pm, w_end - w_lo, block_for(c, d, nsteps - d, 8)));
+    }
+    for (uint32_t j = 0; j < d; j++) {
+        const bool last = j + 1 == d;
+        HB_TRY(c.small_weights ? launch_enc_tiled<true>(ctx, "k_enc_tiled_D", dst, ld_dst, dst, ld_dst, batch, c.tsteps[d + j], 0, last ? (uint32_t)c.len : 0, last ? z_hi : 0)
+                               : launch_enc_tiled<false>(ctx, "k_enc_tiled_fullw_D", dst, ld_dst, dst, ld_dst, batch, c.tsteps[d + j], 0, last ? (uint32_t)c.len : 0, last ? z_hi : 0));
+    }
+    return 0;
+}
+
 int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t ld_dst, long long n, size_t batch, int write_msg) {
     DeviceCode &c = ctx->code;
     if (c.n != n) return ctx->fail(HOBBIT_ESTATE, "encode: graphs for this n are not finalized (hobbit_graph_finalize)");
     if (batch == 0) return 0;
-    if ((size_t)c.len * 16 > 160 * 1024) return ctx->fail(HOBBIT_EINVAL, "encode: codeword does not fit in 160 KB of LDS (n <= 4096 supported)");
+    if ((size_t)c.len * 16 > 160 * 1024) {
+        if (!c.tiled_depth) return ctx->fail(HOBBIT_ESTATE, "encode: long code without its tiled steps (hobbit_graph_finalize)");
+        return launch_encode_long(ctx, src, ld_src, dst, ld_dst, batch, write_msg);
+    }
     const uint32_t nn = (uint32_t)n, nsteps = (uint32_t)c.steps.size();
     const bool split = nsteps >= 2 && (size_t)c.len * 16 > 80 * 1024;     // cannot co-schedule two workgroups per CU otherwise
     if (!split) {
