@@ -160,3 +160,67 @@ def test_open_transcript_fixture_is_self_consistent():
         rec = np.array(d["records"], np.uint64).reshape(-1, 6)
         assert rec.shape[0] == d["count"] > 200 and hashlib.sha256(rec.tobytes()).hexdigest() == d["sha256"], k
         assert "undefined symbol: SHA3_256" in d["died_with"] and d["rc"] != 0, k
+
+
+# ---- the oracle on structured and worst-case inputs (tests/adversarial.py), against plain Python integers ----------------------------
+# tests/test_adversarial_inputs.py trusts the oracle on exactly these inputs; here the oracle itself is checked on them.
+def _obj(a):
+    return np.asarray(a, np.uint64).astype(object)
+
+
+def test_adversarial_field_ops_vs_bigint(oracle):
+    """F_{p^2} add, sub and mul on every family (against its reverse and against itself) and on the full (re, im) x (re, im) cross product
+    of the limb-edge component values -- the set the GPU field test runs -- against big-integer arithmetic"""
+    import adversarial as A
+    P = A.P
+    cases = {}
+    for name, x in A.families(1024).items():
+        cases[name + "/rev"] = (x, x[::-1].copy())
+        cases[name + "/self"] = (x, x)
+    cases["limb_cross"] = A.cross_pairs(A.LIMB_EDGES)
+    for name, (a, b) in cases.items():
+        ar, ai, br, bi = _obj(a[:, 0]), _obj(a[:, 1]), _obj(b[:, 0]), _obj(b[:, 1])
+        want = {"add": ((ar + br) % P, (ai + bi) % P), "sub": ((ar - br) % P, (ai - bi) % P),
+                "mul": ((ar * br - ai * bi) % P, (ar * bi + ai * br) % P)}
+        for op, fn in (("add", oracle.f_add), ("sub", oracle.f_sub), ("mul", oracle.f_mul)):
+            got = fn(a, b)
+            assert (got[:, 0].astype(object) == want[op][0]).all() and (got[:, 1].astype(object) == want[op][1]).all(), (name, op)
+
+
+@pytest.mark.parametrize("logn", [0, 1, 2, 3, 4, 5, 6])
+def test_adversarial_dft_vs_definition(oracle, logn):
+    """oracle.fft (forward and inverse) on every family against X[k] = sum_j x[j] w^(jk) computed from the definition with Python integers,
+    w = oracle.root_of_unity(logn) (checked to be a primitive 2^logn-th root of unity), w^-1 and 1/n for the inverse"""
+    import adversarial as A
+    n = 1 << logn
+    w = tuple(int(v) for v in oracle.root_of_unity(logn))
+    assert A.py_pow(w, n) == (1, 0) and (logn == 0 or A.py_pow(w, n // 2) != (1, 0))
+    w_inv = A.py_pow(w, n - 1)
+    n_inv = pow(n, A.P - 2, A.P)
+    for name, x in A.families(n, seed=logn).items():
+        xs = A.to_py(x)
+        fwd = A.py_dft(xs, w)
+        inv = [A.py_mul(v, (n_inv, 0)) for v in A.py_dft(xs, w_inv)]
+        assert np.array_equal(oracle.fft(x), A.from_py(fwd)), (name, logn, "forward")
+        assert np.array_equal(oracle.fft(x, inverse=True), A.from_py(inv)), (name, logn, "inverse")
+
+
+@pytest.mark.parametrize("n", [14, 64, 100])
+def test_adversarial_encode_vs_edge_sums(oracle, n):
+    """oracle.encode_monolithic on every family against the codeword as a plain sum over the edge lists of oracle.graph, with the drawn
+    weights, with every weight 2^32 - 1 (the largest 32-bit weight: the GPU's unreduced 96-bit sums) and with every weight (p-1, p-1)"""
+    import adversarial as A
+    oracle.rng_reset(); oracle.expander_init_store(n)
+    lv = A.graphs_from(oracle, n)
+    fams = A.families(n, seed=n)
+    try:
+        for wname, w in (("drawn", None), ("2^32-1", [(1 << 32) - 1, 0]), ("full_p-1", [A.P - 1, A.P - 1])):
+            if w is not None:
+                lv = A.set_weights(oracle, lv, w)
+            for name, x in fams.items():
+                got, ln = oracle.encode_monolithic(x)
+                want = A.py_encode(lv, A.to_py(x))
+                assert ln == len(want) and np.array_equal(got[:ln], A.from_py(want)), (n, wname, name)
+                assert not got[ln:].any()
+    finally:
+        oracle.rng_reset(); oracle.expander_init_store(n); oracle.rng_reset()   # the drawn weights back for whoever comes next
