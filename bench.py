@@ -7,7 +7,12 @@ encode, BLAKE3 Merkle-Damgard leaf chain over the K chunks, Merkle tree) followe
 test_PC(2^28, 4, 32) -- all on the GPU through the C ABI (libhobbit_hip.so), with the polynomial already resident in HBM when the
 timed region starts.  --phase commit times the commit alone.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 28] [--chunks 32] [--mode replicas|sharded] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 28] [--chunks 32] [--mode replicas|sharded] [--dump-outputs DIR] [--full]
+
+A plain run sets up, primes, warms up, times the K steps and prints the result line; the per-kernel and roofline figures in it come from the
+event brackets of the timed steps themselves.  --full adds what takes runs of its own: one extra fully bracketed step for the complete per-kernel
+table, a fresh commitment for `root`, the CPU baselines (the reference's single-thread commit, the all-cores restatement, the open on the CPU) and
+the reference-shaped drop-in driver (`dropin`); --no-cpu-baseline / --no-dropin leave those legs out of a --full run.
 
 --dump-outputs DIR writes what the last timed step returned to its caller (the commitment's root and Merkle levels, the opening's
 arrays) as DIR/<name>.npy, so that two builds can be compared output for output; the inputs depend only on the arguments.
@@ -249,9 +254,12 @@ def main():
                     help="commit+open adds the whole prover side of open_standard (recursive_prover_Spielman with both shockwave_prove/WHIR proofs); "
                          "commit+opencore stops before the two shockwave_prove calls")
     ap.add_argument("--queries", type=int, default=5900)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the reference-shaped driver leg (host/test_pc <logN> 4 <K>: host vector in, PCIe inclusive)")
-    ap.add_argument("--cpu-logn", type=int, default=24, help="size of the CPU-baseline sample (2^24: about 17 s of single-thread reference time)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what takes runs of its own: a fully bracketed extra step (kernels_ms_extra_profiled_step), "
+                         "a fresh commitment (root), the CPU baselines and the drop-in driver leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-dropin", action="store_true", help="--full: skip the reference-shaped driver leg (host/test_pc <logN> 4 <K>: host vector in, PCIe inclusive)")
+    ap.add_argument("--cpu-logn", type=int, default=24, help="--full: size of the CPU-baseline sample (2^24: about 17 s of single-thread reference time)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (commitment root and Merkle levels, opening) as DIR/<name>.npy, float64, at most 64 MB")
     args = ap.parse_args()
@@ -381,10 +389,12 @@ def main():
             outputs["open"] = open_last["res"]
     prof = hb.profile_report()
     prof.pop("k_fill_splitmix", None)          # the untimed filler in front of the barrier
-    hb.profile(1); hb.profile_reset()
-    step()                                     # untimed: every launch bracketed, for the full per-kernel table
-    hb.sync()
-    prof_full = hb.profile_report()
+    prof_full = None
+    if args.full:
+        hb.profile(1); hb.profile_reset()
+        step()                                 # untimed: every launch bracketed, for the full per-kernel table
+        hb.sync()
+        prof_full = hb.profile_report()
     hb.profile(0)
 
     t = torch.tensor([wall], dtype=torch.float64, device="cuda")
@@ -393,12 +403,14 @@ def main():
     wall_max = float(t.item())
 
     # a commitment to report (root of rank 0's polynomial / of the sharded commitment)
-    if sharded:
-        root = bytes(last["res"]["root"]).hex()
-    else:
-        c = hb.commit_standard((d_poly, N), K, trs, 1)
-        root = bytes(c.root()).hex()
-        c.free()
+    root = None
+    if args.full:
+        if sharded:
+            root = bytes(last["res"]["root"]).hex()
+        else:
+            c = hb.commit_standard((d_poly, N), K, trs, 1)
+            root = bytes(c.root()).hex()
+            c.free()
 
     if rank == 0:
         ms_per_step = 1e3 * wall_max / args.steps
@@ -443,16 +455,19 @@ def main():
             "blake3_compressions_per_s": comp * (1 if sharded else world) / (wall_max / args.steps),
             "op_counts": {"f_mul": mul, "f_add": add, "blake3_compress": comp, "blake3_compress_nominal": comp_nominal, "expander_edges": edges, "open_f_mul": omul, "open_f_add": oadd},
             "kernels_ms_per_step": {k: v[0] / args.steps for k, v in sorted(prof.items())},
-            "kernels_ms_note": "k_fft4096 and k_transpose run on two streams, overlapped (chunk group g's transpose beside group g+1's FFT): their durations sum to more than their wall-clock span; kernels_ms_extra_profiled_step / launches_extra_profiled_step come from one extra untimed step with every launch bracketed, which runs the open on ONE thread and stream (the timed steps run shockwave_prove(C_c) on a helper context from a second thread and the inner commitments on a third stream)",
-            "kernels_ms_extra_profiled_step": {k: v[0] for k, v in sorted(prof_full.items())},
-            "launches_extra_profiled_step": {"total": int(sum(v[1] for v in prof_full.values())),
-                                             "open": int(sum(v[1] for k, v in prof_full.items() if not (k.startswith(("k_leaf_chain", "k_enc")) or k in ("k_fft4096", "k_transpose", "k_merkle_level", "k_merkle_top"))))},
+            "kernels_ms_note": "k_fft4096 and k_transpose run on two streams, overlapped (chunk group g's transpose beside group g+1's FFT): their durations sum to more than their wall-clock span",
             "roofline": {"bound": KERNEL_BOUND.get(dom, "hbm"), "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": measured_traffic(dom, args.logn, K)[0], "traffic_source": measured_traffic(dom, args.logn, K)[1],
                          "algorithmic_bytes_per_launch": ab[dom], "avg_launch_ms": dom_ms, "note": ROOFLINE_NOTES.get(dom, "")},
             "roofline_kernels": roofline_kernels,
-            "root": root,
         }
+        if args.full:
+            out["kernels_ms_note"] += ("; kernels_ms_extra_profiled_step / launches_extra_profiled_step come from one extra untimed step with every launch bracketed, which runs the open on ONE "
+                                       "thread and stream (the timed steps run shockwave_prove(C_c) on a helper context from a second thread and the inner commitments on a third stream)")
+            out["kernels_ms_extra_profiled_step"] = {k: v[0] for k, v in sorted(prof_full.items())}
+            out["launches_extra_profiled_step"] = {"total": int(sum(v[1] for v in prof_full.values())),
+                                                   "open": int(sum(v[1] for k, v in prof_full.items() if not (k.startswith(("k_leaf_chain", "k_enc")) or k in ("k_fft4096", "k_transpose", "k_merkle_level", "k_merkle_top"))))}
+            out["root"] = root
         if dom == "k_leaf_chain" and not sharded:
             # the binding resource of the dominant kernel: VALU issue.  2023 SIMD-cycles per wave-compression (7 rounds x 8 G x 36 issue
             # cycles + message/finalisation moves; profiles/r01_microbench.txt), 64 compressions per wave, 1024 SIMDs: the clock at which
@@ -465,12 +480,12 @@ def main():
             # primary fraction for a VALU-bound kernel: issue cycles the instruction stream needs / cycles available at the sustained clock
             out["roofline"]["frac_valu"] = cyc / (dom_ms * 1e-3 * SUSTAINED_GHZ * 1e9)
             out["roofline"]["frac_valu_of_peak_clock"] = cyc / (dom_ms * 1e-3 * PEAK_GHZ * 1e9)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_logn, K)
             out["cpu_baseline_all_cores"] = cpu_all_cores(K)
             if do_open:
                 out["cpu_baseline_open_port"] = cpu_open_port(args.cpu_logn, K, args.queries, full_open)
-        if not args.no_dropin and world == 1 and do_open and full_open:
+        if args.full and not args.no_dropin and world == 1 and do_open and full_open:
             out["dropin"] = dropin_leg(args.logn, K)
         if outputs is not None:
             out["dump_outputs"] = dump_outputs(args.dump_outputs, flatten_outputs(outputs))

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/ab_env; mkdir -p $O
 for s in "$@"; do
   IFS=, read -ra kv <<< "$s"
-  env "${kv[@]}" python3 $R/bench.py --steps 20 --no-cpu-baseline --no-dropin > $O/out.json 2> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
+  env "${kv[@]}" python3 $R/bench.py --steps 20 --full --no-cpu-baseline --no-dropin > $O/out.json 2> $O/err.txt || { tail -5 $O/err.txt; exit 1; }
   python3 - "$s" $O/out.json <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

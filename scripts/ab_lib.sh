@@ -5,7 +5,7 @@ OTHER=$1; STEPS=${2:-20}
 for rep in 1 2; do
   for lib in default $OTHER; do
     if [ "$lib" = default ]; then unset HOBBIT_HIP_LIB; else export HOBBIT_HIP_LIB=$(realpath $lib); fi
-    python bench.py --steps $STEPS --warmup 2 --no-cpu-baseline --no-dropin 2>/dev/null | python -c "
+    python bench.py --steps $STEPS --warmup 2 --full --no-cpu-baseline --no-dropin 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1])
 k = d.get('kernels_ms_extra_profiled_step', {})
