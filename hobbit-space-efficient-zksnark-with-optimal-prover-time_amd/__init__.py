@@ -50,6 +50,9 @@ ABI_SYMBOLS = [
     "hobbit_open_core", "hobbit_open_standard", "hobbit_open_from_aggregate", "hobbit_tensor_gather", "hobbit_u64_bias_fold", "hobbit_gate_sumcheck", "hobbit_compute2p_error_terms", "hobbit_compute3p_error_terms", "hobbit_compute4p_error_terms", "hobbit_fold_axpy",
     "hobbit_fold_axpy_i32", "hobbit_batch_prod",
     "hobbit_aggregate", "hobbit_sumcheck2", "hobbit_sumcheck3", "hobbit_fill_splitmix",
+    "hobbit_encode_interleaved", "hobbit_brakedown_shape", "hobbit_brakedown_commit", "hobbit_brakedown_free", "hobbit_brakedown_dims",
+    "hobbit_brakedown_matrix_dev", "hobbit_brakedown_levels_dev", "hobbit_brakedown_levels", "hobbit_brakedown_root", "hobbit_brakedown_tensor",
+    "hobbit_brakedown_open",
 ]
 
 
@@ -77,6 +80,9 @@ def load_library(path=LIB_PATH):
     lib.hobbit_commitment_num_leaves.restype = c_sz
     lib.hobbit_commitment_levels_dev.restype = c_vp
     lib.hobbit_commitment_tensor_dev.restype = c_vp
+    lib.hobbit_brakedown_matrix_dev.restype = c_vp
+    lib.hobbit_brakedown_levels_dev.restype = c_vp
+    lib.hobbit_brakedown_free.restype = None
     # explicit prototypes: a bare Python int would otherwise be passed as a 32-bit C int and
     # truncate device pointers / sizes
     V, S, I, L, U64 = c_vp, c_sz, c_int, c_ll, ctypes.c_uint64
@@ -122,6 +128,10 @@ def load_library(path=LIB_PATH):
         "hobbit_axpy_aggregate": [V, V, V, V, S], "hobbit_stream_fold": [V, I, V, V, S, V], "hobbit_gate_consistency_lookups_stream": [V, V, V, S, S, V, V],
         "hobbit_tensorcode_chunks": [V, V, S, I, I, I, V], "hobbit_inner_digests": [V, V, S, I, I, V],
         "hobbit_chain_digests": [V, V, S, I, S, V], "hobbit_blake3_64_host": [V, V, S],
+        "hobbit_encode_interleaved": [V, V, V, L, ctypes.c_uint32], "hobbit_brakedown_shape": [S, V, V], "hobbit_brakedown_commit": [V, V, S, I, V],
+        "hobbit_brakedown_free": [V], "hobbit_brakedown_dims": [V, V, V, V], "hobbit_brakedown_matrix_dev": [V], "hobbit_brakedown_levels_dev": [V],
+        "hobbit_brakedown_levels": [V, V, V], "hobbit_brakedown_root": [V, V, V], "hobbit_brakedown_tensor": [V, V, S, S, V],
+        "hobbit_brakedown_open": [V, V, V, V, V, S, V, V, V, V],
     }
     for name, args in protos.items():
         getattr(lib, name).argtypes = args
@@ -211,6 +221,46 @@ class Commitment:
     def free(self):
         if self.h and self.hb.ctx:
             self.hb.lib.hobbit_commitment_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class BrakedownCommitment:
+    """Handle on a device-resident Brakedown commitment (hobbit_brakedown_commit): the encoded matrix, rows-innermost, and the Merkle levels
+    over its 2B column digests."""
+
+    def __init__(self, hb, handle, N):
+        self.hb, self.h, self.N = hb, handle, N
+        B, rows, ln = c_sz(), ctypes.c_uint32(), c_ll()
+        hb.lib.hobbit_brakedown_dims(handle, ctypes.byref(B), ctypes.byref(rows), ctypes.byref(ln))
+        self.B, self.rows, self.len = B.value, rows.value, ln.value
+        self.W = 2 * self.B                     # columns = leaves of the tree
+
+    def levels(self):
+        out = np.zeros((2 * self.W - 1, 32), np.uint8)
+        self.hb._chk(self.hb.lib.hobbit_brakedown_levels(self.hb.ctx, self.h, _hp(out)))
+        return out
+
+    def root(self):
+        out = np.zeros(32, np.uint8)
+        self.hb._chk(self.hb.lib.hobbit_brakedown_root(self.hb.ctx, self.h, _hp(out)))
+        return out
+
+    def tensor(self, col_lo=0, ncols=None):
+        """the reference's tensor[0][i][c] for every row i and c in [col_lo, col_lo + ncols): shape (rows, ncols, 2)"""
+        ncols = self.W - col_lo if ncols is None else ncols
+        out = np.zeros((self.rows, ncols, 2), np.uint64)
+        self.hb._chk(self.hb.lib.hobbit_brakedown_tensor(self.hb.ctx, self.h, c_sz(col_lo), c_sz(ncols), _hp(out)))
+        return out
+
+    def free(self):
+        if self.h and self.hb.ctx:
+            self.hb.lib.hobbit_brakedown_free(self.h)
         self.h = None
 
     def __del__(self):
@@ -472,6 +522,57 @@ class Hobbit:
         self._chk(self.lib.hobbit_commit_standard_host(self.ctx, _hp(p), c_vp(d.ptr), c_sz(N), c_int(K), c_int(trs), c_int(lin), ctypes.byref(h)))
         self.sync()
         return Commitment(self, h, N, K, trs), d
+
+    # ---- Brakedown baseline (src/Our_PC.cpp:197-236, 432-520)
+    @staticmethod
+    def brakedown_shape(N):
+        """(B, rows) of commit_standard_brakedown for N = 2^n, 16 <= n <= 29"""
+        lib = load_library()
+        B, rows = c_sz(), ctypes.c_uint32()
+        if lib.hobbit_brakedown_shape(c_sz(N), ctypes.byref(B), ctypes.byref(rows)) != 0:
+            raise HobbitError("brakedown: N = %d is not 2^n with 16 <= n <= 29" % N)
+        return B.value, rows.value
+
+    def encode_interleaved(self, src, in_place=False):
+        """encode_monolithic of rows messages at once, rows-innermost: src (n, rows, 2) -> (2n, rows, 2); graphs for n finalized"""
+        s = Fh(src)
+        n, rows = s.shape[0], s.shape[1]
+        if in_place:
+            buf = np.full((2 * n, rows, 2), 0x0123456789ABCDEF, np.uint64); buf[:n] = s      # whatever the buffer held before must not matter
+            dd = self.to_device(buf); ds = dd
+        else:
+            ds = self.to_device(s); dd = self.alloc(32 * n * rows)
+        self._chk(self.lib.hobbit_encode_interleaved(self.ctx, c_vp(ds.ptr), c_vp(dd.ptr), c_ll(n), ctypes.c_uint32(rows)))
+        return self.to_host(dd, (2 * n, rows, 2), np.uint64)
+
+    def brakedown_commit(self, poly, quirk=1):
+        """commit_standard_brakedown: poly is a host array (N, 2) or (DeviceBuffer/ptr, N); the graphs for n = B must be finalized
+        (expander_init_store(B) / upload_graphs).  Returns a BrakedownCommitment."""
+        if isinstance(poly, tuple):
+            ptr, N = poly
+            ptr = ptr.ptr if isinstance(ptr, DeviceBuffer) else int(ptr)
+        else:
+            p = Fh(poly).reshape(-1, 2)
+            N = p.shape[0]
+            keep = self.to_device(p); ptr = keep.ptr
+        h = c_vp()
+        self._chk(self.lib.hobbit_brakedown_commit(self.ctx, c_vp(ptr), c_sz(N), c_int(quirk), ctypes.byref(h)))
+        self.sync()
+        return BrakedownCommitment(self, h, N)
+
+    def brakedown_open(self, c, x, r, I, want_paths=True):
+        """open_brakedown_standard's prover side with the host's draws: x (>= log2 rows F of the point), r (rows F), I (column indices < 2B).
+        Returns dict(aggr_beta, aggr_r, reply (nq, rows, 2), paths (nq, log2 2B, 32) -- leaf 0's path for every query, as the reference builds it)"""
+        lr = c.rows.bit_length() - 1
+        x = Fh(x).reshape(-1, 2)[:lr].copy(); r = Fh(r).reshape(-1, 2)
+        assert r.shape[0] == c.rows
+        I = np.ascontiguousarray(I, np.uint64); nq = I.shape[0]
+        depth = c.W.bit_length() - 1
+        out = dict(aggr_beta=np.zeros((c.B, 2), np.uint64), aggr_r=np.zeros((c.B, 2), np.uint64), reply=np.zeros((nq, c.rows, 2), np.uint64),
+                   paths=np.zeros((nq, depth, 32), np.uint8) if want_paths else None)
+        self._chk(self.lib.hobbit_brakedown_open(self.ctx, c.h, _hp(x), _hp(r), _hp(I), c_sz(nq), _hp(out["aggr_beta"]), _hp(out["aggr_r"]),
+                                                 _hp(out["reply"]), _hp(out["paths"]) if want_paths else None))
+        return out
 
     def open_from_aggregate(self, aggr, K, trs, queries=5900):
         """open_standard's prover side from a given aggregate vector (host array or (DeviceBuffer/ptr, M)); multi-GPU open"""

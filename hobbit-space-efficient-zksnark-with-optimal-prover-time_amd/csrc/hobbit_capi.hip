@@ -146,6 +146,7 @@ static void free_code(DeviceCode &c) {
     if (c.d_pm_idx) hipFree(c.d_pm_idx);
     if (c.d_pm_w) hipFree(c.d_pm_w);
     for (void *q : {(void *)c.d_tile_ptr, (void *)c.d_tile_width, (void *)c.d_tile_out, (void *)c.d_tile_e32, (void *)c.d_tile_eidx, (void *)c.d_tile_ew}) if (q) hipFree(q);
+    for (void *q : {(void *)c.d_ilv_ptr, (void *)c.d_ilv_e32, (void *)c.d_ilv_eidx, (void *)c.d_ilv_ew}) if (q) hipFree(q);
     c = DeviceCode();
 }
 
@@ -415,7 +416,7 @@ int hobbit_f_binop(hobbit_ctx *ctx, int op, const hobbit_F *a, const hobbit_F *b
 int hobbit_fill_splitmix(hobbit_ctx *ctx, hobbit_F *o, size_t n, uint64_t seed) { if (!n) return 0; return launch_fill_splitmix(ctx, mF(o), n, seed); }
 
 // ---- expander graphs --------------------------------------------------------------------------
-int hobbit_graph_reset(hobbit_ctx *ctx) { ctx->graphs.clear(); hipStreamSynchronize(ctx->stream); free_code(ctx->code); return 0; }
+int hobbit_graph_reset(hobbit_ctx *ctx) { ctx->graphs.clear(); ctx->graph_gen++; hipStreamSynchronize(ctx->stream); free_code(ctx->code); return 0; }
 int hobbit_graph_upload(hobbit_ctx *ctx, int dep, int kind, long long L, long long R, int degree, const long long *nbr, const hobbit_F *w) {
     if (dep < 0 || dep >= 100 || (kind != 0 && kind != 1) || L <= 0 || R <= 0 || degree <= 0) return ctx->fail(HOBBIT_EINVAL, "graph_upload: bad dims");
     HostGraph g; g.L = L; g.R = R; g.degree = degree;
@@ -423,6 +424,7 @@ int hobbit_graph_upload(hobbit_ctx *ctx, int dep, int kind, long long L, long lo
     g.w.resize((size_t)(L * degree)); for (size_t i = 0; i < g.w.size(); i++) g.w[i] = cF(w)[i];
     for (long long t : g.nbr) if (t < 0 || t >= R) return ctx->fail(HOBBIT_EINVAL, "graph_upload: neighbour out of range");
     ctx->graphs[{dep, kind}] = std::move(g);
+    ctx->graph_gen++;
     return 0;
 }
 // fat form of one step (hobbit_ctx.hpp FatStep); returns false (and leaves f.ok false) when a degree exceeds the kernel's caps
@@ -572,6 +574,116 @@ static bool build_mid(const std::vector<MidPlanStep> &steps, uint32_t win_off, u
     m.ok = up(&m.d_wt, wt) && up(&m.d_ot, ot) && up(&m.d_oidx, oidx) && up(&m.d_w, wid);
     return m.ok;
 }
+// Long codes (codeword over 160 KB): the outer steps whose windows do not fit in LDS, in tiled form (hobbit_ctx.hpp TiledStep).  Built by the
+// first launch_encode of the finalized code, from the plan hobbit_graph_finalize kept.
+}  // extern "C"
+namespace hobbit {
+int ensure_tiled(hobbit_ctx *ctx) {
+    DeviceCode &c = ctx->code;
+    if (c.tiled_built) return 0;
+    if (c.graph_gen != ctx->graph_gen) return ctx->fail(HOBBIT_ESTATE, "encode: the graphs changed after hobbit_graph_finalize");
+    const std::vector<PlanStep> &plan = c.plan;
+    const std::vector<long long> &cwlen = c.cwlen;
+    const uint32_t D = (uint32_t)cwlen.size() - 1;
+    auto up = [&](void **d, const void *h, size_t bytes) -> int {
+        if (hipMalloc(d, bytes ? bytes : 16) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "graph alloc failed");
+        if (bytes) HB_CHECK(ctx, hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    uint32_t d = 0;
+    while (d < (uint32_t)D && cwlen[d] > TILE_MID_MAX) d++;
+    c.tiled_depth = d;
+    std::vector<uint32_t> tptr, twid, tout, teidx; std::vector<uint2> te32; std::vector<F> tew;
+    for (size_t si = 0; si < plan.size(); si++) {
+        if (si >= d && si < plan.size() - d) continue;
+        const HostGraph &g = *plan[si].g;
+        TiledStep t;
+        t.in_off = (uint32_t)plan[si].in_off; t.in_len = (uint32_t)g.L; t.out_off = (uint32_t)plan[si].out_off; t.out_len = (uint32_t)g.R;
+        t.ntiles = (t.in_len + TILE_ELEMS - 1) / TILE_ELEMS;
+        t.n_slices = (t.out_len + 63) / 64;
+        t.groups = (t.n_slices + TILE_WAVES * TILE_MAXS - 1) / (TILE_WAVES * TILE_MAXS);
+        t.tile_base = (uint32_t)tptr.size(); t.out_base = (uint32_t)tout.size();
+        // in-edges of every output in input order, so that those of one tile are a contiguous run: tile k of output o is [beg(o, k), beg(o, k + 1))
+        std::vector<std::vector<std::pair<uint32_t, F>>> rows(g.R);
+        for (long long i = 0; i < g.L; i++)
+            for (int j = 0; j < g.degree; j++) rows[g.nbr[i * g.degree + j]].push_back({(uint32_t)i, g.w[i * g.degree + j]});
+        auto beg = [&](uint32_t o, uint32_t k) {
+            return (size_t)(std::lower_bound(rows[o].begin(), rows[o].end(), k * TILE_ELEMS, [](const std::pair<uint32_t, F> &e, uint32_t v) { return e.first < v; }) - rows[o].begin());
+        };
+        std::vector<uint32_t> order((size_t)g.R);
+        for (size_t q = 0; q < order.size(); q++) order[q] = (uint32_t)q;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].size() > rows[b].size(); });
+        for (uint32_t sl = 0; sl < t.n_slices; sl++) {
+            for (uint32_t l = 0; l < 64; l++) { const size_t q = (size_t)sl * 64 + l; tout.push_back(q < order.size() ? order[q] : 0xFFFFFFFFu); }
+            for (uint32_t k = 0; k < t.ntiles; k++) {
+                size_t lo[64], hi[64], width = 0;
+                for (uint32_t l = 0; l < 64; l++) {
+                    const size_t q = (size_t)sl * 64 + l;
+                    lo[l] = hi[l] = 0;
+                    if (q < order.size()) { lo[l] = beg(order[q], k); hi[l] = beg(order[q], k + 1); width = std::max(width, hi[l] - lo[l]); }
+                }
+                width = (width + ENC_UNROLL - 1) / ENC_UNROLL * ENC_UNROLL;
+                tptr.push_back((uint32_t)c.tile_records); twid.push_back((uint32_t)width);
+                for (size_t e = 0; e < width; e++)
+                    for (uint32_t l = 0; l < 64; l++) {
+                        uint32_t id = 0; F w = fmake(0);
+                        if (lo[l] + e < hi[l]) { const auto &r = rows[order[(size_t)sl * 64 + l]][lo[l] + e]; id = r.first - k * TILE_ELEMS; w = r.second; }
+                        if (c.small_weights) te32.push_back(make_uint2(id, (uint32_t)w.re)); else { teidx.push_back(id); tew.push_back(w); }
+                    }
+                c.tile_records += width * 64;
+            }
+        }
+        c.tsteps.push_back(t);
+    }
+    HB_TRY(up((void **)&c.d_tile_ptr, tptr.data(), tptr.size() * 4));
+    HB_TRY(up((void **)&c.d_tile_width, twid.data(), twid.size() * 4));
+    HB_TRY(up((void **)&c.d_tile_out, tout.data(), tout.size() * 4));
+    if (c.small_weights) HB_TRY(up((void **)&c.d_tile_e32, te32.data(), te32.size() * sizeof(uint2)));
+    else { HB_TRY(up((void **)&c.d_tile_eidx, teidx.data(), teidx.size() * 4)); HB_TRY(up((void **)&c.d_tile_ew, tew.data(), tew.size() * sizeof(F))); }
+    c.tiled_built = true;
+    return 0;
+}
+// The rows-innermost encode's steps (hobbit_ctx.hpp IlvStep): every step of the plan, its outputs' in-edges in input order (a counting sort by
+// output), built by the first hobbit_encode_interleaved / hobbit_brakedown_commit of the finalized code.
+int ensure_ilv(hobbit_ctx *ctx) {
+    DeviceCode &c = ctx->code;
+    if (c.ilv_built) return 0;
+    if (c.graph_gen != ctx->graph_gen) return ctx->fail(HOBBIT_ESTATE, "encode: the graphs changed after hobbit_graph_finalize");
+    std::vector<uint32_t> ptr; std::vector<uint2> e32; std::vector<uint32_t> eidx; std::vector<F> ew;
+    size_t total = 0;
+    for (const PlanStep &p : c.plan) total += (size_t)p.g->L * p.g->degree;
+    if (total >= 0xFFFFFFFFu) return ctx->fail(HOBBIT_EINVAL, "encode_interleaved: too many edges");
+    if (c.small_weights) e32.resize(total); else { eidx.resize(total); ew.resize(total); }
+    size_t base = 0;
+    c.isteps.clear();
+    for (const PlanStep &p : c.plan) {
+        const HostGraph &g = *p.g;
+        const size_t R = (size_t)g.R, E = (size_t)g.L * g.degree;
+        c.isteps.push_back({(uint32_t)p.in_off, (uint32_t)p.out_off, (uint32_t)R, (uint32_t)ptr.size()});
+        std::vector<uint32_t> cnt(R + 1, 0);
+        for (size_t e = 0; e < E; e++) cnt[(size_t)g.nbr[e] + 1]++;
+        for (size_t t = 0; t < R; t++) cnt[t + 1] += cnt[t];
+        for (size_t t = 0; t <= R; t++) ptr.push_back((uint32_t)(base + cnt[t]));
+        for (long long i = 0; i < g.L; i++)                     // edges of input i in increasing i: each output's list is in input order
+            for (int j = 0; j < g.degree; j++) {
+                const size_t e = (size_t)i * g.degree + j, at = base + cnt[(size_t)g.nbr[e]]++;
+                if (c.small_weights) e32[at] = make_uint2((uint32_t)i, (uint32_t)g.w[e].re); else { eidx[at] = (uint32_t)i; ew[at] = g.w[e]; }
+            }
+        base += E;
+    }
+    auto up = [&](void **d, const void *h, size_t bytes) -> int {
+        if (hipMalloc(d, bytes ? bytes : 16) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "graph alloc failed");
+        if (bytes) HB_CHECK(ctx, hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    HB_TRY(up((void **)&c.d_ilv_ptr, ptr.data(), ptr.size() * 4));
+    if (c.small_weights) HB_TRY(up((void **)&c.d_ilv_e32, e32.data(), e32.size() * sizeof(uint2)));
+    else { HB_TRY(up((void **)&c.d_ilv_eidx, eidx.data(), eidx.size() * 4)); HB_TRY(up((void **)&c.d_ilv_ew, ew.data(), ew.size() * sizeof(F))); }
+    c.ilv_built = true;
+    return 0;
+}
+}  // namespace hobbit
+extern "C" {
 int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
     hipStreamSynchronize(ctx->stream);
     free_code(ctx->code);
@@ -657,59 +769,10 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
         for (size_t i = 1; i + 1 < plan.size(); i++) ms.push_back({plan[i].g, plan[i].in_off, plan[i].out_off});
         build_mid(ms, (uint32_t)plan[1].in_off, (uint32_t)plan[1].g->L, c.mid);
     }
-    // long codes: the outer steps whose windows do not fit in LDS, in tiled form (hobbit_ctx.hpp TiledStep)
-    if ((size_t)c.len * 16 > 160 * 1024) {
-        uint32_t d = 0;
-        while (d < (uint32_t)D && cwlen[d] > TILE_MID_MAX) d++;
-        c.tiled_depth = d;
-        std::vector<uint32_t> tptr, twid, tout, teidx; std::vector<uint2> te32; std::vector<F> tew;
-        for (size_t si = 0; si < plan.size(); si++) {
-            if (si >= d && si < plan.size() - d) continue;
-            const HostGraph &g = *plan[si].g;
-            TiledStep t;
-            t.in_off = (uint32_t)plan[si].in_off; t.in_len = (uint32_t)g.L; t.out_off = (uint32_t)plan[si].out_off; t.out_len = (uint32_t)g.R;
-            t.ntiles = (t.in_len + TILE_ELEMS - 1) / TILE_ELEMS;
-            t.n_slices = (t.out_len + 63) / 64;
-            t.groups = (t.n_slices + TILE_WAVES * TILE_MAXS - 1) / (TILE_WAVES * TILE_MAXS);
-            t.tile_base = (uint32_t)tptr.size(); t.out_base = (uint32_t)tout.size();
-            // in-edges of every output in input order, so that those of one tile are a contiguous run: tile k of output o is [beg(o, k), beg(o, k + 1))
-            std::vector<std::vector<std::pair<uint32_t, F>>> rows(g.R);
-            for (long long i = 0; i < g.L; i++)
-                for (int j = 0; j < g.degree; j++) rows[g.nbr[i * g.degree + j]].push_back({(uint32_t)i, g.w[i * g.degree + j]});
-            auto beg = [&](uint32_t o, uint32_t k) {
-                return (size_t)(std::lower_bound(rows[o].begin(), rows[o].end(), k * TILE_ELEMS, [](const std::pair<uint32_t, F> &e, uint32_t v) { return e.first < v; }) - rows[o].begin());
-            };
-            std::vector<uint32_t> order((size_t)g.R);
-            for (size_t q = 0; q < order.size(); q++) order[q] = (uint32_t)q;
-            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].size() > rows[b].size(); });
-            for (uint32_t sl = 0; sl < t.n_slices; sl++) {
-                for (uint32_t l = 0; l < 64; l++) { const size_t q = (size_t)sl * 64 + l; tout.push_back(q < order.size() ? order[q] : 0xFFFFFFFFu); }
-                for (uint32_t k = 0; k < t.ntiles; k++) {
-                    size_t lo[64], hi[64], width = 0;
-                    for (uint32_t l = 0; l < 64; l++) {
-                        const size_t q = (size_t)sl * 64 + l;
-                        lo[l] = hi[l] = 0;
-                        if (q < order.size()) { lo[l] = beg(order[q], k); hi[l] = beg(order[q], k + 1); width = std::max(width, hi[l] - lo[l]); }
-                    }
-                    width = (width + ENC_UNROLL - 1) / ENC_UNROLL * ENC_UNROLL;
-                    tptr.push_back((uint32_t)c.tile_records); twid.push_back((uint32_t)width);
-                    for (size_t e = 0; e < width; e++)
-                        for (uint32_t l = 0; l < 64; l++) {
-                            uint32_t id = 0; F w = fmake(0);
-                            if (lo[l] + e < hi[l]) { const auto &r = rows[order[(size_t)sl * 64 + l]][lo[l] + e]; id = r.first - k * TILE_ELEMS; w = r.second; }
-                            if (c.small_weights) te32.push_back(make_uint2(id, (uint32_t)w.re)); else { teidx.push_back(id); tew.push_back(w); }
-                        }
-                    c.tile_records += width * 64;
-                }
-            }
-            c.tsteps.push_back(t);
-        }
-        HB_TRY(up((void **)&c.d_tile_ptr, tptr.data(), tptr.size() * 4));
-        HB_TRY(up((void **)&c.d_tile_width, twid.data(), twid.size() * 4));
-        HB_TRY(up((void **)&c.d_tile_out, tout.data(), tout.size() * 4));
-        if (c.small_weights) HB_TRY(up((void **)&c.d_tile_e32, te32.data(), te32.size() * sizeof(uint2)));
-        else { HB_TRY(up((void **)&c.d_tile_eidx, teidx.data(), teidx.size() * 4)); HB_TRY(up((void **)&c.d_tile_ew, tew.data(), tew.size() * sizeof(F))); }
-    }
+    // the long codes' tiled steps and the rows-innermost CSR steps are built on first use (ensure_tiled / ensure_ilv): a context that only runs
+    // one of the two encodes does not pay for the other's plan
+    for (auto &p : plan) c.plan.push_back({p.g, p.in_off, p.out_off});
+    c.cwlen = cwlen; c.graph_gen = ctx->graph_gen;
     if (len_out) *len_out = c.len;
     return 0;
 }
@@ -2969,4 +3032,112 @@ int hobbit_sumcheck3(hobbit_ctx *ctx, const hobbit_F *d_v1, const hobbit_F *d_v2
     return launch_sumcheck3(ctx, cF(d_v1), cF(d_v2), cF(d_v3), n, *cF(prev_r), mF(h_cpoly), mF(h_r), mF(h_vr), mF(h_final));
 }
 
+// ---- Brakedown (src/Our_PC.cpp:197-236 commit_standard_brakedown, 432-520 open_brakedown_standard) --------------------------------------
+int hobbit_encode_interleaved(hobbit_ctx *ctx, const hobbit_F *d_src, hobbit_F *d_dst, long long n, uint32_t rows) {
+    if (n <= 0 || rows == 0 || (rows & (rows - 1)) || (size_t)2 * n * rows >= ((size_t)1 << 31))
+        return ctx->fail(HOBBIT_EINVAL, "encode_interleaved: rows must be a power of two and 2 n rows < 2^31");
+    if (ctx->code.n != n) return ctx->fail(HOBBIT_ESTATE, "encode_interleaved: graphs for this n are not finalized (hobbit_graph_finalize)");
+    HB_TRY(ensure_ilv(ctx));
+    return launch_encode_ilv(ctx, cF(d_src), mF(d_dst), rows);
+}
+struct hobbit_brakedown {
+    hobbit_ctx *ctx;
+    size_t N, B; uint32_t rows; long long len; int quirk;
+    F *d_mat; uint8_t *d_levels;           // 2B columns x rows, element (i, c) at c * rows + i | flat levels over the 2B column digests
+};
+int hobbit_brakedown_shape(size_t N, size_t *B, uint32_t *rows) {
+    const int n = ilog2_exact(N);
+    if (n < 16 || n > 29) return HOBBIT_EINVAL;       // fewer than 4 rows below; B > 2^20 (the longest code hobbit_graph_finalize builds) above
+    const size_t b = (size_t)1 << (n % 2 == 0 ? n / 2 + 6 : (n - 1) / 2 + 6);     // src/Our_PC.cpp:199-206
+    if (B) *B = b;
+    if (rows) *rows = (uint32_t)(N / b);
+    return 0;
+}
+void hobbit_brakedown_free(hobbit_brakedown *c) {
+    if (!c) return;
+    hipStreamSynchronize(c->ctx->stream);
+    if (c->d_mat) hipFree(c->d_mat);
+    if (c->d_levels) hipFree(c->d_levels);
+    delete c;
+}
+int hobbit_brakedown_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int left_left_quirk, hobbit_brakedown **out) {
+    *out = nullptr;
+    size_t B; uint32_t rows;
+    if (hobbit_brakedown_shape(N, &B, &rows)) return ctx->fail(HOBBIT_EINVAL, "brakedown_commit: N must be 2^n with 16 <= n <= 29");
+    if (ctx->code.n != (long long)B) return ctx->fail(HOBBIT_ESTATE, "brakedown_commit: graphs for n = B are not finalized (expander_init_store(B))");
+    HB_TRY(ensure_ilv(ctx));
+    const size_t W = 2 * B;
+    hobbit_brakedown *c = new hobbit_brakedown{ctx, N, B, rows, ctx->code.len, left_left_quirk ? 1 : 0, nullptr, nullptr};
+    if (hipMalloc((void **)&c->d_mat, W * rows * sizeof(F)) != hipSuccess || hipMalloc((void **)&c->d_levels, (2 * W - 1) * 32) != hipSuccess) {
+        hobbit_brakedown_free(c); return ctx->fail(HOBBIT_ENOMEM, "brakedown_commit: device allocation failed");
+    }
+    // row i of the message (poly[i B .. (i + 1) B)) becomes entry i of columns 0 .. B - 1; every row is then encoded in place (tensor[0][i])
+    int r = launch_transpose(ctx, cF(d_poly), 0, rows, (uint32_t)B, c->d_mat, 0, rows, 1);
+    if (!r) r = launch_encode_ilv(ctx, c->d_mat, c->d_mat, rows);
+    // MT_commit_Blake of every column -> level 0 (columns [len, 2B) are zero), then create_tree_blake over the 2B digests
+    if (!r) r = launch_brakedown_digests(ctx, c->d_mat, rows, (size_t)c->len, W - (size_t)c->len, c->quirk, c->d_levels);
+    if (!r) r = launch_merkle_levels(ctx, c->d_levels, W, c->quirk);
+    if (r) { hobbit_brakedown_free(c); return r; }
+    *out = c;
+    return 0;
+}
+int hobbit_brakedown_dims(const hobbit_brakedown *c, size_t *B, uint32_t *rows, long long *len) {
+    if (B) *B = c->B;
+    if (rows) *rows = c->rows;
+    if (len) *len = c->len;
+    return 0;
+}
+const hobbit_F *hobbit_brakedown_matrix_dev(const hobbit_brakedown *c) { return reinterpret_cast<const hobbit_F *>(c->d_mat); }
+const uint8_t *hobbit_brakedown_levels_dev(const hobbit_brakedown *c) { return c->d_levels; }
+int hobbit_brakedown_levels(hobbit_ctx *ctx, const hobbit_brakedown *c, uint8_t *h_levels) { return hobbit_memcpy_d2h(ctx, h_levels, c->d_levels, 32 * (4 * c->B - 1)); }
+int hobbit_brakedown_root(hobbit_ctx *ctx, const hobbit_brakedown *c, uint8_t *h_root) { return hobbit_memcpy_d2h(ctx, h_root, c->d_levels + 32 * (4 * c->B - 2), 32); }
+int hobbit_brakedown_tensor(hobbit_ctx *ctx, const hobbit_brakedown *c, size_t col_lo, size_t ncols, hobbit_F *h_out) {
+    if (col_lo > 2 * c->B || ncols > 2 * c->B - col_lo) return ctx->fail(HOBBIT_EINVAL, "brakedown_tensor: columns out of range");
+    if (!ncols) return 0;
+    F *tmp; HB_TRY(ctx->workspace(ncols * c->rows * sizeof(F), (void **)&tmp));
+    HB_TRY(launch_transpose(ctx, c->d_mat + col_lo * c->rows, 0, (uint32_t)ncols, c->rows, tmp, 0, ncols, 1));
+    return hobbit_memcpy_d2h(ctx, h_out, tmp, ncols * c->rows * sizeof(F));
+}
+int hobbit_brakedown_open(hobbit_ctx *ctx, const hobbit_brakedown *c, const hobbit_F *h_x, const hobbit_F *h_r, const uint64_t *h_I, size_t nq,
+                          hobbit_F *h_aggr_beta, hobbit_F *h_aggr_r, hobbit_F *h_reply, uint8_t *h_paths) {
+    const size_t W = 2 * c->B, rows = c->rows;
+    const int lr = ilog2_exact(rows), depth = ilog2_exact(W);
+    for (size_t q = 0; q < nq; q++) if (h_I[q] >= W) return ctx->fail(HOBBIT_EINVAL, "brakedown_open: query out of range");
+    StageScope sc(ctx);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_rows = al(rows * sizeof(F)), b_aggr = al(c->B * sizeof(F)), b_rep = al(nq * rows * sizeof(F)), b_I = al(nq * 4), b_pos = al(nq * 8);
+    uint8_t *ws;
+    HB_TRY(ctx->workspace(2 * b_rows + 2 * b_aggr + b_rep + b_I + b_pos + al(nq * depth * 32) + 256, (void **)&ws));
+    F *d_beta = reinterpret_cast<F *>(ws), *d_r = reinterpret_cast<F *>(ws + b_rows);
+    F *d_ab = reinterpret_cast<F *>(ws + 2 * b_rows), *d_ar = reinterpret_cast<F *>(ws + 2 * b_rows + b_aggr);
+    F *d_rep = reinterpret_cast<F *>(ws + 2 * b_rows + 2 * b_aggr);
+    uint32_t *d_I = reinterpret_cast<uint32_t *>(ws + 2 * b_rows + 2 * b_aggr + b_rep);
+    uint64_t *d_pos = reinterpret_cast<uint64_t *>(ws + 2 * b_rows + 2 * b_aggr + b_rep + b_I);
+    uint8_t *d_paths = ws + 2 * b_rows + 2 * b_aggr + b_rep + b_I + b_pos;
+    // beta1 = precompute_beta(x[0 .. log2 rows)); aggr_beta / aggr_r over the message columns j < B (src/Our_PC.cpp:447-457)
+    if (h_aggr_beta || h_aggr_r) {
+        HB_TRY(launch_eq_table(ctx, cF(h_x), lr, d_beta));
+        HB_TRY(h2d_staged(ctx, d_r, h_r, rows * sizeof(F)));
+        HB_TRY(launch_brakedown_aggr(ctx, c->d_mat, c->rows, c->B, d_beta, d_r, d_ab, d_ar));
+        if (h_aggr_beta) HB_TRY(d2h_staged(ctx, h_aggr_beta, d_ab, c->B * sizeof(F)));
+        if (h_aggr_r) HB_TRY(d2h_staged(ctx, h_aggr_r, d_ar, c->B * sizeof(F)));
+    }
+    if (nq && h_reply) {                                   // reply[q][i] = T[i][I[q]] (:462-468)
+        std::vector<uint32_t> I32(h_I, h_I + nq);
+        HB_TRY(h2d_staged(ctx, d_I, I32.data(), nq * 4));
+        HB_TRY(launch_brakedown_reply(ctx, c->d_mat, c->rows, d_I, nq, d_rep));
+        HB_TRY(d2h_staged(ctx, h_reply, d_rep, nq * rows * sizeof(F)));
+    }
+    if (nq && h_paths) {
+        // open_tree_blake(MT, {0, I[q]}, 0) (:471-475) takes leaf (I[q] / 4) * 0 + 0: every path is leaf 0's
+        std::vector<uint64_t> pos(nq);
+        for (size_t q = 0; q < nq; q++) pos[q] = (h_I[q] / 4) * 0 + 0;
+        HB_TRY(h2d_staged(ctx, d_pos, pos.data(), nq * 8));
+        HB_TRY(launch_merkle_paths(ctx, c->d_levels, W, d_pos, nq, depth, d_paths));
+        HB_TRY(d2h_staged(ctx, h_paths, d_paths, nq * depth * 32));
+    }
+    return sc.finish();
+}
+
 }  // extern "C"
+

@@ -89,6 +89,13 @@ struct TiledStep {
     uint32_t out_base;                      // index of this step's first entry in tile_out (64 per slice)
 };
 
+// Brakedown's matrix (hobbit_brakedown_commit): `rows` codewords stored rows-innermost, element (i, c) at c*rows + i, so that one edge of a step
+// gathers `rows` contiguous elements.  Every step of the code runs as one launch of k_enc_ilv over its outputs; step s keeps its outputs' in-edges
+// as CSR: output t owns records [rowptr[ptr_base + t], rowptr[ptr_base + t + 1]) (input index relative to in_off, weight).
+struct IlvStep { uint32_t in_off, out_off, out_len, ptr_base; };
+
+struct PlanStep { const HostGraph *g; long long in_off, out_off; };
+
 struct DeviceCode {         // finalized code for one message length n
     long long n = 0, len = 0;
     bool small_weights = true;               // all weights real and < 2^32
@@ -107,6 +114,15 @@ struct DeviceCode {         // finalized code for one message length n
     uint2 *d_tile_e32 = nullptr;             // {index in the tile, w32}   (small_weights)
     uint32_t *d_tile_eidx = nullptr; F *d_tile_ew = nullptr;   // general weights
     size_t tile_records = 0;
+    // Built on first use, not by hobbit_graph_finalize: the tiled steps (a long code through launch_encode: ensure_tiled) and the CSR steps of
+    // the rows-innermost encode (ensure_ilv).  `plan` lists the steps in order (C_0 .. C_{D-1}, D_{D-1} .. D_0) over the uploaded graphs of
+    // generation `graph_gen` (hobbit_ctx::graph_gen); `cwlen[d]`: length of the sub-codeword of depth d.
+    std::vector<PlanStep> plan; std::vector<long long> cwlen; uint64_t graph_gen = 0; bool tiled_built = false;
+    bool ilv_built = false;
+    std::vector<IlvStep> isteps;
+    uint32_t *d_ilv_ptr = nullptr;
+    uint2 *d_ilv_e32 = nullptr;              // {index relative to in_off, w32}   (small_weights)
+    uint32_t *d_ilv_eidx = nullptr; F *d_ilv_ew = nullptr;   // general weights
     // H^T in CSR (evaluate_parity_matrix), built on first use
     uint32_t *d_pm_rowptr = nullptr, *d_pm_idx = nullptr; F *d_pm_w = nullptr; size_t pm_rows = 0;
 };
@@ -163,6 +179,7 @@ struct hobbit_ctx {
     hobbit::F tw8_w8[2], tw8_w83[2]; int tw8_w4_plus_i[2] = {0, 0};
     // graphs
     std::map<std::pair<int, int>, hobbit::HostGraph> graphs;   // (dep, kind)
+    uint64_t graph_gen = 0;                                     // bumped by every hobbit_graph_upload / hobbit_graph_reset
     hobbit::DeviceCode code;
     // the reference's globals has_lookups / lookup_rand[0..1] (src/main.cpp:67,70), set through hobbit_set_lookups
     bool has_lookups = false; hobbit::F lookup_rand[2];

@@ -1291,6 +1291,7 @@ int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t l
     if (c.n != n) return ctx->fail(HOBBIT_ESTATE, "encode: graphs for this n are not finalized (hobbit_graph_finalize)");
     if (batch == 0) return 0;
     if ((size_t)c.len * 16 > 160 * 1024) {
+        HB_TRY(ensure_tiled(ctx));
         if (!c.tiled_depth) return ctx->fail(HOBBIT_ESTATE, "encode: long code without its tiled steps (hobbit_graph_finalize)");
         return launch_encode_long(ctx, src, ld_src, dst, ld_dst, batch, write_msg);
     }
@@ -3264,6 +3265,155 @@ int launch_copy(hobbit_ctx *ctx, void *d, const void *s, size_t bytes) {
         hipError_t e = hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, ctx->stream); return e == hipSuccess ? 0 : ctx->hip(e, "hipMemcpyAsync");
     }
     HB_LAUNCH(ctx, "k_copy16", k_copy16, dim3(grid_for(bytes / 16, 256, 8192)), dim3(256), 0, reinterpret_cast<uint4 *>(d), reinterpret_cast<const uint4 *>(s), bytes / 16);
+    return 0;
+}
+
+// ============================================================================================
+// Brakedown (hobbit_brakedown_commit / _open): `rows` codewords of one code stored rows-innermost, element (i, c) at mat[c * rows + i]
+// ============================================================================================
+// One step of the encode over all rows at once (hobbit_ctx.hpp IlvStep): lane (t, i) owns output t of the step in row i and walks t's in-edge
+// list; every edge gathers the `rows` contiguous inputs of its column, so a wave reads one 1 KB run per edge (rows >= 64) and the edge records
+// are wave-uniform (scalar loads).  No LDS window: each step reads what the step before it wrote.  Same exact arithmetic as k_encode (four
+// unreduced 96-bit sums per output and one fold; general weights: a canonical fmul / fadd per edge), so every codeword is bit-identical to
+// hobbit_encode_batch's.
+template <bool SMALLW>
+__global__ void __launch_bounds__(256)
+k_enc_ilv(F *__restrict__ mat, uint32_t rows, uint32_t lg_rows, IlvStep st, const uint32_t *__restrict__ ptr, const uint2 *__restrict__ e32,
+          const uint32_t *__restrict__ eidx, const F *__restrict__ ew) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;              // out_len * rows < 2^31 (hobbit_encode_interleaved)
+    const uint32_t t = g >> lg_rows, i = g & (rows - 1);
+    if (t >= st.out_len) return;
+    const F *in = mat + (size_t)st.in_off * rows + i;
+    uint32_t beg = ptr[st.ptr_base + t], end = ptr[st.ptr_base + t + 1];
+    if (rows >= 64) { beg = __builtin_amdgcn_readfirstlane(beg); end = __builtin_amdgcn_readfirstlane(end); }     // one output per wave
+    F out;
+    if (SMALLW) {
+        Acc96 rl = {0, 0}, rh = {0, 0}, il = {0, 0}, ih = {0, 0};
+        uint32_t e = beg;
+        for (; e + 4 <= end; e += 4) {
+            uint2 r[4]; uint4 x[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) r[u] = e32[e + u];
+#pragma unroll
+            for (int u = 0; u < 4; u++) x[u] = *reinterpret_cast<const uint4 *>(in + (size_t)r[u].x * rows);
+#pragma unroll
+            for (int u = 0; u < 4; u++) acc96_mad4(rl, rh, il, ih, r[u].y, x[u]);
+        }
+        for (; e < end; e++) {
+            const uint2 r = e32[e];
+            acc96_mad4(rl, rh, il, ih, r.y, *reinterpret_cast<const uint4 *>(in + (size_t)r.x * rows));
+        }
+        out = fmake(acc_fold(rl, rh), acc_fold(il, ih));
+    } else {
+        out = fmake(0);
+        for (uint32_t e = beg; e < end; e++) out = fadd(out, fmul(ldF(in + (size_t)eidx[e] * rows), ldF(ew + e)));
+    }
+    stF(mat + (size_t)(st.out_off + t) * rows + i, out);
+}
+int launch_encode_ilv(hobbit_ctx *ctx, const F *src, F *dst, uint32_t rows) {
+    const DeviceCode &c = ctx->code;
+    uint32_t lg = 0; while ((1u << lg) < rows) lg++;
+    if (src != dst) HB_TRY(launch_copy(ctx, dst, src, (size_t)c.n * rows * sizeof(F)));
+    for (const IlvStep &st : c.isteps) {
+        const size_t threads = (size_t)st.out_len * rows;
+        if (c.small_weights)
+            HB_LAUNCH(ctx, "k_enc_ilv", k_enc_ilv<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, dst, rows, lg, st, c.d_ilv_ptr, c.d_ilv_e32,
+                      c.d_ilv_eidx, c.d_ilv_ew);
+        else
+            HB_LAUNCH(ctx, "k_enc_ilv_fullw", k_enc_ilv<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, dst, rows, lg, st, c.d_ilv_ptr,
+                      c.d_ilv_e32, c.d_ilv_eidx, c.d_ilv_ew);
+    }
+    return launch_zero(ctx, dst + (size_t)c.len * rows, (size_t)(2 * c.n - c.len) * rows * sizeof(F));    // the codewords' zero tail
+}
+
+// Column digests of the matrix (MT_commit_Blake over the `rows` entries of column c, src/merkle_tree.cpp:193-221): leaf l = H(rows 4l..4l+3),
+// which is 64 contiguous bytes here.  quirk (create_tree_blake's parent H(left | left), src/merkle_tree.cpp:275-280): the digest is leaf 0
+// re-hashed log2(rows / 4) times, 1 + log2(rows / 4) compressions.  Otherwise the full tree over the rows / 4 leaves (rows <= 512), folded
+// bottom-up through a stack of at most 8 pending nodes.  The codewords' zero tail makes the last columns all zero: the launcher hashes the first
+// of them here and copies its digest to the rest (k_bd_fill).
+__global__ void __launch_bounds__(256)
+k_bd_digest(const F *__restrict__ mat, uint32_t rows, size_t ncols, int quirk, uint8_t *__restrict__ out) {
+    for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < ncols; c += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t *col = reinterpret_cast<const uint32_t *>(mat + c * rows);
+        const uint32_t leaves = rows / 4;
+        uint32_t m[16], h[8];
+        if (quirk) {
+#pragma unroll
+            for (int q = 0; q < 16; q++) m[q] = col[q];
+            blake3_compress64(m, h);
+            for (uint32_t n = leaves; n > 1; n >>= 1) {
+#pragma unroll
+                for (int q = 0; q < 8; q++) { m[q] = h[q]; m[8 + q] = h[q]; }
+                blake3_compress64(m, h);
+            }
+            store8w(out + 32 * c, h);
+            continue;
+        }
+        uint32_t stk[8][8]; int sp = 0;
+        for (uint32_t l = 0; l < leaves; l++) {
+            for (int q = 0; q < 16; q++) m[q] = col[16 * l + q];
+            blake3_compress64(m, h);
+            for (uint32_t k = l; k & 1; k >>= 1) {                // the pending left sibling of every completed subtree
+                sp--;
+                for (int q = 0; q < 8; q++) { m[q] = stk[sp][q]; m[8 + q] = h[q]; }
+                blake3_compress64(m, h);
+            }
+            for (int q = 0; q < 8; q++) stk[sp][q] = h[q];
+            sp++;
+        }
+        store8w(out + 32 * c, stk[0]);
+    }
+}
+__global__ void k_bd_fill(uint8_t *__restrict__ out, size_t from, size_t n) {
+    const uint4 *s = reinterpret_cast<const uint4 *>(out + 32 * (from - 1));
+    const uint4 a = s[0], b = s[1];
+    for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < n; c += (size_t)gridDim.x * blockDim.x) {
+        uint4 *d = reinterpret_cast<uint4 *>(out + 32 * (from + c));
+        d[0] = a; d[1] = b;
+    }
+}
+// digests of columns [0, ncols) into out[0 .. ncols + nz): the last nz columns are zero, so their digest is computed once (column ncols) and copied
+int launch_brakedown_digests(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t ncols, size_t nz, int quirk, uint8_t *out) {
+    const size_t comp = ncols + (nz ? 1 : 0);
+    HB_LAUNCH(ctx, "k_bd_digest", k_bd_digest, dim3(grid_for(comp, 256, 8192)), dim3(256), 0, mat, rows, comp, quirk, out);
+    if (nz > 1) HB_LAUNCH(ctx, "k_bd_fill", k_bd_fill, dim3(grid_for(nz - 1, 256)), dim3(256), 0, out, comp, nz - 1);
+    return 0;
+}
+
+// aggr_beta[j] = sum_i beta[i] T[i][j], aggr_r[j] = sum_i r[i] T[i][j] for j < B (src/Our_PC.cpp:452-457), both from ONE read of the message
+// columns: G = min(rows, 64) lanes per column, each summing rows / G entries, then a butterfly over the G lanes.
+__global__ void __launch_bounds__(256)
+k_bd_aggr(const F *__restrict__ mat, uint32_t rows, uint32_t lg_g, size_t B, const F *__restrict__ beta, const F *__restrict__ r, F *__restrict__ ab,
+          F *__restrict__ ar) {
+    const uint32_t G = 1u << lg_g;
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x, j = g >> lg_g;
+    const uint32_t sub = (uint32_t)g & (G - 1);
+    F sb = fmake(0), sr = fmake(0);
+    if (j < B)
+        for (uint32_t i = sub; i < rows; i += G) {
+            const F x = ldF(mat + j * rows + i);
+            sb = fadd(sb, fmul(ldF(beta + i), x)); sr = fadd(sr, fmul(ldF(r + i), x));
+        }
+    for (uint32_t m = 1; m < G; m <<= 1) { sb = fadd(sb, shfl_xor_F(sb, (int)m)); sr = fadd(sr, shfl_xor_F(sr, (int)m)); }
+    if (j < B && sub == 0) { stF(ab + j, sb); stF(ar + j, sr); }
+}
+int launch_brakedown_aggr(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t B, const F *beta, const F *r, F *aggr_beta, F *aggr_r) {
+    uint32_t lg = 0; while ((1u << lg) < rows && lg < 6) lg++;
+    const size_t threads = B << lg;
+    HB_LAUNCH(ctx, "k_bd_aggr", k_bd_aggr, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, mat, rows, lg, B, beta, r, aggr_beta, aggr_r);
+    return 0;
+}
+// reply[q][i] = T[i][I[q]] (src/Our_PC.cpp:462-468): one contiguous run of `rows` elements per query
+__global__ void __launch_bounds__(256)
+k_bd_reply(const F *__restrict__ mat, uint32_t rows, const uint32_t *__restrict__ I, size_t nq, F *__restrict__ reply) {
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (g >= nq * rows) return;
+    const size_t q = g / rows, i = g % rows;
+    stF(reply + g, ldF(mat + (size_t)I[q] * rows + i));
+}
+int launch_brakedown_reply(hobbit_ctx *ctx, const F *mat, uint32_t rows, const uint32_t *d_I, size_t nq, F *reply) {
+    if (!nq) return 0;
+    HB_LAUNCH(ctx, "k_bd_reply", k_bd_reply, dim3((unsigned)((nq * rows + 255) / 256)), dim3(256), 0, mat, rows, d_I, nq, reply);
     return 0;
 }
 

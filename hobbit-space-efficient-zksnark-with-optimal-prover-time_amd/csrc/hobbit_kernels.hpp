@@ -3,6 +3,13 @@
 #include "hobbit_ctx.hpp"
 
 namespace hobbit {
+// plans built on first use (hobbit_capi.hip): the tiled steps of a long code, the CSR steps of the rows-innermost encode
+int ensure_tiled(hobbit_ctx *ctx);
+int ensure_ilv(hobbit_ctx *ctx);
+int launch_encode_ilv(hobbit_ctx *ctx, const F *src, F *dst, uint32_t rows);
+int launch_brakedown_digests(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t ncols, size_t nz, int quirk, uint8_t *out);
+int launch_brakedown_aggr(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t B, const F *beta, const F *r, F *aggr_beta, F *aggr_r);
+int launch_brakedown_reply(hobbit_ctx *ctx, const F *mat, uint32_t rows, const uint32_t *d_I, size_t nq, F *reply);
 int launch_f_binop(hobbit_ctx *ctx, int op, const F *a, const F *b, F *o, size_t n);
 int launch_fill_splitmix(hobbit_ctx *ctx, F *o, size_t n, uint64_t seed);
 int launch_u64_bias_fold(hobbit_ctx *ctx, uint64_t *w, size_t n, uint64_t bias, int fold);

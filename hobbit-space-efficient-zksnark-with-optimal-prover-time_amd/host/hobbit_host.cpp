@@ -17,6 +17,7 @@ graph _C[100], D[100];
 
 static hobbit_ctx *g_ctx = nullptr;
 static hobbit_commitment *g_commit = nullptr;
+static hobbit_brakedown *g_bd = nullptr;                            // the last commit_standard_brakedown's matrix and tree
 static int g_commit_K = 0, g_commit_trs = 0; static size_t g_commit_cols = 0;
 static void *g_poly_dev = nullptr; static size_t g_poly_n = 0;      // device copy of the committed polynomial, kept for open_standard
 static uint8_t g_commit_root[32];
@@ -69,6 +70,7 @@ hobbit_ctx *hobbit_host_ctx() {
 void hobbit_host_shutdown() {
     if (g_ctx) free_prev();
     if (g_commit) { hobbit_commitment_free(g_commit); g_commit = nullptr; }
+    if (g_bd) { hobbit_brakedown_free(g_bd); g_bd = nullptr; }
     if (g_poly_dev) { hobbit_free(g_ctx, g_poly_dev); g_poly_dev = nullptr; g_poly_n = 0; }
     if (g_ctx) { hobbit_ctx_destroy(g_ctx); g_ctx = nullptr; }
 }
@@ -1177,11 +1179,79 @@ bool hobbit_host_deserialize_rs_open(const uint8_t *buf, size_t n, hobbit_host_e
            sec.complete({T_NCOLS, T_COLS, T_ROWS, T_REPLY, T_PATHS, T_QPOLY, T_R, T_VR, T_FIN, T_RV0, T_CFROOT, T_RX, T_SPF}, nsec);
 }
 
-// ---- driver (src/Our_PC.cpp:757-826, option 4, commit phase) ---------------------------------------
+// ---- Brakedown baseline (src/Our_PC.cpp:197-236, 432-520) ----------------------------------------
+static hobbit_host_brakedown_transcript g_bd_open;
+hobbit_host_brakedown_transcript &hobbit_host_last_brakedown() { return g_bd_open; }
+void commit_standard_brakedown(vector<F> &poly, _hash &comm, vector<vector<_hash>> &MT_hashes) {
+    (void)comm;                                                     // the reference never writes it either
+    const size_t N = poly.size(); size_t B = 0; uint32_t rows = 0;
+    if (hobbit_brakedown_shape(N, &B, &rows) != 0) { printf("Error: Brakedown needs N = 2^n with 16 <= n <= 29\n"); exit(-1); }
+    expander_init_store((long long)B);                              // (:199-206: the graphs of the row code, drawn here)
+    if (g_bd) { hobbit_brakedown_free(g_bd); g_bd = nullptr; }
+    DevBuf d(poly.data(), N * sizeof(F));
+    HCHK(hobbit_brakedown_commit(g_ctx, (const hobbit_F *)d.p, N, 1, &g_bd));
+    // MT_hashes: level 0 = the 2B column digests (MT_commit_Blake of every column), then create_tree_blake (:222-235)
+    const size_t W = 2 * B, levels = (size_t)log2((double)W) + 1;
+    vector<_hash> flat(2 * W - 1);
+    HCHK(hobbit_brakedown_levels(g_ctx, g_bd, flat.data()->arr));
+    MT_hashes.assign(levels, vector<_hash>());
+    for (size_t l = 0, off = 0, sz = W; l < levels; l++, off += sz, sz /= 2) MT_hashes[l].assign(flat.begin() + off, flat.begin() + off + sz);
+}
+void open_brakedown_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>> &Commitment_MT) {
+    if (!g_bd) { printf("Error: open_brakedown_standard without commit_standard_brakedown\n"); exit(-1); }
+    auto t1 = std::chrono::steady_clock::now();                    // (the reference times with clock(): CPU time of its one core)
+    size_t B = 0; uint32_t rows = 0; long long len = 0;
+    hobbit_brakedown_dims(g_bd, &B, &rows, &len);
+    if (poly.size() != B * rows) { printf("Error: open_brakedown_standard on a polynomial of another size\n"); exit(-1); }
+    const size_t W = 2 * B; const int lr = (int)log2((double)rows), depth = (int)log2((double)W);
+    hobbit_host_brakedown_transcript &t = g_bd_open;
+    t.r.clear();
+    for (uint32_t i = 0; i < rows; i++) t.r.push_back(F(random()));                    // (:449-451)
+    const int queries = 2900;
+    t.I.assign(queries, 0);
+    for (int i = 0; i < queries; i++) t.I[i] = (uint64_t)(rand() % W);               // (:458-461)
+    t.aggr_beta.assign(B, F(0)); t.aggr_r.assign(B, F(0)); t.reply.assign((size_t)queries * rows, F(0)); t.paths.assign((size_t)queries * depth * 32, 0);
+    vector<F> xs(x.begin(), x.begin() + lr);
+    HCHK(hobbit_brakedown_open(g_ctx, g_bd, hF(xs.data()), hF(t.r.data()), t.I.data(), queries, hF(t.aggr_beta.data()), hF(t.aggr_r.data()),
+                               hF(t.reply.data()), t.paths.data()));
+    const double pt = std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t1).count();
+    // verifier side (:487-514): only its proof-size accounting.  `double ps;` is uninitialised there (:508); it starts from 0 here.  The
+    // reference's re-hash of the replies and re-encode of the aggregates feed nothing, and its `j < reply.size()` loops read out of bounds.
+    t1 = std::chrono::steady_clock::now();
+    double ps = 0.0;
+    vector<size_t> pos(t.I.begin(), t.I.end());
+    path_ps(Commitment_MT.empty() ? W : Commitment_MT[0].size(), depth, pos, ps);     // verify_claim_opt_blake(.., I[i], ..) (:509-511)
+    ps += (double)((size_t)queries * rows * sizeof(F)) / 1024.0;                        // (:515)
+    ps += (double)((2 * B * sizeof(F)) / 1024);                                         // (:516, integer division as built)
+    const double vt = std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t1).count();
+    t.ps = ps; t.pt = pt; t.vt = vt;
+    printf("PC Open: pt = %lf, ps = %lf KB, vt = %lf sec\n", pt, ps, vt);
+}
+
+// ---- driver (src/Our_PC.cpp:757-826: options 4 and 1, commit + open; option 3, the Brakedown baseline) ---------------
 void test_PC(size_t N, int option, int K) {
-    if (option != 4 && option != 1) { printf("Error: options 2 and 3 are the Orion / Brakedown comparison baselines, not built on the device path\n"); exit(-1); }
+    if (option != 4 && option != 1 && option != 3) {
+        printf("Error: option %d is a comparison baseline not built on the device path (2: Orion, 5: Braking base, 6 and others: WHIR)\n", option); exit(-1);
+    }
     vector<F> poly = generate_randomness((int)N);
     _hash comm; vector<vector<_hash>> MT_hashes;
+    if (option == 3) {                                              // (:794-805; K is unused)
+        (void)K;
+        auto start = std::chrono::steady_clock::now();
+        commit_standard_brakedown(poly, comm, MT_hashes);
+        auto end = std::chrono::steady_clock::now();
+        double elapsed_seconds = std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+        std::cout << "Commit time: " << elapsed_seconds << " seconds" << std::endl;
+        printf("root ");
+        for (int i = 0; i < 32; i++) printf("%02x", MT_hashes.back()[0].arr[i]);
+        printf("\n");
+        start = std::chrono::steady_clock::now();
+        open_brakedown_standard(poly, generate_randomness((int)log2((double)N)), MT_hashes);
+        end = std::chrono::steady_clock::now();
+        elapsed_seconds += std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+        std::cout << "Total time: " << elapsed_seconds << " seconds" << std::endl;
+        return;
+    }
     if (option == 1) { linear_time = false; tensor_row_size = 128; }                     // (:764-766: RS x RS)
     else {
         linear_time = true;

@@ -147,7 +147,16 @@ vector<_hash> open_tree_blake(vector<vector<_hash>> &MT_hashes, vector<size_t> c
 void compute_tensorcode(vector<F> &message, vector<vector<F>> &tensor);
 /* src/Our_PC.hpp:11-15 */
 void commit_standard(vector<F> &poly, _hash &comm, vector<vector<_hash>> &MT_hashes, vector<vector<vector<F>>> &_tensor, int K);
-void test_PC(size_t N, int option, int K);
+void test_PC(size_t N, int option, int K);                                          /* options 4, 1 and 3 (Brakedown) */
+/* src/Our_PC.hpp: the Brakedown comparison baseline (src/Our_PC.cpp:197-236, 432-520).  commit_standard_brakedown draws the row code's graphs
+ * (expander_init_store(B)) and keeps the encoded matrix on the device; open_brakedown_standard draws r (rows x random()) and the 2900 columns
+ * (rand() % 2B), opens, and prints the reference's "PC Open: pt = .., ps = .. KB, vt = .. sec" line. */
+void commit_standard_brakedown(vector<F> &poly, _hash &comm, vector<vector<_hash>> &MT_hashes);
+void open_brakedown_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>> &Commitment_MT);
+/* the messages of the last open_brakedown_standard (the reference returns none); ps as printed, from 0 (the reference's `double ps;` is
+ * uninitialised, src/Our_PC.cpp:508) */
+struct hobbit_host_brakedown_transcript { vector<F> r, aggr_beta, aggr_r, reply; vector<uint64_t> I; vector<uint8_t> paths; double ps = 0, pt = 0, vt = 0; };
+hobbit_host_brakedown_transcript &hobbit_host_last_brakedown();
 void open_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>> &Commitment_MT, vector<vector<vector<F>>> &_tensor, int K, double &vt, double &ps);
 /* The reference's open_standard returns nothing but vt / ps (it never serialises its proof); the messages the device prover
  * produced for the last open_standard call are kept here.  Layouts as hobbit_open_out / hobbit_shockwave_out (include/hobbit_hip.h). */

@@ -39,6 +39,7 @@ typedef struct hobbit_ctx hobbit_ctx;
 typedef struct hobbit_commitment hobbit_commitment;
 typedef struct hobbit_elastic hobbit_elastic;
 typedef struct hobbit_elastic_open hobbit_elastic_open;
+typedef struct hobbit_brakedown hobbit_brakedown;
 typedef struct { uint64_t re, im; } hobbit_F;
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
@@ -159,6 +160,36 @@ int hobbit_commitment_gather(hobbit_ctx *ctx, const hobbit_commitment *c, const 
 int hobbit_commitment_path(hobbit_ctx *ctx, const hobbit_commitment *c, size_t col, size_t row, uint8_t *h_path);
 int hobbit_commitment_paths(hobbit_ctx *ctx, const hobbit_commitment *c, const uint32_t *h_cols, const uint32_t *h_rows, size_t nq,
                             uint8_t *h_paths);
+
+/* ---- Brakedown baseline (src/Our_PC.cpp:197-236 commit_standard_brakedown, 432-520 open_brakedown_standard) -- */
+/* encode_monolithic of `rows` messages at once, stored ROWS-INNERMOST: element (i, c) of message / codeword i at d[c*rows + i].
+ * d_src holds n x rows F, d_dst receives 2n x rows F (the codewords, then zeros from column n+L+R on); d_src may equal d_dst (in place),
+ * other overlaps are not allowed.  rows a power of two, 2*n*rows < 2^31; graphs for n finalized.  Bit-identical to hobbit_encode_batch. */
+int hobbit_encode_interleaved(hobbit_ctx *ctx, const hobbit_F *d_src, hobbit_F *d_dst, long long n, uint32_t rows);
+/* Brakedown's shape for N = 2^n, 16 <= n <= 29 (else HOBBIT_EINVAL): row length B = 2^(n/2+6) (n even) or 2^((n-1)/2+6) (n odd),
+ * rows = N/B (16 ... 512). */
+int hobbit_brakedown_shape(size_t N, size_t *B, uint32_t *rows);
+/* commit_standard_brakedown: d_poly (N F, device) cut into rows of B, each row encoded (graphs for n = B finalized, i.e. the host's
+ * expander_init_store(B) ran), every one of the 2B columns committed with MT_commit_Blake (its digest is level 0), then create_tree_blake
+ * over the 2B digests.  left_left_quirk=1 reproduces the reference: parents are H(left | left) in both trees, so a column's digest
+ * depends on its rows 0..3 only and the root on column 0 only; 0 builds conventional H(left | right) trees.  The object owns the
+ * matrix (2B x rows, rows-innermost) and the (4B-1) x 32-byte levels.  Stream semantics as hobbit_commit_standard. */
+int hobbit_brakedown_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int left_left_quirk, hobbit_brakedown **out);
+void hobbit_brakedown_free(hobbit_brakedown *c);
+int hobbit_brakedown_dims(const hobbit_brakedown *c, size_t *B, uint32_t *rows, long long *len);   /* len: codeword length n+L+R */
+const hobbit_F *hobbit_brakedown_matrix_dev(const hobbit_brakedown *c);      /* device, 2B x rows, element (i, c) at c*rows + i */
+const uint8_t *hobbit_brakedown_levels_dev(const hobbit_brakedown *c);       /* device, flat levels: 2B digests ... root */
+int hobbit_brakedown_levels(hobbit_ctx *ctx, const hobbit_brakedown *c, uint8_t *h_levels);        /* (4B-1)*32 B */
+int hobbit_brakedown_root(hobbit_ctx *ctx, const hobbit_brakedown *c, uint8_t *h_root);
+/* the reference's tensor[0][i][c] for every row i and c in [col_lo, col_lo+ncols): h_out[i*ncols + (c-col_lo)] */
+int hobbit_brakedown_tensor(hobbit_ctx *ctx, const hobbit_brakedown *c, size_t col_lo, size_t ncols, hobbit_F *h_out);
+/* open_brakedown_standard, prover side.  The host passes the draws: h_x (log2(rows) F: the first coordinates of the point), h_r (rows F:
+ * the random() draws), h_I (nq columns < 2B: the rand() % 2B draws).  Outputs (any may be NULL to skip it):
+ *   h_aggr_beta / h_aggr_r (B F): sum_i beta1[i] T[i][j] and sum_i r[i] T[i][j], beta1 = precompute_beta(h_x);
+ *   h_reply (nq x rows F): reply[q][i] = T[i][I[q]];
+ *   h_paths (nq x log2(2B) x 32 B): open_tree_blake(MT, {0, I[q]}, 0), i.e. the path of leaf (I[q]/4)*0 + 0 = 0 for every query, as built. */
+int hobbit_brakedown_open(hobbit_ctx *ctx, const hobbit_brakedown *c, const hobbit_F *h_x, const hobbit_F *h_r, const uint64_t *h_I, size_t nq,
+                          hobbit_F *h_aggr_beta, hobbit_F *h_aggr_r, hobbit_F *h_reply, uint8_t *h_paths);
 
 /* ---- Elastic_PC streaming commit (src/Elastic_PC.cpp:174-285 commit) ------------------------- */
 /* The stream stays with the host (read_stream_PC); each B-element chunk is pushed as a device
