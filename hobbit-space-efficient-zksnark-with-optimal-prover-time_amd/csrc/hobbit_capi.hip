@@ -134,7 +134,6 @@ static int fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_l
 
 static void free_code(DeviceCode &c) {
     for (FatStep *f : {&c.fatA, &c.fatC1, &c.fatD}) { if (f->d_wt) hipFree(f->d_wt); if (f->d_ot) hipFree(f->d_ot); if (f->d_oidx) hipFree(f->d_oidx); if (f->d_w) hipFree(f->d_w); }
-    { MidCode &m = c.mid; if (m.d_wt) hipFree(m.d_wt); if (m.d_ot) hipFree(m.d_ot); if (m.d_oidx) hipFree(m.d_oidx); if (m.d_w) hipFree(m.d_w); }
     if (c.d_steps) hipFree(c.d_steps);
     if (c.d_slice_ptr) hipFree(c.d_slice_ptr);
     if (c.d_slice_width) hipFree(c.d_slice_width);
@@ -427,20 +426,42 @@ int hobbit_graph_upload(hobbit_ctx *ctx, int dep, int kind, long long L, long lo
     ctx->graph_gen++;
     return 0;
 }
-// fat form of one step (hobbit_ctx.hpp FatStep); returns false (and leaves f.ok false) when a degree exceeds the kernel's caps
-static bool build_fat_step(const HostGraph &g, uint32_t in_off, uint32_t out_off, uint32_t nout, uint32_t ncons, const uint32_t *cap, FatStep &f) {
-    const size_t R = (size_t)g.R, lanes = (size_t)ncons * 64;
-    if (R > nout * lanes || (size_t)g.L * 16 > 65536) return false;
-    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> rows(R);
+}  // extern "C"
+namespace hobbit {
+// in-edges of every output of a step, in input order: (input index, weight)
+using InEdges = std::vector<std::vector<std::pair<uint32_t, F>>>;
+static InEdges in_edges(const HostGraph &g) {
+    InEdges rows((size_t)g.R);
     for (long long i = 0; i < g.L; i++)
-        for (int j = 0; j < g.degree; j++) rows[g.nbr[i * g.degree + j]].push_back({(uint32_t)i, (uint32_t)g.w[i * g.degree + j].re});
-    std::vector<uint32_t> order(R);
-    for (size_t t = 0; t < R; t++) order[t] = (uint32_t)t;
+        for (int j = 0; j < g.degree; j++) rows[g.nbr[i * g.degree + j]].push_back({(uint32_t)i, g.w[i * g.degree + j]});
+    return rows;
+}
+// the outputs in order of in-degree, heaviest first (stable: equal in-degrees keep output order)
+static std::vector<uint32_t> by_in_degree(const InEdges &rows) {
+    std::vector<uint32_t> order(rows.size());
+    for (size_t t = 0; t < order.size(); t++) order[t] = (uint32_t)t;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].size() > rows[b].size(); });
+    return order;
+}
+// a host table into a fresh device allocation (16 bytes for an empty one)
+template <class T>
+static int upload(hobbit_ctx *ctx, T **d, const std::vector<T> &h) {
+    const size_t bytes = h.size() * sizeof(T);
+    if (hipMalloc((void **)d, bytes ? bytes : 16) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "graph alloc failed");
+    if (bytes) HB_CHECK(ctx, hipMemcpy(*d, h.data(), bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+// fat form of one step (hobbit_ctx.hpp FatStep): `nout` outputs per lane of `ncons` consumer waves, cap[j] register slots at position j.
+// Leaves f.ok false when the step's degrees exceed the caps.
+static int build_fat_step(hobbit_ctx *ctx, const PlanStep &p, uint32_t nout, uint32_t ncons, const uint32_t *cap, FatStep &f) {
+    const HostGraph &g = *p.g;
+    const size_t R = (size_t)g.R, lanes = (size_t)ncons * 64;
+    if (R > nout * lanes || (size_t)g.L * 16 > 65536) return 0;
+    const InEdges rows = in_edges(g);
+    const std::vector<uint32_t> order = by_in_degree(rows);
     uint32_t base[4] = {0, 0, 0, 0}, tot = 0;
     for (uint32_t j = 0; j < nout; j++) { base[j] = tot; tot += cap[j]; }
     std::vector<uint32_t> wt((size_t)tot * lanes, 0), ot((size_t)(tot / 2) * lanes, 0), oidx((size_t)nout * lanes, 0xFFFFFFFFu), wid((size_t)ncons * nout, 0);
-    const char *bs_env = getenv("HOBBIT_ENC_BANK_SCHED"); const bool bank_sched = !(bs_env && bs_env[0] == '0');
     // which output each (position, lane) owns, and the widths
     std::vector<int64_t> own((size_t)nout * lanes, -1);
     for (uint32_t j = 0; j < nout; j++)
@@ -448,7 +469,7 @@ static bool build_fat_step(const HostGraph &g, uint32_t in_off, uint32_t out_off
             const size_t i = (j % 2 == 0) ? (size_t)j * lanes + l : (size_t)(j + 1) * lanes - 1 - l;      // serpentine: heavy with light
             if (i >= R) continue;
             const auto &row = rows[order[i]];
-            if (row.size() > cap[j]) return false;
+            if (row.size() > cap[j]) return 0;
             own[(size_t)j * lanes + l] = order[i]; oidx[(size_t)j * lanes + l] = order[i];
             uint32_t &w = wid[(l / 64) * nout + j];
             w = std::max(w, (uint32_t)((row.size() + 3) / 4 * 4));
@@ -460,25 +481,21 @@ static bool build_fat_step(const HostGraph &g, uint32_t in_off, uint32_t out_off
     // is shorter than the wave's width, else takes any edge; padding slots point at a quad nobody else uses.
     static const int GROUPS[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27}, {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
                                       {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59}, {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
-    auto put = [&](uint32_t j, size_t l, uint32_t k, uint32_t idx, uint32_t w32) {
+    auto put = [&](uint32_t j, size_t l, uint32_t k, uint32_t idx, F w) {
         const size_t slot = base[j] + k;
-        wt[slot * lanes + l] = w32;
+        wt[slot * lanes + l] = (uint32_t)w.re;
         ot[(slot / 2) * lanes + l] |= (idx * 16u) << (16 * (slot & 1));
     };
     for (uint32_t j = 0; j < nout; j++)
         for (uint32_t wv = 0; wv < ncons; wv++) {
             const uint32_t W = wid[wv * nout + j];
             for (int gi = 0; gi < 4; gi++) {
-                std::vector<std::pair<uint32_t, uint32_t>> rem[16]; int slack[16];
+                std::vector<std::pair<uint32_t, F>> rem[16]; int slack[16];
                 for (int q = 0; q < 16; q++) {
                     const size_t l = (size_t)wv * 64 + GROUPS[gi][q];
                     const int64_t t = own[(size_t)j * lanes + l];
                     if (t >= 0) rem[q] = rows[(size_t)t];
                     slack[q] = (int)W - (int)rem[q].size();
-                }
-                if (!bank_sched) {                                                                // graph order (A/B)
-                    for (int q = 0; q < 16; q++) { for (uint32_t k = 0; k < rem[q].size(); k++) put(j, (size_t)wv * 64 + GROUPS[gi][q], k, rem[q][k].first, rem[q][k].second); rem[q].clear(); }
-                    continue;
                 }
                 for (uint32_t k = 0; k < W; k++) {
                     int lane_of[16], quad_of[16]; for (int q = 0; q < 16; q++) { lane_of[q] = -1; quad_of[q] = -1; }
@@ -512,72 +529,16 @@ static bool build_fat_step(const HostGraph &g, uint32_t in_off, uint32_t out_off
                         if ((uint32_t)r < (uint32_t)g.L) ot[(slot / 2) * lanes + l] |= ((uint32_t)r * 16u) << (16 * (slot & 1));
                     }
                 }
-                for (int q = 0; q < 16; q++) if (!rem[q].empty()) return false;                  // (cannot happen: every lane places one edge per slot once its slack is spent)
+                for (int q = 0; q < 16; q++) if (!rem[q].empty()) return 0;                      // (cannot happen: every lane places one edge per slot once its slack is spent)
             }
         }
-    f.nout = nout; f.ncons = ncons; for (uint32_t j = 0; j < 3; j++) f.cap[j] = j < nout ? cap[j] : 0;
-    f.in_off = in_off; f.in_len = (uint32_t)g.L; f.out_off = out_off; f.out_len = (uint32_t)R;
-    f.slots_used = 0; for (uint32_t v : wid) f.slots_used += v;
-    auto up = [&](uint32_t **d, const std::vector<uint32_t> &h) { return hipMalloc((void **)d, h.size() * 4) == hipSuccess && hipMemcpy(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice) == hipSuccess; };
-    f.ok = up(&f.d_wt, wt) && up(&f.d_ot, ot) && up(&f.d_oidx, oidx) && up(&f.d_w, wid);
-    return f.ok;
-}
-// the narrow middle steps in lane-group form (hobbit_ctx.hpp MidCode); false when the shapes do not fit what k_enc_mid was compiled for
-struct MidPlanStep { const HostGraph *g; long long in_off, out_off; };
-static bool build_mid(const std::vector<MidPlanStep> &steps, uint32_t win_off, uint32_t in_len, MidCode &m) {
-    const uint32_t ns = (uint32_t)steps.size();
-    if (ns == 0 || ns > MID_MAX_STEPS) return false;
-    const size_t lanes = (size_t)MID_WAVES * 64;
-    uint32_t base[MID_MAX_STEPS + 1] = {0};
-    for (uint32_t s = 0; s < ns; s++) base[s + 1] = base[s] + MID_CAP[s];
-    const uint32_t tot = base[ns];
-    std::vector<uint32_t> wt((size_t)tot * lanes, 0), ot((size_t)(tot / 2) * lanes, 0), oidx((size_t)ns * lanes, 0xFFFFFFFFu), wid((size_t)MID_WAVES * ns, 0);
-    uint32_t win_end = 0;
-    for (uint32_t s = 0; s < ns; s++) {
-        const HostGraph &g = *steps[s].g; const size_t R = (size_t)g.R;
-        if (steps[s].in_off < win_off || (steps[s].in_off - win_off + g.L) * 16 > 65536) return false;
-        std::vector<std::vector<std::pair<uint32_t, uint32_t>>> rows(R);
-        size_t maxdeg = 0;
-        for (long long i = 0; i < g.L; i++)
-            for (int j = 0; j < g.degree; j++) rows[g.nbr[i * g.degree + j]].push_back({(uint32_t)i, (uint32_t)g.w[i * g.degree + j].re});
-        for (auto &r : rows) maxdeg = std::max(maxdeg, r.size());
-        // lanes per output: as many as the workgroup has for this step, but no more than leaves every lane at least ~2 records of the widest row; the lanes of an
-        // output sit in one wave
-        uint32_t lg = 0;
-        while (lg < 5 && (R << (lg + 1)) <= lanes && ((size_t)2 << (lg + 1)) <= maxdeg) lg++;
-        while ((maxdeg + ((size_t)1 << lg) - 1) >> lg > MID_CAP[s]) { if (lg == 5 || (R << (lg + 1)) > lanes) return false; lg++; }
-        const uint32_t G = 1u << lg;
-        m.lg[s] = lg; m.R[s] = (uint32_t)R; m.out_rel[s] = (uint32_t)(steps[s].out_off - win_off);
-        win_end = std::max(win_end, (uint32_t)(steps[s].out_off - win_off + R));
-        std::vector<uint32_t> order(R);
-        for (size_t t = 0; t < R; t++) order[t] = (uint32_t)t;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].size() > rows[b].size(); });
-        const uint32_t in_rel = (uint32_t)(steps[s].in_off - win_off);
-        for (size_t i = 0; i < R; i++) {
-            const auto &row = rows[order[i]];
-            for (uint32_t q = 0; q < G; q++) {
-                const size_t l = i * G + q;
-                if (q == 0) oidx[(size_t)s * lanes + l] = order[i];
-                uint32_t cnt = 0;
-                for (size_t k = q; k < row.size(); k += G, cnt++) {
-                    const size_t slot = base[s] + cnt;
-                    wt[slot * lanes + l] = row[k].second;
-                    ot[(slot / 2) * lanes + l] |= ((in_rel + row[k].first) * 16u) << (16 * (slot & 1));
-                }
-                uint32_t &w = wid[(l / 64) * ns + s];
-                w = std::max(w, (cnt + 1) / 2 * 2);
-            }
-        }
-    }
-    m.nsteps = ns; m.win_off = win_off; m.in_len = in_len; m.win_len = win_end; m.st_lo = in_len;
-    auto up = [&](uint32_t **d, const std::vector<uint32_t> &h) { return hipMalloc((void **)d, h.size() * 4) == hipSuccess && hipMemcpy(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice) == hipSuccess; };
-    m.ok = up(&m.d_wt, wt) && up(&m.d_ot, ot) && up(&m.d_oidx, oidx) && up(&m.d_w, wid);
-    return m.ok;
+    f.in_off = (uint32_t)p.in_off; f.in_len = (uint32_t)g.L; f.out_off = (uint32_t)p.out_off; f.out_len = (uint32_t)R;
+    HB_TRY(upload(ctx, &f.d_wt, wt)); HB_TRY(upload(ctx, &f.d_ot, ot)); HB_TRY(upload(ctx, &f.d_oidx, oidx)); HB_TRY(upload(ctx, &f.d_w, wid));
+    f.ok = true;
+    return 0;
 }
 // Long codes (codeword over 160 KB): the outer steps whose windows do not fit in LDS, in tiled form (hobbit_ctx.hpp TiledStep).  Built by the
 // first launch_encode of the finalized code, from the plan hobbit_graph_finalize kept.
-}  // extern "C"
-namespace hobbit {
 int ensure_tiled(hobbit_ctx *ctx) {
     DeviceCode &c = ctx->code;
     if (c.tiled_built) return 0;
@@ -585,11 +546,6 @@ int ensure_tiled(hobbit_ctx *ctx) {
     const std::vector<PlanStep> &plan = c.plan;
     const std::vector<long long> &cwlen = c.cwlen;
     const uint32_t D = (uint32_t)cwlen.size() - 1;
-    auto up = [&](void **d, const void *h, size_t bytes) -> int {
-        if (hipMalloc(d, bytes ? bytes : 16) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "graph alloc failed");
-        if (bytes) HB_CHECK(ctx, hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-        return 0;
-    };
     uint32_t d = 0;
     while (d < (uint32_t)D && cwlen[d] > TILE_MID_MAX) d++;
     c.tiled_depth = d;
@@ -603,16 +559,12 @@ int ensure_tiled(hobbit_ctx *ctx) {
         t.n_slices = (t.out_len + 63) / 64;
         t.groups = (t.n_slices + TILE_WAVES * TILE_MAXS - 1) / (TILE_WAVES * TILE_MAXS);
         t.tile_base = (uint32_t)tptr.size(); t.out_base = (uint32_t)tout.size();
-        // in-edges of every output in input order, so that those of one tile are a contiguous run: tile k of output o is [beg(o, k), beg(o, k + 1))
-        std::vector<std::vector<std::pair<uint32_t, F>>> rows(g.R);
-        for (long long i = 0; i < g.L; i++)
-            for (int j = 0; j < g.degree; j++) rows[g.nbr[i * g.degree + j]].push_back({(uint32_t)i, g.w[i * g.degree + j]});
+        // in-edges in input order, so that those of one tile are a contiguous run: tile k of output o is [beg(o, k), beg(o, k + 1))
+        const InEdges rows = in_edges(g);
         auto beg = [&](uint32_t o, uint32_t k) {
             return (size_t)(std::lower_bound(rows[o].begin(), rows[o].end(), k * TILE_ELEMS, [](const std::pair<uint32_t, F> &e, uint32_t v) { return e.first < v; }) - rows[o].begin());
         };
-        std::vector<uint32_t> order((size_t)g.R);
-        for (size_t q = 0; q < order.size(); q++) order[q] = (uint32_t)q;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].size() > rows[b].size(); });
+        const std::vector<uint32_t> order = by_in_degree(rows);
         for (uint32_t sl = 0; sl < t.n_slices; sl++) {
             for (uint32_t l = 0; l < 64; l++) { const size_t q = (size_t)sl * 64 + l; tout.push_back(q < order.size() ? order[q] : 0xFFFFFFFFu); }
             for (uint32_t k = 0; k < t.ntiles; k++) {
@@ -635,11 +587,11 @@ int ensure_tiled(hobbit_ctx *ctx) {
         }
         c.tsteps.push_back(t);
     }
-    HB_TRY(up((void **)&c.d_tile_ptr, tptr.data(), tptr.size() * 4));
-    HB_TRY(up((void **)&c.d_tile_width, twid.data(), twid.size() * 4));
-    HB_TRY(up((void **)&c.d_tile_out, tout.data(), tout.size() * 4));
-    if (c.small_weights) HB_TRY(up((void **)&c.d_tile_e32, te32.data(), te32.size() * sizeof(uint2)));
-    else { HB_TRY(up((void **)&c.d_tile_eidx, teidx.data(), teidx.size() * 4)); HB_TRY(up((void **)&c.d_tile_ew, tew.data(), tew.size() * sizeof(F))); }
+    HB_TRY(upload(ctx, &c.d_tile_ptr, tptr));
+    HB_TRY(upload(ctx, &c.d_tile_width, twid));
+    HB_TRY(upload(ctx, &c.d_tile_out, tout));
+    if (c.small_weights) HB_TRY(upload(ctx, &c.d_tile_e32, te32));
+    else { HB_TRY(upload(ctx, &c.d_tile_eidx, teidx)); HB_TRY(upload(ctx, &c.d_tile_ew, tew)); }
     c.tiled_built = true;
     return 0;
 }
@@ -671,14 +623,9 @@ int ensure_ilv(hobbit_ctx *ctx) {
             }
         base += E;
     }
-    auto up = [&](void **d, const void *h, size_t bytes) -> int {
-        if (hipMalloc(d, bytes ? bytes : 16) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "graph alloc failed");
-        if (bytes) HB_CHECK(ctx, hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-        return 0;
-    };
-    HB_TRY(up((void **)&c.d_ilv_ptr, ptr.data(), ptr.size() * 4));
-    if (c.small_weights) HB_TRY(up((void **)&c.d_ilv_e32, e32.data(), e32.size() * sizeof(uint2)));
-    else { HB_TRY(up((void **)&c.d_ilv_eidx, eidx.data(), eidx.size() * 4)); HB_TRY(up((void **)&c.d_ilv_ew, ew.data(), ew.size() * sizeof(F))); }
+    HB_TRY(upload(ctx, &c.d_ilv_ptr, ptr));
+    if (c.small_weights) HB_TRY(upload(ctx, &c.d_ilv_e32, e32));
+    else { HB_TRY(upload(ctx, &c.d_ilv_eidx, eidx)); HB_TRY(upload(ctx, &c.d_ilv_ew, ew)); }
     c.ilv_built = true;
     return 0;
 }
@@ -706,29 +653,23 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
     }
     c.n = n; c.len = cwlen[0];
     if (c.len > 2 * n) return ctx->fail(HOBBIT_EINVAL, "graph_finalize: codeword longer than 2n");
-    struct Plan { const HostGraph *g; long long in_off, out_off; };
-    std::vector<Plan> plan;
+    std::vector<PlanStep> &plan = c.plan;
     for (int d = 0; d < D; d++) plan.push_back({&ctx->graphs[{d, 0}], off[d], off[d] + nd[d]});
     for (int d = D - 1; d >= 0; d--) plan.push_back({&ctx->graphs[{d, 1}], off[d + 1], off[d + 1] + cwlen[d + 1]});
     c.small_weights = true;
     for (auto &p : plan) for (auto &w : p.g->w) if (w.im != 0 || w.re >> 32) { c.small_weights = false; break; }
-    const char *wm_env = getenv("HOBBIT_ENC_WIDE_MIN"); const uint32_t wide_min = wm_env ? (uint32_t)atoi(wm_env) : ENC_WIDE_MIN;
     std::vector<uint32_t> slice_ptr, slice_width, slice_out, eidx; std::vector<uint2> e32; std::vector<F> ew;
     size_t pos = 0;
     for (auto &p : plan) {
         const HostGraph &g = *p.g;
-        std::vector<std::vector<std::pair<uint32_t, F>>> rows(g.R);
-        for (long long i = 0; i < g.L; i++)
-            for (int j = 0; j < g.degree; j++) rows[g.nbr[i * g.degree + j]].push_back({(uint32_t)i, g.w[i * g.degree + j]});
+        const InEdges rows = in_edges(g);
         EncStep s; s.in_off = (uint32_t)p.in_off; s.out_off = (uint32_t)p.out_off; s.out_len = (uint32_t)g.R;
-        const uint32_t sw = (uint32_t)g.R >= wide_min ? 64u : ENC_SW, split = 64 / sw;
+        const uint32_t sw = (uint32_t)g.R >= ENC_WIDE_MIN ? 64u : ENC_SW, split = 64 / sw;
         // records per output are padded to the lane-group count, and for the wide steps to whole unrolled groups (no remainder loop)
         const uint32_t pad = sw == 64 ? ENC_UNROLL : split;
         s.sw = sw; s.out_base = (uint32_t)slice_out.size();
         s.n_slices = (uint32_t)((g.R + sw - 1) / sw); s.slice_base = (uint32_t)slice_ptr.size();
-        std::vector<uint32_t> order((size_t)g.R);
-        for (size_t t = 0; t < (size_t)g.R; t++) order[t] = (uint32_t)t;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].size() > rows[b].size(); });
+        const std::vector<uint32_t> order = by_in_degree(rows);
         for (uint32_t sl = 0; sl < s.n_slices; sl++) {
             size_t width = 0;
             for (uint32_t l = 0; l < sw; l++) { size_t q = (size_t)sl * sw + l; if (q < (size_t)g.R) width = std::max(width, rows[order[q]].size()); }
@@ -747,31 +688,21 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
         c.steps.push_back(s);
     }
     c.n_edges_padded = pos;
-    auto up = [&](void **d, const void *h, size_t bytes) -> int {
-        if (hipMalloc(d, bytes ? bytes : 16) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "graph alloc failed");
-        if (bytes) HB_CHECK(ctx, hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-        return 0;
-    };
-    HB_TRY(up((void **)&c.d_steps, c.steps.data(), c.steps.size() * sizeof(EncStep)));
-    HB_TRY(up((void **)&c.d_slice_ptr, slice_ptr.data(), slice_ptr.size() * 4));
-    HB_TRY(up((void **)&c.d_slice_width, slice_width.data(), slice_width.size() * 4));
-    HB_TRY(up((void **)&c.d_slice_out, slice_out.data(), slice_out.size() * 4));
-    if (c.small_weights) HB_TRY(up((void **)&c.d_edges32, e32.data(), e32.size() * sizeof(uint2)));
-    else { HB_TRY(up((void **)&c.d_eidx, eidx.data(), eidx.size() * 4)); HB_TRY(up((void **)&c.d_ew, ew.data(), ew.size() * sizeof(F))); }
-    // deep codes (n = 4096: the codeword does not leave room for two workgroups per CU): first and last step also in fat form
+    HB_TRY(upload(ctx, &c.d_steps, c.steps));
+    HB_TRY(upload(ctx, &c.d_slice_ptr, slice_ptr));
+    HB_TRY(upload(ctx, &c.d_slice_width, slice_width));
+    HB_TRY(upload(ctx, &c.d_slice_out, slice_out));
+    if (c.small_weights) HB_TRY(upload(ctx, &c.d_edges32, e32));
+    else { HB_TRY(upload(ctx, &c.d_eidx, eidx)); HB_TRY(upload(ctx, &c.d_ew, ew)); }
+    // deep codes (n = 4096: the codeword does not leave room for two workgroups per CU): first, second and last step also in fat form
     if (c.small_weights && c.steps.size() >= 4 && (size_t)c.len * 16 > 80 * 1024 && (size_t)c.len * 16 <= 160 * 1024) {
-        const uint32_t capA[3] = {FAT_A_CAP0, FAT_A_CAP1, 0}, capD[3] = {FAT_D_CAP0, FAT_D_CAP1, FAT_D_CAP2};
-        build_fat_step(*plan.front().g, (uint32_t)plan.front().in_off, (uint32_t)plan.front().out_off, FAT_A_NOUT, FAT_A_CONS, capA, c.fatA);
-        build_fat_step(*plan.back().g, (uint32_t)plan.back().in_off, (uint32_t)plan.back().out_off, FAT_D_NOUT, FAT_D_CONS, capD, c.fatD);
-        const uint32_t capC1[3] = {FAT_C1_CAP0, 0, 0};
-        build_fat_step(*plan[1].g, (uint32_t)plan[1].in_off, (uint32_t)plan[1].out_off, FAT_C1_NOUT, FAT_C1_CONS, capC1, c.fatC1);
-        std::vector<MidPlanStep> ms;
-        for (size_t i = 1; i + 1 < plan.size(); i++) ms.push_back({plan[i].g, plan[i].in_off, plan[i].out_off});
-        build_mid(ms, (uint32_t)plan[1].in_off, (uint32_t)plan[1].g->L, c.mid);
+        const uint32_t capA[3] = {FAT_A_CAP0, FAT_A_CAP1, 0}, capC1[3] = {FAT_C1_CAP0, 0, 0}, capD[3] = {FAT_D_CAP0, FAT_D_CAP1, FAT_D_CAP2};
+        HB_TRY(build_fat_step(ctx, plan.front(), FAT_A_NOUT, FAT_A_CONS, capA, c.fatA));
+        HB_TRY(build_fat_step(ctx, plan.back(), FAT_D_NOUT, FAT_D_CONS, capD, c.fatD));
+        HB_TRY(build_fat_step(ctx, plan[1], FAT_C1_NOUT, FAT_C1_CONS, capC1, c.fatC1));
     }
-    // the long codes' tiled steps and the rows-innermost CSR steps are built on first use (ensure_tiled / ensure_ilv): a context that only runs
-    // one of the two encodes does not pay for the other's plan
-    for (auto &p : plan) c.plan.push_back({p.g, p.in_off, p.out_off});
+    // the long codes' tiled steps and the rows-innermost CSR steps are built on first use from c.plan (ensure_tiled / ensure_ilv): a context
+    // that only runs one of the two encodes does not pay for the other's plan
     c.cwlen = cwlen; c.graph_gen = ctx->graph_gen;
     if (len_out) *len_out = c.len;
     return 0;
@@ -1006,8 +937,7 @@ static int commit_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int K,
         }
     }
     const char *st_env = getenv("HOBBIT_COMMIT_SKIP_TAIL");
-    const char *zs_env = getenv("HOBBIT_LEAF_ZERO_SKIP");           // (a leaf chain told to hash the zero rows too needs them in memory)
-    ctx->enc_skip_tail = linear_time && !(st_env && st_env[0] == '0') && !(zs_env && zs_env[0] == '0'); ctx->enc_tail_skipped = false;
+    ctx->enc_skip_tail = linear_time && !(st_env && st_env[0] == '0'); ctx->enc_tail_skipped = false;
     int r = tensorcode_chunks(ctx, cF(d_poly), M, K, trs, linear_time, c->d_tensor, up);
     c->rows_valid = (!r && ctx->enc_tail_skipped) ? std::min<uint32_t>((uint32_t)rows2, ((uint32_t)ctx->code.len + 3) & ~3u) : (uint32_t)rows2;
     ctx->enc_skip_tail = false; ctx->enc_tail_skipped = false;

@@ -373,8 +373,7 @@ int launch_fft4096(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_es, 
     Fft4kConst cst; cst.w8 = w8; cst.w8_3 = w8_3; cst.w4_plus_i = w4_plus_i;
     if (src_len == 2048) {
         hipFuncSetAttribute((const void *)k_fft4096<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        static const int remap_mode = [] { const char *e = getenv("HOBBIT_FFT_LINE_REMAP"); return e ? atoi(e) : 1; }();
-        const int remap = (remap_mode && dst_ld == 1 && dst_es > 1 && rows_per_group % 64 == 0) ? 1 : 0;
+        const int remap = (dst_ld == 1 && dst_es > 1 && rows_per_group % 64 == 0) ? 1 : 0;
         HB_LAUNCH(ctx, "k_fft4096", k_fft4096<true>, dim3((unsigned)blocks), dim3(512), lds, src, src_ld, src_es, dst, dst_ld, dst_es, tw1, tw2, tw3, cst,
                   scale, do_scale, rows_per_group, src_gs, dst_gs, remap);
     } else {
@@ -972,18 +971,20 @@ static uint32_t block_for(const DeviceCode &c, uint32_t s_lo, uint32_t s_hi, uin
 
 // ============================================================================================
 // Wide SpMV steps of a deep code (n = 4096), persistent and register-resident (hobbit_ctx.hpp FatStep).
-// One workgroup of NW fat waves per CU for the whole launch.  A lane owns NOUT outputs of the step for good and keeps their edge records --
-// 32-bit weight, 16-bit LDS byte offset -- in registers: the inner loop is one address add (SDWA word select), one ds_read_b128 and the
-// 4 v_mad_u64_u32 + 4 v_addc of the unreduced 96-bit sums per edge; after the prologue no edge record, slice descriptor or index comes from
-// memory.  The step's input window of the NEXT column streams into the second of two LDS buffers by LDS-DMA (global_load_lds_dwordx4, 1 KiB
-// per wave-instruction, no registers) while the waves work on the current one; every wave issues its share of the pieces right after the
-// one barrier per column that hands the buffers over.  The outputs of column c are stored one iteration late, behind that barrier, so that
-// the `vmcnt(0)` which retires a wave's DMA pieces never waits for a store it has just issued.
+// One workgroup of NW fat waves and one loader wave per CU for the whole launch.  A lane owns NOUT outputs of the step for good and keeps
+// their edge records -- 32-bit weight, 16-bit LDS byte offset -- in registers: the inner loop is one address add (SDWA word select), one
+// ds_read_b128 and the 4 v_mad_u64_u32 + 4 v_addc of the unreduced 96-bit sums per edge; after the prologue no edge record, slice descriptor
+// or index comes from memory.  The step's input window of the NEXT column streams into the second of two LDS buffers by LDS-DMA
+// (global_load_lds_dwordx4, 1 KiB per wave-instruction, no registers) while the fat waves work on the current one; the loader wave issues
+// all the pieces right after the one barrier per column that hands the buffers over (a wave's DMA pieces cost it ~100+ cycles each under
+// load: with a dedicated loader the fat waves never stall on them -- 2.5 vs 3.3 ms for C_0 at 2^28 against every wave issuing its share;
+// 2 / 4 / 6 pieces per fat wave beside the loader: 3.06 / 3.15 / 3.27 ms against 2.65 with the loader alone).  The outputs of column c
+// are stored one iteration late, behind that barrier.
 // (The one-workgroup-per-column k_encode re-reads 8 bytes of record per edge and column through L2 -- 40 GB per commit at 2^28 -- and its
 // window load, barriers and slice loop do not overlap: DESIGN.md section 4.)
 // ============================================================================================
-template <int NOUT, int CAP0, int CAP1, int CAP2, int NW, int NLOAD, int CP>
-__global__ void __launch_bounds__((NW + NLOAD) * 64)
+template <int NOUT, int CAP0, int CAP1, int CAP2, int NW>
+__global__ void __launch_bounds__((NW + 1) * 64)
 k_enc_fat(F *__restrict__ tensor, size_t ld, uint32_t ncols, uint32_t in_off, uint32_t in_len, uint32_t out_off, uint32_t z_lo, uint32_t z_hi,
           const uint32_t *__restrict__ wt, const uint32_t *__restrict__ ot, const uint32_t *__restrict__ oidx, const uint32_t *__restrict__ wid) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -991,36 +992,28 @@ k_enc_fat(F *__restrict__ tensor, size_t ld, uint32_t ncols, uint32_t in_off, ui
     constexpr int CAP[3] = {CAP0, CAP1, CAP2}, BASE[3] = {0, CAP0, CAP0 + CAP1};
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint32_t pieces = (in_len + 63) >> 6, win_bytes = pieces << 10;             // whole 1-KiB DMA pieces
-    // NLOAD > 0: the last NLOAD waves only load (a wave's DMA pieces cost it ~100+ cycles each under load: with dedicated loaders the consumers
-    // never stall on them -- 2.5 vs 3.3 ms for C_0 at 2^28); NLOAD = 0: every wave issues its share right after the barrier
-    // CP > 0 (with NLOAD > 0): every consumer wave also issues CP pieces per column right after the barrier, the loaders the rest -- one wave can keep
-    // at most 63 vector-memory instructions in flight and its pieces cost it ~100+ cycles each, so a single loader caps the window stream
-    constexpr int NISS = NLOAD > 0 ? NLOAD : NW;
-    const bool loader = NLOAD > 0 && wave >= NW;
-    const uint32_t first_piece = NLOAD > 0 ? (loader ? NW * CP + (wave - NW) : wave * CP) : wave;
-    const uint32_t end_piece = (NLOAD > 0 && !loader) ? wave * CP + CP : 0xFFFFFFFFu, step_piece = (NLOAD > 0 && !loader) ? 1u : (uint32_t)NISS;
-    auto issue = [&](uint32_t c, uint32_t buf) {                                         // this wave's pieces of column c's window -> buffer buf
-        const F *colp = tensor + (size_t)c * ld + in_off;
-        for (uint32_t p = first_piece; p < pieces && p < end_piece; p += step_piece) {
-            uint32_t i = (p << 6) + lane; i = i < in_len ? i : in_len - 1;             // (the pad lanes of the last piece re-read the last element)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(colp + i),
-                                             (__attribute__((address_space(3))) void *)(lds_raw + buf * win_bytes + (p << 10)), 16, 0, 0);
-        }
-    };
-    if (NLOAD > 0) {
-        if (loader) {
-            uint32_t c = blockIdx.x, it = 0;
-            if (c < ncols) issue(c, 0);
-            for (; c < ncols; c += gridDim.x, it++) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // this column's window has landed
-                __builtin_amdgcn_s_barrier();                                              // ... and the consumers are done with the other buffer
-                const uint32_t cn = c + gridDim.x;
-                if (cn < ncols) issue(cn, (it + 1) & 1);
+    // [first_piece, end_piece): the pieces of a window this wave issues -- all of them for the loader (wave NW), none for a fat wave
+    const bool loader = wave >= NW;
+    const uint32_t first_piece = loader ? wave - NW : 0, end_piece = loader ? 0xFFFFFFFFu : 0;
+    if (loader) {
+        auto issue = [&](uint32_t c, uint32_t buf) {                                     // column c's window -> buffer buf
+            const F *colp = tensor + (size_t)c * ld + in_off;
+            for (uint32_t p = first_piece; p < pieces && p < end_piece; p++) {
+                uint32_t i = (p << 6) + lane; i = i < in_len ? i : in_len - 1;         // (the pad lanes of the last piece re-read the last element)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(colp + i),
+                                                 (__attribute__((address_space(3))) void *)(lds_raw + buf * win_bytes + (p << 10)), 16, 0, 0);
             }
-            return;
+        };
+        uint32_t c = blockIdx.x, it = 0;
+        if (c < ncols) issue(c, 0);
+        for (; c < ncols; c += gridDim.x, it++) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                             // this column's window has landed
+            __builtin_amdgcn_s_barrier();                                                  // ... and the fat waves are done with the other buffer
+            const uint32_t cn = c + gridDim.x;
+            if (cn < ncols) issue(cn, (it + 1) & 1);
         }
+        return;
     }
-    if ((NLOAD == 0 || CP > 0) && blockIdx.x < ncols) issue(blockIdx.x, 0);
     // edge records into registers, once
     uint32_t w[TOT], o[TOT / 2], oi[NOUT], W[NOUT];
 #pragma unroll
@@ -1033,14 +1026,13 @@ k_enc_fat(F *__restrict__ tensor, size_t ld, uint32_t ncols, uint32_t in_off, ui
     F *hcol = nullptr;
     uint32_t it = 0;
     for (uint32_t c = blockIdx.x; c < ncols; c += gridDim.x, it++) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                 // my pieces of this column's window have landed
-        __builtin_amdgcn_s_barrier();                                                      // ... everyone's have, and everyone is done with the other buffer
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                 // (this wave's own loads and stores: the window is the loader's)
+        __builtin_amdgcn_s_barrier();                                                      // this column's window has landed, and everyone is done with the other buffer
         if (hcol) {
 #pragma unroll
             for (int j = 0; j < NOUT; j++) if (oi[j] != 0xFFFFFFFFu) stF(hcol + out_off + oi[j], held[j]);
             for (uint32_t i = z_lo + threadIdx.x; i < z_hi; i += LANES) stF(hcol + i, fmake(0));
         }
-        if (NLOAD == 0 || CP > 0) { const uint32_t cn = c + gridDim.x; if (cn < ncols) issue(cn, (it + 1) & 1); }
         const unsigned char *win = lds_raw + (it & 1) * win_bytes;
 #pragma unroll
         for (int j = 0; j < NOUT; j++) {
@@ -1069,106 +1061,14 @@ k_enc_fat(F *__restrict__ tensor, size_t ld, uint32_t ncols, uint32_t in_off, ui
         for (uint32_t i = z_lo + threadIdx.x; i < z_hi; i += LANES) stF(hcol + i, fmake(0));
     }
 }
-template <int NOUT, int CAP0, int CAP1, int CAP2, int NW, int NLOAD, int CP = 0>
+template <int NOUT, int CAP0, int CAP1, int CAP2, int NW>
 static int launch_enc_fat(hobbit_ctx *ctx, const char *name, const FatStep &f, F *tensor, size_t ld, size_t ncols, uint32_t z_lo, uint32_t z_hi, uint32_t wgs) {
     const size_t lds = (size_t)2 * ((f.in_len + 63) / 64) * 1024;
-    auto kern = k_enc_fat<NOUT, CAP0, CAP1, CAP2, NW, NLOAD, CP>;
+    auto kern = k_enc_fat<NOUT, CAP0, CAP1, CAP2, NW>;
     hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     const size_t grid = std::min(ncols, (size_t)wgs);
-    HB_LAUNCH(ctx, name, kern, dim3((unsigned)grid), dim3((NW + NLOAD) * 64), lds, tensor, ld, (uint32_t)ncols, f.in_off, f.in_len, f.out_off, z_lo, z_hi,
+    HB_LAUNCH(ctx, name, kern, dim3((unsigned)grid), dim3((NW + 1) * 64), lds, tensor, ld, (uint32_t)ncols, f.in_off, f.in_len, f.out_off, z_lo, z_hi,
               f.d_wt, f.d_ot, f.d_oidx, f.d_w);
-    return 0;
-}
-
-// The narrow dependent steps between the first and the last one (hobbit_ctx.hpp MidCode), persistent: one workgroup of MID_WAVES waves per CU
-// walks the columns.  Each step hands an output to 2^lg adjacent lanes that split its in-edges, hold their share of the records in registers,
-// accumulate unreduced, fold once and combine by shuffles; one barrier per step.  x_1 of the next column arrives by LDS-DMA into the other
-// window buffer meanwhile, and the finished [x_2 .. z_1] of this column leaves one iteration late (held in a register per lane), so that the
-// vmcnt(0) which retires the DMA never waits for a store just issued.  (The one-workgroup-per-column k_encode spends 2.6 ms on these 21 % of
-// the edges at 2^28: descriptor -> record -> gather -> fold -> barrier chains of ~4 K cycles per step and column.)
-struct MidArgs { uint32_t nsteps, win_off, win_len, in_len, st_lo, lg[MID_MAX_STEPS], R[MID_MAX_STEPS], out_rel[MID_MAX_STEPS]; };
-__global__ void __launch_bounds__(MID_WAVES * 64)
-k_enc_mid(F *__restrict__ tensor, size_t ld, uint32_t ncols, MidArgs a, const uint32_t *__restrict__ wt, const uint32_t *__restrict__ ot,
-          const uint32_t *__restrict__ oidx, const uint32_t *__restrict__ wid) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    constexpr int NW = MID_WAVES, LANES = NW * 64, NS = MID_MAX_STEPS;
-    constexpr int CAP[NS] = {(int)MID_CAP[0], (int)MID_CAP[1], (int)MID_CAP[2], (int)MID_CAP[3], (int)MID_CAP[4], (int)MID_CAP[5]};
-    constexpr int BASE[NS] = {0, CAP[0], CAP[0] + CAP[1], CAP[0] + CAP[1] + CAP[2], CAP[0] + CAP[1] + CAP[2] + CAP[3], CAP[0] + CAP[1] + CAP[2] + CAP[3] + CAP[4]};
-    constexpr int TOT = BASE[5] + CAP[5];
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const uint32_t pieces = (a.in_len + 63) >> 6, win_bytes = ((a.win_len + 63) >> 6) << 10;
-    auto issue = [&](uint32_t c, uint32_t buf) {
-        const F *colp = tensor + (size_t)c * ld + a.win_off;
-        for (uint32_t p = wave; p < pieces; p += NW) {
-            uint32_t i = (p << 6) + lane; i = i < a.in_len ? i : a.in_len - 1;          // (pad lanes land on slots the first step overwrites later)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(colp + i),
-                                             (__attribute__((address_space(3))) void *)(lds_raw + buf * win_bytes + (p << 10)), 16, 0, 0);
-        }
-    };
-    if (blockIdx.x < ncols) issue(blockIdx.x, 0);
-    uint32_t w[TOT], o[TOT / 2], oi[NS], W[NS];
-#pragma unroll
-    for (int k = 0; k < TOT; k++) w[k] = wt[(size_t)k * LANES + threadIdx.x];
-#pragma unroll
-    for (int k = 0; k < TOT / 2; k++) o[k] = ot[(size_t)k * LANES + threadIdx.x];
-#pragma unroll
-    for (int s = 0; s < NS; s++) {
-        oi[s] = (uint32_t)s < a.nsteps ? oidx[(size_t)s * LANES + threadIdx.x] : 0xFFFFFFFFu;
-        W[s] = (uint32_t)s < a.nsteps ? __builtin_amdgcn_readfirstlane(wid[wave * a.nsteps + s]) : 0u;
-    }
-    F held = fmake(0); F *hcol = nullptr;
-    const uint32_t my_st = a.st_lo + threadIdx.x;                                        // the window element this lane carries back to memory
-    uint32_t it = 0;
-    for (uint32_t c = blockIdx.x; c < ncols; c += gridDim.x, it++) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (hcol && my_st < a.win_len) stF(hcol + a.win_off + my_st, held);
-        const uint32_t cn = c + gridDim.x;
-        if (cn < ncols) issue(cn, (it + 1) & 1);
-        unsigned char *win = lds_raw + (it & 1) * win_bytes;
-#pragma unroll
-        for (int s = 0; s < NS; s++) {
-            if ((uint32_t)s < a.nsteps) {
-                Acc96 rl = {0, 0}, rh = {0, 0}, il = {0, 0}, ih = {0, 0};
-#pragma unroll
-                for (int g = 0; g < CAP[s]; g += 2) {
-                    if ((uint32_t)g < W[s]) {
-                        uint4 x[2];
-#pragma unroll
-                        for (int u = 0; u < 2; u++) {
-                            const int k = BASE[s] + g + u;
-                            const uint32_t off = (k & 1) ? (o[k >> 1] >> 16) : (o[k >> 1] & 0xFFFFu);
-                            x[u] = *reinterpret_cast<const uint4 *>(win + off);
-                        }
-#pragma unroll
-                        for (int u = 0; u < 2; u++) acc96_mad4(rl, rh, il, ih, w[BASE[s] + g + u], x[u]);
-                    }
-                }
-                F v = fmake(acc_fold(rl, rh), acc_fold(il, ih));
-                const uint32_t lg = a.lg[s];
-                if (lg > 0) v = fadd(v, shfl_xor_F(v, 1));
-                if (lg > 1) v = fadd(v, shfl_xor_F(v, 2));
-                if (lg > 2) v = fadd(v, shfl_xor_F(v, 4));
-                if (lg > 3) v = fadd(v, shfl_xor_F(v, 8));
-                if (lg > 4) v = fadd(v, shfl_xor_F(v, 16));
-                if (oi[s] != 0xFFFFFFFFu) stF(reinterpret_cast<F *>(win) + a.out_rel[s] + oi[s], v);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
-        }
-        if (my_st < a.win_len) held = ldF(reinterpret_cast<const F *>(win) + my_st);
-        hcol = tensor + (size_t)c * ld;
-    }
-    if (hcol && my_st < a.win_len) stF(hcol + a.win_off + my_st, held);
-}
-static int launch_enc_mid(hobbit_ctx *ctx, const MidCode &m, F *tensor, size_t ld, size_t ncols, uint32_t wgs) {
-    if (m.win_len - m.st_lo > MID_WAVES * 64) return ctx->fail(HOBBIT_EINVAL, "encode: middle window longer than the workgroup");
-    MidArgs a{}; a.nsteps = m.nsteps; a.win_off = m.win_off; a.win_len = m.win_len; a.in_len = m.in_len; a.st_lo = m.st_lo;
-    for (uint32_t s = 0; s < MID_MAX_STEPS; s++) { a.lg[s] = m.lg[s]; a.R[s] = m.R[s]; a.out_rel[s] = m.out_rel[s]; }
-    const size_t lds = (size_t)2 * ((m.win_len + 63) / 64) * 1024;
-    hipFuncSetAttribute((const void *)k_enc_mid, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const size_t grid = std::min(ncols, (size_t)wgs);
-    HB_LAUNCH(ctx, "k_enc_mid", k_enc_mid, dim3((unsigned)grid), dim3(MID_WAVES * 64), lds, tensor, ld, (uint32_t)ncols, a, m.d_wt, m.d_ot, m.d_oidx, m.d_w);
     return 0;
 }
 
@@ -1308,58 +1208,31 @@ int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t l
     EncPass pa = {0, 0, nn, 0, 1, write_msg ? 0u : nn, write_msg ? nn : nn, 1};
     // pass B: the remaining steps on the window [n, len)
     EncPass pb = {nn, nn, nn + r0, 1, nsteps, nn + r0, 2 * nn, 0};
-    // persistent register-resident first step (in place only: the message is where the codeword goes)
-    const char *fat_env = getenv("HOBBIT_ENC_FAT"); const int fat = fat_env ? atoi(fat_env) : 3;       // bit 0: C_0 fat; bit 1: D_0 fat (+ the middle steps as their own pass); bit 2: middle steps by k_enc_mid (measured slower: DESIGN.md 4)
-    if (c.small_weights && (fat & 1) && c.fatA.ok && src == dst && ld_src == ld_dst && !write_msg) {
-        const char *wg_env = getenv("HOBBIT_ENC_FAT_WGS");
-        const uint32_t wgs = wg_env ? (uint32_t)atoi(wg_env) : 256u;
-        // (CP = 2 / 4 / 6 pieces per consumer wave beside the loader were measured: 3.06 / 3.15 / 3.27 ms against 2.65 with the loader alone, same call)
-        HB_TRY((launch_enc_fat<FAT_A_NOUT, FAT_A_CAP0, FAT_A_CAP1, 0, FAT_A_CONS, 1>(ctx, "k_enc_fat_A", c.fatA, dst, ld_dst, batch, 0, 0, wgs)));
-        if ((fat & 2) && c.fatD.ok && nsteps >= 4) {
-            // the narrow dependent steps C_1 .. D_1 on the 24 KB window [x_1 .. z_1], then D_0 in fat form (it also writes the zero tail)
-            const EncStep &last = c.steps[nsteps - 1];
-            EncPass pm = {nn, nn, nn + r0, 1, nsteps - 1, nn + r0, last.out_off, 0};
-            const char *m2_env = getenv("HOBBIT_ENC_M2"); const int m2 = m2_env ? atoi(m2_env) : 2;
-            if (m2 > 0 && nsteps >= 5) {
-                // the middle as two launches (HOBBIT_ENC_M2=0: one, k_encode_M): C_1 alone -- 21 % of the edges on a 14 KB window: fat form, three workgroups per CU --
-                // then the five short steps behind it with a two-wave workgroup per column on the 10 KB window [x_2 .. z_1] (sixteen of them per CU
-                // hide the dependent step chains).  2^28: 2.44 ms as one launch, 0.93 + 1.05 split, 0.63 + 1.05 with C_1 fat
-                const uint32_t r1 = c.steps[1].out_len, x2 = nn + r0;
-                EncPass p1 = {nn, nn, nn + r0, 1, 2, x2, x2, 1};
-                const char *c1_env = getenv("HOBBIT_ENC_FAT_C1");
-                if (c.fatC1.ok && !(c1_env && c1_env[0] == '0')) {
-                    const char *wc_env = getenv("HOBBIT_ENC_FAT_WGS_C1");
-                    HB_TRY((launch_enc_fat<FAT_C1_NOUT, FAT_C1_CAP0, 0, 0, FAT_C1_CONS, 1>(ctx, "k_enc_fat_C1", c.fatC1, dst, ld_dst, batch, 0, 0, wc_env ? (uint32_t)atoi(wc_env) : 768u)));
-                } else
-                    HB_TRY(launch_encode_pass<true>(ctx, "k_encode_C1", dst, ld_dst, dst, ld_dst, batch, p1, r0, block_for(c, 1, 2, 8)));
-                EncPass p2 = {x2, x2, x2 + r1, 2, nsteps - 1, x2 + r1, last.out_off, 0};
-                HB_TRY(launch_encode_pass<true>(ctx, "k_encode_M2", dst, ld_dst, dst, ld_dst, batch, p2, last.out_off - x2, block_for(c, 2, nsteps - 1, (uint32_t)m2)));
-            } else if ((fat & 4) && c.mid.ok) {
-                const char *wm_env = getenv("HOBBIT_ENC_MID_WGS");
-                HB_TRY(launch_enc_mid(ctx, c.mid, dst, ld_dst, batch, wm_env ? (uint32_t)atoi(wm_env) : 512u));
-            } else
-                HB_TRY(launch_encode_pass<true>(ctx, "k_encode_M", dst, ld_dst, dst, ld_dst, batch, pm, last.out_off - nn, block_for(c, 1, nsteps - 1, 8)));
-            const char *wd_env = getenv("HOBBIT_ENC_FAT_WGS_D");
-            // the zero tail [len, 2n): a caller that answers those rows as zeros itself (commit_impl: leaf chain, gathers and row reads know the
-            // codeword length) asks for the rows up to the next multiple of four only -- the leaf group that straddles the codeword's end is read whole
-            uint32_t z_hi = 2 * nn;
-            if (ctx->enc_skip_tail) { z_hi = std::min<uint32_t>(2 * nn, ((uint32_t)c.len + 3) & ~3u); ctx->enc_tail_skipped = true; }
-            return launch_enc_fat<FAT_D_NOUT, FAT_D_CAP0, FAT_D_CAP1, FAT_D_CAP2, FAT_D_CONS, 1>(ctx, "k_enc_fat_D", c.fatD, dst, ld_dst, batch, (uint32_t)c.len, z_hi,
-                                                                                                     wd_env ? (uint32_t)atoi(wd_env) : 256u);
-        }
-        return launch_encode_pass<true>(ctx, "k_encode_B", dst, ld_dst, dst, ld_dst, batch, pb, (uint32_t)c.len - nn, block_for(c, 1, nsteps, 8));
-    }
-    const char *s3_env = getenv("HOBBIT_ENC_SPLIT3"); const int split3 = s3_env ? atoi(s3_env) : 0;      // (read per call: scripts/ab_commit.py alternates it in one process)
-    if (c.small_weights && split3 && nsteps >= 4) {
-        // EXPERIMENT: pass B as two launches -- the narrow dependent steps C_1 .. D_1 on the 24 KB window [x_1 .. z_1] (six workgroups per CU), then
-        // D_0 alone: it reads that window back and streams its outputs and the zero tail to global memory
+    // deep codes in place (the message is where the codeword goes): C_0 by the persistent register-resident kernel, then the rest as one
+    // pass B unless D_0 fits that kernel too
+    if (c.small_weights && c.fatA.ok && src == dst && ld_src == ld_dst && !write_msg) {
+        HB_TRY((launch_enc_fat<FAT_A_NOUT, FAT_A_CAP0, FAT_A_CAP1, 0, FAT_A_CONS>(ctx, "k_enc_fat_A", c.fatA, dst, ld_dst, batch, 0, 0, FAT_A_WGS)));
+        if (!c.fatD.ok || nsteps < 5)
+            return launch_encode_pass<true>(ctx, "k_encode_B", dst, ld_dst, dst, ld_dst, batch, pb, (uint32_t)c.len - nn, block_for(c, 1, nsteps, 8));
+        // C_1 alone -- 21 % of the edges on a 14 KB window: fat form, three workgroups per CU -- then the five short steps C_2 .. D_1 with a
+        // two-wave workgroup per column on the 10 KB window [x_2 .. z_1] (sixteen of them per CU hide the dependent step chains), then D_0 in
+        // fat form (it also writes the zero tail).  2^28: 2.44 ms for C_1 .. D_1 as one launch, 0.93 + 1.05 split, 0.63 + 1.05 with C_1 fat
         const EncStep &last = c.steps[nsteps - 1];
-        const uint32_t w_end = last.in_off + (uint32_t)(last.out_off - last.in_off);      // = out_off of D_0 = end of cw_1
-        EncPass pm = {nn, nn, nn + r0, 1, nsteps - 1, nn + r0, w_end, 0};
-        EncPass pd = {nn, nn, w_end, nsteps - 1, nsteps, (uint32_t)c.len, 2 * nn, 1};
-        HB_TRY(launch_encode_pass<true>(ctx, "k_encode_A", src, ld_src, dst, ld_dst, batch, pa, nn, block_for(c, 0, 1, 16)));
-        HB_TRY(launch_encode_pass<true>(ctx, "k_encode_M", dst, ld_dst, dst, ld_dst, batch, pm, w_end - nn, block_for(c, 1, nsteps - 1, 8)));
-        return launch_encode_pass<true>(ctx, "k_encode_D", dst, ld_dst, dst, ld_dst, batch, pd, w_end - nn, block_for(c, nsteps - 1, nsteps, 8));
+        const uint32_t r1 = c.steps[1].out_len, x2 = nn + r0;
+        if (c.fatC1.ok) {
+            HB_TRY((launch_enc_fat<FAT_C1_NOUT, FAT_C1_CAP0, 0, 0, FAT_C1_CONS>(ctx, "k_enc_fat_C1", c.fatC1, dst, ld_dst, batch, 0, 0, FAT_C1_WGS)));
+        } else {
+            EncPass p1 = {nn, nn, nn + r0, 1, 2, x2, x2, 1};
+            HB_TRY(launch_encode_pass<true>(ctx, "k_encode_C1", dst, ld_dst, dst, ld_dst, batch, p1, r0, block_for(c, 1, 2, 8)));
+        }
+        EncPass p2 = {x2, x2, x2 + r1, 2, nsteps - 1, x2 + r1, last.out_off, 0};
+        HB_TRY(launch_encode_pass<true>(ctx, "k_encode_M2", dst, ld_dst, dst, ld_dst, batch, p2, last.out_off - x2, block_for(c, 2, nsteps - 1, 2)));
+        // the zero tail [len, 2n): a caller that answers those rows as zeros itself (commit_impl: leaf chain, gathers and row reads know the
+        // codeword length) asks for the rows up to the next multiple of four only -- the leaf group that straddles the codeword's end is read whole
+        uint32_t z_hi = 2 * nn;
+        if (ctx->enc_skip_tail) { z_hi = std::min<uint32_t>(2 * nn, ((uint32_t)c.len + 3) & ~3u); ctx->enc_tail_skipped = true; }
+        return launch_enc_fat<FAT_D_NOUT, FAT_D_CAP0, FAT_D_CAP1, FAT_D_CAP2, FAT_D_CONS>(ctx, "k_enc_fat_D", c.fatD, dst, ld_dst, batch, (uint32_t)c.len, z_hi,
+                                                                                         FAT_D_WGS);
     }
     if (c.small_weights) {
         HB_TRY(launch_encode_pass<true>(ctx, "k_encode_A", src, ld_src, dst, ld_dst, batch, pa, nn, block_for(c, 0, 1, 16)));
@@ -1586,8 +1459,7 @@ int launch_leaf_chain_relay(hobbit_ctx *ctx, const F *tensor, size_t chunk_strid
                             const uint8_t *state_in, uint8_t *state_out, uint8_t *leaves, uint32_t zero_rows_from, int leaves_inout) {
     if (!g_count) return 0;
     ZeroDig zd; { uint32_t z[16] = {0}; blake3_compress64(z, zd.w); }
-    const char *ge = getenv("HOBBIT_LEAF_GRID");
-    HB_LAUNCH(ctx, "k_leaf_chain_relay", k_leaf_chain_relay, dim3(grid_for(g_count, 256, ge ? atoi(ge) : 4096)), dim3(256), 0, tensor, chunk_stride, K, cols, half_trs, g_begin,
+    HB_LAUNCH(ctx, "k_leaf_chain_relay", k_leaf_chain_relay, dim3(grid_for(g_count, 256, 4096)), dim3(256), 0, tensor, chunk_stride, K, cols, half_trs, g_begin,
               g_count, state_in, state_out, leaves, (zero_rows_from + 3) / 4, zd, leaves_inout);
     return 0;
 }
@@ -1824,7 +1696,6 @@ int launch_hash_md(hobbit_ctx *ctx, const F *xyzw, const uint8_t *prev, uint8_t 
     return 0;
 }
 int launch_merkle_levels(hobbit_ctx *ctx, uint8_t *levels, size_t n, int quirk) {
-    static const int sub_mode = [] { const char *e = getenv("HOBBIT_MERKLE_SUB"); return e ? atoi(e) : 1; }();
     size_t off = 0, tot = n;
     for (size_t sz = n / 2; sz >= 1;) {
         if (sz <= 1024) {                                   // this level and all above it in one workgroup
@@ -1834,7 +1705,7 @@ int launch_merkle_levels(hobbit_ctx *ctx, uint8_t *levels, size_t n, int quirk) 
         // levels of more than 1024 nodes: up to 11 of them per launch (every workgroup's 1024 nodes carry their own ancestors), but only
         // while the level is small enough that the idle upper levels of a workgroup cost less than the launches they replace
         int wide = 0; for (size_t t = sz; t > 1024; t >>= 1) wide++;
-        if (sub_mode && sz % 1024 == 0 && sz <= ((size_t)1 << 21) && (n & (n - 1)) == 0) {
+        if (sz % 1024 == 0 && sz <= ((size_t)1 << 21) && (n & (n - 1)) == 0) {
             const int g = wide < 11 ? wide : 11;
             HB_LAUNCH(ctx, "k_merkle_level", k_merkle_sub, dim3((unsigned)(sz / 1024)), dim3(1024), 0, levels + 32 * off, levels + 32 * tot, sz, g, quirk);
             for (int lv = 0; lv < g; lv++) { off = tot; tot += sz; sz >>= 1; }
@@ -1850,13 +1721,10 @@ int launch_leaf_chain(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int
     size_t total = (size_t)cols * half_trs;
     constexpr int NL = 1;   // 2 interleaved chains measured no faster: the kernel sits at the VALU issue limit (profiles/r01_microbench.txt)
     ZeroDig zd; { uint32_t z[16] = {0}; blake3_compress64(z, zd.w); }
-    const char *e = getenv("HOBBIT_LEAF_ZERO_SKIP");
-    const uint32_t zero_from = (e && e[0] == '0') ? 0xFFFFFFFFu : (zero_rows_from + 3) / 4;
     // 4096 resident-ish workgroups walking the leaves instead of one workgroup per 256 leaves (32 768 at 2^28): 10.15 -> 9.65 ms, same call
-    // (2048: 9.7, 8192: 9.7; HOBBIT_LEAF_GRID for the A/B) -- fewer dispatches, and the per-pass rotation spreads the cheap all-zero groups evenly
-    const char *ge = getenv("HOBBIT_LEAF_GRID");
-    HB_LAUNCH(ctx, "k_leaf_chain", k_leaf_chain<NL>, dim3(grid_for((total + NL - 1) / NL, 256, ge ? atoi(ge) : 4096)), dim3(256), 0, tensor, chunk_stride, K, cols,
-              half_trs, leaves, zero_from, zd);
+    // (2048: 9.7, 8192: 9.7) -- fewer dispatches, and the per-pass rotation spreads the cheap all-zero groups evenly
+    HB_LAUNCH(ctx, "k_leaf_chain", k_leaf_chain<NL>, dim3(grid_for((total + NL - 1) / NL, 256, 4096)), dim3(256), 0, tensor, chunk_stride, K, cols,
+              half_trs, leaves, (zero_rows_from + 3) / 4, zd);
     return 0;
 }
 int launch_merkle_paths(hobbit_ctx *ctx, const uint8_t *levels, size_t n, const uint64_t *d_pos, size_t nq, int depth, uint8_t *d_paths) {

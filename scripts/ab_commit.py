@@ -1,6 +1,6 @@
 """Same-box A/B of commit_standard(2^28) under environment switches, alternating in ONE process (the FFT kernel's time differs by
 several per cent between boxes of the pool: only same-call comparisons mean anything).
-usage: ab_commit.py VAR=a,b[,c] [logN] [reps]     e.g.  ab_commit.py HOBBIT_ENC_STRIDED=0,1 28 4"""
+usage: ab_commit.py VAR=a,b[,c] [logN] [reps]     e.g.  ab_commit.py HOBBIT_COMMIT_PIPE=0,8 28 4"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -3,7 +3,6 @@ into HBM bytes per launch and kernel.  gfx950 corrections per the guide: counter
 wide coalesced reads, so it is doubled.  usage: hbm_traffic.py <fetch counter_collection.csv> <write counter_collection.csv> <out.json> <command...>"""
 import collections, csv, json, sys
 
-deep = True     # at trs = 4096 (the 2^28 workload) the 512-thread pass is the middle pass M of round 3's three-launch encode (HOBBIT_ENC_FAT=3, the default)
 def load(path, counter):
     acc = collections.defaultdict(lambda: [0.0, 0])
     for r in csv.DictReader(open(path)):
@@ -14,8 +13,8 @@ def load(path, counter):
         if name == "k_enc_fat":                               # one template: C_0 has two outputs per lane, C_1 one, D_0 three
             name = "k_enc_fat_" + {"2": "A", "1": "C1", "3": "D"}.get(full.split("<")[1][:1], "?")
         elif name.startswith("k_encode"):                     # the one-workgroup-per-column passes are one template: tell them apart by their workgroup size
-            wgs = int(r["Workgroup_Size"])
-            name = "k_encode_A" if wgs > 512 else "k_encode_M2" if wgs <= 128 else ("k_encode_M" if deep else "k_encode_B")
+            wgs = int(r["Workgroup_Size"])                    # (of these, the in-place chain of trs = 4096, the 2^28 workload, launches only k_encode_M2)
+            name = "k_encode_A" if wgs > 512 else "k_encode_M2" if wgs <= 128 else "k_encode_B"
         a = acc[name]; a[0] += float(r["Counter_Value"]); a[1] += 1
     return acc
 

@@ -156,6 +156,20 @@ def graphs_from(oracle, n):
     return lv
 
 
+def encode_with_kernels(hb, x, in_place):
+    """hb.encode_monolithic(x, in_place) under the profiler: the codewords and the names of the kernels that ran"""
+    hb.profile(True); hb.profile_reset()
+    try:
+        y = hb.encode_monolithic(x, in_place=in_place)
+        return y, set(hb.profile_report())
+    finally:
+        hb.profile(False); hb.profile_reset()
+
+
+# n = 4096 in place with small weights: C_0, C_1 and D_0 by the persistent register-resident kernels, C_2 .. D_1 by k_encode_M2
+FAT_CHAIN_4096 = {"k_enc_fat_A", "k_enc_fat_C1", "k_encode_M2", "k_enc_fat_D"}
+
+
 def set_weights(oracle, lv, w):
     """every edge weight of every level set to the F element w, on the oracle and in lv (returned for upload_graphs)"""
     w = np.asarray(w, np.uint64).reshape(2)

@@ -10,7 +10,8 @@ import sys
 import numpy as np
 import pytest
 import adversarial as A
-from adversarial import P, families, graphs_from, set_weights
+from adversarial import FAT_CHAIN_4096, P, encode_with_kernels, families, graphs_from, set_weights
+from oracle.pyoracle import splitmix_field
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,18 +157,57 @@ def test_encode_families(hb, oracle, n, modes, wname):
 
 
 @pytest.mark.parametrize("wname", list(WEIGHTS))
-def test_encode_4096_in_place_paths_families(hb, oracle, wname, monkeypatch):
-    """n = 4096 in place, the commit's form: the persistent k_enc_fat kernels and the middle steps as one launch, as k_encode_C1/M2 or
-    k_enc_mid (HOBBIT_ENC_FAT 0 / 3 / 7 x HOBBIT_ENC_M2 0 / 2, read on every call), plus the out-of-place A/B split"""
+def test_encode_4096_in_place_paths_families(hb, oracle, wname):
+    """n = 4096 in place, the commit's form (the persistent k_enc_fat chain under 32-bit weights, the full-weight A/B split otherwise), and
+    the out-of-place A/B split: both against the oracle, and against each other on every column"""
     lv = _graphs(oracle, 4096, WEIGHTS[wname])
     hb.upload_graphs(4096, lv)
     names, x = _stack(families(4096, seed=4096))
     wants = _oracle_encode(oracle, x)
-    _check_encode(hb.encode_monolithic(x), wants, names, (wname, "out"))
-    for fat in ("0", "3", "7"):
-        for m2 in ("0", "2"):
-            monkeypatch.setenv("HOBBIT_ENC_FAT", fat); monkeypatch.setenv("HOBBIT_ENC_M2", m2)
-            _check_encode(hb.encode_monolithic(x, in_place=True), wants, names, (wname, "fat" + fat, "m2_" + m2))
+    fullw = wname == "full_p-1"
+    out, ran = encode_with_kernels(hb, x, in_place=False)
+    assert ran == ({"k_encode_fullw_A", "k_encode_fullw_B"} if fullw else {"k_encode_A", "k_encode_B"}), (wname, ran)
+    _check_encode(out, wants, names, (wname, "out"))
+    got, ran = encode_with_kernels(hb, x, in_place=True)
+    assert ran == ({"k_encode_fullw_A", "k_encode_fullw_B"} if fullw else FAT_CHAIN_4096), (wname, ran)
+    _check_encode(got, wants, names, (wname, "in"))
+    assert np.array_equal(got, out), wname
+
+
+def _raise_in_degree(g, t, deg):
+    """re-point edges of graph g (upload_graphs' form) at output t, in input order, until t has in-degree deg"""
+    nbr = np.array(g["nbr"], np.int64).reshape(-1)
+    have = int((nbr == t).sum())
+    moved = np.flatnonzero(nbr != t)[:deg - have]
+    nbr[moved] = t
+    assert int((nbr == t).sum()) == deg
+    return dict(g, nbr=nbr.reshape(np.shape(g["nbr"])))
+
+
+# (level, in-degree one past the fat kernel's first register cap (hobbit_ctx.hpp FAT_*_CAP0), kernels in place)
+FAT_FALLBACKS = {
+    "C1_over_64": ((1, 0), 65, {"k_enc_fat_A", "k_encode_C1", "k_encode_M2", "k_enc_fat_D"}),
+    "D0_over_28": ((0, 1), 29, {"k_enc_fat_A", "k_encode_B"}),
+    "C0_over_72": ((0, 0), 73, {"k_encode_A", "k_encode_B"}),
+}
+
+
+@pytest.mark.parametrize("case", list(FAT_FALLBACKS))
+def test_encode_4096_in_place_fat_fallbacks(hb, oracle, case):
+    """n = 4096 in place with one output of a fat step past the kernel's register cap: that step falls back to the one-workgroup-per-column
+    kernels, chosen from the graph alone; bit for bit the out-of-place A/B split on every column"""
+    key, deg, kernels = FAT_FALLBACKS[case]
+    oracle.rng_reset(); oracle.expander_init_store(4096)
+    lv = graphs_from(oracle, 4096)
+    lv[key] = _raise_in_degree(lv[key], 0, deg)
+    hb.upload_graphs(4096, lv)
+    x = np.concatenate([_stack(families(4096, seed=4096))[1], splitmix_field(300 * 4096, 4096).reshape(300, 4096, 2)])
+    got, ran = encode_with_kernels(hb, x, in_place=True)
+    assert ran == kernels, (case, ran)
+    out, ran = encode_with_kernels(hb, x, in_place=False)
+    assert ran == {"k_encode_A", "k_encode_B"}, (case, ran)
+    assert np.array_equal(got, out), case
+    assert not got[:, 7045:].any(), case
 
 
 # ---- through the library -------------------------------------------------------------------------

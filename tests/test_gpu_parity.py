@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import golden_cases
 from golden_cases import dg, samp
+from adversarial import FAT_CHAIN_4096, encode_with_kernels
 from oracle.pyoracle import splitmix_field, P
 
 pytestmark = pytest.mark.gpu
@@ -299,29 +300,21 @@ def test_encode_batch_linearity_4096(hb, oracle):
 
 
 @pytest.mark.parametrize("batch", [1, 255, 700])
-def test_encode_in_place_4096_persistent_kernels(hb, oracle, batch, monkeypatch):
-    """n = 4096 in place -- the commit's form, served by the persistent register-resident kernels (k_enc_fat for C_0 and D_0, LDS-DMA
+def test_encode_in_place_4096_persistent_kernels(hb, oracle, batch):
+    """n = 4096 in place -- the commit's form, served by the persistent register-resident kernels (k_enc_fat for C_0, C_1 and D_0, LDS-DMA
     double-buffered windows): fewer columns than workgroups, one short of a full round, and several rounds with a ragged last one; against
-    the oracle on sampled columns and against the one-workgroup-per-column kernels (HOBBIT_ENC_FAT=0) and every mix of the two on all of them."""
+    the oracle on sampled columns and against the one-workgroup-per-column kernels of the out-of-place form on all of them."""
     oracle.rng_reset(); oracle.expander_init_store(4096)
     hb.upload_graphs(4096, graphs_from(oracle, 4096))
     x = splitmix_field(batch * 4096, 77 + batch).reshape(batch, 4096, 2)
-    got = {}
-    for mode in ("0", "1", "3", "7"):
-        monkeypatch.setenv("HOBBIT_ENC_FAT", mode)
-        got[mode] = hb.encode_monolithic(x, in_place=True)
-    monkeypatch.delenv("HOBBIT_ENC_FAT")
-    for m2, c1 in (("0", "1"), ("1", "1"), ("2", "0"), ("4", "1")):                   # the middle steps: one launch / C_1 + narrow remainder, C_1 generic or fat
-        monkeypatch.setenv("HOBBIT_ENC_M2", m2); monkeypatch.setenv("HOBBIT_ENC_FAT_C1", c1)
-        got["m2_%s_%s" % (m2, c1)] = hb.encode_monolithic(x, in_place=True)
-    monkeypatch.delenv("HOBBIT_ENC_M2"); monkeypatch.delenv("HOBBIT_ENC_FAT_C1")
-    got["default"] = hb.encode_monolithic(x, in_place=True)
-    for mode in got:
-        assert np.array_equal(got[mode], got["0"]), mode
-    assert np.array_equal(got["0"], hb.encode_monolithic(x))                          # the out-of-place form
+    got, ran = encode_with_kernels(hb, x, in_place=True)
+    assert ran == FAT_CHAIN_4096, ran
+    out, ran = encode_with_kernels(hb, x, in_place=False)
+    assert ran == {"k_encode_A", "k_encode_B"}, ran
+    assert np.array_equal(got, out)
     for b in sorted({0, batch // 2, batch - 1}):
         want, ln = oracle.encode_monolithic(x[b])
-        assert ln == 7045 and np.array_equal(got["default"][b][:ln], want[:ln]) and not got["default"][b][ln:].any()
+        assert ln == 7045 and np.array_equal(got[b][:ln], want[:ln]) and not got[b][ln:].any()
 
 
 @pytest.mark.parametrize("logN,K,lin", [(18, 32, 1), (22, 32, 1), (24, 32, 1), (24, 16, 0), (23, 2, 0)])
