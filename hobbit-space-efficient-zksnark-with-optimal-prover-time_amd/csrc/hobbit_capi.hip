@@ -852,7 +852,7 @@ static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, i
         // data) runs on the main one.  Same kernels, same bytes, bit-identical tensor; DESIGN.md section 4 has the A/B.
         const char *pp_env = getenv("HOBBIT_COMMIT_PIPE");
         int pipe = pp_env ? atoi(pp_env) : (K % 8 == 0 ? 8 : K % 4 == 0 ? 4 : K % 2 == 0 ? 2 : 0);
-        if (pipe > 56) pipe = 56;                                    // side_ev[0 .. pipe) are this loop's; 60-63 belong to open_impl, 64/65 to the brackets below
+        if (pipe > 56) pipe = 56;                                    // side_ev[0 .. pipe) are this loop's; 60, 62, 63 belong to the opening (OpenRun), 61 is free, 64/65 to the brackets below
         if (pipe > 1 && K % pipe == 0) {
             HB_TRY(ctx->side_init());
             const int per = K / pipe; hipStream_t mainS = ctx->stream;
@@ -2641,44 +2641,49 @@ int hobbit_gate_consistency_lookups_stream(hobbit_ctx *ctx, hobbit_trace_source 
 // challenge powers; device: everything that touches a table.
 // With a commitment `c`: the aggregate is computed from d_poly (N = M K coefficients).  With c == NULL (multi-GPU open): d_poly is the
 // M-element aggregate itself, summed by the caller from per-rank partials; dims = {K, trs}; replies and paths are the caller's business.
-static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
-                          bool full);
-static int open_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
-                     bool full) {
-    const int rc = open_impl_body(ctx, d_poly, N, c, dims, h_x, queries, o, full);
-    if (rc) {
-        // an error return may leave work queued on the helper contexts' streams (inner commitments, query answers, their staged read-backs
-        // into THIS context's arena): drain them before the caller -- or the next call's StageScope -- re-uses those buffers
-        for (hobbit_ctx *h : {ctx->helper, ctx->helper2}) if (h) hipStreamSynchronize(h->stream);
-        if (ctx->side) hipStreamSynchronize(ctx->side);
-        hipStreamSynchronize(ctx->stream);
+// One opening: what its stages share, and the stages in the reference's order (open_impl_body is the list).  Two schedules, chosen once:
+//   serial      everything on the caller's thread and stream.  open_core, HOBBIT_OPEN_THREADS=0, a full per-kernel profile (mode 1) and
+//               HOBBIT_TRACE=1 run it; the transcript recorder is per calling thread, so the tests against the reference's transcript need it.
+//   overlapped  after the aggregate's tensor code the two inner commitments (needed only by the shockwave_prove calls at the very end) and behind
+//               them the query answers (which feed nothing) go to helper2's stream, P1 -> P2 -> P3 -> P4 stay on the caller's thread and stream;
+//               after P4, shockwave_prove(C_c) runs on the helper context from a second host thread beside P5 -> shockwave_prove(C_f).  Each
+//               chain is a sequence of small dependent launches and host round trips that leaves the GPU mostly idle on its own.
+//               Events: side_ev[62] tensor code final (main -> helper2), [63] inner commitments final, [60] query answers final (-> main).
+struct OpenRun {
+    hobbit_ctx *ctx; const hobbit_F *d_poly; size_t N; const hobbit_commitment *c; const hobbit_F *h_x; int queries; hobbit_open_out *o; bool full, overlapped;
+    OpenTrace tr; StageScope sc;
+    int K, trs, logK, logc, R1, R3; size_t M, cols, rows2, big, nc_el;
+    F *d_aggr, *BIG, *Mp, *C, *Tcm, *d_b, *d_bb, *d_s, *d_ev, *d_ac, *d_b1, *tmpv, *encf, *encc; uint64_t *tmpi; uint8_t *lvf, *lvc;       // device arena
+    std::vector<F> beta, sv, r1; std::vector<uint32_t> qc, qr; std::vector<uint64_t> Iv; F s2, a; size_t nnz = 0;      // host: beta over the chunk variables, the libc draws, buff2's length
+    hobbit_F *Q1, *Q2, *Q3, *Q4, *Q5, *Rr1, *Rr2, *Rr3, *Rr4, *Rr5;                                                    // the output cursors of P1..P5
+    std::thread q_thread, sp_thread; ShockPlan plan_c; int sp_rc = 0;      // overlapped only: the hand-over of the query answers, shockwave_prove(C_c) with its libc draws
+    OpenRun(hobbit_ctx *ctx_, const hobbit_F *d_poly_, size_t N_, const hobbit_commitment *c_, const hobbit_F *h_x_, int queries_, hobbit_open_out *o_, bool full_)
+        : ctx(ctx_), d_poly(d_poly_), N(N_), c(c_), h_x(h_x_), queries(queries_), o(o_), full(full_), tr(ctx_), sc(ctx_) {
+        const char *ot_env = getenv("HOBBIT_OPEN_THREADS");
+        overlapped = full && o->sp_c && !(ot_env && ot_env[0] == '0') && ctx->prof_on != 1 && !tr.drain;
     }
-    return rc;
-}
-static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
-                          bool full) {
-    if ((!c && !dims) || !o || queries <= 0 || queries >= (1 << 20) || (full && (!o->sp_c || !o->sp_f))) return ctx->fail(HOBBIT_EINVAL, "open: bad arguments");
-    if (!c && (o->reply || o->paths)) return ctx->fail(HOBBIT_EINVAL, "open_from_aggregate: replies and paths come from the tensor shards, not from here");
-    OpenTrace tr(ctx);
-    tr.mark("entry (stream drain)");
-    if (c && !c->lin) return ctx->fail(HOBBIT_EINVAL, "open_core: only the RS x expander (linear_time) code is built");
-    const int K = c ? c->K : dims[0], trs = c ? c->trs : dims[1];
-    if (K <= 0 || trs < 4 || N % (size_t)K) return ctx->fail(HOBBIT_EINVAL, "open: bad K / trs");
-    const size_t M = N / (size_t)K, cols = 2 * M / (size_t)trs, rows2 = 2 * (size_t)trs, big = rows2 * cols;
-    const int logK = ilog2_exact((size_t)K), logc = ilog2_exact(cols), R1 = ilog2_exact(rows2), R3 = R1 + logc;
-    if (logK < 0 || (c && (M != c->M || cols != c->cols)) || logc != 12 || R1 < 0) return ctx->fail(HOBBIT_EINVAL, "open_core: needs K a power of two and 4096-point row codes");
-    // beta over the chunk variables (precompute_beta, host: K <= 64 entries) and the r_v[0] draw (:619-623)
-    std::vector<F> beta((size_t)K); beta[0] = fmake(1);
-    if (c) for (int i = 0; i < logK; i++) for (size_t j = ((size_t)1 << i); j-- > 0;) { F t = fmul(cF(h_x)[logK - 1 - i], beta[j]); beta[2 * j + 1] = t; beta[2 * j] = fsub(beta[j], t); }
-    { F rv0 = fmake((uint64_t)random()); rv0 = fadd(rv0, fmake((uint64_t)rand())); memcpy(&o->scalars[0], &rv0, sizeof(F)); }   // generate_randomness(1)
-    StageScope sc(ctx);
-    // device arena
-    F *arena = nullptr;
-    // + the two inner shockwave commitments kept for the later shockwave_prove: encoded matrices (2M and 2*trs*cols F) and their trees
-    const size_t nc_el = (size_t)trs * cols, sw_el = 2 * M + 2 * nc_el + 2 * (2 * M / 32 + 2 * nc_el / 32) * 2 + 64;
-    const size_t n_el = M + 4 * big + 2 * cols + 4 * rows2 + 2 * (size_t)queries + 128 + sw_el;
-    HB_TRY(ctx->workspace3(n_el * sizeof(F), (void **)&arena));
-    {   // size the shared scratch buffers once for the largest user below (the 4M-element sumchecks, the 32-row long FFTs of
+    ~OpenRun() { for (std::thread *t : {&sp_thread, &q_thread}) if (t->joinable()) t->join(); }       // every return path joins its threads
+    int dims_beta_first_draw(const int *dims) {
+        tr.mark("entry (stream drain)");
+        if (c && !c->lin) return ctx->fail(HOBBIT_EINVAL, "open_core: only the RS x expander (linear_time) code is built");
+        K = c ? c->K : dims[0]; trs = c ? c->trs : dims[1];
+        if (K <= 0 || trs < 4 || N % (size_t)K) return ctx->fail(HOBBIT_EINVAL, "open: bad K / trs");
+        M = N / (size_t)K; cols = 2 * M / (size_t)trs; rows2 = 2 * (size_t)trs; big = rows2 * cols; nc_el = (size_t)trs * cols;
+        logK = ilog2_exact((size_t)K); logc = ilog2_exact(cols); R1 = ilog2_exact(rows2); R3 = R1 + logc;
+        if (logK < 0 || (c && (M != c->M || cols != c->cols)) || logc != 12 || R1 < 0) return ctx->fail(HOBBIT_EINVAL, "open_core: needs K a power of two and 4096-point row codes");
+        // beta over the chunk variables (precompute_beta, host: K <= 64 entries) and the r_v[0] draw (:619-623), the first libc draw of the call
+        beta.resize((size_t)K); beta[0] = fmake(1);
+        if (c) for (int i = 0; i < logK; i++) for (size_t j = ((size_t)1 << i); j-- > 0;) { F t = fmul(cF(h_x)[logK - 1 - i], beta[j]); beta[2 * j + 1] = t; beta[2 * j] = fsub(beta[j], t); }
+        F rv0 = fmake((uint64_t)random()); rv0 = fadd(rv0, fmake((uint64_t)rand())); memcpy(&o->scalars[0], &rv0, sizeof(F));   // generate_randomness(1)
+        return 0;
+    }
+    int size_scratch_and_lay_out_arena() {
+        F *arena = nullptr;
+        // + the two inner shockwave commitments kept for the later shockwave_prove: encoded matrices (2M and 2*trs*cols F) and their trees
+        const size_t sw_el = 2 * M + 2 * nc_el + 2 * (2 * M / 32 + 2 * nc_el / 32) * 2 + 64;
+        const size_t n_el = M + 4 * big + 2 * cols + 4 * rows2 + 2 * (size_t)queries + 128 + sw_el;
+        HB_TRY(ctx->workspace3(n_el * sizeof(F), (void **)&arena));
+        // size the shared scratch buffers once for the largest user below (the 4M-element sumchecks, the 32-row long FFTs of
         // the inner commitments): growing them step by step frees and re-maps device memory several times per call
         void *dummy;
         const size_t sc_need = (3 * big / 2 + 3 * 1024 + 64) * sizeof(F), fft_need = (size_t)2 * nc_el * sizeof(F);
@@ -2689,127 +2694,117 @@ static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
         // lands in the NEXT call, measured on the second open of a process.)
         if (full) HB_TRY(ctx->workspace4((shockwave_nested_elems(nc_el / 32) + shockwave_own_elems(nc_el / 32, 32)) * sizeof(F), &dummy));
         HB_TRY(ctx->pinned(std::max((size_t)queries * (sizeof(F) + 8) + 4096, (WHIR_DIN * 6 + WHIR_DRES) * sizeof(F)), &dummy));
+        tr.mark("scratch sizing");
+        if (tr.on) fprintf(stderr, "[hobbit open] scratch at entry: ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws_bytes, ctx->ws2_bytes, ctx->ws3_bytes, ctx->ws4_bytes, ctx->pin_bytes);
+        d_aggr = arena; BIG = d_aggr + M; Tcm = BIG + big; d_b = Tcm + big; d_bb = d_b + big; d_s = d_bb + big; d_ev = d_s + cols; d_ac = d_ev + cols; d_b1 = d_ac + rows2;
+        Mp = BIG; C = BIG + nc_el;
+        tmpv = d_b1 + rows2; tmpi = reinterpret_cast<uint64_t *>(tmpv + queries + 1);                 // the sparse buff2: (index, value) lists
+        encf = d_b1 + rows2 + 2 * (size_t)queries + 64; encc = encf + 2 * M;                          // the inner commitments' encoded matrices ...
+        lvf = reinterpret_cast<uint8_t *>(encc + 2 * nc_el); lvc = lvf + 64 * (2 * M / 32);           // ... and their trees
+        Q1 = o->qpoly; Q2 = Q1 + 3 * R1; Q3 = Q2 + 3 * logc; Q4 = Q3 + 3 * R3; Q5 = Q4 + 3 * R3;
+        Rr1 = o->r; Rr2 = Rr1 + R1; Rr3 = Rr2 + logc; Rr4 = Rr3 + R3; Rr5 = Rr4 + R3;
+        tr.mark("beta + arena");
+        return 0;
     }
-    tr.mark("scratch sizing");
-    if (tr.on) fprintf(stderr, "[hobbit open] scratch at entry: ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws_bytes, ctx->ws2_bytes, ctx->ws3_bytes, ctx->ws4_bytes, ctx->pin_bytes);
-    F *d_aggr = arena, *BIG = d_aggr + M, *Tcm = BIG + big, *d_b = Tcm + big, *d_bb = d_b + big, *d_s = d_bb + big, *d_ev = d_s + cols,
-      *d_ac = d_ev + cols, *d_b1 = d_ac + rows2;
-    F *Mp = BIG, *C = BIG + (size_t)trs * cols;
-    tr.mark("beta + arena");
-    if (c) HB_TRY(hobbit_aggregate(ctx, d_poly, N, reinterpret_cast<const hobbit_F *>(beta.data()), K, reinterpret_cast<hobbit_F *>(d_aggr)));   // _aggregate axpy (:258-272)
-    else HB_TRY(launch_copy(ctx, d_aggr, d_poly, M * sizeof(F)));
-    // compute_tensorcode(aggr) (:277): M' = row FFTs (row-major), codeword-major copy, expander encode, parity half back to row-major C
-    tr.mark("beta, arena, aggregate");
-    HB_TRY(fft_rows(ctx, d_aggr, cols / 2, (uint32_t)(cols / 2), Mp, cols, 1, logc, false, 1, (uint32_t)trs, 0, 0));
-    tr.mark("row FFTs");
-    HB_TRY(launch_transpose(ctx, Mp, 0, (uint32_t)trs, (uint32_t)cols, Tcm, 0, rows2, 1));
-    tr.mark("transpose");
-    if (ctx->code.n != trs) { long long l; HB_TRY(hobbit_graph_finalize(ctx, trs, &l)); }
-    HB_TRY(launch_encode(ctx, Tcm, rows2, Tcm, rows2, trs, cols, 0));
-    tr.mark("encode");
-    HB_TRY(launch_transpose_ld(ctx, Tcm + trs, 0, rows2, (uint32_t)cols, (uint32_t)trs, C, 0, cols, 1));
-    tr.mark("aggregate+tensorcode");
+    int aggregate_and_tensor_code() {
+        if (c) HB_TRY(hobbit_aggregate(ctx, d_poly, N, reinterpret_cast<const hobbit_F *>(beta.data()), K, reinterpret_cast<hobbit_F *>(d_aggr)));   // _aggregate axpy (:258-272)
+        else HB_TRY(launch_copy(ctx, d_aggr, d_poly, M * sizeof(F)));
+        // compute_tensorcode(aggr) (:277): M' = row FFTs (row-major), codeword-major copy, expander encode, parity half back to row-major C
+        tr.mark("beta, arena, aggregate");
+        HB_TRY(fft_rows(ctx, d_aggr, cols / 2, (uint32_t)(cols / 2), Mp, cols, 1, logc, false, 1, (uint32_t)trs, 0, 0));
+        tr.mark("row FFTs");
+        HB_TRY(launch_transpose(ctx, Mp, 0, (uint32_t)trs, (uint32_t)cols, Tcm, 0, rows2, 1));
+        tr.mark("transpose");
+        if (ctx->code.n != trs) { long long l; HB_TRY(hobbit_graph_finalize(ctx, trs, &l)); }
+        HB_TRY(launch_encode(ctx, Tcm, rows2, Tcm, rows2, trs, cols, 0));
+        tr.mark("encode");
+        HB_TRY(launch_transpose_ld(ctx, Tcm + trs, 0, rows2, (uint32_t)cols, (uint32_t)trs, C, 0, cols, 1));
+        tr.mark("aggregate+tensorcode");
+        return 0;
+    }
     // _aggregate's inner commitments (src/Our_PC.cpp:274-287): C_f = shockwave_commit(aggr, 32), C_c = shockwave_commit(parity half, 32)
-    F *sw = d_b1 + rows2 + 2 * (size_t)queries + 64;
-    F *encf = sw, *encc = encf + 2 * M;
-    uint8_t *lvf = nullptr, *lvc = nullptr;
-    // The open as a dependency graph rather than a list (HOBBIT_OPEN_THREADS=0, a full per-kernel profile (mode 1) or HOBBIT_TRACE keep
-    // the reference's order on one thread and one stream).  After the aggregate's tensor code four things are independent:
-    //   A  the two inner commitments -- needed only by the shockwave_prove calls at the very end: queued on helper2's stream;
-    //   B  the query answers -- feed nothing: queued behind A on the same stream;
-    //   C  P1 -> P2 -- start from constants, every libc draw they use is taken up front below: this thread, this context;
-    //   D  P3 -- likewise; beside C on the helper context from a second thread only when HOBBIT_OPEN_P3_THREAD=1 (measured neutral).
-    // P4 needs C and D; after it shockwave_prove(C_c) (helper context, second thread, its libc draws taken here first) runs beside
-    // P5 -> shockwave_prove(C_f).  Each of these chains is a sequence of small dependent launches and host round trips that leaves the
-    // GPU mostly idle on its own.  DESIGN.md section 4 has the A/B of every step.
-    const char *ot_env = getenv("HOBBIT_OPEN_THREADS");
-    const bool par = full && o->sp_c && !(ot_env && ot_env[0] == '0') && ctx->prof_on != 1 && !tr.drain;
-    if (par) {
-        for (hobbit_ctx **h : {&ctx->helper, &ctx->helper2}) if (!*h) {
-            if (hobbit_ctx_create(ctx->device, h) != 0) return ctx->fail(HOBBIT_EHIP, "open: helper context creation failed");
-            (*h)->sync_mode = ctx->sync_mode;
+    int inner_commitments() {
+        hobbit_F *aggr = reinterpret_cast<hobbit_F *>(d_aggr), *parity = reinterpret_cast<hobbit_F *>(C), *ef = reinterpret_cast<hobbit_F *>(encf), *ec = reinterpret_cast<hobbit_F *>(encc);
+        if (overlapped) {
+            for (hobbit_ctx **h : {&ctx->helper, &ctx->helper2}) if (!*h) {
+                if (hobbit_ctx_create(ctx->device, h) != 0) return ctx->fail(HOBBIT_EHIP, "open: helper context creation failed");
+                (*h)->sync_mode = ctx->sync_mode;
+            }
+            HB_TRY(ctx->side_init());
+            hobbit_ctx *hc = ctx->helper2;
+            HB_CHECK(ctx, hipEventRecord(ctx->side_ev[62], ctx->stream)); HB_CHECK(ctx, hipStreamWaitEvent(hc->stream, ctx->side_ev[62], 0));
+            if (hobbit_shockwave_commit(hc, aggr, M, 32, ef, lvf) || hobbit_shockwave_commit(hc, parity, nc_el, 32, ec, lvc)) return ctx->fail(HOBBIT_EHIP, hc->err);
+            HB_CHECK(ctx, hipEventRecord(ctx->side_ev[63], hc->stream));            // their roots are read in start_prove_cc, behind this event
+        } else {
+            HB_TRY(hobbit_shockwave_commit(ctx, aggr, M, 32, ef, lvf));
+            HB_TRY(hobbit_shockwave_commit(ctx, parity, nc_el, 32, ec, lvc));
+            HB_TRY(read_roots());
         }
-        HB_TRY(ctx->side_init());
+        tr.mark("shockwave_commit C_f, C_c");
+        return 0;
     }
-    const char *oc_env = getenv("HOBBIT_OPEN_COMMITS_SIDE");
-    const bool commits_side = par && !(oc_env && oc_env[0] == '0');
-    lvf = reinterpret_cast<uint8_t *>(encc + 2 * nc_el); lvc = lvf + 64 * (2 * M / 32);
-    if (commits_side) {
-        hobbit_ctx *hc = ctx->helper2;
-        HB_CHECK(ctx, hipEventRecord(ctx->side_ev[62], ctx->stream)); HB_CHECK(ctx, hipStreamWaitEvent(hc->stream, ctx->side_ev[62], 0));
-        if (hobbit_shockwave_commit(hc, reinterpret_cast<hobbit_F *>(d_aggr), M, 32, reinterpret_cast<hobbit_F *>(encf), lvf) ||
-            hobbit_shockwave_commit(hc, reinterpret_cast<hobbit_F *>(C), nc_el, 32, reinterpret_cast<hobbit_F *>(encc), lvc)) return ctx->fail(HOBBIT_EHIP, hc->err);
-        HB_CHECK(ctx, hipEventRecord(ctx->side_ev[63], hc->stream));
-    } else {
-        HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(d_aggr), M, 32, reinterpret_cast<hobbit_F *>(encf), lvf));
-        HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(C), nc_el, 32, reinterpret_cast<hobbit_F *>(encc), lvc));
-        if (o->roots) {
-            // (asynchronous: complete at the next of the many synchronisation points below)
-            HB_TRY(d2h_staged(ctx, o->roots, lvf + 32 * (2 * (2 * M / 32) - 2), 32));
-            HB_TRY(d2h_staged(ctx, o->roots + 32, lvc + 32 * (2 * (2 * nc_el / 32) - 2), 32));
+    int read_roots() {      // (asynchronous: complete at the next of the many synchronisation points that follow)
+        if (!o->roots) return 0;
+        HB_TRY(d2h_staged(ctx, o->roots, lvf + 32 * (2 * (2 * M / 32) - 2), 32));
+        return d2h_staged(ctx, o->roots + 32, lvc + 32 * (2 * (2 * nc_el / 32) - 2), 32);
+    }
+    // Every libc draw of the opening after r_v[0], in the reference's order -- queries (:633-641), s (src/PC_utils.cpp:293), r1
+    // (prove_linear_code's generate_randomness, src/sumcheck.cpp:3225), s2 (:331), a (:342) -- none depends on device data, and nothing between
+    // them draws.  Taken here, while the GPU still works through the aggregate's tensor code and inner commitments queued above: the GPU
+    // never waits for the host later.  (shockwave_prove's own draws follow P4, where the reference runs that proof.)
+    void libc_draws() {
+        qc.resize(queries); qr.resize(queries); Iv.resize(queries); sv.resize(cols); r1.resize(R1);
+        for (int q = 0; q < queries; q++) { qc[q] = (uint32_t)(rand() % (long)cols); qr[q] = (uint32_t)(rand() % (long)rows2); Iv[q] = qc[q] + cols * (uint64_t)qr[q]; }
+        sv[0] = fmake((uint64_t)random()); o->scalars[1] = *reinterpret_cast<hobbit_F *>(&sv[0]);
+        { F cst = fmake(0); for (int i = 0; i < R1; i++) { if (i % 100 == 0) cst = fmake((uint64_t)random()); r1[i] = fadd(cst, fmake((uint64_t)rand())); } }
+        s2 = fmake((uint64_t)random()); o->scalars[2] = *reinterpret_cast<const hobbit_F *>(&s2);
+        a = fmake((uint64_t)random()); o->scalars[3] = *reinterpret_cast<const hobbit_F *>(&a);
+        if (o->cols) memcpy(o->cols, qc.data(), 4 * (size_t)queries);
+        if (o->rows) memcpy(o->rows, qr.data(), 4 * (size_t)queries);
+        tr.mark("libc draws");
+    }
+    // replies (:291-305) and Merkle paths (:645-647) at the drawn positions.  Without a commitment (multi-GPU open) they are the caller's business.
+    int query_answers() {
+        if (c && overlapped) HB_TRY(query_answers_on_helper2());
+        else if (c) {
+            if (o->reply) HB_TRY(hobbit_commitment_gather(ctx, c, qr.data(), qc.data(), (size_t)queries, o->reply));
+            if (o->paths) HB_TRY(hobbit_commitment_paths(ctx, c, qc.data(), qr.data(), (size_t)queries, o->paths));
         }
+        tr.mark("queries: gather + paths queued");
+        return 0;
     }
-    tr.mark("shockwave_commit C_f, C_c");
-    // Every libc draw of this function, in the reference's order -- queries (:633-641), s (src/PC_utils.cpp:293), r1 (prove_linear_code's
-    // generate_randomness, src/sumcheck.cpp:3225), s2 (:331), a (:342) -- none depends on device data, and nothing between them draws.
-    // Taken here, while the GPU still works through the aggregate's tensor code and inner commitments queued above, together with
-    // the host tables derived from them (powers of s, powers of s2 at the queried positions): the GPU never waits for the host later.
-    std::vector<uint32_t> qc(queries), qr(queries); std::vector<uint64_t> Iv(queries);
-    for (int q = 0; q < queries; q++) { qc[q] = (uint32_t)(rand() % (long)cols); qr[q] = (uint32_t)(rand() % (long)rows2); Iv[q] = qc[q] + cols * (uint64_t)qr[q]; }
-    std::vector<F> sv(cols);
-    sv[0] = fmake((uint64_t)random()); o->scalars[1] = *reinterpret_cast<hobbit_F *>(&sv[0]);
-    std::vector<F> r1(R1);
-    { F cst = fmake(0); for (int i = 0; i < R1; i++) { if (i % 100 == 0) cst = fmake((uint64_t)random()); r1[i] = fadd(cst, fmake((uint64_t)rand())); } }
-    const F s2 = fmake((uint64_t)random()); o->scalars[2] = *reinterpret_cast<const hobbit_F *>(&s2);
-    const F a = fmake((uint64_t)random()); o->scalars[3] = *reinterpret_cast<const hobbit_F *>(&a);
-    if (o->cols) memcpy(o->cols, qc.data(), 4 * (size_t)queries);
-    if (o->rows) memcpy(o->rows, qr.data(), 4 * (size_t)queries);
-    tr.mark("libc draws");
-    // B: the query answers feed nothing below.  With the inner commitments on helper2's stream they are queued behind them there (the
-    // staging arena stays this context's; scratch is lent from helper2), off the chain P1 -> ... -> shockwave_prove(C_f).
-    const char *qs_env = getenv("HOBBIT_OPEN_QUERIES_SIDE");
-    const bool queries_side = commits_side && c && !(qs_env && qs_env[0] == '0');
-    // The answers are 7 MB (replies + Merkle paths): handing them from the pinned staging arena to the caller's buffers at the closing
-    // synchronisation cost 0.7 ms of single-threaded memcpy at the very end of the critical path.  They are final long before that, so a
-    // short-lived thread waits for their event and copies them out while the main chain runs.
-    std::thread q_thread; struct QJoiner { std::thread &t; ~QJoiner() { if (t.joinable()) t.join(); } } q_join{q_thread};
-    if (queries_side) {
-        hobbit_ctx *hc = ctx->helper2; hipStream_t mainS = ctx->stream;
-        const size_t n_def0 = ctx->deferred.size();
+    // The answers feed nothing below: queued behind the inner commitments on helper2's stream (the staging arena stays this context's;
+    // scratch is lent from helper2), off the chain P1 -> ... -> shockwave_prove(C_f).
+    int query_answers_on_helper2() {
+        hobbit_ctx *hc = ctx->helper2; const size_t n_def0 = ctx->deferred.size();
         const size_t lend = (size_t)queries * ((size_t)K * sizeof(F) + 8 + 32 * 40) + 4096;
         void *lp; if (hc->workspace2(lend, &lp) != 0) return ctx->fail(HOBBIT_ENOMEM, hc->err);      // (in stream order behind the commitments' last use of it)
+        hipStream_t mainS = ctx->stream; int rc = 0;
         ctx->stream = hc->stream; ctx->ws_lent = lp; ctx->ws_lent_bytes = lend;
-        int rc = 0;
-        if (o->reply) rc = hobbit_commitment_gather(ctx, c, qr.data(), qc.data(), (size_t)queries, o->reply);            // replies (:291-305)
-        if (!rc && o->paths) rc = hobbit_commitment_paths(ctx, c, qc.data(), qr.data(), (size_t)queries, o->paths);      // Merkle paths (:645-647)
-        ctx->stream = mainS; ctx->ws_lent = nullptr; ctx->ws_lent_bytes = 0;
+        if (o->reply) rc = hobbit_commitment_gather(ctx, c, qr.data(), qc.data(), (size_t)queries, o->reply);
+        if (!rc && o->paths) rc = hobbit_commitment_paths(ctx, c, qc.data(), qr.data(), (size_t)queries, o->paths);
+        ctx->stream = mainS; ctx->ws_lent = nullptr; ctx->ws_lent_bytes = 0;                         // restored before any return
         if (rc) return rc;
         HB_CHECK(ctx, hipEventRecord(ctx->side_ev[60], hc->stream));
-        const char *qe_env = getenv("HOBBIT_OPEN_QUERIES_EAGER");
-        if (!(qe_env && qe_env[0] == '0') && ctx->deferred.size() > n_def0) {
-            std::vector<hobbit_ctx::Deferred> qdef(ctx->deferred.begin() + (long)n_def0, ctx->deferred.end());
-            try {
-                q_thread = std::thread([qdef, ev = ctx->side_ev[60], dev = ctx->device] {
-                    hipSetDevice(dev);
-                    if (hipEventSynchronize(ev) != hipSuccess) return;          // (the closing synchronisation reports the error)
-                    for (const auto &d : qdef) memcpy(d.dst, d.src, d.bytes);
-                });
-                ctx->deferred.resize(n_def0);                                   // the thread owns these hand-overs now
-            } catch (const std::exception &) { /* no thread: the closing hand-over copies them as before */ }
-        }
-    } else {
-        if (c && o->reply) HB_TRY(hobbit_commitment_gather(ctx, c, qr.data(), qc.data(), (size_t)queries, o->reply));     // replies (:291-305)
-        if (c && o->paths) HB_TRY(hobbit_commitment_paths(ctx, c, qc.data(), qr.data(), (size_t)queries, o->paths));      // Merkle paths (:645-647)
+        // The answers are 7 MB: handing them from the pinned staging arena to the caller's buffers at the closing synchronisation cost
+        // 0.7 ms of single-threaded memcpy at the very end of the critical path.  They are final long before that, so a short-lived
+        // thread waits for their event and copies them out while the main chain runs.
+        if (ctx->deferred.size() == n_def0) return 0;
+        std::vector<hobbit_ctx::Deferred> qdef(ctx->deferred.begin() + (long)n_def0, ctx->deferred.end());
+        try {
+            q_thread = std::thread([qdef, ev = ctx->side_ev[60], dev = ctx->device] {
+                hipSetDevice(dev);
+                if (hipEventSynchronize(ev) != hipSuccess) return;          // (the closing synchronisation reports the error)
+                for (const auto &d : qdef) memcpy(d.dst, d.src, d.bytes);
+            });
+            ctx->deferred.resize(n_def0);                                   // the thread owns these hand-overs now
+        } catch (const std::exception &) { /* no thread: the closing hand-over copies them */ }
+        return 0;
     }
-    tr.mark("queries: gather + paths queued");
-    for (size_t i = 1; i < cols; i++) sv[i] = fmul(sv[i - 1], sv[0]);                                                   // s powers (:293-297)
-    HB_TRY(h2d_staged(ctx, d_s, sv.data(), cols * sizeof(F)));
-    // buff2: s2 powers at the queried positions, last write wins (:331-336).  P3 takes it as a sorted (index, value) list -- 5900 non-zeros
-    // of 2^25 -- unless HOBBIT_OPEN_SPARSE_P3=0 asks for the dense table.
-    const char *sp_env = getenv("HOBBIT_OPEN_SPARSE_P3"); const bool sparse_p3 = !(sp_env && sp_env[0] == '0');
-    F *const tmpv = d_b1 + rows2; uint64_t *const tmpi = reinterpret_cast<uint64_t *>(tmpv + queries + 1);      // arena tail
-    size_t nnz = 0;
-    {
+    int host_tables() {
+        for (size_t i = 1; i < cols; i++) sv[i] = fmul(sv[i - 1], sv[0]);                                                   // s powers (:293-297)
+        HB_TRY(h2d_staged(ctx, d_s, sv.data(), cols * sizeof(F)));
+        // buff2: s2 powers at the queried positions, last write wins (:331-336).  P3 takes it as a sorted (index, value) list: 5900 non-zeros of 2^25.
         // (position, draw number) sorted as one key: the last draw of a position is the one whose power stays (a std::map here cost 0.6 ms of host time)
         std::vector<uint64_t> key((size_t)queries); std::vector<F> pws((size_t)queries);
         F pw = s2;
@@ -2821,119 +2816,122 @@ static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
         nnz = idx.size();
         HB_TRY(h2d_staged(ctx, tmpv, val.data(), val.size() * sizeof(F)));
         HB_TRY(h2d_staged(ctx, tmpi, idx.data(), idx.size() * 8));
-        if (!sparse_p3) {
-            HB_TRY(launch_zero(ctx, d_b, big * sizeof(F)));
-            HB_TRY(launch_scatter(ctx, tmpi, tmpv, idx.size(), d_b));
-        }
+        tr.mark("queries+gather+paths, host tables");
+        return 0;
     }
-    tr.mark("queries+gather+paths, host tables");
-    hobbit_F *Q = o->qpoly, *Rr = o->r;
-    hobbit_F *const Q1 = Q, *const Rr1 = Rr, *const Q2 = Q1 + 3 * R1, *const Rr2 = Rr1 + R1, *const Q3 = Q2 + 3 * logc, *const Rr3 = Rr2 + logc;
-    const hobbit_F *r_p1 = Rr1, *r_p2 = Rr2, *r_p3 = Rr3;
-    hobbit_F p17 = {021, 0}, p121 = {121, 0};
-    // C: aggr_c = [M' | C] . s (:298-309); P1 = prove_linear_code(aggr_c, trs) with r1 = generate_randomness(log2 2trs) (:310;
+    // aggr_c = [M' | C] . s (:298-309); P1 = prove_linear_code(aggr_c, trs) with r1 = generate_randomness(log2 2trs) (:310;
     // src/sumcheck.cpp:3223-3235); evals = beta(P1.r)^T [M' | C] (:311-320); P2 = sumcheck(s, evals, F(021) -- octal) (:322)
-    auto chain_c = [=](hobbit_ctx *cx) -> int {
-        HB_TRY(launch_matvec_rows(cx, BIG, rows2, cols, d_s, d_ac));
-        HB_TRY(hobbit_prove_linear_code(cx, reinterpret_cast<hobbit_F *>(d_ac), rows2, trs, reinterpret_cast<const hobbit_F *>(r1.data()), Q1, Rr1, o->vr, o->fin));
-        HB_TRY(hobbit_eq_table(cx, r_p1, R1, reinterpret_cast<hobbit_F *>(d_b1)));
-        HB_TRY(launch_vecmat(cx, BIG, rows2, cols, d_b1, d_ev));
-        return hobbit_sumcheck2(cx, reinterpret_cast<hobbit_F *>(d_s), reinterpret_cast<hobbit_F *>(d_ev), cols, &p17, Q2, Rr2, o->vr + 2, o->fin + 1);
-    };
-    // D: P3 (:339) against buff2 (built above).  On the helper context from a second thread while this thread runs C on the main context
-    // (prove_linear_code needs the context's expander graphs; a plain sumcheck needs nothing).
-    auto chain_d = [=](hobbit_ctx *cx) -> int {
-        if (sparse_p3) return launch_sumcheck2_sparse(cx, BIG, tmpi, tmpv, nnz, big, *cF(&p121), mF(Q3), mF(Rr3), mF(o->vr + 4), mF(o->fin + 2));
-        return hobbit_sumcheck2(cx, reinterpret_cast<hobbit_F *>(BIG), reinterpret_cast<hobbit_F *>(d_b), big, &p121, Q3, Rr3, o->vr + 4, o->fin + 2);
-    };
-    const char *p3_env = getenv("HOBBIT_OPEN_P3_THREAD");
-    const bool p3_thread = par && p3_env && p3_env[0] == '1';        // measured neutral (36.58 vs 36.55 ms per step): off unless asked for
-    std::thread d_thread; int d_rc = 0;
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } d_join{d_thread};          // every return path below joins
-    if (p3_thread) {
-        hobbit_ctx *hc = ctx->helper;
-        HB_CHECK(ctx, hipEventRecord(ctx->side_ev[61], ctx->stream)); HB_CHECK(ctx, hipStreamWaitEvent(hc->stream, ctx->side_ev[61], 0));   // BIG, buff2 are final for the helper
-        try { d_thread = std::thread([hc, &chain_d, &d_rc] { hipSetDevice(hc->device); d_rc = chain_d(hc); }); }
-        catch (const std::exception &e) { return ctx->fail(HOBBIT_ESTATE, std::string("open: cannot start the helper thread: ") + e.what()); }
+    int p1_evals_p2() {
+        hobbit_F p17 = {021, 0};
+        HB_TRY(launch_matvec_rows(ctx, BIG, rows2, cols, d_s, d_ac));
+        HB_TRY(hobbit_prove_linear_code(ctx, reinterpret_cast<hobbit_F *>(d_ac), rows2, trs, reinterpret_cast<const hobbit_F *>(r1.data()), Q1, Rr1, o->vr, o->fin));
+        HB_TRY(hobbit_eq_table(ctx, Rr1, R1, reinterpret_cast<hobbit_F *>(d_b1)));
+        HB_TRY(launch_vecmat(ctx, BIG, rows2, cols, d_b1, d_ev));
+        HB_TRY(hobbit_sumcheck2(ctx, reinterpret_cast<hobbit_F *>(d_s), reinterpret_cast<hobbit_F *>(d_ev), cols, &p17, Q2, Rr2, o->vr + 2, o->fin + 1));
+        tr.mark("s, aggr_c, P1, evals, P2");
+        return 0;
     }
-    HB_TRY(chain_c(ctx));
-    tr.mark("s, aggr_c, P1, evals, P2");
-    if (p3_thread) {
-        d_thread.join();
-        if (d_rc) return ctx->fail(d_rc, std::string("P3 on the helper context: ") + ctx->helper->err);
-    } else {
-        HB_TRY(chain_d(ctx));
+    int p3() {              // P3 (:339) against the sparse buff2
+        hobbit_F p121 = {121, 0};
+        HB_TRY(launch_sumcheck2_sparse(ctx, BIG, tmpi, tmpv, nnz, big, *cF(&p121), mF(Q3), mF(Rr3), mF(o->vr + 4), mF(o->fin + 2)));
         tr.mark("buff2, P3");
+        return 0;
     }
-    { CHP q2 = cF(Q2); F c2 = fadd(fadd(q2[0], q2[1]), fadd(q2[2], q2[2])); o->checks[0] = feq(c2, cF(o->vr)[1]); }       // "Error recursion 1" (:323-326)
-    Q = Q3 + 3 * R3; Rr = Rr3 + R3;
-    // a, beta(P2.r | P1.r) + a * beta(P3.r) (:342-349); P4 against [M' | C] (:362); "Error recursion 2" (:364-367)
-    std::vector<hobbit_F> rcat(R3);
-    memcpy(rcat.data(), r_p2, sizeof(hobbit_F) * logc); memcpy(rcat.data() + logc, r_p1, sizeof(hobbit_F) * R1);
-    HB_TRY(launch_eq_pair_axpy(ctx, cF(rcat.data()), cF(r_p3), R3, a, d_bb, d_b));      // d_b = beta(r) + a * beta(P3.r), d_bb: scratch
-    hobbit_F p312 = {312, 0};
-    HB_TRY(hobbit_sumcheck2(ctx, reinterpret_cast<hobbit_F *>(d_b), reinterpret_cast<hobbit_F *>(BIG), big, &p312, Q, Rr, o->vr + 6, o->fin + 3));
-    const hobbit_F *r_p4 = Rr; CHP q4 = cF(Q);
-    { F c4 = fadd(fadd(q4[0], q4[1]), fadd(q4[2], q4[2])); F want = fadd(fmul(a, cF(o->vr)[4]), cF(o->vr)[3]); o->checks[1] = feq(c4, want); }
-    Q += 3 * R3; Rr += R3;
-    tr.mark("betas, P4");
-    // shockwave_prove(C_c, P4.r minus its last entry) (src/PC_utils.cpp:368): nothing after it depends on it (it only adds to the proof),
-    // and every challenge in it is a libc draw.  So its draws are taken HERE, where the reference takes them (ShockPlan), and the proof
-    // itself runs on the helper context from a second host thread, beside P5 and shockwave_prove(C_f) below -- three chains of small
-    // dependent launches and host round trips that each leave the GPU mostly idle.  HOBBIT_OPEN_THREADS=0, a full per-kernel
-    // profile (mode 1) or HOBBIT_TRACE keep everything on this thread.
-    if (queries_side) HB_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[60], 0));      // ... and the query answers (their read-back is staged)
-    if (commits_side) {                                                          // the inner commitments are complete from here on
-        HB_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[63], 0));
-        if (o->roots) {
-            HB_TRY(d2h_staged(ctx, o->roots, lvf + 32 * (2 * (2 * M / 32) - 2), 32));
-            HB_TRY(d2h_staged(ctx, o->roots + 32, lvc + 32 * (2 * (2 * nc_el / 32) - 2), 32));
-        }
+    // "Error recursion 1" (:323-326); a, beta(P2.r | P1.r) + a * beta(P3.r) (:342-349); P4 against [M' | C] (:362); "Error recursion 2" (:364-367)
+    int p4() {
+        { CHP q2 = cF(Q2); F c2 = fadd(fadd(q2[0], q2[1]), fadd(q2[2], q2[2])); o->checks[0] = feq(c2, cF(o->vr)[1]); }
+        std::vector<hobbit_F> rcat(R3); hobbit_F p312 = {312, 0};
+        memcpy(rcat.data(), Rr2, sizeof(hobbit_F) * logc); memcpy(rcat.data() + logc, Rr1, sizeof(hobbit_F) * R1);
+        HB_TRY(launch_eq_pair_axpy(ctx, cF(rcat.data()), cF(Rr3), R3, a, d_bb, d_b));      // d_b = beta(r) + a * beta(P3.r), d_bb: scratch
+        HB_TRY(hobbit_sumcheck2(ctx, reinterpret_cast<hobbit_F *>(d_b), reinterpret_cast<hobbit_F *>(BIG), big, &p312, Q4, Rr4, o->vr + 6, o->fin + 3));
+        { CHP q4 = cF(Q4); F c4 = fadd(fadd(q4[0], q4[1]), fadd(q4[2], q4[2])); F want = fadd(fmul(a, cF(o->vr)[4]), cF(o->vr)[3]); o->checks[1] = feq(c4, want); }
+        tr.mark("betas, P4");
+        return 0;
     }
-    const bool sp_threaded = par;
-    ShockPlan plan_c; std::thread sp_thread; int sp_rc = 0;
-    Joiner sp_join{sp_thread};                                                   // every return path below joins
-    if (sp_threaded) {
-        if (shockwave_plan(nc_el, 32, plan_c) != 0) return ctx->fail(HOBBIT_EINVAL, "open: C_c has no shockwave plan");
-        HB_TRY(ctx->sync());                                                     // C, encc, lvc and P4's challenges are final
-        hobbit_ctx *hc = ctx->helper;
-        if (commits_side) HB_CHECK(ctx, hipStreamWaitEvent(hc->stream, ctx->side_ev[63], 0));       // the inner commitments (helper2's stream)
-        const hobbit_F *rc4 = r_p4; const int rl = R3 - 1; hobbit_shockwave_out *oc = o->sp_c;
-        const hobbit_F *dC = reinterpret_cast<hobbit_F *>(C), *dE = reinterpret_cast<hobbit_F *>(encc); const uint8_t *dL = lvc; const size_t ncel = nc_el;
-        try {
-            sp_thread = std::thread([hc, dC, dE, dL, ncel, rc4, rl, oc, &plan_c, &sp_rc] {
-                hipSetDevice(hc->device);
-                sp_rc = shockwave_prove_run(hc, dC, dE, dL, ncel, 32, rc4, rl, oc, plan_c);
-            });
-        } catch (const std::exception &e) { return ctx->fail(HOBBIT_ESTATE, std::string("open: cannot start the helper thread: ") + e.what()); }
-    }
-    tr.mark("  plan C_c, drain, helper thread started");
-    // y1 = evaluate_vector(M', P4.r minus its last entry) (:372-373); P5 = prove_fft_matrix(initial tensor, r, y1) (:383)
-    F y1;
-    HB_TRY(hobbit_eval_vector(ctx, reinterpret_cast<hobbit_F *>(Mp), (size_t)trs * cols, r_p4, reinterpret_cast<hobbit_F *>(&y1)));
-    o->scalars[4] = *reinterpret_cast<hobbit_F *>(&y1);
-    tr.mark("  y1 = evaluate_vector");
-    HB_TRY(hobbit_prove_fft_matrix(ctx, reinterpret_cast<hobbit_F *>(d_aggr), (size_t)trs, cols / 2, r_p4, Q, Rr, o->vr + 8, o->fin + 4));
-    { CHP q5 = cF(Q); F c5 = fadd(fadd(q5[0], q5[1]), fadd(q5[2], q5[2])); o->checks[2] = feq(c5, y1); }
-    tr.mark("y1, P5");   // src/sumcheck.cpp:3016-3019
-    if (!full) return sc.finish();
-    if (!sp_threaded) {
-        // shockwave_prove(C_c, P4.r minus its last entry) (src/PC_utils.cpp:368) -- in the reference it runs before P5; P5 draws nothing
-        // from libc, so running it here leaves every draw where the reference has it
-        HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<hobbit_F *>(C), reinterpret_cast<hobbit_F *>(encc), lvc, nc_el, 32, r_p4, R3 - 1, o->sp_c));
+    int prove_cc() {        // shockwave_prove(C_c, P4.r minus its last entry) (src/PC_utils.cpp:368)
+        HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<hobbit_F *>(C), reinterpret_cast<hobbit_F *>(encc), lvc, nc_el, 32, Rr4, R3 - 1, o->sp_c));
         tr.mark("shockwave_prove C_c");
+        return 0;
+    }
+    // Overlapped, where the reference runs shockwave_prove(C_c): nothing after that proof depends on it and every challenge in it is a libc draw.
+    // So its draws are taken HERE, on the calling thread (ShockPlan); the proof runs on the helper context from a second host thread.
+    int start_prove_cc() {
+        if (overlapped) {
+            if (c) HB_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[60], 0));      // the query answers (their read-back is staged) ...
+            HB_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[63], 0));             // ... and the inner commitments are complete from here on
+            HB_TRY(read_roots());
+            if (shockwave_plan(nc_el, 32, plan_c) != 0) return ctx->fail(HOBBIT_EINVAL, "open: C_c has no shockwave plan");
+            HB_TRY(ctx->sync());                                                             // C, encc, lvc and P4's challenges are final ...
+            hobbit_ctx *hc = ctx->helper;
+            HB_CHECK(ctx, hipStreamWaitEvent(hc->stream, ctx->side_ev[63], 0));              // ... for the helper's stream too (the commitments ran on helper2's)
+            try {       // (this object outlives the thread: its destructor joins)
+                sp_thread = std::thread([this, hc] {
+                    hipSetDevice(hc->device);
+                    sp_rc = shockwave_prove_run(hc, reinterpret_cast<hobbit_F *>(C), reinterpret_cast<hobbit_F *>(encc), lvc, nc_el, 32, Rr4, R3 - 1, o->sp_c, plan_c);
+                });
+            } catch (const std::exception &e) { return ctx->fail(HOBBIT_ESTATE, std::string("open: cannot start the helper thread: ") + e.what()); }
+        }
+        tr.mark("  plan C_c, drain, helper thread started");
+        return 0;
+    }
+    // y1 = evaluate_vector(M', P4.r minus its last entry) (:372-373); P5 = prove_fft_matrix(initial tensor, r, y1) (:383)
+    int y1_p5() {
+        F y1;
+        HB_TRY(hobbit_eval_vector(ctx, reinterpret_cast<hobbit_F *>(Mp), nc_el, Rr4, reinterpret_cast<hobbit_F *>(&y1)));
+        o->scalars[4] = *reinterpret_cast<hobbit_F *>(&y1);
+        tr.mark("  y1 = evaluate_vector");
+        HB_TRY(hobbit_prove_fft_matrix(ctx, reinterpret_cast<hobbit_F *>(d_aggr), (size_t)trs, cols / 2, Rr4, Q5, Rr5, o->vr + 8, o->fin + 4));
+        { CHP q5 = cF(Q5); F c5 = fadd(fadd(q5[0], q5[1]), fadd(q5[2], q5[2])); o->checks[2] = feq(c5, y1); }
+        tr.mark("y1, P5");   // src/sumcheck.cpp:3016-3019
+        return 0;
     }
     // shockwave_prove(C_f, P5.randomness minus its last entry) (:384-385); P5.randomness = [sumcheck r | r1 = P4.r[logc .. logc+log2 trs)] (src/sumcheck.cpp:3021-3023)
-    std::vector<hobbit_F> x5((size_t)logc + (size_t)(R1 - 1));
-    memcpy(x5.data(), Rr, sizeof(hobbit_F) * (size_t)logc); memcpy(x5.data() + logc, r_p4 + logc, sizeof(hobbit_F) * (size_t)(R1 - 1));
-    HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<hobbit_F *>(d_aggr), reinterpret_cast<hobbit_F *>(encf), lvf, M, 32, x5.data(), (int)x5.size() - 1, o->sp_f));
-    tr.mark("shockwave_prove C_f");
-    if (sp_threaded) {
-        sp_thread.join();
-        if (sp_rc) return ctx->fail(sp_rc, std::string("shockwave_prove(C_c) on the helper context: ") + ctx->helper->err);
+    int prove_cf() {
+        std::vector<hobbit_F> x5((size_t)logc + (size_t)(R1 - 1));
+        memcpy(x5.data(), Rr5, sizeof(hobbit_F) * (size_t)logc); memcpy(x5.data() + logc, Rr4 + logc, sizeof(hobbit_F) * (size_t)(R1 - 1));
+        HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<hobbit_F *>(d_aggr), reinterpret_cast<hobbit_F *>(encf), lvf, M, 32, x5.data(), (int)x5.size() - 1, o->sp_f));
+        tr.mark("shockwave_prove C_f");
+        return 0;
     }
-    if (tr.on) fprintf(stderr, "[hobbit open] scratch at exit:  ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws_bytes, ctx->ws2_bytes, ctx->ws3_bytes, ctx->ws4_bytes, ctx->pin_bytes);
-    return sc.finish();
+};
+static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
+                          bool full) {
+    if ((!c && !dims) || !o || queries <= 0 || queries >= (1 << 20) || (full && (!o->sp_c || !o->sp_f))) return ctx->fail(HOBBIT_EINVAL, "open: bad arguments");
+    if (!c && (o->reply || o->paths)) return ctx->fail(HOBBIT_EINVAL, "open_from_aggregate: replies and paths come from the tensor shards, not from here");
+    OpenRun r(ctx, d_poly, N, c, h_x, queries, o, full);
+    HB_TRY(r.dims_beta_first_draw(dims));
+    HB_TRY(r.size_scratch_and_lay_out_arena());
+    HB_TRY(r.aggregate_and_tensor_code());
+    HB_TRY(r.inner_commitments());                   // overlapped: on helper2's stream
+    r.libc_draws();
+    HB_TRY(r.query_answers());                       // overlapped: behind them on helper2's stream, handed over by a short-lived thread
+    HB_TRY(r.host_tables());
+    HB_TRY(r.p1_evals_p2());
+    HB_TRY(r.p3());
+    HB_TRY(r.p4());
+    HB_TRY(r.start_prove_cc());                      // overlapped: helper2's work joins the main stream; shockwave_prove(C_c) on the helper context, second thread
+    HB_TRY(r.y1_p5());
+    if (!full) return r.sc.finish();
+    if (!r.overlapped) HB_TRY(r.prove_cc());         // serial: the reference runs it before P5; P5 draws nothing from libc, so every draw stays where the reference has it
+    HB_TRY(r.prove_cf());
+    if (r.overlapped) {
+        r.sp_thread.join();
+        if (r.sp_rc) return ctx->fail(r.sp_rc, std::string("shockwave_prove(C_c) on the helper context: ") + ctx->helper->err);
+    }
+    if (r.tr.on) fprintf(stderr, "[hobbit open] scratch at exit:  ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws_bytes, ctx->ws2_bytes, ctx->ws3_bytes, ctx->ws4_bytes, ctx->pin_bytes);
+    return r.sc.finish();
+}
+static int open_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
+                     bool full) {
+    const int rc = open_impl_body(ctx, d_poly, N, c, dims, h_x, queries, o, full);
+    if (rc) {
+        // an error return may leave work queued on the helper contexts' streams (inner commitments, query answers, their staged read-backs
+        // into THIS context's arena): drain them before the caller -- or the next call's StageScope -- re-uses those buffers
+        for (hobbit_ctx *h : {ctx->helper, ctx->helper2}) if (h) hipStreamSynchronize(h->stream);
+        if (ctx->side) hipStreamSynchronize(ctx->side);
+        hipStreamSynchronize(ctx->stream);
+    }
+    return rc;
 }
 int hobbit_open_core(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const hobbit_F *h_x, int queries, hobbit_open_out *o) {
     if (!c) return ctx->fail(HOBBIT_EINVAL, "open_core: null commitment");

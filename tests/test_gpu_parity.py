@@ -1233,11 +1233,14 @@ def test_open_standard_vs_oracle(hb, oracle, N, K):
 @pytest.mark.gpu
 def test_execution_modes_bit_identical(hb, monkeypatch):
     """The step as a dependency graph -- chunk groups' layout changes on a side stream beside the next group's row FFT
-    (HOBBIT_COMMIT_PIPE), shockwave_prove(C_c) on a helper context from a second host thread with its libc draws taken first
-    (HOBBIT_OPEN_THREADS), the inner commitments and the query answers on a third stream (HOBBIT_OPEN_COMMITS_SIDE, HOBBIT_OPEN_QUERIES_SIDE), P3 beside
-    P1/P2 (HOBBIT_OPEN_P3_THREAD), P3 against its second table as a sparse list (HOBBIT_OPEN_SPARSE_P3) --
-    and the plain list on one stream and one thread must produce the same commitment and the same transcript, message for message, and
-    leave the libc generator in the same state."""
+    (HOBBIT_COMMIT_PIPE: 0, the default, 4, 16), and the opening's overlapped schedule (the default: inner commitments and query answers
+    on a third stream, shockwave_prove(C_c) on a helper context from a second host thread with its libc draws taken first) --
+    and the plain list on one stream and one thread (HOBBIT_OPEN_THREADS=0, the serial schedule) must produce the same commitment and
+    the same transcript, message for message, and leave the libc generator in the same state: both schedules against every pipe depth.
+    That P3 against the sparse list equals P3 against the dense second table is test_open_standard_vs_oracle's: the CPU oracle restates
+    the reference's dense table, at this shape (1 << 24, 32) and six others, against the default (overlapped, sparse) opening.
+    The knob must do something: the transcript recorder is per calling thread, so it sees shockwave_prove(C_c)'s hashes in the serial
+    schedule only -- the overlapped record is the serial one with exactly that one block cut out."""
     import ctypes
     libc = ctypes.CDLL(None)
     N, K = 1 << 24, 32
@@ -1245,18 +1248,24 @@ def test_execution_modes_bit_identical(hb, monkeypatch):
     d = hb.fill_splitmix(N, 99)
     hb.rng_reset(); hb.expander_init_store(trs)
     x = splitmix_field(24, 5)
-    runs = []
-    for env in ({}, {"HOBBIT_COMMIT_PIPE": "0", "HOBBIT_OPEN_THREADS": "0", "HOBBIT_OPEN_SPARSE_P3": "0"}, {"HOBBIT_COMMIT_PIPE": "4", "HOBBIT_OPEN_COMMITS_SIDE": "0"},
-                {"HOBBIT_COMMIT_PIPE": "16", "HOBBIT_OPEN_P3_THREAD": "1", "HOBBIT_OPEN_QUERIES_SIDE": "0"}):
+    envs = ({}, {"HOBBIT_COMMIT_PIPE": "0", "HOBBIT_OPEN_THREADS": "0"}, {"HOBBIT_COMMIT_PIPE": "4"}, {"HOBBIT_COMMIT_PIPE": "16", "HOBBIT_OPEN_THREADS": "0"})
+    runs, recs = [], []
+    for env in envs:
         with monkeypatch.context() as m:
             for k, v in env.items():
                 m.setenv(k, v)
             c = hb.commit_standard((d, N), K, trs, 1)
             root = c.root().tobytes()
-            libc.srandom(31); a = hb.open_standard((d, N), c, x, 5900, want_paths=True)
+            libc.srandom(31)
+            hb.lib.hobbit_transcript_record(1)
+            a = hb.open_standard((d, N), c, x, 5900, want_paths=True)
+            hb.lib.hobbit_transcript_record(0)
             after = int(libc.random())
             c.free()
-        runs.append((root, a, after))
+        n = hb.lib.hobbit_transcript_count()
+        rec = np.zeros((n, 6), np.uint64)
+        hb.lib.hobbit_transcript_read(rec.ctypes.data, n)
+        runs.append((root, a, after)); recs.append(rec)
     root0, a0, after0 = runs[0]
     assert a0["checks"].tolist() == [1, 1, 1]
     for root, a, after in runs[1:]:
@@ -1266,6 +1275,13 @@ def test_execution_modes_bit_identical(hb, monkeypatch):
         for sp in ("sp_c", "sp_f"):
             for k in a0[sp]:
                 assert np.array_equal(a[sp][k], a0[sp][k]), (sp, k)
+    ovl, ser = recs[0], recs[1]
+    assert np.array_equal(recs[2], ovl) and np.array_equal(recs[3], ser)
+    cut = len(ser) - len(ovl)
+    assert cut > 0, "HOBBIT_OPEN_THREADS=0 recorded no more hashes on the calling thread than the default: the knob is ignored"
+    same = (ser[:len(ovl)] == ovl).all(axis=1)
+    head = len(ovl) if same.all() else int(np.argmin(same))      # the first record that differs: where the serial schedule starts C_c's proof
+    assert np.array_equal(ser[:head], ovl[:head]) and np.array_equal(ser[head + cut:], ovl[head:]), "the schedules differ by more than shockwave_prove(C_c)'s block"
 
 
 def test_open_standard_2e26_selfchecks(hb):
