@@ -403,6 +403,11 @@ int hobbit_open_standard_rs(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, c
  * h_qpoly: rounds x 3 F (a,b,c highest degree first); h_r: rounds F; h_vr: 2 F; h_final: 1 F. */
 int hobbit_sumcheck2(hobbit_ctx *ctx, const hobbit_F *d_v1, const hobbit_F *d_v2, size_t n, const hobbit_F *prev_r,
                      hobbit_F *h_qpoly, hobbit_F *h_r, hobbit_F *h_vr, hobbit_F *h_final);
+/* generate_2product_sumcheck_proof(v1, v2, prev_r) with v2 given as m (index, value) pairs on the device: indices strictly increasing and < n,
+ * every other entry of v2 zero; 1 <= m <= 2^20 (the open's P3, src/PC_utils.cpp:331-339).  A listed value may be zero.  The list is NOT
+ * checked: an unsorted list or an index >= n is undefined behaviour.  Same outputs as hobbit_sumcheck2. */
+int hobbit_sumcheck2_sparse(hobbit_ctx *ctx, const hobbit_F *d_v1, const uint64_t *d_idx, const hobbit_F *d_val, size_t m, size_t n,
+                            const hobbit_F *prev_r, hobbit_F *h_qpoly, hobbit_F *h_r, hobbit_F *h_vr, hobbit_F *h_final);
 /* Degree-4 gate-consistency sumcheck: the in-memory phase of prove_gate_consistency (src/sumcheck.cpp:875-929) over the six
  * folded tables fold_add, fold_beta, fold_L, fold_R, fold_O, fold_mul (n F each, device):
  *   sum_j  add*beta*(a0 L + a1 R) + a2*mul*beta*L*R + a3*beta*O,   h_a = a[0..3] (generate_randomness(4), :873).

@@ -201,3 +201,95 @@ def py_encode(lv, src):
                 z[t] = py_add(z[t], py_mul(cw[i], w))
         return list(x) + cw + z
     return rec(list(src), 0)
+
+
+# ---- sorted index lists for the sparse 2-product sumcheck (tests/test_sumcheck_shapes.py) -------------------------------------------
+# k_sc2_sparse_round cuts the list into 1024 slices of per = ceil(m / 1024) entries and regroups the entries into quads (index >> 2)
+# that may straddle those slices; each list below puts the cut, the quads or the list length somewhere the opening's own lists never do.
+SPARSE_PURPOSE = {
+    "single_first": "m = 1 at index 0: one thread owns the whole list, quad 0",
+    "single_last": "m = 1 at index n - 1: the last element of the last quad",
+    "single_mid": "m = 1 at index n / 2 + 1",
+    "one_quad_last": "the four indices of the last quad: one full quad, per = 1, each entry in another thread's slice",
+    "full_quads": "all four entries of 300 consecutive quads from quad 777: m = 1200, per = 2, every quad cut across two slices",
+    "odd_run": "2^16 + 3 consecutive indices from 4099: per = 65, slice boundaries at every phase of a quad",
+    "powers_of_4": "4^j for every 4^j < n, and n - 1: loses entries at every fold, two entries long before the dense hand-over",
+    "m_1023": "1023 uniform indices: one thread owns nothing",
+    "m_1024": "1024 uniform indices: exactly one entry per thread",
+    "m_1025": "1025 uniform indices: per = 2, half the threads own nothing",
+    "open_like": "5900 draws with replacement, last write wins, values the powers of one scalar: the opening's own buff2",
+    "max_spread": "n / 4 entries, one per quad at offset q % 4: the most entries that survive the first fold",
+}
+
+
+def open_like_list(n, queries=5900, seed=0):
+    """(idx, val) as OpenRun::host_tables builds buff2 (src/PC_utils.cpp:331-336): position q drawn with replacement gets s^(q+1), the last
+    write of a position wins; sorted by position"""
+    rng = np.random.default_rng(9000 + seed)
+    pos = rng.integers(0, n, queries)
+    s = tuple(int(v) for v in _splitmix(1, 9100 + seed)[0])
+    last, pw = {}, s
+    for q in range(queries):
+        last[int(pos[q])] = pw
+        pw = py_mul(pw, s)
+    idx = np.array(sorted(last), np.uint64)
+    return idx, from_py([last[int(i)] for i in idx])
+
+
+def sparse_lists(n, seed=0):
+    """{name: strictly increasing uint64 indices < n} for a table of n >= 2^17 entries (SPARSE_PURPOSE); open_like's values come from open_like_list"""
+    assert n >= 1 << 17 and n & (n - 1) == 0
+    rng = np.random.default_rng(7000 + seed)
+    out = {"single_first": [0], "single_last": [n - 1], "single_mid": [n // 2 + 1], "one_quad_last": [n - 4, n - 3, n - 2, n - 1]}
+    out["full_quads"] = np.arange(4 * 777, 4 * (777 + 300))
+    out["odd_run"] = np.arange(4099, 4099 + (1 << 16) + 3)
+    p4 = [4 ** j for j in range(32) if 4 ** j < n]
+    out["powers_of_4"] = sorted(set(p4 + [n - 1]))
+    for m in (1023, 1024, 1025):
+        out["m_%d" % m] = np.sort(rng.choice(n, m, replace=False))
+    out["open_like"] = open_like_list(n, seed=seed)[0]
+    q = np.arange(n // 4)
+    out["max_spread"] = 4 * q + q % 4
+    out = {k: np.ascontiguousarray(v, dtype=np.uint64) for k, v in out.items()}
+    for k, v in out.items():
+        assert k in SPARSE_PURPOSE and len(v) >= 1 and int(v[-1]) < n and (np.diff(v.astype(np.int64)) > 0).all(), k
+    return out
+
+
+def short_sparse_lists(n, seed=0):
+    """the lists for tables short enough to be scattered at once: one entry at either end, every entry, and min(n / 2, 1000) uniform ones"""
+    rng = np.random.default_rng(7500 + seed)
+    out = {"single_first": [0], "single_last": [n - 1], "all": np.arange(n), "uniform": np.sort(rng.choice(n, min(n // 2, 1000), replace=False))}
+    return {k: np.ascontiguousarray(v, dtype=np.uint64) for k, v in out.items()}
+
+
+def pm1_with_zeros(m):
+    """m values, all (p-1, p-1) but every seventh, which is exactly zero: a listed zero has to act as a zero"""
+    v = np.full((m, 2), P - 1, np.uint64)
+    v[6::7] = 0
+    return v
+
+
+def scatter_dense(n, idx, val):
+    """the dense table the list stands for"""
+    v = np.zeros((n, 2), np.uint64)
+    v[np.asarray(idx, np.int64)] = val
+    return v
+
+
+def with_kernels(hb, fn):
+    """fn() under the profiler: its result and the names of the kernels that ran"""
+    hb.profile(True); hb.profile_reset()
+    try:
+        return fn(), set(hb.profile_report())
+    finally:
+        hb.profile(False); hb.profile_reset()
+
+
+def gate_sumcheck_inputs(n):
+    """six full-range tables (add, beta, L, R, O, mul: the folded selectors are full-range after the streaming phase), a[0..3] and the
+    transcript seed of the degree-4 gate sumcheck"""
+    from oracle.pyoracle import splitmix_field
+    add = splitmix_field(n, 801); mul = splitmix_field(n, 802)
+    tabs = [add, splitmix_field(n, 803), splitmix_field(n, 804), splitmix_field(n, 805), splitmix_field(n, 806), mul]
+    return tabs, splitmix_field(4, 807), splitmix_field(1, 808)[0]

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import golden_cases
 from golden_cases import dg, samp
-from adversarial import FAT_CHAIN_4096, encode_with_kernels
+from adversarial import FAT_CHAIN_4096, encode_with_kernels, gate_sumcheck_inputs
 from oracle.pyoracle import splitmix_field, P
 
 pytestmark = pytest.mark.gpu
@@ -1347,11 +1347,7 @@ def test_gate_standard_vs_golden(hb):
 def test_gate_sumcheck_vs_oracle(hb, oracle, logn):
     """src/sumcheck.cpp:875-929 over six folded tables; B = 2^18 is the MLP config's chunk size.  The oracle's loop is the
     restatement (not runnable in oracle/_ref: inline in prove_gate_consistency); the reference's own round check must hold."""
-    n = 1 << logn
-    sel = (np.arange(n) % 3 == 0)
-    add = splitmix_field(n, 801); mul = splitmix_field(n, 802)          # folded selectors are full-range after the streaming phase
-    tabs = [add, splitmix_field(n, 803), splitmix_field(n, 804), splitmix_field(n, 805), splitmix_field(n, 806), mul]
-    a = splitmix_field(4, 807); rand0 = splitmix_field(1, 808)[0]
+    tabs, a, rand0 = gate_sumcheck_inputs(1 << logn)
     claim = oracle.gate_claim(tabs, a)
     want = oracle.gate_sumcheck(tabs, a, rand0, claim)
     got = hb.gate_sumcheck(tabs, a, rand0, claim)
