@@ -134,6 +134,7 @@ static int fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_l
 
 static void free_code(DeviceCode &c) {
     for (FatStep *f : {&c.fatA, &c.fatC1, &c.fatD}) { if (f->d_wt) hipFree(f->d_wt); if (f->d_ot) hipFree(f->d_ot); if (f->d_oidx) hipFree(f->d_oidx); if (f->d_w) hipFree(f->d_w); }
+    for (uint32_t *q : {c.narrow.d_wt, c.narrow.d_ot, c.narrow.d_q}) if (q) hipFree(q);
     if (c.d_steps) hipFree(c.d_steps);
     if (c.d_slice_ptr) hipFree(c.d_slice_ptr);
     if (c.d_slice_width) hipFree(c.d_slice_width);
@@ -537,6 +538,47 @@ static int build_fat_step(hobbit_ctx *ctx, const PlanStep &p, uint32_t nout, uin
     f.ok = true;
     return 0;
 }
+// Narrow form of the steps between C_1 and D_0 (hobbit_ctx.hpp NarrowPlan).  Leaves np.ok false when the code does not have the five-step shape the
+// kernel was compiled for, or an output has more in-edges than the lanes of its position have slots: launch_encode then runs these steps as before.
+static int build_narrow(hobbit_ctx *ctx, const std::vector<PlanStep> &plan, NarrowPlan &np) {
+    if (plan.size() != NARROW_STEPS + 3) return 0;
+    const long long x2 = plan[2].in_off;
+    for (uint32_t s = 0; s < NARROW_STEPS; s++) {
+        const PlanStep &p = plan[2 + s];
+        if (p.g->L != (long long)NARROW_L[s] || p.g->R != (long long)NARROW_R[s] || p.in_off != x2 + NARROW_IN[s] || p.out_off != x2 + NARROW_OUT[s]) return 0;
+    }
+    std::vector<uint32_t> wt((size_t)NARROW_SLOTS * 64, 0), ot((size_t)NARROW_OREGS * 64, 0), q((size_t)NARROW_QREGS * 64, 0xFFFFFFFFu);
+    uint32_t pos = 0, slot8 = 0, slot16 = 0, wslot = 0;
+    for (uint32_t s = 0; s < NARROW_STEPS; s++) {
+        const InEdges rows = in_edges(*plan[2 + s].g);
+        const std::vector<uint32_t> order = by_in_degree(rows);
+        size_t next = 0;
+        for (; pos < NARROW_POS && NARROW_STEP_OF[pos] == s; pos++) {
+            const uint32_t lpo = NARROW_LPO[pos], cap = NARROW_CAP[pos], cnt = 64 / lpo;
+            const bool bytes = pos < NARROW_BYTE_POS;
+            for (uint32_t t = 0; t < cnt && next + t < rows.size(); t++) {
+                const uint32_t out = order[next + t];
+                const auto &row = rows[out];
+                if (row.size() > (size_t)cap * lpo) return 0;
+                for (size_t e = 0; e < row.size(); e++) {                  // edge e of the output: slot e / lpo of lane group member e % lpo
+                    const uint32_t lane = t * lpo + (uint32_t)(e % lpo), k = (uint32_t)(e / lpo);
+                    wt[(size_t)(wslot + k) * 64 + lane] = (uint32_t)row[e].second.re;
+                    if (bytes) { const uint32_t sl = slot8 + k; ot[(size_t)(sl >> 2) * 64 + lane] |= row[e].first << (8 * (sl & 3)); }
+                    else { const uint32_t sl = slot16 + k; ot[(size_t)((NARROW_SLOTS8 + 3) / 4 + (sl >> 1)) * 64 + lane] |= ((NARROW_IN[s] + row[e].first) * 16u) << (16 * (sl & 1)); }
+                }
+                uint32_t &qq = q[(size_t)(pos >> 1) * 64 + t * lpo];       // the group's first lane stores the output
+                qq = (qq & ~(0xFFFFu << (16 * (pos & 1)))) | (((NARROW_OUT[s] + out) * 16u) << (16 * (pos & 1)));
+            }
+            next = std::min(rows.size(), next + cnt);
+            wslot += cap; (bytes ? slot8 : slot16) += cap;
+        }
+        if (next < rows.size()) return 0;
+    }
+    np.x2_off = (uint32_t)x2;
+    HB_TRY(upload(ctx, &np.d_wt, wt)); HB_TRY(upload(ctx, &np.d_ot, ot)); HB_TRY(upload(ctx, &np.d_q, q));
+    np.ok = true;
+    return 0;
+}
 // Long codes (codeword over 160 KB): the outer steps whose windows do not fit in LDS, in tiled form (hobbit_ctx.hpp TiledStep).  Built by the
 // first launch_encode of the finalized code, from the plan hobbit_graph_finalize kept.
 int ensure_tiled(hobbit_ctx *ctx) {
@@ -700,6 +742,7 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
         HB_TRY(build_fat_step(ctx, plan.front(), FAT_A_NOUT, FAT_A_CONS, capA, c.fatA));
         HB_TRY(build_fat_step(ctx, plan.back(), FAT_D_NOUT, FAT_D_CONS, capD, c.fatD));
         HB_TRY(build_fat_step(ctx, plan[1], FAT_C1_NOUT, FAT_C1_CONS, capC1, c.fatC1));
+        HB_TRY(build_narrow(ctx, plan, c.narrow));
     }
     // the long codes' tiled steps and the rows-innermost CSR steps are built on first use from c.plan (ensure_tiled / ensure_ilv): a context
     // that only runs one of the two encodes does not pay for the other's plan

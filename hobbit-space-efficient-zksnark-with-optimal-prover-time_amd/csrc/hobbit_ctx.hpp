@@ -60,6 +60,31 @@ static constexpr uint32_t FAT_A_NOUT = 2, FAT_A_CONS = 7, FAT_A_CAP0 = 72, FAT_A
 static constexpr uint32_t FAT_C1_NOUT = 1, FAT_C1_CONS = 3, FAT_C1_CAP0 = 64, FAT_C1_WGS = 768;                       // C_1: 182 outputs, in-degree 42.7 (max ~62): three waves, a few workgroups per CU
 static constexpr uint32_t FAT_D_NOUT = 3, FAT_D_CONS = 8, FAT_D_CAP0 = 28, FAT_D_CAP1 = 16, FAT_D_CAP2 = 12, FAT_D_WGS = 256;   // D_0: 1463 outputs, in-degree 12.2 +- 3.5
 
+// The five NARROW steps C_2, C_3, D_3, D_2, D_1 of n = 4096 for the persistent one-wave-per-column kernel (hobbit_kernels.hip, k_enc_narrow):
+// 6 612 edges on the 622-element window [x_2 .. z_1].  A step is a run of POSITIONS; in a position a lane works for one output, NARROW_LPO
+// lanes share an output (lane = t * LPO + g: output t of the position, edges g, g + LPO, ... of it) and combine after one fold each; the
+// position's outputs are the next 64 / LPO of the step in order of in-degree, heaviest first, and every lane has NARROW_CAP register slots
+// for its share of the edges (weight 0 past the end).  The tables are the cheapest cover of the libc-drawn graphs' degrees (slots + about
+// three per fold + one per combine round): 136 slots for the 103.3 edges per lane.  A record is the 32-bit weight (one register) and the
+// input's place in the window: for the first four steps an 8-bit element index relative to the step's input (four to a register), for D_1
+// a 16-bit byte offset (two to a register).  Built by hobbit_graph_finalize when the code has this shape and the degrees fit.
+static constexpr uint32_t NARROW_STEPS = 5, NARROW_POS = 12;
+static constexpr uint32_t NARROW_L[NARROW_STEPS] = {182, 38, 8, 65, 313}, NARROW_R[NARROW_STEPS] = {38, 8, 19, 66, 309};   // inputs / outputs per step
+static constexpr uint32_t NARROW_IN[NARROW_STEPS] = {0, 182, 220, 182, 0}, NARROW_OUT[NARROW_STEPS] = {182, 220, 228, 247, 313};   // first input / output, window-relative
+static constexpr uint32_t NARROW_WIN = 622, NARROW_X2 = 182;             // the window, and its head x_2 that the launch reads from the column
+static constexpr uint32_t NARROW_STEP_OF[NARROW_POS] = {0, 0, 1, 2, 3, 3, 4, 4, 4, 4, 4, 4};
+static constexpr uint32_t NARROW_LPO[NARROW_POS] = {8, 2, 8, 2, 4, 1, 8, 1, 1, 1, 1, 1};
+static constexpr uint32_t NARROW_CAP[NARROW_POS] = {8, 24, 8, 6, 6, 14, 4, 20, 14, 12, 12, 8};
+static constexpr uint32_t NARROW_BYTE_POS = 6;                           // positions [0, 6): 8-bit records; [6, 12) = D_1: 16-bit records
+static constexpr uint32_t NARROW_SLOTS8 = 66, NARROW_SLOTS16 = 70, NARROW_SLOTS = NARROW_SLOTS8 + NARROW_SLOTS16;
+static constexpr uint32_t NARROW_OREGS = (NARROW_SLOTS8 + 3) / 4 + NARROW_SLOTS16 / 2, NARROW_QREGS = NARROW_POS / 2;
+static constexpr uint32_t NARROW_WGS = 2048;                             // one-wave workgroups per launch: two waves per SIMD (the 200 record registers)
+struct NarrowPlan {
+    bool ok = false;
+    uint32_t x2_off = 0;                                                 // x_2's place in the column
+    uint32_t *d_wt = nullptr, *d_ot = nullptr, *d_q = nullptr;           // slot-major [slot][lane]: weights, packed places, packed output byte offsets
+};
+
 // Long codes (codeword over 160 KB: n >= ~6000, tensor_row_size 8192 / 16384 of Our_PC): the outer steps C_0 .. C_{d-1} and D_{d-1} .. D_0,
 // whose input windows are too long for one workgroup's LDS, run one launch each through k_enc_tiled (hobbit_kernels.hip); the sub-codeword of
 // depth d (the first that fits TILE_MID_MAX) is encoded by one k_encode pass on its own window.  A tiled step cuts its input window into tiles
@@ -93,6 +118,7 @@ struct DeviceCode {         // finalized code for one message length n
     uint32_t *d_eidx = nullptr; F *d_ew = nullptr;   // general weights
     size_t n_edges_padded = 0, n_edges = 0;
     FatStep fatA, fatC1, fatD;               // first, second and last step in fat form (deep codes only: n = 4096)
+    NarrowPlan narrow;                       // the five steps between them, one wave per column (n = 4096 with the degrees the kernel was compiled for)
     // long codes: steps [0, tiled_depth) and [nsteps - tiled_depth, nsteps) in tiled form (tiled_depth = 0: the codeword fits in LDS)
     uint32_t tiled_depth = 0;
     std::vector<TiledStep> tsteps;           // C_0 .. C_{d-1}, then D_{d-1} .. D_0 (the order of `steps`)

@@ -1073,6 +1073,114 @@ static int launch_enc_fat(hobbit_ctx *ctx, const char *name, const FatStep &f, F
 }
 
 // ============================================================================================
+// The five narrow steps C_2 .. D_1 of a deep code (n = 4096), persistent, register-resident and barrier-free (hobbit_ctx.hpp NarrowPlan).
+// One wave owns one column at a time and walks columns c, c + gridDim.x, ...; its workgroup is that wave alone, with the 622-element window
+// [x_2 .. z_1] in LDS.  The records of all five steps stay in registers for the whole launch (k_enc_fat's form: after the prologue no edge
+// record, descriptor or index comes from memory), and the steps follow one another in program order: the LDS stores of a step, one
+// lgkmcnt(0) wait, the gathers of the next.  Per position (hobbit_ctx.hpp) the inner loop is k_enc_fat's -- one operation for the address,
+// one ds_read_b128, the 4 v_mad_u64_u32 + 4 v_addc of the unreduced 96-bit sums -- then one fold per lane, the xor-shuffle combine of the
+// lanes that share an output, and the store into the window.  The next column's x_2 arrives by LDS-DMA in a staging area while the current
+// column is worked on and is copied to the window's head when the columns change; the outputs [x_3 .. z_1] of a column leave as coalesced
+// 16-byte stores from LDS at the start of the next iteration, so that the vmcnt(0) in front of the staging area never waits for a store
+// just issued.
+// ============================================================================================
+static constexpr uint32_t NARROW_STAGE = 10240, NARROW_LDS = NARROW_STAGE + 3 * 1024;   // byte offset of the x_2 staging area (three 1-KiB DMA pieces), LDS per workgroup
+static_assert(NARROW_WIN * 16 <= NARROW_STAGE && NARROW_X2 <= 3 * 64, "narrow window layout");
+template <int P> struct NarrowPos {
+    static constexpr int slot_base(int p) { int b = 0; for (int i = 0; i < p; i++) b += (int)NARROW_CAP[i]; return b; }
+    static constexpr int LPO = NARROW_LPO[P], CAP = NARROW_CAP[P], WB = slot_base(P);
+    static constexpr bool BYTES = P < (int)NARROW_BYTE_POS;
+    static constexpr int SB = BYTES ? WB : WB - (int)NARROW_SLOTS8;                   // first slot among the records of its kind
+    static constexpr int IN_BYTES = (int)NARROW_IN[NARROW_STEP_OF[P]] * 16;
+    static constexpr bool STEP_END = P + 1 == (int)NARROW_POS || NARROW_STEP_OF[P + 1 < (int)NARROW_POS ? P + 1 : P] != NARROW_STEP_OF[P];
+};
+static_assert(NarrowPos<NARROW_BYTE_POS>::WB == NARROW_SLOTS8 && NarrowPos<NARROW_POS - 1>::WB + NarrowPos<NARROW_POS - 1>::CAP == NARROW_SLOTS, "narrow slot counts");
+template <int P>
+__device__ __forceinline__ void narrow_pos(unsigned char *lds, const uint32_t (&w)[NARROW_SLOTS], const uint32_t (&o)[NARROW_OREGS], const uint32_t (&q)[NARROW_QREGS]) {
+    using NP = NarrowPos<P>;
+    Acc96 rl = {0, 0}, rh = {0, 0}, il = {0, 0}, ih = {0, 0};
+#pragma unroll
+    for (int g = 0; g < NP::CAP; g += 4) {
+        uint4 x[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if (g + u >= NP::CAP) continue;
+            const int k = NP::SB + g + u;
+            if (NP::BYTES) x[u] = *reinterpret_cast<const uint4 *>(lds + NP::IN_BYTES + (((o[k >> 2] >> (8 * (k & 3))) & 0xFFu) << 4));
+            else { const uint32_t r = o[(NARROW_SLOTS8 + 3) / 4 + (k >> 1)]; x[u] = *reinterpret_cast<const uint4 *>(lds + ((k & 1) ? (r >> 16) : (r & 0xFFFFu))); }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) if (g + u < NP::CAP) acc96_mad4(rl, rh, il, ih, w[NP::WB + g + u], x[u]);
+    }
+    F acc = fmake(acc_fold(rl, rh), acc_fold(il, ih));
+#pragma unroll
+    for (int m = 1; m < NP::LPO; m <<= 1) acc = fadd(acc, shfl_xor_F(acc, m));
+    const uint32_t ob = (P & 1) ? (q[P >> 1] >> 16) : (q[P >> 1] & 0xFFFFu);
+    if (ob != 0xFFFFu) stF(reinterpret_cast<F *>(lds + ob), acc);
+    if (NP::STEP_END) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // this step's outputs are in the window before the next step gathers
+}
+template <int... P>
+__device__ __forceinline__ void narrow_steps(unsigned char *lds, const uint32_t (&w)[NARROW_SLOTS], const uint32_t (&o)[NARROW_OREGS], const uint32_t (&q)[NARROW_QREGS],
+                                             std::integer_sequence<int, P...>) {
+    (narrow_pos<P>(lds, w, o, q), ...);
+}
+__global__ void __launch_bounds__(64)
+k_enc_narrow(F *__restrict__ tensor, size_t ld, uint32_t ncols, uint32_t x2_off, const uint32_t *__restrict__ wt, const uint32_t *__restrict__ ot,
+             const uint32_t *__restrict__ qt) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const uint32_t lane = threadIdx.x;
+    auto issue = [&](uint32_t c) {                                                       // column c's x_2 -> the staging area
+        const F *colp = tensor + (size_t)c * ld + x2_off;
+#pragma unroll
+        for (uint32_t p = 0; p < 3; p++) {
+            uint32_t i = (p << 6) + lane; i = i < NARROW_X2 ? i : NARROW_X2 - 1;        // (the pad lanes of the last piece re-read the last element)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(colp + i),
+                                             (__attribute__((address_space(3))) void *)(lds_raw + NARROW_STAGE + (p << 10)), 16, 0, 0);
+        }
+    };
+    const uint32_t stride = gridDim.x;
+    uint32_t c = blockIdx.x;
+    if (c < ncols) issue(c);
+    // edge records into registers, once
+    uint32_t w[NARROW_SLOTS], o[NARROW_OREGS], q[NARROW_QREGS];
+#pragma unroll
+    for (uint32_t k = 0; k < NARROW_SLOTS; k++) w[k] = wt[k * 64 + lane];
+#pragma unroll
+    for (uint32_t k = 0; k < NARROW_OREGS; k++) o[k] = ot[k * 64 + lane];
+#pragma unroll
+    for (uint32_t k = 0; k < NARROW_QREGS; k++) q[k] = qt[k * 64 + lane];
+    auto store_out = [&](F *col) {                                                       // [x_3 .. z_1] of the window -> the column
+#pragma unroll
+        for (uint32_t i0 = NARROW_X2; i0 < NARROW_WIN; i0 += 64) { const uint32_t i = i0 + lane; if (i < NARROW_WIN) stF(col + i, ldF(reinterpret_cast<const F *>(lds_raw) + i)); }
+    };
+    F *prev = nullptr;
+    for (; c < ncols; c += stride) {
+        // (the packed places are opaque to the compiler from one column to the next: it would otherwise hoist the 136 unpacked LDS addresses
+        // out of the loop, one register each on top of the weights -- 322 registers, one wave per SIMD)
+#pragma unroll
+        for (uint32_t k = 0; k < NARROW_OREGS; k++) asm volatile("" : "+v"(o[k]));
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                 // this column's x_2 has landed in the staging area
+        if (prev) store_out(prev);
+#pragma unroll
+        for (uint32_t p = 0; p < 3; p++) {
+            const uint32_t i = (p << 6) + lane;
+            if (i < NARROW_X2) stF(reinterpret_cast<F *>(lds_raw) + i, ldF(reinterpret_cast<const F *>(lds_raw + NARROW_STAGE) + i));
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                               // x_2 is in the window, the staging area is free
+        const uint32_t cn = c + stride;
+        if (cn < ncols) issue(cn);
+        narrow_steps(lds_raw, w, o, q, std::make_integer_sequence<int, NARROW_POS>());
+        prev = tensor + (size_t)c * ld + x2_off;
+    }
+    if (prev) store_out(prev);
+}
+static int launch_enc_narrow(hobbit_ctx *ctx, const char *name, const NarrowPlan &np, F *tensor, size_t ld, size_t ncols) {
+    const size_t grid = std::min(ncols, (size_t)NARROW_WGS);
+    HB_LAUNCH(ctx, name, k_enc_narrow, dim3((unsigned)grid), dim3(64), (size_t)NARROW_LDS, tensor, ld, (uint32_t)ncols, np.x2_off, np.d_wt, np.d_ot, np.d_q);
+    return 0;
+}
+
+// ============================================================================================
 // Long codes (hobbit_ctx.hpp TiledStep): one SpMV step whose input window is longer than LDS, one workgroup per (column, output group).
 // The window streams through LDS one 64 KB tile at a time; a wave owns up to TILE_MAXS slices of 64 outputs (one output per lane) and keeps
 // their four unreduced 96-bit sums per output in registers across the tiles -- the same acc96_mad4 / acc_fold arithmetic as k_encode, one
@@ -1214,9 +1322,13 @@ int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t l
         HB_TRY((launch_enc_fat<FAT_A_NOUT, FAT_A_CAP0, FAT_A_CAP1, 0, FAT_A_CONS>(ctx, "k_enc_fat_A", c.fatA, dst, ld_dst, batch, 0, 0, FAT_A_WGS)));
         if (!c.fatD.ok || nsteps < 5)
             return launch_encode_pass<true>(ctx, "k_encode_B", dst, ld_dst, dst, ld_dst, batch, pb, (uint32_t)c.len - nn, block_for(c, 1, nsteps, 8));
-        // C_1 alone -- 21 % of the edges on a 14 KB window: fat form, three workgroups per CU -- then the five short steps C_2 .. D_1 with a
-        // two-wave workgroup per column on the 10 KB window [x_2 .. z_1] (sixteen of them per CU hide the dependent step chains), then D_0 in
-        // fat form (it also writes the zero tail).  2^28: 2.44 ms for C_1 .. D_1 as one launch, 0.93 + 1.05 split, 0.63 + 1.05 with C_1 fat
+        // C_1 alone -- 21 % of the edges on a 14 KB window: fat form, three workgroups per CU -- then the five short steps C_2 .. D_1 on the
+        // 10 KB window [x_2 .. z_1], then D_0 in fat form (it also writes the zero tail).  The five steps run under the profile name
+        // k_encode_M2 in one of two forms, chosen from the graph at finalize: k_enc_narrow, one persistent wave per column with every edge
+        // record in registers and no barrier (the code's own five-step shape with the degrees the kernel was compiled for), or else the
+        // one-workgroup-per-column k_encode with two-wave workgroups, sixteen per CU, which re-reads records and descriptors for every
+        // column.  2^28: 2.44 ms for C_1 .. D_1 as one k_encode launch, 0.93 + 1.05 split, 0.63 + 1.05 with C_1 fat; the narrow form's
+        // figures are in DESIGN.md section 4
         const EncStep &last = c.steps[nsteps - 1];
         const uint32_t r1 = c.steps[1].out_len, x2 = nn + r0;
         if (c.fatC1.ok) {
@@ -1225,8 +1337,12 @@ int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t l
             EncPass p1 = {nn, nn, nn + r0, 1, 2, x2, x2, 1};
             HB_TRY(launch_encode_pass<true>(ctx, "k_encode_C1", dst, ld_dst, dst, ld_dst, batch, p1, r0, block_for(c, 1, 2, 8)));
         }
-        EncPass p2 = {x2, x2, x2 + r1, 2, nsteps - 1, x2 + r1, last.out_off, 0};
-        HB_TRY(launch_encode_pass<true>(ctx, "k_encode_M2", dst, ld_dst, dst, ld_dst, batch, p2, last.out_off - x2, block_for(c, 2, nsteps - 1, 2)));
+        if (c.narrow.ok) {
+            HB_TRY(launch_enc_narrow(ctx, "k_encode_M2", c.narrow, dst, ld_dst, batch));
+        } else {
+            EncPass p2 = {x2, x2, x2 + r1, 2, nsteps - 1, x2 + r1, last.out_off, 0};
+            HB_TRY(launch_encode_pass<true>(ctx, "k_encode_M2", dst, ld_dst, dst, ld_dst, batch, p2, last.out_off - x2, block_for(c, 2, nsteps - 1, 2)));
+        }
         // the zero tail [len, 2n): a caller that answers those rows as zeros itself (commit_impl: leaf chain, gathers and row reads know the
         // codeword length) asks for the rows up to the next multiple of four only -- the leaf group that straddles the codeword's end is read whole
         uint32_t z_hi = 2 * nn;
