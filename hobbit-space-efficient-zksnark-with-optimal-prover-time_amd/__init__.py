@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "hobbit_batch_3product_sumcheck", "hobbit_mul_tree", "hobbit_shockwave_commit", "hobbit_change_form", "hobbit_whir_commit",
     "hobbit_open_core", "hobbit_open_standard", "hobbit_open_from_aggregate", "hobbit_tensor_gather", "hobbit_u64_bias_fold", "hobbit_gate_sumcheck", "hobbit_compute2p_error_terms", "hobbit_compute3p_error_terms", "hobbit_compute4p_error_terms", "hobbit_fold_axpy",
     "hobbit_fold_axpy_i32", "hobbit_batch_prod",
-    "hobbit_aggregate", "hobbit_sumcheck2", "hobbit_sumcheck2_sparse", "hobbit_sumcheck3", "hobbit_fill_splitmix",
+    "hobbit_aggregate", "hobbit_sumcheck2", "hobbit_sumcheck2_sparse", "hobbit_sumcheck2_eq", "hobbit_sumcheck3", "hobbit_fill_splitmix",
     "hobbit_encode_interleaved", "hobbit_brakedown_shape", "hobbit_brakedown_commit", "hobbit_brakedown_free", "hobbit_brakedown_dims",
     "hobbit_brakedown_matrix_dev", "hobbit_brakedown_levels_dev", "hobbit_brakedown_levels", "hobbit_brakedown_root", "hobbit_brakedown_tensor",
     "hobbit_brakedown_open",
@@ -102,6 +102,7 @@ def load_library(path=LIB_PATH):
         "hobbit_commitment_root": [V, V, V], "hobbit_commitment_tensor_row": [V, V, I, I, V], "hobbit_commitment_gather": [V, V, V, V, S, V],
         "hobbit_commitment_path": [V, V, S, S, V], "hobbit_commitment_paths": [V, V, V, V, S, V], "hobbit_aggregate": [V, V, S, V, I, V],
         "hobbit_sumcheck2": [V, V, V, S, V, V, V, V, V], "hobbit_sumcheck2_sparse": [V, V, V, V, S, S, V, V, V, V, V], "hobbit_sumcheck3": [V, V, V, V, S, V, V, V, V, V],
+        "hobbit_sumcheck2_eq": [V, I, V, V, V, V, S, V, V, V, V, V],
         "hobbit_fill_splitmix": [V, V, S, U64],
         "hobbit_parity_matrix": [V, V, S, L, V], "hobbit_phi_g": [V, V, I, V, I, V], "hobbit_prepare_matrix_cols": [V, V, S, S, V, I, V],
         "hobbit_prove_linear_code": [V, V, S, L, V, V, V, V, V], "hobbit_prove_fft": [V, V, S, V, V, V, V, V],
@@ -1180,6 +1181,18 @@ class Hobbit:
         pr = Fh(previous_r).reshape(2)
         q = np.zeros((rounds, 3, 2), np.uint64); r = np.zeros((rounds, 2), np.uint64); vr = np.zeros((2, 2), np.uint64); fin = np.zeros(2, np.uint64)
         self._chk(self.lib.hobbit_sumcheck2_sparse(self.ctx, c_vp(p1), c_vp(di.ptr), c_vp(dv.ptr), c_sz(idx.shape[0]), c_sz(n), _hp(pr), _hp(q), _hp(r), _hp(vr), _hp(fin)))
+        return dict(poly=q, r=r, vr=vr, fin=fin)
+
+    def generate_2product_sumcheck_proof_eq(self, points, scalars, v2, previous_r):
+        """generate_2product_sumcheck_proof(v1, v2, previous_r) with v1 = sum_j scalars[j] * precompute_beta(points[j]) given by its one or
+        two points (hobbit_sumcheck2_eq: the open's P4); v1 is not built where the table takes two rounds per round trip."""
+        p2, n, k2 = self._dev_table(v2)
+        rounds = n.bit_length() - 1
+        pts = [np.ascontiguousarray(Fh(p).reshape(-1, 2)) for p in points]; sc = np.ascontiguousarray(Fh(scalars).reshape(-1, 2))
+        assert len(pts) == sc.shape[0] and all(p.shape[0] == rounds for p in pts)
+        pr = Fh(previous_r).reshape(2)
+        q = np.zeros((rounds, 3, 2), np.uint64); r = np.zeros((rounds, 2), np.uint64); vr = np.zeros((2, 2), np.uint64); fin = np.zeros(2, np.uint64)
+        self._chk(self.lib.hobbit_sumcheck2_eq(self.ctx, len(pts), _hp(pts[0]), _hp(pts[-1]), _hp(sc), c_vp(p2), c_sz(n), _hp(pr), _hp(q), _hp(r), _hp(vr), _hp(fin)))
         return dict(poly=q, r=r, vr=vr, fin=fin)
 
     def generate_3product_sumcheck_proof(self, v1, v2, v3, previous_r):

@@ -2696,7 +2696,7 @@ struct OpenRun {
     hobbit_ctx *ctx; const hobbit_F *d_poly; size_t N; const hobbit_commitment *c; const hobbit_F *h_x; int queries; hobbit_open_out *o; bool full, overlapped;
     OpenTrace tr; StageScope sc;
     int K, trs, logK, logc, R1, R3; size_t M, cols, rows2, big, nc_el;
-    F *d_aggr, *BIG, *Mp, *C, *Tcm, *d_b, *d_bb, *d_s, *d_ev, *d_ac, *d_b1, *tmpv, *encf, *encc; uint64_t *tmpi; uint8_t *lvf, *lvc;       // device arena
+    F *d_aggr, *BIG, *Mp, *C, *Tcm, *d_s, *d_ev, *d_ac, *d_b1, *tmpv, *encf, *encc; uint64_t *tmpi; uint8_t *lvf, *lvc;       // device arena
     std::vector<F> beta, sv, r1; std::vector<uint32_t> qc, qr; std::vector<uint64_t> Iv; F s2, a; size_t nnz = 0;      // host: beta over the chunk variables, the libc draws, buff2's length
     hobbit_F *Q1, *Q2, *Q3, *Q4, *Q5, *Rr1, *Rr2, *Rr3, *Rr4, *Rr5;                                                    // the output cursors of P1..P5
     std::thread q_thread, sp_thread; ShockPlan plan_c; int sp_rc = 0;      // overlapped only: the hand-over of the query answers, shockwave_prove(C_c) with its libc draws
@@ -2724,7 +2724,7 @@ struct OpenRun {
         F *arena = nullptr;
         // + the two inner shockwave commitments kept for the later shockwave_prove: encoded matrices (2M and 2*trs*cols F) and their trees
         const size_t sw_el = 2 * M + 2 * nc_el + 2 * (2 * M / 32 + 2 * nc_el / 32) * 2 + 64;
-        const size_t n_el = M + 4 * big + 2 * cols + 4 * rows2 + 2 * (size_t)queries + 128 + sw_el;
+        const size_t n_el = M + 2 * big + 2 * cols + 4 * rows2 + 2 * (size_t)queries + 128 + sw_el;
         HB_TRY(ctx->workspace3(n_el * sizeof(F), (void **)&arena));
         // size the shared scratch buffers once for the largest user below (the 4M-element sumchecks, the 32-row long FFTs of
         // the inner commitments): growing them step by step frees and re-maps device memory several times per call
@@ -2739,7 +2739,7 @@ struct OpenRun {
         HB_TRY(ctx->pinned(std::max((size_t)queries * (sizeof(F) + 8) + 4096, (WHIR_DIN * 6 + WHIR_DRES) * sizeof(F)), &dummy));
         tr.mark("scratch sizing");
         if (tr.on) fprintf(stderr, "[hobbit open] scratch at entry: ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws_bytes, ctx->ws2_bytes, ctx->ws3_bytes, ctx->ws4_bytes, ctx->pin_bytes);
-        d_aggr = arena; BIG = d_aggr + M; Tcm = BIG + big; d_b = Tcm + big; d_bb = d_b + big; d_s = d_bb + big; d_ev = d_s + cols; d_ac = d_ev + cols; d_b1 = d_ac + rows2;
+        d_aggr = arena; BIG = d_aggr + M; Tcm = BIG + big; d_s = Tcm + big; d_ev = d_s + cols; d_ac = d_ev + cols; d_b1 = d_ac + rows2;
         Mp = BIG; C = BIG + nc_el;
         tmpv = d_b1 + rows2; tmpi = reinterpret_cast<uint64_t *>(tmpv + queries + 1);                 // the sparse buff2: (index, value) lists
         encf = d_b1 + rows2 + 2 * (size_t)queries + 64; encc = encf + 2 * M;                          // the inner commitments' encoded matrices ...
@@ -2885,8 +2885,8 @@ struct OpenRun {
         { CHP q2 = cF(Q2); F c2 = fadd(fadd(q2[0], q2[1]), fadd(q2[2], q2[2])); o->checks[0] = feq(c2, cF(o->vr)[1]); }
         std::vector<hobbit_F> rcat(R3); hobbit_F p312 = {312, 0};
         memcpy(rcat.data(), Rr2, sizeof(hobbit_F) * logc); memcpy(rcat.data() + logc, Rr1, sizeof(hobbit_F) * R1);
-        HB_TRY(launch_eq_pair_axpy(ctx, cF(rcat.data()), cF(Rr3), R3, a, d_bb, d_b));      // d_b = beta(r) + a * beta(P3.r), d_bb: scratch
-        HB_TRY(hobbit_sumcheck2(ctx, reinterpret_cast<hobbit_F *>(d_b), reinterpret_cast<hobbit_F *>(BIG), big, &p312, Q4, Rr4, o->vr + 6, o->fin + 3));
+        const F sc[2] = {fmake(1), a};             // beta(r) + a * beta(P3.r), never in memory: the sumcheck takes it by its two points
+        HB_TRY(launch_sumcheck2_eq(ctx, 2, cF(rcat.data()), cF(Rr3), CHP(sc), BIG, big, *cF(&p312), mF(Q4), mF(Rr4), mF(o->vr + 6), mF(o->fin + 3)));
         { CHP q4 = cF(Q4); F c4 = fadd(fadd(q4[0], q4[1]), fadd(q4[2], q4[2])); F want = fadd(fmul(a, cF(o->vr)[4]), cF(o->vr)[3]); o->checks[1] = feq(c4, want); }
         tr.mark("betas, P4");
         return 0;
@@ -2997,6 +2997,11 @@ int hobbit_sumcheck2_sparse(hobbit_ctx *ctx, const hobbit_F *d_v1, const uint64_
                             hobbit_F *h_qpoly, hobbit_F *h_r, hobbit_F *h_vr, hobbit_F *h_final) {
     if (m > n) return ctx->fail(HOBBIT_EINVAL, "sumcheck2_sparse: more non-zeros than table entries");
     return launch_sumcheck2_sparse(ctx, cF(d_v1), d_idx, cF(d_val), m, n, *cF(prev_r), mF(h_qpoly), mF(h_r), mF(h_vr), mF(h_final));
+}
+int hobbit_sumcheck2_eq(hobbit_ctx *ctx, int T, const hobbit_F *h_r1, const hobbit_F *h_r2, const hobbit_F *h_a, const hobbit_F *d_v2, size_t n, const hobbit_F *prev_r,
+                        hobbit_F *h_qpoly, hobbit_F *h_r, hobbit_F *h_vr, hobbit_F *h_final) {
+    if (!prev_r) return ctx->fail(HOBBIT_EINVAL, "sumcheck2_eq: null transcript seed");
+    return launch_sumcheck2_eq(ctx, T, cF(h_r1), cF(h_r2), cF(h_a), cF(d_v2), n, *cF(prev_r), mF(h_qpoly), mF(h_r), mF(h_vr), mF(h_final));
 }
 int hobbit_gate_sumcheck(hobbit_ctx *ctx, const hobbit_F *d_add, const hobbit_F *d_beta, const hobbit_F *d_L, const hobbit_F *d_R, const hobbit_F *d_O, const hobbit_F *d_mul,
                          size_t n, const hobbit_F *h_a, hobbit_F *h_rand, hobbit_F *h_sum, hobbit_F *h_poly, hobbit_F *h_r, hobbit_F *h_final, int *h_check) {

@@ -1891,15 +1891,6 @@ __global__ void __launch_bounds__(256) k_eq_head(EqHead r, int h, F *__restrict_
     }
     for (uint32_t j = threadIdx.x; j < (1u << h); j += 256) stF(out + j, ldF(&s[j]));
 }
-// last doubling step of TWO tables fused with their combination: out = eq(r1) + a * eq(r2)  (src/PC_utils.cpp:344-349), from the
-// two half-size tables o1, o2 and the last challenges c1, c2 -- the full-size tables are never written and read back
-__global__ void k_eq_final_axpy(const F *__restrict__ o1, const F *__restrict__ o2, size_t m, F c1, F c2, F a, F *__restrict__ out) {
-    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < m; j += (size_t)gridDim.x * blockDim.x) {
-        const F x = ldF(o1 + j), y = ldF(o2 + j), t1 = fmul(c1, x), t2 = fmul(c2, y);
-        stF(out + 2 * j, fadd(fsub(x, t1), fmul(a, fsub(y, t2))));
-        stF(out + 2 * j + 1, fadd(t1, fmul(a, t2)));
-    }
-}
 int launch_eq_table(hobbit_ctx *ctx, CHP h_r, int k, F *d_out) {
     // head in one workgroup, then ping-pong between d_out (final) and workspace so that the last step lands in d_out
     size_t n = (size_t)1 << k;
@@ -1920,15 +1911,6 @@ int launch_eq_table(hobbit_ctx *ctx, CHP h_r, int k, F *d_out) {
         else { HB_LAUNCH(ctx, "k_eq_step", k_eq_step2, dim3(grid_for(m, 256)), dim3(256), 0, cur, nxt, m, h_r[k - 1 - i], h_r[k - 2 - i]); i += 2; }
         cur = nxt;
     }
-    return 0;
-}
-// d_out[0..2^k) = eq(r1) + a * eq(r2); d_half: scratch of 2^k elements (the two half-size tables)
-int launch_eq_pair_axpy(hobbit_ctx *ctx, CHP h_r1, CHP h_r2, int k, F a, F *d_half, F *d_out) {
-    if (k < 1) return ctx->fail(HOBBIT_EINVAL, "eq_pair_axpy: k must be >= 1");
-    const size_t m = (size_t)1 << (k - 1);
-    HB_TRY(launch_eq_table(ctx, h_r1 + 1, k - 1, d_half));             // levels 0..k-2 use r[k-1] .. r[1]; the last level uses r[0]
-    HB_TRY(launch_eq_table(ctx, h_r2 + 1, k - 1, d_half + m));
-    HB_LAUNCH(ctx, "k_eq_final_axpy", k_eq_final_axpy, dim3(grid_for(m, 256)), dim3(256), 0, d_half, d_half + m, m, h_r1[0], h_r2[0], a, d_out);
     return 0;
 }
 // aggr[j] = sum_i beta[i] * poly[i*M + j]   (src/Our_PC.cpp:258-272)
@@ -2580,10 +2562,14 @@ int launch_fill_F(hobbit_ctx *ctx, F *p, size_t stride, size_t n, F v) {
 
 // ---- 2-product sumcheck whose SECOND table is sparse (the open's P3: 5900 non-zeros of 2^25, src/PC_utils.cpp:331-339) -------------------
 // The round polynomials only see the quads in which the sparse table is non-zero, so the large levels need no dense pass over it and no
-// products over the dense table: per round trip one plain 4 -> 1 fold of the dense table (k_sc2_fold4) and ONE workgroup that folds the
-// sparse list two levels (sorted (index, value) pairs in, one pair per surviving quad out) and evaluates G(r, t) on the surviving quads
-// (k_sc2_sparse_round, which also posts to the mailbox: no separate reduction launch).  Same field sums as the dense kernels, so the
-// transcript is bit-identical.  Below SC_DOUBLE_MIN the list is scattered into a dense table and the dense path takes over.
+// products over the dense table: per round trip one plain 4 -> 1 fold of the dense table (k_sc2_fold4) and one pass over the LIST
+// (k_sc2_sparse_round).  Everything the sumcheck does with the sparse table is linear in it, so the list is never regrouped: entry e keeps
+// the caller's index x_e for good and stands, at level i, for the value v_e prod_{b < i} (x_e bit b ? r_b : 1 - r_b) at index x_e >> i
+// (entries that meet in one index simply add up).  One thread per entry, any number of workgroups: with FOLD it multiplies its value by the
+// weight of the two index bits just folded and stores it, then it gathers the four elements of its quad of the dense table and adds its
+// share of the nine values of G(r, t) -- for the element at position p of the quad, b_p = v and the other three are zero in the sums
+// k_sc2_double forms.  k_sc_reduce_post adds the workgroups' partials and posts them.  Exact field sums: the transcript is bit-identical
+// to the dense kernels'.  Below SC_DOUBLE_MIN the list is summed into a dense table (k_scatter_counted) and the dense path takes over.
 __global__ void __launch_bounds__(256) k_sc2_fold4(const F *__restrict__ s, F *__restrict__ d, size_t nout, F r0, F r1) {
     for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < nout; g += (size_t)gridDim.x * blockDim.x) {
         const F *e = s + 4 * g;
@@ -2592,110 +2578,177 @@ __global__ void __launch_bounds__(256) k_sc2_fold4(const F *__restrict__ s, F *_
         stF(d + g, fadd(f0, fmul(r1, fsub(f1, f0))));
     }
 }
-// gather the (up to four, consecutive in the sorted list) entries of the quad that entry e leads
-__device__ __forceinline__ void sparse_quad(const uint64_t *__restrict__ idx, const F *__restrict__ val, uint32_t e, uint32_t m, uint64_t q, F (&b)[4]) {
-    b[0] = b[1] = b[2] = b[3] = fmake(0);
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-        if (e + k < m) {
-            const uint64_t ix = idx[e + k];
-            if ((ix >> 2) == q) { const F v = ldF(val + e + k); const uint32_t p = (uint32_t)(ix & 3); if (p == 0) b[0] = v; else if (p == 1) b[1] = v; else if (p == 2) b[2] = v; else b[3] = v; }
-        }
-    }
-}
+__device__ __forceinline__ F fkeep(bool c, const F &t) { const uint64_t m = 0 - (uint64_t)c; return fmake(t.re & m, t.im & m); }      // c ? t : 0, no select
+// lvl: the level of `dense` (index x >> lvl); with FOLD the values come in at level lvl - 2
 template <bool FOLD>
-__global__ void __launch_bounds__(1024) k_sc2_sparse_round(const uint64_t *__restrict__ idx_in, const F *__restrict__ val_in, const uint32_t *__restrict__ m_in, uint32_t m_arg,
-                                                           uint64_t *__restrict__ idx_out, F *__restrict__ val_out, uint32_t *__restrict__ m_out,
-                                                           const F *__restrict__ dense, F r0, F r1, Mailbox *mb, uint32_t seq) {
-    __shared__ uint32_t scan[1024];
-    __shared__ F red2[9][16];
-    const uint32_t t = threadIdx.x;
-    uint32_t m = m_in ? *m_in : m_arg;             // (the caller's own list: its length is a launch argument)
-    const uint64_t *idx = idx_in; const F *val = val_in;
-    if (FOLD) {                                   // two levels: one output pair per quad that holds a non-zero
-        const uint32_t per = (m + 1023) / 1024, lo = min(m, t * per), hi = min(m, lo + per);
-        uint32_t c = 0;
-        for (uint32_t e = lo; e < hi; e++) c += (e == 0 || (idx_in[e] >> 2) != (idx_in[e - 1] >> 2)) ? 1u : 0u;
-        scan[t] = c;
-        __syncthreads();
-        for (uint32_t d = 1; d < 1024; d <<= 1) {   // inclusive Hillis-Steele scan
-            const uint32_t v = t >= d ? scan[t - d] : 0;
-            __syncthreads();
-            scan[t] += v;
-            __syncthreads();
-        }
-        uint32_t base = scan[t] - c;
-        const uint32_t total = scan[1023];
-        for (uint32_t e = lo; e < hi; e++) {
-            const uint64_t q = idx_in[e] >> 2;
-            if (e == 0 || (idx_in[e - 1] >> 2) != q) {
-                F b[4]; sparse_quad(idx_in, val_in, e, m, q, b);
-                const F k0 = fadd(b[0], fmul(r0, fsub(b[1], b[0]))), k1 = fadd(b[2], fmul(r0, fsub(b[3], b[2])));
-                idx_out[base] = q; stF(val_out + base, fadd(k0, fmul(r1, fsub(k1, k0)))); base++;
-            }
-        }
-        if (t == 0) *m_out = total;
-        __threadfence_block();
-        __syncthreads();
-        m = total; idx = idx_out; val = val_out;
-    }
-    // G(r, t) over the quads of this level that hold a non-zero: the nine values of k_sc2_double
+__global__ void __launch_bounds__(256) k_sc2_sparse_round(const uint64_t *__restrict__ idx, const F *val_in, F *val_out, uint32_t m, int lvl,
+                                                           const F *__restrict__ dense, F r0, F r1, F *__restrict__ partials) {
     F c[9];
 #pragma unroll
     for (int q = 0; q < 9; q++) c[q] = fmake(0);
-    {
-        const uint32_t per = (m + 1023) / 1024, lo = min(m, t * per), hi = min(m, lo + per);
-        for (uint32_t e = lo; e < hi; e++) {
-            const uint64_t Q = idx[e] >> 2;
-            if (e == 0 || (idx[e - 1] >> 2) != Q) {
-                F b[4]; sparse_quad(idx, val, e, m, Q, b);
-                const F *ap = dense + 4 * Q;
-                const F a0 = ldF(ap), a1 = ldF(ap + 1), a2 = ldF(ap + 2), a3 = ldF(ap + 3);
-                c[0] = fadd(c[0], fmul(a0, b[0])); c[1] = fadd(c[1], fmul(a1, b[1])); c[3] = fadd(c[3], fmul(a2, b[2])); c[4] = fadd(c[4], fmul(a3, b[3]));
-                const F da01 = fsub(a1, a0), da23 = fsub(a3, a2), db01 = fsub(b[1], b[0]), db23 = fsub(b[3], b[2]);
-                c[2] = fadd(c[2], fmul(da01, db01)); c[5] = fadd(c[5], fmul(da23, db23));
-                c[6] = fadd(c[6], fmul(fsub(a2, a0), fsub(b[2], b[0]))); c[7] = fadd(c[7], fmul(fsub(a3, a1), fsub(b[3], b[1])));
-                c[8] = fadd(c[8], fmul(fsub(da23, da01), fsub(db23, db01)));
-            }
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < m; e += gridDim.x * blockDim.x) {
+        const uint64_t x = idx[e];
+        F v = ldF(val_in + e);
+        const uint64_t y = x >> lvl;
+        const F *ap = dense + 4 * (y >> 2);
+        const F a0 = ldF(ap), a1 = ldF(ap + 1), a2 = ldF(ap + 2), a3 = ldF(ap + 3);
+        if (FOLD) {
+            const uint32_t pp = (uint32_t)(x >> (lvl - 2)) & 3;      // position b0 + 2 b1 in the folded quad: weight (b0 ? r0 : 1 - r0) (b1 ? r1 : 1 - r1)
+            v = fmul(v, fmul((pp & 1) ? r0 : fsub(fmake(1), r0), (pp & 2) ? r1 : fsub(fmake(1), r1)));
+            stF(val_out + e, v);
         }
+        const uint32_t p = (uint32_t)y & 3;
+        const bool odd = p & 1, up = p & 2;
+        const F nv = fneg(v);
+        const F t0 = fmul(ldF(ap + p), v);                                                    // a_p b_p: (0,0) (1,0) (0,1) (1,1)
+        c[0] = fadd(c[0], fkeep(p == 0, t0)); c[1] = fadd(c[1], fkeep(p == 1, t0)); c[3] = fadd(c[3], fkeep(p == 2, t0)); c[4] = fadd(c[4], fkeep(p == 3, t0));
+        const F da01 = fsub(a1, a0), da23 = fsub(a3, a2);
+        const F t1 = fmul(up ? da23 : da01, odd ? v : nv);                                    // (a1 - a0)(b1 - b0) | (a3 - a2)(b3 - b2)
+        c[2] = fadd(c[2], fkeep(!up, t1)); c[5] = fadd(c[5], fkeep(up, t1));
+        const F t2 = fmul(odd ? fsub(a3, a1) : fsub(a2, a0), up ? v : nv);                    // (a2 - a0)(b2 - b0) | (a3 - a1)(b3 - b1)
+        c[6] = fadd(c[6], fkeep(!odd, t2)); c[7] = fadd(c[7], fkeep(odd, t2));
+        c[8] = fadd(c[8], fmul(fsub(da23, da01), (odd != up) ? nv : v));                      // ((a3 - a2) - (a1 - a0)) ((b3 - b2) - (b1 - b0))
     }
-    const int lane = t & 63, wv = t >> 6;
-#pragma unroll
-    for (int q = 0; q < 9; q++) { F sm = wave_sum(c[q]); if (lane == 0) red2[q][wv] = sm; }
-    __syncthreads();
-    if (t == 0) {
-        for (int q = 0; q < 9; q++) {
-            F sm = red2[q][0];
-            for (int w = 1; w < 16; w++) sm = fadd(sm, red2[q][w]);
-            uint64_t *o = reinterpret_cast<uint64_t *>(&mb->vals[q]);
-            __hip_atomic_store(o, sm.re, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); __hip_atomic_store(o + 1, sm.im, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        __hip_atomic_store(&mb->flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    block_reduce_store<9>(c, partials);
 }
-__global__ void __launch_bounds__(256) k_scatter_counted(const uint64_t *__restrict__ idx, const F *__restrict__ val, const uint32_t *__restrict__ m, F *__restrict__ out) {
-    const uint32_t n = *m;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) stF(out + idx[i], ldF(val + i));
+// out[x >> lvl] = the sum of the entries that meet there (out zeroed by the caller).  The list is sorted, so they are consecutive: the first
+// of a run adds it up.  (A run is one entry long through the opening; 2^lvl at the most.)
+__global__ void __launch_bounds__(256) k_scatter_counted(const uint64_t *__restrict__ idx, const F *__restrict__ val, uint32_t m, int lvl, F *__restrict__ out) {
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < m; e += gridDim.x * blockDim.x) {
+        const uint64_t y = idx[e] >> lvl;
+        if (e && (idx[e - 1] >> lvl) == y) continue;
+        F sm = ldF(val + e);
+        for (uint32_t f = e + 1; f < m && (idx[f] >> lvl) == y; f++) sm = fadd(sm, ldF(val + f));
+        stF(out + y, sm);
+    }
 }
 
-static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint64_t *sp_idx, const F *sp_val, size_t sp_m, size_t n, F prev_r, MHP h_qpoly, MHP h_r,
-                          MHP h_vr, MHP h_final);
+// ---- 2-product sumcheck whose FIRST table is a sum of eq tables (the open's P4: eq(P2.r | P1.r) + a eq(P3.r) against [M' | C]) -----------------
+// eq(r)[x] = prod_b (x_b ? r[b] : 1 - r[b]) and the sumcheck folds bit 0 first, so after i challenges c_0 .. c_{i-1} the folded table is
+//   T_i[y] = sigma_i prod_{b >= i} (y_{b-i} ? r[b] : 1 - r[b]),    sigma_0 = 1,  sigma_{i+1} = sigma_i ((1 - r[i]) + c_i (2 r[i] - 1)):
+// a host scalar times a shorter eq table.  The table is therefore never in memory.  More than that: the quad m of T_i is
+//   (a0, a1, a2, a3) = A[m] (e0 f0, e1 f0, e0 f1, e1 f1),   e = (1 - r[i], r[i]),  f = (1 - r[i+1], r[i+1]),  A = T_{i+2} / its two folds,
+// so X(rho, tau) = A[m] E(rho) F(tau) with E, F host scalars, and every one of the nine values of G(rho, tau) = sum_m X Y (see k_sc2_double) is
+// E(rho) F(tau) times a combination of only FOUR sums over the dense table's quads (b0 .. b3),  W_p = sum_m A[m] b_p[m]:  one product per
+// element and point where k_sc2_double spends four (k_sc2_double is at the VALU-issue limit, not at the memory's: DESIGN.md section 4).
+// A[m] = sigma Lo[m mod 2^sh] Hi[m >> sh] with Hi = eq(r[s .. k-1]) and Lo = eq(r[i+2 .. s-1]) for a fixed split bit s: both a few thousand
+// entries (cache-resident), built by ONE launch for every level the double rounds visit (k_eq_factors: each entry is its own product, no
+// doubling passes); sigma is applied on the host, Hi once per run of equal m >> sh.  Only the dense table is read, and with FOLD folded and
+// stored.  Exact field arithmetic throughout: the transcript is bit-identical to launch_sumcheck2 on the materialised table.
+struct EqPts { F r[2][40]; };          // the points, entry b = the challenge of index bit b
+__device__ __forceinline__ F eq_prod(const EqPts &p, int j, int from, int cnt, size_t x) {
+    F v = fmake(1);
+    for (int b = 0; b < cnt; b++) { const F rb = p.r[j][from + b]; v = fmul(v, ((x >> b) & 1) ? rb : fsub(fmake(1), rb)); }
+    return v;
+}
+// blockIdx.y = table: per point first Hi (bits s .. k-1), then Lo of levels 2, 4, .., 2 nlev (bits level .. s-1), packed in that order
+__global__ void __launch_bounds__(256) k_eq_factors(EqPts p, int k, int s, int nlev, F *__restrict__ out) {
+    const int per = nlev + 1, j = blockIdx.y / per, t = blockIdx.y % per;
+    size_t per_pt = (size_t)1 << (k - s), off = 0;
+    for (int l = 1; l <= nlev; l++) { if (l == t) off = per_pt; per_pt += (size_t)1 << (s - 2 * l); }
+    const int from = t == 0 ? s : 2 * t, cnt = t == 0 ? k - s : s - from;
+    F *o = out + (size_t)j * per_pt + off;
+    for (size_t x = blockIdx.x * (size_t)blockDim.x + threadIdx.x; x < ((size_t)1 << cnt); x += (size_t)gridDim.x * blockDim.x) stF(o + x, eq_prod(p, j, from, cnt, x));
+}
+// out[y] = sum_j al_j prod_{b < cnt} (y_b ? r_j[from + b] : 1 - r_j[from + b]): the folded table itself, for the levels that take the dense path
+template <int T>
+__global__ void __launch_bounds__(256) k_eq_sum_table(EqPts p, int from, int cnt, F al0, F al1, F *__restrict__ out) {
+    for (size_t y = blockIdx.x * (size_t)blockDim.x + threadIdx.x; y < ((size_t)1 << cnt); y += (size_t)gridDim.x * blockDim.x) {
+        F v = fmul(al0, eq_prod(p, 0, from, cnt, y));
+        if (T == 2) v = fadd(v, fmul(al1, eq_prod(p, 1, from, cnt, y)));
+        stF(out + y, v);
+    }
+}
+// One lane per element of the level-i dense table (n4 = 4Q of them), as k_sc2_double; lane q of a quad sums A_j[m] b_q into its own W_{j,q}
+// (a lane's q never changes: every stride is a multiple of four), so no lane exchange.  sh = s - (i + 2).  A workgroup walks spans of 256 U
+// consecutive elements (n4 is a power of two >= SC_DOUBLE_MIN: spans never straddle its end), all of a span's loads issued before the first
+// is used.  Partials: 4 T per workgroup, W_{j,p} at [4 j + p].
+struct EqSide { const F *lo0, *lo1, *hi0, *hi1; };
+template <bool FOLD, int T>
+__global__ void __launch_bounds__(256) k_sc2_eq_double(EqSide eq, int sh, const F *__restrict__ s2, F *__restrict__ d2, size_t n4, F r0, F r1, F *__restrict__ partials) {
+    constexpr int U = FOLD ? 2 : 4;
+    F W0 = fmake(0), W1 = fmake(0), in0 = fmake(0), in1 = fmake(0), hv0 = fmake(0), hv1 = fmake(0);      // W_j = sum over finished runs; in_j: the current run's sum of Lo b
+    size_t hcur = ~(size_t)0;
+    const size_t lmask = ((size_t)1 << sh) - 1;
+    for (size_t g0 = blockIdx.x * (size_t)(256 * U) + threadIdx.x; g0 < n4; g0 += (size_t)gridDim.x * (256 * U)) {
+        F bv[U];
+        if (FOLD) {
+            F e[U][4];
+#pragma unroll
+            for (int u = 0; u < U; u++) { const F *h = s2 + 4 * (g0 + 256 * u); e[u][0] = ldF(h); e[u][1] = ldF(h + 1); e[u][2] = ldF(h + 2); e[u][3] = ldF(h + 3); }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const F k0 = fadd(e[u][0], fmul(r0, fsub(e[u][1], e[u][0]))), k1 = fadd(e[u][2], fmul(r0, fsub(e[u][3], e[u][2])));
+                bv[u] = fadd(k0, fmul(r1, fsub(k1, k0)));
+                stF(d2 + g0 + 256 * u, bv[u]);
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; u++) bv[u] = ldF(s2 + g0 + 256 * u);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const size_t m = (g0 + 256 * u) >> 2, h = m >> sh, l = m & lmask;
+            if (h != hcur) {                                  // a new run: close the last one with its Hi (the first time with zeros)
+                W0 = fadd(W0, fmul(hv0, in0)); in0 = fmake(0); hv0 = ldF(eq.hi0 + h);
+                if (T == 2) { W1 = fadd(W1, fmul(hv1, in1)); in1 = fmake(0); hv1 = ldF(eq.hi1 + h); }
+                hcur = h;
+            }
+            in0 = fadd(in0, fmul(ldF(eq.lo0 + l), bv[u]));
+            if (T == 2) in1 = fadd(in1, fmul(ldF(eq.lo1 + l), bv[u]));
+        }
+    }
+    W0 = fadd(W0, fmul(hv0, in0));
+    if (T == 2) W1 = fadd(W1, fmul(hv1, in1));
+    const int q = threadIdx.x & 3;
+    const F z = fmake(0);
+    F c[4 * T];
+#pragma unroll
+    for (int p = 0; p < 4; p++) { c[p] = q == p ? W0 : z; if (T == 2) c[4 + p] = q == p ? W1 : z; }
+    block_reduce_store<4 * T>(c, partials);
+}
+struct EqSum { int T; CHP r[2]; F a[2]; };
+
+static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint64_t *sp_idx, const F *sp_val, size_t sp_m, const EqSum *eq, size_t n, F prev_r, MHP h_qpoly,
+                          MHP h_r, MHP h_vr, MHP h_final);
 int launch_sumcheck2(hobbit_ctx *ctx, const F *v1, const F *v2, size_t n, F prev_r, MHP h_qpoly, MHP h_r, MHP h_vr, MHP h_final) {
-    return sumcheck2_impl(ctx, v1, v2, nullptr, nullptr, 0, n, prev_r, h_qpoly, h_r, h_vr, h_final);
+    return sumcheck2_impl(ctx, v1, v2, nullptr, nullptr, 0, nullptr, n, prev_r, h_qpoly, h_r, h_vr, h_final);
+}
+// v1 = sum_{j < T} a_j eq(r_j) given by its T <= 2 points (k = log2 n host entries each) and scalars; v2 dense on the device
+int launch_sumcheck2_eq(hobbit_ctx *ctx, int T, CHP h_r1, CHP h_r2, CHP h_a, const F *v2, size_t n, F prev_r, MHP h_qpoly, MHP h_r, MHP h_vr, MHP h_final) {
+    if (T < 1 || T > 2) return ctx->fail(HOBBIT_EINVAL, "sumcheck2_eq: one or two eq tables");
+    if (!h_r1 || (T == 2 && !h_r2) || !h_a || !v2) return ctx->fail(HOBBIT_EINVAL, "sumcheck2_eq: null points, scalars or table");
+    if (n > ((size_t)1 << 40)) return ctx->fail(HOBBIT_EINVAL, "sumcheck2_eq: n must be a power of two >= 2, at most 2^40");
+    EqSum e; e.T = T; e.r[0] = h_r1; e.r[1] = T == 2 ? h_r2 : h_r1; e.a[0] = h_a[0]; e.a[1] = T == 2 ? (F)h_a[1] : fmake(0);
+    return sumcheck2_impl(ctx, nullptr, v2, nullptr, nullptr, 0, &e, n, prev_r, h_qpoly, h_r, h_vr, h_final);
 }
 // v2 given as sp_m sorted, distinct (index, value) pairs on the device (every other entry zero)
 int launch_sumcheck2_sparse(hobbit_ctx *ctx, const F *v1, const uint64_t *d_idx, const F *d_val, size_t m, size_t n, F prev_r, MHP h_qpoly, MHP h_r, MHP h_vr, MHP h_final) {
     if (!m || m > ((size_t)1 << 20)) return ctx->fail(HOBBIT_EINVAL, "sumcheck2_sparse: between 1 and 2^20 non-zeros");
-    return sumcheck2_impl(ctx, v1, nullptr, d_idx, d_val, m, n, prev_r, h_qpoly, h_r, h_vr, h_final);
+    return sumcheck2_impl(ctx, v1, nullptr, d_idx, d_val, m, nullptr, n, prev_r, h_qpoly, h_r, h_vr, h_final);
 }
-static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint64_t *sp_idx, const F *sp_val, size_t sp_m, size_t n, F prev_r, MHP h_qpoly, MHP h_r,
-                          MHP h_vr, MHP h_final) {
+static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint64_t *sp_idx, const F *sp_val, size_t sp_m, const EqSum *eq, size_t n, F prev_r, MHP h_qpoly,
+                          MHP h_r, MHP h_vr, MHP h_final) {
     int rounds = 0; while (((size_t)1 << rounds) < n) rounds++;
     if (((size_t)1 << rounds) != n || n < 2) return ctx->fail(HOBBIT_EINVAL, "sumcheck2: n must be a power of two >= 2");
-    const int MAXB = 1024;
+    const int MAXB = 1024, EQ_MAXB = 2048;
     F rnd = prev_r;
     std::vector<F> ta, tb;
+    EqPts pts;
+    if (eq) for (int j = 0; j < 2; j++) for (int b = 0; b < 40; b++) pts.r[j][b] = (j < eq->T && b < rounds) ? (F)eq->r[j][b] : fmake(0);
+    // the eq-sum table itself, level `from` with scalars al: what the dense path reads where the table is short
+    auto eq_table = [&](int from, const F *al, F *out) -> int {
+        const size_t len = (size_t)1 << (rounds - from);
+        if (eq->T == 2) HB_LAUNCH(ctx, "k_eq_sum_table", k_eq_sum_table<2>, dim3(grid_for(len, 256)), dim3(256), 0, pts, from, rounds - from, al[0], al[1], out);
+        else HB_LAUNCH(ctx, "k_eq_sum_table", k_eq_sum_table<1>, dim3(grid_for(len, 256)), dim3(256), 0, pts, from, rounds - from, al[0], al[1], out);
+        return 0;
+    };
     if (n <= SC_TAIL) {                       // small instance: all rounds on the host
+        if (eq) {
+            F *dv1; HB_TRY(ctx->workspace(n * sizeof(F), (void **)&dv1));
+            HB_TRY(eq_table(0, eq->a, dv1));
+            v1 = dv1;
+        }
         if (sp_idx) {
             F *dv2; HB_TRY(ctx->workspace(n * sizeof(F), (void **)&dv2));
             HB_TRY(launch_zero(ctx, dv2, n * sizeof(F)));
@@ -2710,18 +2763,28 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
     } else {
         size_t szA = n / 2, szB = n / 4;
         const bool sparse = sp_idx && n >= 16 * SC_DOUBLE_MIN;            // (shorter tables: scatter at once, dense path)
-        const size_t sp_elems = sp_idx ? 2 * (sp_m + (sp_m + 1) / 2) + 8 + (sparse ? 0 : n) : 0;      // two (value | index) lists + counters (+ a dense copy)
-        F *ws; HB_TRY(ctx->workspace((2 * szA + 2 * szB + (size_t)MAXB * 9 + 4 + sp_elems) * sizeof(F), (void **)&ws));
+        const size_t sp_elems = sp_idx ? sp_m + (sparse ? 0 : n) : 0;      // the list's values at the current level (or a dense copy)
+        // eq form: its own partials, the table where the dense path takes over (at most 4 SC_DOUBLE_MIN entries) and the factor tables
+        const bool eq_double = eq && n >= SC_DOUBLE_MIN;
+        const int eq_s = std::max(rounds - 12, (rounds + 1) / 2);               // split bit: Hi <= 4096 entries or both halves of k; every double level has i + 2 <= k - 12 <= s
+        int eq_nlev = 0; while (eq_double && (n >> (2 * eq_nlev)) >= SC_DOUBLE_MIN) eq_nlev++;
+        size_t eq_per_pt = (size_t)1 << (rounds - eq_s); for (int l = 1; l <= eq_nlev; l++) eq_per_pt += (size_t)1 << (eq_s - 2 * l);
+        const size_t eq_elems = eq ? (size_t)EQ_MAXB * 8 + 4 + 4 * SC_DOUBLE_MIN + (eq_double ? 2 * eq_per_pt : 0) : 0;
+        F *ws; HB_TRY(ctx->workspace((2 * szA + 2 * szB + (size_t)MAXB * 9 + 4 + sp_elems + eq_elems) * sizeof(F), (void **)&ws));
         F *A1 = ws, *A2 = A1 + szA, *B1 = A2 + szA, *B2 = B1 + szB, *part = B2 + szB;
         F *spw = part + (size_t)MAXB * 9 + 4;
-        F *lval[2] = {spw, spw + sp_m + (sp_m + 1) / 2}; uint64_t *lidx[2] = {reinterpret_cast<uint64_t *>(lval[0] + sp_m), reinterpret_cast<uint64_t *>(lval[1] + sp_m)};
-        uint32_t *lcnt = reinterpret_cast<uint32_t *>(spw + 2 * (sp_m + (sp_m + 1) / 2));       // [0]: the caller's count, [1], [2]: the two lists'
         if (sp_idx && !sparse) {
-            F *dv2 = spw + 2 * (sp_m + (sp_m + 1) / 2) + 8;
+            F *dv2 = spw + sp_m;
             HB_TRY(launch_zero(ctx, dv2, n * sizeof(F)));
             HB_TRY(launch_scatter(ctx, sp_idx, sp_val, sp_m, dv2));
             v2 = dv2;
         }
+        F *eq_part = spw + sp_elems, *eq_tab = eq_part + (size_t)EQ_MAXB * 8 + 4, *eq_fac = eq_tab + 4 * SC_DOUBLE_MIN;
+        F sig[2] = {fmake(1), fmake(1)}, eq_al[2] = {fmake(0), fmake(0)};        // sigma_{j,i}; a_j sigma_{j,i} of the last launch
+        if (eq && !eq_double) { HB_TRY(eq_table(0, eq->a, eq_tab)); v1 = eq_tab; }      // round by round from the start: n < SC_DOUBLE_MIN entries
+        if (eq_double)
+            HB_LAUNCH(ctx, "k_eq_factors", k_eq_factors, dim3(grid_for((size_t)1 << std::max(eq_s, rounds - eq_s), 256, 64), eq->T * (eq_nlev + 1)), dim3(256), 0, pts, rounds,
+                      eq_s, eq_nlev, eq_fac);
         Mailbox *mb; unsigned *ticket; HB_TRY(ctx->mailbox(&mb, &ticket));
         const F *s1 = v1, *s2 = v2;
         F *d1 = A1, *d2 = A2;
@@ -2732,22 +2795,39 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
             const F *S1 = v1, *S2 = v2; size_t S_size = n;            // the materialised tables: level i - 2 (or the inputs)
             F *D1 = B1, *D2 = B2;                                     // T_2 has n/4 elements: fits B; later levels fit either
             bool pend = false; F pr0 = fmake(0), pr1 = fmake(0);      // (r_{i-2}, r_{i-1}): still to be applied to S
-            const uint64_t *cidx = sp_idx; const F *cval = sp_val; const uint32_t *ccnt = nullptr; int lnext = 0;  // the sparse list at the level S1 is at
+            const F *cval = sp_val;                                   // the sparse list's values at the level S1 is at
             while ((n >> i) >= SC_DOUBLE_MIN) {
                 const size_t Q = (n >> i) / 4;
                 const int nb = grid_for(4 * Q, 256, MAXB);
                 const uint32_t seq = ++ctx->mbox_seq;
                 if (sparse) {
-                    if (!pend) HB_LAUNCH(ctx, "k_sc2_sparse_round", k_sc2_sparse_round<false>, dim3(1), dim3(1024), 0, cidx, cval, ccnt, (uint32_t)sp_m, (uint64_t *)nullptr,
-                                         (F *)nullptr, (uint32_t *)nullptr, S1, pr0, pr1, mb, seq);
+                    const int nbs = grid_for(sp_m, 256, MAXB);
+                    if (!pend) HB_LAUNCH(ctx, "k_sc2_sparse_round", k_sc2_sparse_round<false>, dim3(nbs), dim3(256), 0, sp_idx, cval, (F *)nullptr, (uint32_t)sp_m, i, S1, pr0, pr1, part);
                     else {
                         HB_LAUNCH(ctx, "k_sc2_fold4", k_sc2_fold4, dim3(grid_for(4 * Q, 256, 4096)), dim3(256), 0, S1, D1, 4 * Q, pr0, pr1);      // the dense table: level i - 2 -> level i
-                        HB_LAUNCH(ctx, "k_sc2_sparse_round", k_sc2_sparse_round<true>, dim3(1), dim3(1024), 0, cidx, cval, ccnt, (uint32_t)sp_m, lidx[lnext], lval[lnext],
-                                  lcnt + 1 + lnext, (const F *)D1, pr0, pr1, mb, seq);
-                        cidx = lidx[lnext]; cval = lval[lnext]; ccnt = lcnt + 1 + lnext; lnext ^= 1;
+                        HB_LAUNCH(ctx, "k_sc2_sparse_round", k_sc2_sparse_round<true>, dim3(nbs), dim3(256), 0, sp_idx, cval, spw, (uint32_t)sp_m, i, (const F *)D1, pr0, pr1, part);
+                        cval = spw;                                   // (each thread rewrites its own entry: in place from the second fold on)
                         S1 = D1; S_size = 4 * Q;
                         if (D1 == B1) { D1 = A1; D2 = A2; } else { D1 = B1; D2 = B2; }
                     }
+                    HB_LAUNCH(ctx, "k_sc_reduce", k_sc_reduce_post<9>, dim3(1), dim3(256), 0, part, nbs, mb, seq);
+                } else if (eq) {
+                    size_t lo_off = (size_t)1 << (rounds - eq_s); for (int l = 1; l <= i / 2; l++) lo_off += (size_t)1 << (eq_s - 2 * l);      // Lo of level i + 2
+                    const F *f1 = eq->T == 2 ? eq_fac + eq_per_pt : eq_fac;
+                    for (int j = 0; j < 2; j++) eq_al[j] = fmul(eq->a[j], sig[j]);
+                    const EqSide es = {eq_fac + lo_off, f1 + lo_off, eq_fac, f1};
+                    const int sh = eq_s - (i + 2), nbe = grid_for(4 * Q, pend ? 512 : 1024, EQ_MAXB);      // spans of 256 U elements
+                    if (!pend) {
+                        if (eq->T == 2) HB_LAUNCH(ctx, "k_sc2_eq_double", (k_sc2_eq_double<false, 2>), dim3(nbe), dim3(256), 0, es, sh, S2, (F *)nullptr, 4 * Q, pr0, pr1, eq_part);
+                        else HB_LAUNCH(ctx, "k_sc2_eq_double", (k_sc2_eq_double<false, 1>), dim3(nbe), dim3(256), 0, es, sh, S2, (F *)nullptr, 4 * Q, pr0, pr1, eq_part);
+                    } else {
+                        if (eq->T == 2) HB_LAUNCH(ctx, "k_sc2_eq_double", (k_sc2_eq_double<true, 2>), dim3(nbe), dim3(256), 0, es, sh, S2, D2, 4 * Q, pr0, pr1, eq_part);
+                        else HB_LAUNCH(ctx, "k_sc2_eq_double", (k_sc2_eq_double<true, 1>), dim3(nbe), dim3(256), 0, es, sh, S2, D2, 4 * Q, pr0, pr1, eq_part);
+                        S2 = D2; S_size = 4 * Q;
+                        if (D1 == B1) { D1 = A1; D2 = A2; } else { D1 = B1; D2 = B2; }
+                    }
+                    if (eq->T == 2) HB_LAUNCH(ctx, "k_sc_reduce", k_sc_reduce_post<8>, dim3(1), dim3(256), 0, eq_part, nbe, mb, seq);
+                    else HB_LAUNCH(ctx, "k_sc_reduce", k_sc_reduce_post<4>, dim3(1), dim3(256), 0, eq_part, nbe, mb, seq);
                 } else {
                 if (!pend) HB_LAUNCH(ctx, "k_sc2_double", k_sc2_double<false>, dim3(nb), dim3(256), 0, S1, S2, (F *)nullptr, (F *)nullptr, Q, pr0, pr1, part);
                 else {
@@ -2759,6 +2839,17 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
                 }
                 HB_TRY(ctx->mbox_wait(seq));
                 F G[9]; for (int q = 0; q < 9; q++) G[q] = mb->vals[q];            // G(r, t) at (0,0) (1,0) (inf,0) | (0,1) (1,1) (inf,1) | (0,inf) (1,inf) (inf,inf)
+                if (eq) {                                                           // posted: W_{j,p}.  G(rho, tau) = sum_j al_j E_j(rho) F_j(tau) S_j(rho, tau)
+                    for (int q = 0; q < 9; q++) G[q] = fmake(0);
+                    for (int j = 0; j < eq->T; j++) {
+                        const F W[4] = {mb->vals[4 * j], mb->vals[4 * j + 1], mb->vals[4 * j + 2], mb->vals[4 * j + 3]};
+                        const F d01 = fsub(W[1], W[0]), d23 = fsub(W[3], W[2]);
+                        const F S[9] = {W[0], W[1], d01, W[2], W[3], d23, fsub(W[2], W[0]), fsub(W[3], W[1]), fsub(d23, d01)};
+                        const F e1 = pts.r[j][i], e0 = fsub(fmake(1), e1), f1v = pts.r[j][i + 1], f0 = fsub(fmake(1), f1v);
+                        const F E[3] = {e0, e1, fsub(e1, e0)}, Fv[3] = {fmul(eq_al[j], f0), fmul(eq_al[j], f1v), fmul(eq_al[j], fsub(f1v, f0))};
+                        for (int tau = 0; tau < 3; tau++) for (int rho = 0; rho < 3; rho++) G[3 * tau + rho] = fadd(G[3 * tau + rho], fmul(fmul(E[rho], Fv[tau]), S[3 * tau + rho]));
+                    }
+                }
                 // round i: G(r, 0) + G(r, 1) as (a, b, c) from its values at r = inf, 1, 0
                 F p0[3]; p0[0] = fadd(G[2], G[5]); p0[2] = fadd(G[0], G[3]); p0[1] = fsub(fsub(fadd(G[1], G[4]), p0[0]), p0[2]);
                 for (int q = 0; q < 3; q++) { rnd = mimc_hash(rnd, p0[q]); h_qpoly[3 * i + q] = p0[q]; }
@@ -2769,6 +2860,10 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
                 const F p1[3] = {v[2], fsub(fsub(v[1], v[2]), v[0]), v[0]};         // round i + 1: (a, b, c)
                 for (int q = 0; q < 3; q++) { rnd = mimc_hash(rnd, p1[q]); h_qpoly[3 * (i + 1) + q] = p1[q]; }
                 h_r[i + 1] = rnd;
+                if (eq) for (int j = 0; j < eq->T; j++) for (int b = 0; b < 2; b++) {              // sigma_{j,i+2}: the table's two index bits folded with (r_i, r_{i+1})
+                    const F rho = pts.r[j][i + b], e0 = fsub(fmake(1), rho);
+                    sig[j] = fmul(sig[j], fadd(e0, fmul(b ? rnd : r, fsub(rho, e0))));
+                }
                 pend = true; pr0 = r; pr1 = rnd; i += 2;
             }
             // bridge to the round-by-round loop: it expects s = T_{i-1} and rnd = r_{i-1}.  S = T_{i-2}: fold it once with r_{i-2}
@@ -2776,10 +2871,12 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
             if (sparse) {                                             // the second table, dense from here on: level i - 2, beside S1 (n >= 16 SC_DOUBLE_MIN: S1 is A1 or B1)
                 F *m2 = (S1 == A1) ? A2 : B2;
                 HB_TRY(launch_zero(ctx, m2, S_size * sizeof(F)));
-                HB_LAUNCH(ctx, "k_scatter_counted", k_scatter_counted, dim3(32), dim3(256), 0, cidx, cval, ccnt, m2);
+                HB_LAUNCH(ctx, "k_scatter_counted", k_scatter_counted, dim3(grid_for(sp_m, 256, MAXB)), dim3(256), 0, sp_idx, cval, (uint32_t)sp_m, i - 2, m2);
                 S2 = m2;
             }
-            F *b1 = (S1 == A1) ? B1 : A1, *b2 = (S1 == A1) ? B2 : A2;
+            if (eq) { HB_TRY(eq_table(i - 2, eq_al, eq_tab)); S1 = eq_tab; }      // the first table, dense from here on: level i - 2, S_size <= 2 SC_DOUBLE_MIN entries
+            const bool at_A = eq ? S2 == A2 : S1 == A1;
+            F *b1 = at_A ? B1 : A1, *b2 = at_A ? B2 : A2;
             const size_t L = S_size / 4;
             HB_LAUNCH(ctx, "k_sc2_fold_poly", k_sc2_fold_poly, dim3(grid_for(L, 256, MAXB)), dim3(256), 0, S1, S2, b1, b2, L, pr0, part);
             s1 = b1; s2 = b2; cur = 2 * L;

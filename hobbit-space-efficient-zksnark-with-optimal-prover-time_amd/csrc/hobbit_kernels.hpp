@@ -55,7 +55,6 @@ int launch_vecmat(hobbit_ctx *ctx, const F *Mx, size_t rows, size_t cols, const 
 int launch_gather_strided(hobbit_ctx *ctx, const F *src, const uint64_t *d_idx, size_t nq, uint32_t m, size_t bmul, size_t stride, F *out);
 int launch_dot(hobbit_ctx *ctx, const F *a, const F *b, size_t n, F *part, F *out);
 int launch_change_form_tail(hobbit_ctx *ctx, F *data, size_t n, uint32_t T);
-int launch_eq_pair_axpy(hobbit_ctx *ctx, CHP h_r1, CHP h_r2, int k, F a, F *d_half, F *d_out);
 int launch_scatter(hobbit_ctx *ctx, const uint64_t *idx, const F *val, size_t n, F *out);
 int launch_axpy(hobbit_ctx *ctx, F *y, const F *x, F a, size_t n);
 int launch_err_terms(hobbit_ctx *ctx, int kind, const F *const *tables, const int32_t *gate, size_t n, MHP h_K);
@@ -75,6 +74,7 @@ int launch_eq_step_batched(hobbit_ctx *ctx, const F *old, F *nw, size_t m, size_
 int launch_eq_head_batched(hobbit_ctx *ctx, F *out, size_t ld, const F *z, int v, int h, int reps);
 int launch_fill_F(hobbit_ctx *ctx, F *p, size_t stride, size_t n, F v);
 int launch_sumcheck2(hobbit_ctx *ctx, const F *v1, const F *v2, size_t n, F prev_r, MHP h_qpoly, MHP h_r, MHP h_vr, MHP h_final);
+int launch_sumcheck2_eq(hobbit_ctx *ctx, int T, CHP h_r1, CHP h_r2, CHP h_a, const F *v2, size_t n, F prev_r, MHP h_qpoly, MHP h_r, MHP h_vr, MHP h_final);
 int launch_sumcheck2_sparse(hobbit_ctx *ctx, const F *v1, const uint64_t *d_idx, const F *d_val, size_t m, size_t n, F prev_r, MHP h_qpoly, MHP h_r, MHP h_vr, MHP h_final);
 int launch_gate_lkp_sumcheck(hobbit_ctx *ctx, const F *const tabs[9], size_t n, CHP h_a, MHP h_rand, MHP h_sum, MHP h_poly, MHP h_r, MHP h_final, int *h_check);
 int launch_lkp_prepare(hobbit_ctx *ctx, const int32_t *S, const F *L, const F *R, const F *O, int32_t *s2, int32_t *s3, F *blo, size_t n);

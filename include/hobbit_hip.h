@@ -408,6 +408,12 @@ int hobbit_sumcheck2(hobbit_ctx *ctx, const hobbit_F *d_v1, const hobbit_F *d_v2
  * checked: an unsorted list or an index >= n is undefined behaviour.  Same outputs as hobbit_sumcheck2. */
 int hobbit_sumcheck2_sparse(hobbit_ctx *ctx, const hobbit_F *d_v1, const uint64_t *d_idx, const hobbit_F *d_val, size_t m, size_t n,
                             const hobbit_F *prev_r, hobbit_F *h_qpoly, hobbit_F *h_r, hobbit_F *h_vr, hobbit_F *h_final);
+/* generate_2product_sumcheck_proof(v1, v2, prev_r) with v1 = sum_{j<T} h_a[j] eq(r_j), T = 1 or 2, given by its points: h_r1, h_r2 (host,
+ * log2 n entries each; h_r2 is ignored when T = 1) and the T scalars h_a.  eq(r)[x] = prod_b (x_b ? r[b] : 1 - r[b]), bit 0 the least
+ * significant: hobbit_eq_table's table.  v1 is never built at the sizes that take two rounds per round trip (the open's P4,
+ * src/PC_utils.cpp:342-362).  Same outputs as hobbit_sumcheck2 on the materialised table, bit for bit; h_vr[0] is v1's value. */
+int hobbit_sumcheck2_eq(hobbit_ctx *ctx, int T, const hobbit_F *h_r1, const hobbit_F *h_r2, const hobbit_F *h_a, const hobbit_F *d_v2, size_t n,
+                        const hobbit_F *prev_r, hobbit_F *h_qpoly, hobbit_F *h_r, hobbit_F *h_vr, hobbit_F *h_final);
 /* Degree-4 gate-consistency sumcheck: the in-memory phase of prove_gate_consistency (src/sumcheck.cpp:875-929) over the six
  * folded tables fold_add, fold_beta, fold_L, fold_R, fold_O, fold_mul (n F each, device):
  *   sum_j  add*beta*(a0 L + a1 R) + a2*mul*beta*L*R + a3*beta*O,   h_a = a[0..3] (generate_randomness(4), :873).
