@@ -53,6 +53,10 @@ ABI_SYMBOLS = [
     "hobbit_encode_interleaved", "hobbit_brakedown_shape", "hobbit_brakedown_commit", "hobbit_brakedown_free", "hobbit_brakedown_dims",
     "hobbit_brakedown_matrix_dev", "hobbit_brakedown_levels_dev", "hobbit_brakedown_levels", "hobbit_brakedown_root", "hobbit_brakedown_tensor",
     "hobbit_brakedown_open",
+    "hobbit_brakedown_stream_shape", "hobbit_brakedown_stream_begin", "hobbit_brakedown_stream_push", "hobbit_brakedown_stream_finish",
+    "hobbit_brakedown_stream_device_bytes", "hobbit_brakedown_stream_free", "hobbit_brakedown_stream_open_begin",
+    "hobbit_brakedown_stream_open_aggregate_push", "hobbit_brakedown_stream_open_reply_push", "hobbit_brakedown_stream_open_finish",
+    "hobbit_brakedown_stream_open_device_bytes", "hobbit_brakedown_stream_open_free",
 ]
 
 
@@ -83,6 +87,10 @@ def load_library(path=LIB_PATH):
     lib.hobbit_brakedown_matrix_dev.restype = c_vp
     lib.hobbit_brakedown_levels_dev.restype = c_vp
     lib.hobbit_brakedown_free.restype = None
+    lib.hobbit_brakedown_stream_free.restype = None
+    lib.hobbit_brakedown_stream_open_free.restype = None
+    lib.hobbit_brakedown_stream_device_bytes.restype = c_sz
+    lib.hobbit_brakedown_stream_open_device_bytes.restype = c_sz
     # explicit prototypes: a bare Python int would otherwise be passed as a 32-bit C int and
     # truncate device pointers / sizes
     V, S, I, L, U64 = c_vp, c_sz, c_int, c_ll, ctypes.c_uint64
@@ -133,6 +141,11 @@ def load_library(path=LIB_PATH):
         "hobbit_brakedown_free": [V], "hobbit_brakedown_dims": [V, V, V, V], "hobbit_brakedown_matrix_dev": [V], "hobbit_brakedown_levels_dev": [V],
         "hobbit_brakedown_levels": [V, V, V], "hobbit_brakedown_root": [V, V, V], "hobbit_brakedown_tensor": [V, V, S, S, V],
         "hobbit_brakedown_open": [V, V, V, V, V, S, V, V, V, V],
+        "hobbit_brakedown_stream_shape": [S, V, V], "hobbit_brakedown_stream_begin": [V, S, I, V], "hobbit_brakedown_stream_push": [V, V, V],
+        "hobbit_brakedown_stream_finish": [V, V, I, V], "hobbit_brakedown_stream_device_bytes": [V], "hobbit_brakedown_stream_free": [V],
+        "hobbit_brakedown_stream_open_begin": [V, S, S, V, V, V, S, V], "hobbit_brakedown_stream_open_aggregate_push": [V, V, V],
+        "hobbit_brakedown_stream_open_reply_push": [V, V, V], "hobbit_brakedown_stream_open_finish": [V, V, V, V, V, V, V],
+        "hobbit_brakedown_stream_open_device_bytes": [V], "hobbit_brakedown_stream_open_free": [V],
     }
     for name, args in protos.items():
         getattr(lib, name).argtypes = args
@@ -573,6 +586,83 @@ class Hobbit:
                    paths=np.zeros((nq, depth, 32), np.uint8) if want_paths else None)
         self._chk(self.lib.hobbit_brakedown_open(self.ctx, c.h, _hp(x), _hp(r), _hp(I), c_sz(nq), _hp(out["aggr_beta"]), _hp(out["aggr_r"]),
                                                  _hp(out["reply"]), _hp(out["paths"]) if want_paths else None))
+        return out
+
+    # ---- streaming Brakedown baseline (src/Elastic_PC.cpp:112-172, 287-313, 561-623)
+    @staticmethod
+    def brakedown_stream_shape(N):
+        """(B, chunks) of test_Elastic_PC option 3 for N = 2^n, 16 <= n <= 30: B = 2^((n-1)//2 + 6)"""
+        lib = load_library()
+        B, chunks = c_sz(), ctypes.c_uint32()
+        if lib.hobbit_brakedown_stream_shape(c_sz(N), ctypes.byref(B), ctypes.byref(chunks)) != 0:
+            raise HobbitError("brakedown_stream: N = %d is not 2^n with 16 <= n <= 30" % N)
+        return B.value, chunks.value
+
+    def _chunk_ptrs(self, chunks, B):
+        """device pointer of every chunk of an iterable of host arrays (B, 2) / DeviceBuffers / raw pointers; a host chunk is staged through
+        one device buffer (hobbit_memcpy_h2d waits for what the stream has queued, so its last reader has finished)"""
+        stage = None
+        for ch in chunks:
+            if isinstance(ch, DeviceBuffer):
+                yield ch.ptr
+            elif isinstance(ch, int):
+                yield ch
+            else:
+                a = Fh(ch).reshape(-1, 2)
+                assert a.shape[0] == B
+                if stage is None:
+                    stage = self.alloc(16 * B)
+                self._chk(self.lib.hobbit_memcpy_h2d(self.ctx, c_vp(stage.ptr), _hp(a), c_sz(a.nbytes)))
+                yield stage.ptr
+
+    def brakedown_stream_commit(self, chunks, B, gcc_arg_order=1, quirk=1, levels="host", after_push=None):
+        """commit_brakedown_stream over an iterable of B-element chunks (host arrays or device buffers); the graphs for n = B must be
+        finalized.  Returns the flat levels ((4B-1, 32) host array, or the DeviceBuffer with levels="device").  after_push(handle, count) is
+        called after every push (tests read hobbit_brakedown_stream_device_bytes there)."""
+        h = c_vp()
+        self._chk(self.lib.hobbit_brakedown_stream_begin(self.ctx, c_sz(B), c_int(gcc_arg_order), ctypes.byref(h)))
+        try:
+            n = 0
+            for ptr in self._chunk_ptrs(chunks, B):
+                self._chk(self.lib.hobbit_brakedown_stream_push(self.ctx, h, c_vp(ptr)))
+                n += 1
+                if after_push is not None:
+                    after_push(h, n)
+            lv = self.alloc(32 * (4 * B - 1))
+            self._chk(self.lib.hobbit_brakedown_stream_finish(self.ctx, h, c_int(quirk), c_vp(lv.ptr)))
+            self.sync()
+        finally:
+            self.lib.hobbit_brakedown_stream_free(h)
+        return lv if levels == "device" else self.to_host(lv, (4 * B - 1, 32), np.uint8)
+
+    def brakedown_stream_open(self, chunks_aggr, chunks_reply, B, nchunks, x, r0, I, levels=None):
+        """open_brakedown_stream's prover side: the same stream twice (two iterables of nchunks chunks), x (>= log2(nchunks) F of the point),
+        r0 (the drawn F; r_v are its powers), I (indices < 2B).  levels: the commitment's flat levels (host array or DeviceBuffer) for the
+        paths, or None.  Returns dict(beta, r_v, aggr_beta, aggr_r, reply (nq, nchunks, 2), paths (nq, log2 2B, 32) or None)."""
+        lc = nchunks.bit_length() - 1
+        beta = self.precompute_beta(Fh(x).reshape(-1, 2)[:lc].copy())
+        rv = np.zeros((nchunks, 2), np.uint64); rv[0] = Fh(r0).reshape(2)
+        for i in range(1, nchunks):
+            self.lib.hobbit_f_mul_host(_hp(rv[i - 1:i]), _hp(rv[0:1]), _hp(rv[i:i + 1]), c_sz(1))
+        I = np.ascontiguousarray(I, np.uint64); nq = I.shape[0]
+        depth = (2 * B).bit_length() - 1
+        keep = None
+        if levels is not None and not isinstance(levels, DeviceBuffer):
+            keep = levels = self.to_device(np.ascontiguousarray(levels, np.uint8))
+        out = dict(beta=beta, r_v=rv, aggr_beta=np.zeros((B, 2), np.uint64), aggr_r=np.zeros((B, 2), np.uint64), reply=np.zeros((nq, nchunks, 2), np.uint64),
+                   paths=np.zeros((nq, depth, 32), np.uint8) if levels is not None else None)
+        h = c_vp()
+        self._chk(self.lib.hobbit_brakedown_stream_open_begin(self.ctx, c_sz(B), c_sz(nchunks), _hp(beta), _hp(rv), _hp(I), c_sz(nq), ctypes.byref(h)))
+        try:
+            for ptr in self._chunk_ptrs(chunks_aggr, B):
+                self._chk(self.lib.hobbit_brakedown_stream_open_aggregate_push(self.ctx, h, c_vp(ptr)))
+            for ptr in self._chunk_ptrs(chunks_reply, B):
+                self._chk(self.lib.hobbit_brakedown_stream_open_reply_push(self.ctx, h, c_vp(ptr)))
+            self._chk(self.lib.hobbit_brakedown_stream_open_finish(self.ctx, h, c_vp(levels.ptr) if levels is not None else None, _hp(out["aggr_beta"]),
+                                                                  _hp(out["aggr_r"]), _hp(out["reply"]), _hp(out["paths"]) if levels is not None else None))
+        finally:
+            self.lib.hobbit_brakedown_stream_open_free(h)
+        del keep
         return out
 
     def open_from_aggregate(self, aggr, K, trs, queries=5900):

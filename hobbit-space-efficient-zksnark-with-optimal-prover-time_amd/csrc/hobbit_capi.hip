@@ -3120,5 +3120,145 @@ int hobbit_brakedown_open(hobbit_ctx *ctx, const hobbit_brakedown *c, const hobb
     return sc.finish();
 }
 
-}  // extern "C"
+// ---- streaming Brakedown (src/Elastic_PC.cpp:112-172 commit_brakedown_stream, 287-313, 561-623 open_brakedown_stream) -------------------
+// The host owns the stream and pushes B-element device chunks.  Both objects hold one group of four chunks as a 2B x 4 rows-innermost
+// matrix and nothing that grows with the number of chunks pushed: `bytes` counts every device byte they allocate.
+int hobbit_brakedown_stream_shape(size_t N, size_t *B, uint32_t *chunks) {
+    const int n = ilog2_exact(N);
+    if (n < 16 || n > 30) return HOBBIT_EINVAL;       // chunks <= 4 below ("Decrease buffer size", :113); B > 2^20 above
+    const size_t b = (size_t)1 << ((n - 1) / 2 + 6);  // :785-791: n odd 2^(n/2+6), n even 2^((n-1)/2+6)
+    if (B) *B = b;
+    if (chunks) *chunks = (uint32_t)(N / b);
+    return 0;
+}
+struct hobbit_brakedown_stream {
+    hobbit_ctx *ctx; size_t B; long long len; int shift; size_t count; bool finished; size_t bytes;
+    F *d_mat; uint8_t *state;              // 2B columns x 4 rows | the 2B running leaves
+};
+void hobbit_brakedown_stream_free(hobbit_brakedown_stream *s) {
+    if (!s) return;
+    s->ctx->pool_put(8 * s->B * sizeof(F), s->d_mat);
+    s->ctx->pool_put(2 * s->B * 32, s->state);
+    delete s;
+}
+int hobbit_brakedown_stream_begin(hobbit_ctx *ctx, size_t B, int gcc_arg_order, hobbit_brakedown_stream **out) {
+    if (!out) return HOBBIT_EINVAL;
+    *out = nullptr;
+    if (ilog2_exact(B) < 0 || B > ((size_t)1 << 20)) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_begin: B must be a power of two, at most 2^20");
+    if (ctx->code.n != (long long)B) return ctx->fail(HOBBIT_ESTATE, "brakedown_stream_begin: graphs for n = B are not finalized (expander_init_store(B))");
+    HB_TRY(ensure_ilv(ctx));
+    hobbit_brakedown_stream *s = new hobbit_brakedown_stream{ctx, B, ctx->code.len, gcc_arg_order ? 1 : 0, 0, false, 0, nullptr, nullptr};
+    if (ctx->pool_get(8 * B * sizeof(F), (void **)&s->d_mat) || ctx->pool_get(2 * B * 32, (void **)&s->state)) {
+        hobbit_brakedown_stream_free(s); return ctx->fail(HOBBIT_ENOMEM, "brakedown_stream_begin: allocation failed");
+    }
+    s->bytes = 8 * B * sizeof(F) + 2 * B * 32;
+    int r = launch_zero(ctx, s->state, 2 * B * 32);       // buff_hash starts at zero (:125-130)
+    if (r) { hobbit_brakedown_stream_free(s); return r; }
+    *out = s;
+    return 0;
+}
+size_t hobbit_brakedown_stream_device_bytes(const hobbit_brakedown_stream *s) { return s->bytes; }
+int hobbit_brakedown_stream_push(hobbit_ctx *ctx, hobbit_brakedown_stream *s, const hobbit_F *d_chunk) {
+    if (s->finished) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_push: the commitment is finished");
+    if (ctx->code.n != (long long)s->B) return ctx->fail(HOBBIT_ESTATE, "brakedown_stream_push: graphs for n = B are not finalized");
+    const uint32_t slot = (uint32_t)(s->count % 4);
+    HB_TRY(launch_bds_put(ctx, cF(d_chunk), s->B, slot, s->d_mat));
+    if (slot == 3) {                                       // the group is complete: encode its four rows, chain them into the leaves (:139-150)
+        HB_TRY(launch_encode_ilv(ctx, s->d_mat, s->d_mat, 4));
+        HB_TRY(launch_bds_leaf(ctx, s->d_mat, (size_t)s->len, 2 * s->B, s->shift, s->state));
+    }
+    s->count++;
+    return 0;
+}
+int hobbit_brakedown_stream_finish(hobbit_ctx *ctx, hobbit_brakedown_stream *s, int left_left_quirk, uint8_t *d_levels) {
+    if (s->finished) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_finish: already finished");
+    if (s->count % 4 || s->count <= 4) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_finish: the number of chunks must be a multiple of 4 above 4");
+    HB_TRY(launch_copy(ctx, d_levels, s->state, 2 * s->B * 32));
+    HB_TRY(launch_merkle_levels(ctx, d_levels, 2 * s->B, left_left_quirk ? 1 : 0));     // create_tree_blake(2B, ..) (:171)
+    s->finished = true;
+    return 0;
+}
 
+struct hobbit_brakedown_stream_open {
+    hobbit_ctx *ctx; size_t B, chunks, nq; long long len; size_t n_aggr, n_reply, bytes;
+    F *d_mat, *d_ab, *d_ar, *d_w, *d_reply; uint32_t *d_I;      // d_w: beta (chunks F) then r_v (chunks F)
+    size_t sz[6];
+};
+void hobbit_brakedown_stream_open_free(hobbit_brakedown_stream_open *o) {
+    if (!o) return;
+    void *ptrs[6] = {o->d_mat, o->d_ab, o->d_ar, o->d_w, o->d_reply, o->d_I};
+    for (int i = 0; i < 6; i++) o->ctx->pool_put(o->sz[i], ptrs[i]);
+    delete o;
+}
+int hobbit_brakedown_stream_open_begin(hobbit_ctx *ctx, size_t B, size_t chunks, const hobbit_F *h_beta, const hobbit_F *h_rv, const uint64_t *h_I, size_t nq,
+                                       hobbit_brakedown_stream_open **out) {
+    if (!out) return HOBBIT_EINVAL;
+    *out = nullptr;
+    if (ilog2_exact(B) < 0 || B > ((size_t)1 << 20)) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_begin: B must be a power of two, at most 2^20");
+    if (chunks % 4 || chunks <= 4) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_begin: the number of chunks must be a multiple of 4 above 4");
+    if (!h_beta || !h_rv || (nq && !h_I)) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_begin: null input");
+    for (size_t q = 0; q < nq; q++) if (h_I[q] >= 2 * B) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_begin: query out of range");
+    if (ctx->code.n != (long long)B) return ctx->fail(HOBBIT_ESTATE, "brakedown_stream_open_begin: graphs for n = B are not finalized (expander_init_store(B))");
+    HB_TRY(ensure_ilv(ctx));
+    hobbit_brakedown_stream_open *o = new hobbit_brakedown_stream_open();
+    o->ctx = ctx; o->B = B; o->chunks = chunks; o->nq = nq; o->len = ctx->code.len; o->n_aggr = o->n_reply = 0; o->bytes = 0;
+    const size_t sizes[6] = {8 * B * sizeof(F), B * sizeof(F), B * sizeof(F), 2 * chunks * sizeof(F), (nq ? nq : 1) * chunks * sizeof(F), (nq ? nq : 1) * 4};
+    void **slots[6] = {(void **)&o->d_mat, (void **)&o->d_ab, (void **)&o->d_ar, (void **)&o->d_w, (void **)&o->d_reply, (void **)&o->d_I};
+    bool ok = true;
+    for (int i = 0; i < 6; i++) { o->sz[i] = sizes[i]; *slots[i] = nullptr; if (ok) { ok = ctx->pool_get(sizes[i], slots[i]) == 0; if (ok) o->bytes += sizes[i]; } }
+    if (!ok) { hobbit_brakedown_stream_open_free(o); return ctx->fail(HOBBIT_ENOMEM, "brakedown_stream_open_begin: allocation failed"); }
+    StageScope sc(ctx);
+    int r = h2d_staged(ctx, o->d_w, h_beta, chunks * sizeof(F));
+    if (!r) r = h2d_staged(ctx, o->d_w + chunks, h_rv, chunks * sizeof(F));
+    if (!r && nq) { std::vector<uint32_t> I32(h_I, h_I + nq); r = h2d_staged(ctx, o->d_I, I32.data(), nq * 4); }
+    if (!r) r = launch_zero(ctx, o->d_ab, B * sizeof(F));
+    if (!r) r = launch_zero(ctx, o->d_ar, B * sizeof(F));
+    if (!r) r = sc.finish();
+    if (r) { hobbit_brakedown_stream_open_free(o); return r; }
+    *out = o;
+    return 0;
+}
+size_t hobbit_brakedown_stream_open_device_bytes(const hobbit_brakedown_stream_open *o) { return o->bytes; }
+int hobbit_brakedown_stream_open_aggregate_push(hobbit_ctx *ctx, hobbit_brakedown_stream_open *o, const hobbit_F *d_chunk) {
+    if (o->n_aggr >= o->chunks) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_aggregate_push: more chunks than the opening was begun with");
+    const uint32_t slot = (uint32_t)(o->n_aggr % 4);
+    HB_TRY(launch_bds_put(ctx, cF(d_chunk), o->B, slot, o->d_mat));
+    if (slot == 3) HB_TRY(launch_bds_aggr(ctx, o->d_mat, o->B, o->d_w + (o->n_aggr - 3), o->d_w + o->chunks + (o->n_aggr - 3), o->d_ab, o->d_ar));
+    o->n_aggr++;
+    return 0;
+}
+int hobbit_brakedown_stream_open_reply_push(hobbit_ctx *ctx, hobbit_brakedown_stream_open *o, const hobbit_F *d_chunk) {
+    if (o->n_reply >= o->chunks) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_reply_push: more chunks than the opening was begun with");
+    if (ctx->code.n != (long long)o->B) return ctx->fail(HOBBIT_ESTATE, "brakedown_stream_open_reply_push: graphs for n = B are not finalized");
+    const uint32_t slot = (uint32_t)(o->n_reply % 4);
+    HB_TRY(launch_bds_put(ctx, cF(d_chunk), o->B, slot, o->d_mat));
+    if (slot == 3) {
+        HB_TRY(launch_encode_ilv(ctx, o->d_mat, o->d_mat, 4));
+        HB_TRY(launch_bds_reply(ctx, o->d_mat, o->d_I, o->nq, o->chunks, o->n_reply - 3, o->d_reply));
+    }
+    o->n_reply++;
+    return 0;
+}
+int hobbit_brakedown_stream_open_finish(hobbit_ctx *ctx, hobbit_brakedown_stream_open *o, const uint8_t *d_levels, hobbit_F *h_aggr_beta, hobbit_F *h_aggr_r,
+                                        hobbit_F *h_reply, uint8_t *h_paths) {
+    if ((h_aggr_beta || h_aggr_r) && o->n_aggr != o->chunks) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_finish: the aggregate pass is incomplete");
+    if (h_reply && o->nq && o->n_reply != o->chunks) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_finish: the reply pass is incomplete");
+    if (h_paths && o->nq && !d_levels) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_finish: paths need the commitment's levels");
+    StageScope sc(ctx);
+    if (h_aggr_beta) HB_TRY(d2h_staged(ctx, h_aggr_beta, o->d_ab, o->B * sizeof(F)));
+    if (h_aggr_r) HB_TRY(d2h_staged(ctx, h_aggr_r, o->d_ar, o->B * sizeof(F)));
+    if (h_reply && o->nq) HB_TRY(d2h_staged(ctx, h_reply, o->d_reply, o->nq * o->chunks * sizeof(F)));
+    if (h_paths && o->nq) {
+        // open_tree_blake(MT, {0, I[q]}, 0) (:583-587) takes leaf (I[q] / 4) * 0 + 0: every path is leaf 0's
+        const size_t W = 2 * o->B; const int depth = ilog2_exact(W);
+        std::vector<uint64_t> pos(o->nq, 0);
+        uint8_t *buf; const size_t pb = ((o->nq * 8 + 255) / 256) * 256;
+        HB_TRY(ctx->workspace(pb + o->nq * depth * 32 + 64, (void **)&buf));
+        HB_TRY(h2d_staged(ctx, buf, pos.data(), o->nq * 8));
+        HB_TRY(launch_merkle_paths(ctx, d_levels, W, reinterpret_cast<const uint64_t *>(buf), o->nq, depth, buf + pb));
+        HB_TRY(d2h_staged(ctx, h_paths, buf + pb, o->nq * depth * 32));
+    }
+    return sc.finish();
+}
+
+}  // extern "C"

@@ -3498,4 +3498,74 @@ int launch_brakedown_reply(hobbit_ctx *ctx, const F *mat, uint32_t rows, const u
     return 0;
 }
 
+// ============================================================================================
+// Streaming Brakedown (hobbit_brakedown_stream_*, src/Elastic_PC.cpp:112-172, 287-313): a group of four consecutive chunks is kept as a
+// 2B x 4 matrix, rows-innermost (element (i, c) at mat[c * 4 + i]), so a column is one 64-byte line: the xyzw block of the leaf hash, the
+// four summands of the aggregates and the four replies of a query.  The encode of a group is launch_encode_ilv at rows = 4.
+// ============================================================================================
+// the chunk into row `slot` of the message columns: mat[c * 4 + slot] = chunk[c]
+__global__ void __launch_bounds__(256)
+k_bds_put(const F *__restrict__ chunk, size_t B, uint32_t slot, F *__restrict__ mat) {
+    for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < B; c += (size_t)gridDim.x * blockDim.x) stF(mat + 4 * c + slot, ldF(chunk + c));
+}
+int launch_bds_put(hobbit_ctx *ctx, const F *chunk, size_t B, uint32_t slot, F *mat) {
+    HB_LAUNCH(ctx, "k_bds_put", k_bds_put, dim3(grid_for(B, 256, 1 << 16)), dim3(256), 0, chunk, B, slot, mat);
+    return 0;
+}
+// leaf[j] = H( H(c0[j + shift] | c1[j + shift] | c2[j] | c3[j]) | leaf[j] ) for all W = 2B leaves (:145-149; shift = 1 is the call as built by
+// GCC, see k_elastic_leaf): the first 32 bytes of column j + shift and the last 32 bytes of column j, two compressions, the state updated in
+// place.  Columns from `len` on (the codewords' zero tail, and the one past the arrays that leaf 2B - 1 asks for) are taken as zero, not read.
+__global__ void __launch_bounds__(256)
+k_bds_leaf(const F *__restrict__ mat, size_t len, size_t W, int shift, uint8_t *__restrict__ state) {
+    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < W; j += (size_t)gridDim.x * blockDim.x) {
+        const size_t ja = j + (shift ? 1 : 0);
+        uint4 a = make_uint4(0, 0, 0, 0), b = a, c = a, d = a;
+        if (ja < len) { const uint4 *p = reinterpret_cast<const uint4 *>(mat + 4 * ja); a = p[0]; b = p[1]; }
+        if (j < len) { const uint4 *p = reinterpret_cast<const uint4 *>(mat + 4 * j + 2); c = p[0]; d = p[1]; }
+        uint32_t m[16], h[8];
+        m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w; m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
+        m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w; m[12] = d.x; m[13] = d.y; m[14] = d.z; m[15] = d.w;
+        blake3_compress64(m, h);
+#pragma unroll
+        for (int q = 0; q < 8; q++) m[q] = h[q];
+        load8w(state + 32 * j, m + 8);
+        blake3_compress64(m, h);
+        store8w(state + 32 * j, h);
+    }
+}
+int launch_bds_leaf(hobbit_ctx *ctx, const F *mat, size_t len, size_t W, int shift, uint8_t *state) {
+    HB_LAUNCH(ctx, "k_bds_leaf", k_bds_leaf, dim3(grid_for(W, 256, 1 << 16)), dim3(256), 0, mat, len, W, shift, state);
+    return 0;
+}
+// aggregate_brakedown (:287-299) for one group: ab[j] += sum_i beta[i] x[i][j], ar[j] += sum_i rv[i] x[i][j] over the group's four chunks,
+// both from one read of message column j (beta / rv point at the group's four weights)
+__global__ void __launch_bounds__(256)
+k_bds_aggr(const F *__restrict__ mat, size_t B, const F *__restrict__ beta, const F *__restrict__ rv, F *__restrict__ ab, F *__restrict__ ar) {
+    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < B; j += (size_t)gridDim.x * blockDim.x) {
+        F sb = ldF(ab + j), sr = ldF(ar + j);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const F x = ldF(mat + 4 * j + i);
+            sb = fadd(sb, fmul(ldF(beta + i), x)); sr = fadd(sr, fmul(ldF(rv + i), x));
+        }
+        stF(ab + j, sb); stF(ar + j, sr);
+    }
+}
+int launch_bds_aggr(hobbit_ctx *ctx, const F *mat, size_t B, const F *beta, const F *rv, F *ab, F *ar) {
+    HB_LAUNCH(ctx, "k_bds_aggr", k_bds_aggr, dim3(grid_for(B, 256, 1 << 16)), dim3(256), 0, mat, B, beta, rv, ab, ar);
+    return 0;
+}
+// compute_reply (:301-313) for one group: reply[q][first + i] = codeword_{first + i}[I[q]], i < 4: one 64-byte run per query
+__global__ void __launch_bounds__(256)
+k_bds_reply(const F *__restrict__ mat, const uint32_t *__restrict__ I, size_t nq, size_t chunks, size_t first, F *__restrict__ reply) {
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x, q = g >> 2;
+    const uint32_t i = (uint32_t)g & 3;
+    if (q < nq) stF(reply + q * chunks + first + i, ldF(mat + 4 * (size_t)I[q] + i));
+}
+int launch_bds_reply(hobbit_ctx *ctx, const F *mat, const uint32_t *d_I, size_t nq, size_t chunks, size_t first, F *reply) {
+    if (!nq) return 0;
+    HB_LAUNCH(ctx, "k_bds_reply", k_bds_reply, dim3((unsigned)((4 * nq + 255) / 256)), dim3(256), 0, mat, d_I, nq, chunks, first, reply);
+    return 0;
+}
+
 }  // namespace hobbit

@@ -10,6 +10,10 @@ int launch_encode_ilv(hobbit_ctx *ctx, const F *src, F *dst, uint32_t rows);
 int launch_brakedown_digests(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t ncols, size_t nz, int quirk, uint8_t *out);
 int launch_brakedown_aggr(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t B, const F *beta, const F *r, F *aggr_beta, F *aggr_r);
 int launch_brakedown_reply(hobbit_ctx *ctx, const F *mat, uint32_t rows, const uint32_t *d_I, size_t nq, F *reply);
+int launch_bds_put(hobbit_ctx *ctx, const F *chunk, size_t B, uint32_t slot, F *mat);
+int launch_bds_leaf(hobbit_ctx *ctx, const F *mat, size_t len, size_t W, int shift, uint8_t *state);
+int launch_bds_aggr(hobbit_ctx *ctx, const F *mat, size_t B, const F *beta, const F *rv, F *ab, F *ar);
+int launch_bds_reply(hobbit_ctx *ctx, const F *mat, const uint32_t *d_I, size_t nq, size_t chunks, size_t first, F *reply);
 int launch_f_binop(hobbit_ctx *ctx, int op, const F *a, const F *b, F *o, size_t n);
 int launch_fill_splitmix(hobbit_ctx *ctx, F *o, size_t n, uint64_t seed);
 int launch_u64_bias_fold(hobbit_ctx *ctx, uint64_t *w, size_t n, uint64_t bias, int fold);

@@ -18,6 +18,7 @@ graph _C[100], D[100];
 static hobbit_ctx *g_ctx = nullptr;
 static hobbit_commitment *g_commit = nullptr;
 static hobbit_brakedown *g_bd = nullptr;                            // the last commit_standard_brakedown's matrix and tree
+static void *g_bds_levels = nullptr;                                // the last commit_brakedown_stream's levels
 static int g_commit_K = 0, g_commit_trs = 0; static size_t g_commit_cols = 0;
 static void *g_poly_dev = nullptr; static size_t g_poly_n = 0;      // device copy of the committed polynomial, kept for open_standard
 static uint8_t g_commit_root[32];
@@ -71,6 +72,7 @@ void hobbit_host_shutdown() {
     if (g_ctx) free_prev();
     if (g_commit) { hobbit_commitment_free(g_commit); g_commit = nullptr; }
     if (g_bd) { hobbit_brakedown_free(g_bd); g_bd = nullptr; }
+    if (g_bds_levels) { hobbit_free(g_ctx, g_bds_levels); g_bds_levels = nullptr; }
     if (g_poly_dev) { hobbit_free(g_ctx, g_poly_dev); g_poly_dev = nullptr; g_poly_n = 0; }
     if (g_ctx) { hobbit_ctx_destroy(g_ctx); g_ctx = nullptr; }
 }
@@ -730,12 +732,31 @@ void open(stream_descriptor fd, vector<F> x, vector<vector<_hash>> &Commitment_M
     Commitment_MT.clear();
     printf("PC : ps = %lf, vt = %lf\n", ps, vt);
 }
-void test_Elastic_PC(size_t N, int option) {                        // src/Elastic_PC.cpp:736-771
+void test_Elastic_PC(size_t N, int option) {                        // src/Elastic_PC.cpp:736-808
     _hash comm; vector<vector<_hash>> MT_hashes;
     stream_descriptor commit_data; commit_data.name = "test"; commit_data.size = N;
     if (option == 1) { linear_time = false; tensor_row_size = (int)(BUFFER_SPACE / (1ULL << 11)); }
     else if (option == 2) { linear_time = true; int K = (int)(N / BUFFER_SPACE); tensor_row_size = (int)(N / (K * 1ULL << 14)); printf("> %d\n", tensor_row_size); expander_init_store(tensor_row_size); }
-    else { printf("Error: option %d (the Brakedown streaming baseline) is a comparison baseline, not built\n", option); exit(-1); }
+    else {                                                          // (:784-806) the streaming Brakedown baseline; sets BUFFER_SPACE itself
+        size_t B = 0; uint32_t chunks = 0;
+        if (hobbit_brakedown_stream_shape(N, &B, &chunks) != 0) { printf("Error: the streaming Brakedown baseline needs N = 2^n with 16 <= n <= 30\n"); exit(-1); }
+        BUFFER_SPACE = B;                                           // (:785-791)
+        expander_init_store((long long)BUFFER_SPACE);
+        auto start = std::chrono::steady_clock::now();
+        commit_brakedown_stream(commit_data, MT_hashes);
+        auto end = std::chrono::steady_clock::now();
+        double elapsed = std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+        std::cout << "Commit time: " << elapsed << " seconds" << std::endl;
+        printf("root ");
+        for (int i = 0; i < 32; i++) printf("%02x", MT_hashes.back()[0].arr[i]);
+        printf("\n");
+        start = std::chrono::steady_clock::now();
+        open_brakedown_stream(commit_data, generate_randomness((int)log2((double)N)), MT_hashes);
+        end = std::chrono::steady_clock::now();
+        elapsed += std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+        std::cout << "Total time: " << elapsed << " seconds" << std::endl;
+        return;
+    }
     auto start = std::chrono::steady_clock::now();
     commit(commit_data, comm, MT_hashes);
     auto end = std::chrono::steady_clock::now();
@@ -1228,6 +1249,124 @@ void open_brakedown_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>>
     printf("PC Open: pt = %lf, ps = %lf KB, vt = %lf sec\n", pt, ps, vt);
 }
 
+// ---- streaming Brakedown baseline (src/Elastic_PC.cpp:112-172, 287-313, 561-623) ------------------
+// The stream is read on the host, chunk by chunk, with the descriptor by value as in the reference (three passes: commit, aggregate, reply);
+// the device keeps one group of four chunks.  The commitment's levels also stay on the device for the paths of the opening.
+static size_t g_bds_B = 0; static uint8_t g_bds_root[32];
+static hobbit_host_brakedown_stream_transcript g_bds_open;
+hobbit_host_brakedown_stream_transcript &hobbit_host_last_brakedown_stream() { return g_bds_open; }
+static void bds_free_levels() { if (g_bds_levels) { hobbit_free(g_ctx, g_bds_levels); g_bds_levels = nullptr; g_bds_B = 0; } }
+void commit_brakedown_stream(stream_descriptor fd, vector<vector<_hash>> &MT_hashes) {   // (:112-172)
+    PhaseTimer pt__("commit_brakedown_stream");
+    if (fd.size / BUFFER_SPACE <= 4) { printf("Decrease buffer size\n"); exit(-1); }
+    const size_t B = BUFFER_SPACE, W = 2 * B;
+    hobbit_brakedown_stream *s = nullptr;
+    HCHK(hobbit_brakedown_stream_begin(hobbit_host_ctx(), B, 1, &s));
+    vector<F> buff(B);
+    DevBuf d(B * sizeof(F));
+    for (size_t i = 0; i < fd.size / B; i++) {
+        TIMED_READ(read_stream_PC(fd, buff.data(), (int)B));
+        TIMED_UP(HCHK(hobbit_memcpy_h2d(g_ctx, d.p, buff.data(), B * sizeof(F))));     // (waits for the push that read the buffer before)
+        HCHK(hobbit_brakedown_stream_push(g_ctx, s, (const hobbit_F *)d.p));
+    }
+    bds_free_levels();
+    HCHK(hobbit_malloc(g_ctx, (2 * W - 1) * 32, &g_bds_levels)); g_bds_B = B;
+    HCHK(hobbit_brakedown_stream_finish(g_ctx, s, 1, (uint8_t *)g_bds_levels));
+    hobbit_brakedown_stream_free(s);
+    const size_t levels = (size_t)log2((double)W) + 1;
+    vector<_hash> flat(2 * W - 1);
+    HCHK(hobbit_memcpy_d2h(g_ctx, flat.data()->arr, g_bds_levels, (2 * W - 1) * 32));
+    MT_hashes.assign(levels, vector<_hash>());
+    for (size_t l = 0, off = 0, sz = W; l < levels; l++, off += sz, sz /= 2) MT_hashes[l].assign(flat.begin() + off, flat.begin() + off + sz);
+    memcpy(g_bds_root, MT_hashes.back()[0].arr, 32);
+}
+// one pass of the opening over the stream: `aggregate` pushes the raw chunks, otherwise every chunk is encoded again for the replies.
+// aggregate_brakedown and compute_reply keep the reference's signatures, so each begins an opening of its own and uses half of it (the first
+// an unused reply buffer, the second zero weights and two aggregates nobody reads): open_brakedown_stream makes two objects where the C ABI
+// needs one.  Hobbit.brakedown_stream_open (Python) runs both passes on one object and is the path to benchmark.
+static void bds_pass(stream_descriptor &fd, hobbit_brakedown_stream_open *o, bool aggregate) {
+    const size_t B = BUFFER_SPACE;
+    vector<F> buff(B);
+    DevBuf d(B * sizeof(F));
+    for (size_t i = 0; i < fd.size / B; i++) {
+        TIMED_READ(read_stream_PC(fd, buff.data(), (int)B));
+        TIMED_UP(HCHK(hobbit_memcpy_h2d(g_ctx, d.p, buff.data(), B * sizeof(F))));
+        if (aggregate) HCHK(hobbit_brakedown_stream_open_aggregate_push(g_ctx, o, (const hobbit_F *)d.p));
+        else HCHK(hobbit_brakedown_stream_open_reply_push(g_ctx, o, (const hobbit_F *)d.p));
+    }
+}
+void aggregate_brakedown(stream_descriptor fd, vector<F> beta1, vector<F> random_points, vector<F> &aggregated_vector1, vector<F> &aggregated_vector2) {   // (:287-299)
+    const size_t B = BUFFER_SPACE, chunks = fd.size / B;
+    if (beta1.size() < chunks || random_points.size() < chunks) { printf("Error: aggregate_brakedown needs one weight per chunk\n"); exit(-1); }
+    aggregated_vector1.resize(B, F(0)); aggregated_vector2.resize(B, F(0));
+    hobbit_brakedown_stream_open *o = nullptr;
+    HCHK(hobbit_brakedown_stream_open_begin(hobbit_host_ctx(), B, chunks, hF(beta1.data()), hF(random_points.data()), nullptr, 0, &o));
+    bds_pass(fd, o, true);
+    vector<F> a1(B), a2(B);
+    HCHK(hobbit_brakedown_stream_open_finish(g_ctx, o, nullptr, hF(a1.data()), hF(a2.data()), nullptr, nullptr));
+    hobbit_brakedown_stream_open_free(o);
+    for (size_t j = 0; j < B; j++) { aggregated_vector1[j] += a1[j]; aggregated_vector2[j] += a2[j]; }          // `+=` into what the caller passed (:294-295)
+}
+void compute_reply(stream_descriptor fd, vector<size_t> I, vector<vector<F>> &R) {   // (:301-313)
+    const size_t B = BUFFER_SPACE, chunks = fd.size / B, nq = I.size();
+    if (R.size() < nq) { printf("Error: compute_reply needs one reply vector per query\n"); exit(-1); }
+    vector<F> w(chunks, F(0));                                     // no aggregate in this pass
+    vector<uint64_t> I64(I.begin(), I.end());
+    hobbit_brakedown_stream_open *o = nullptr;
+    HCHK(hobbit_brakedown_stream_open_begin(hobbit_host_ctx(), B, chunks, hF(w.data()), hF(w.data()), I64.data(), nq, &o));
+    bds_pass(fd, o, false);
+    vector<F> flat(nq * chunks);
+    HCHK(hobbit_brakedown_stream_open_finish(g_ctx, o, nullptr, nullptr, nullptr, hF(flat.data()), nullptr));
+    hobbit_brakedown_stream_open_free(o);
+    for (size_t q = 0; q < nq; q++) R[q].insert(R[q].end(), flat.begin() + q * chunks, flat.begin() + (q + 1) * chunks);   // push_back per chunk (:309)
+}
+void open_brakedown_stream(stream_descriptor fd, vector<F> x, vector<vector<_hash>> &Commitment_MT) {   // (:561-623)
+    PhaseTimer pt__("open_brakedown_stream");
+    const int queries = 2935;
+    double ps = 0.0, vt = 0.0;
+    const size_t B = BUFFER_SPACE, W = 2 * B, chunks = fd.size / B;
+    const int depth = (int)log2((double)W);
+    hobbit_host_brakedown_stream_transcript &t = g_bds_open;
+    vector<F> x1;
+    for (int i = 0; i < (int)log2((double)chunks); i++) x1.push_back(x[i]);
+    precompute_beta(x1, t.beta);
+    t.r_v.assign(t.beta.size(), F(0));
+    t.r_v[0] = generate_randomness(1)[0];                          // (:570)
+    for (size_t i = 1; i < t.r_v.size(); i++) t.r_v[i] = t.r_v[i - 1] * t.r_v[0];
+    t.aggr_beta.clear(); t.aggr_r.clear();
+    aggregate_brakedown(fd, t.beta, t.r_v, t.aggr_beta, t.aggr_r);
+    vector<size_t> I(queries);
+    for (int i = 0; i < queries; i++) I[i] = rand() % (2 * BUFFER_SPACE);                                        // (:576-578)
+    t.I.assign(I.begin(), I.end());
+    vector<vector<F>> R(I.size());
+    compute_reply(fd, I, R);
+    t.reply.clear();
+    for (auto &row : R) t.reply.insert(t.reply.end(), row.begin(), row.end());
+    // open_tree_blake(Commitment_MT, {0, I[i]}, 0) (:583-587): from the device's copy of the levels when they are this commitment's
+    t.paths.assign((size_t)queries * depth * 32, 0);
+    if (g_bds_levels && g_bds_B == B && !Commitment_MT.empty() && !memcmp(Commitment_MT.back()[0].arr, g_bds_root, 32)) {
+        vector<uint64_t> pos(queries, 0);
+        for (int i = 0; i < queries; i++) pos[i] = (I[i] / 4) * 0 + 0;
+        HCHK(hobbit_merkle_paths(g_ctx, (const uint8_t *)g_bds_levels, W, pos.data(), queries, t.paths.data()));
+    } else {
+        vector<size_t> c(2);
+        for (int i = 0; i < queries; i++) {
+            c[0] = 0; c[1] = I[i];
+            vector<_hash> p = merkle_tree::merkle_tree_prover::open_tree_blake(Commitment_MT, c, 0);
+            memcpy(t.paths.data() + (size_t)i * depth * 32, p.data(), (size_t)depth * 32);
+        }
+    }
+    // verifier side (:589-615): only its proof-size accounting (the re-hash of the replies, the encodes of the aggregates and the sums feed
+    // nothing; verify_claim_opt_blake ends in SHA3)
+    auto t1 = std::chrono::steady_clock::now();
+    path_ps(Commitment_MT.empty() ? W : Commitment_MT[0].size(), depth, I, ps);                                  // verify_claim_opt_blake(.., I[i], ..) (:613-615)
+    vt += std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t1).count();
+    ps += (double)(R.size() * R[0].size() * sizeof(F)) / 1024.0;   // (:619)
+    ps += (2 * BUFFER_SPACE * sizeof(F)) / 1024.0;                 // (:620)
+    t.ps = ps; t.vt = vt;
+    printf("Ps : %lf, Vt : %lf\n", ps, vt);
+}
+
 // ---- driver (src/Our_PC.cpp:757-826: options 4 and 1, commit + open; option 3, the Brakedown baseline) ---------------
 void test_PC(size_t N, int option, int K) {
     if (option != 4 && option != 1 && option != 3) {
@@ -1416,6 +1555,50 @@ int hobbit_host_sumcheck2(const uint64_t *v1, const uint64_t *v2, size_t n, cons
     memcpy(r, P.randomness[0].data(), 16 * P.randomness[0].size());
     memcpy(vr, P.vr.data(), 32); memcpy(fin, &P.final_rand, 16);
     return (int)P.q_poly.size();
+}
+// test_Elastic_PC(N, 3)'s four functions called one by one from a fresh generator state: the levels, the draws and every message
+int hobbit_host_brakedown_stream(size_t N, uint8_t *levels_out, uint64_t *x_out, uint64_t *r0_out, uint64_t *I_out, uint64_t *aggr_beta, uint64_t *aggr_r,
+                                 uint64_t *reply, uint8_t *paths, double *ps_out) {
+    srandom(1);
+    size_t B = 0; uint32_t chunks = 0;
+    if (hobbit_brakedown_stream_shape(N, &B, &chunks) != 0) return -1;
+    BUFFER_SPACE = B;
+    expander_init_store((long long)B);
+    stream_descriptor fd; fd.name = "test"; fd.size = N;
+    vector<vector<_hash>> MT;
+    commit_brakedown_stream(fd, MT);
+    size_t off = 0;
+    for (auto &l : MT) { memcpy(levels_out + 32 * off, l.data(), 32 * l.size()); off += l.size(); }
+    const int lc = (int)log2((double)chunks), queries = 2935, depth = (int)log2((double)(2 * B));
+    vector<F> x = generate_randomness((int)log2((double)N));
+    memcpy(x_out, x.data(), 16 * x.size());
+    // open_brakedown_stream's own steps (src/Elastic_PC.cpp:567-587) through the three mirror functions
+    vector<F> x1(x.begin(), x.begin() + lc), beta, r_v;
+    precompute_beta(x1, beta);
+    r_v.resize(beta.size());
+    r_v[0] = generate_randomness(1)[0];
+    for (size_t i = 1; i < r_v.size(); i++) r_v[i] = r_v[i - 1] * r_v[0];
+    memcpy(r0_out, &r_v[0], 16);
+    vector<F> a1, a2;
+    aggregate_brakedown(fd, beta, r_v, a1, a2);
+    memcpy(aggr_beta, a1.data(), 16 * B); memcpy(aggr_r, a2.data(), 16 * B);
+    vector<size_t> I(queries);
+    for (int i = 0; i < queries; i++) I[i] = rand() % (2 * BUFFER_SPACE);
+    for (int i = 0; i < queries; i++) I_out[i] = I[i];
+    vector<vector<F>> R(queries);
+    compute_reply(fd, I, R);
+    for (int i = 0; i < queries; i++) memcpy(reply + 2 * (size_t)i * chunks, R[i].data(), 16 * (size_t)chunks);
+    // the same draws again through open_brakedown_stream itself: its transcript must be the one assembled above
+    srandom(1);
+    expander_init_store((long long)B);
+    x = generate_randomness((int)log2((double)N));
+    open_brakedown_stream(fd, x, MT);
+    hobbit_host_brakedown_stream_transcript &t = hobbit_host_last_brakedown_stream();
+    if (t.I.size() != (size_t)queries || memcmp(t.I.data(), I_out, 8 * queries) || memcmp(t.aggr_beta.data(), aggr_beta, 16 * B) || memcmp(t.aggr_r.data(), aggr_r, 16 * B) ||
+        memcmp(t.reply.data(), reply, 16 * (size_t)queries * chunks)) return -2;
+    memcpy(paths, t.paths.data(), (size_t)queries * depth * 32);
+    *ps_out = t.ps;
+    return (int)MT.size();
 }
 int hobbit_host_elastic_root(size_t N, size_t B, int option, uint8_t *root_out) {
     srandom(1);

@@ -265,7 +265,17 @@ void prove_gate_consistency_lookups(stream_descriptor tr, vector<F> r, double &v
 /* the messages of the last streaming gate prover (the reference returns none): layouts as hobbit_gate_stream_out / hobbit_gate_lkp_stream_out */
 struct hobbit_host_gate_transcript { vector<F> R, a, poly, gr, fin, Peval, b, q2, r2, vr2; F fin2; int checks[5] = {0, 0, 0, 0, 0}; bool lookups = false; };
 hobbit_host_gate_transcript &hobbit_host_last_gate();
-void test_Elastic_PC(size_t N, int option);                     /* src/Elastic_PC.cpp:736-771: options 1 (commit + open) and 2 (commit; its open is undefined in the reference) */
+void test_Elastic_PC(size_t N, int option);                     /* src/Elastic_PC.cpp:736-808: options 1, 2 and 3 (the streaming Brakedown baseline: sets BUFFER_SPACE itself) */
+/* src/Elastic_PC.cpp:112-172, 287-313, 561-623: the streaming Brakedown baseline.  The stream is read on the host (read_stream_PC, descriptor
+ * by value: three passes); the device keeps one group of four chunks.  open_brakedown_stream draws r_v[0] (generate_randomness(1)) and the
+ * 2935 indices (rand() % 2B) and prints the reference's "Ps : .., Vt : .." line; its verifier side is restated as proof-size accounting only. */
+void commit_brakedown_stream(stream_descriptor fd, vector<vector<_hash>> &MT_hashes);
+void aggregate_brakedown(stream_descriptor fd, vector<F> beta1, vector<F> random_points, vector<F> &aggregated_vector1, vector<F> &aggregated_vector2);
+void compute_reply(stream_descriptor fd, vector<size_t> I, vector<vector<F>> &R);
+void open_brakedown_stream(stream_descriptor fd, vector<F> x, vector<vector<_hash>> &Commitment_MT);
+/* the messages of the last open_brakedown_stream (the reference returns none): reply is queries x chunks, paths queries x log2(2B) x 32 B */
+struct hobbit_host_brakedown_stream_transcript { vector<F> beta, r_v, aggr_beta, aggr_r, reply; vector<uint64_t> I; vector<uint8_t> paths; double ps = 0, vt = 0; };
+hobbit_host_brakedown_stream_transcript &hobbit_host_last_brakedown_stream();
 /* the messages of the last Elastic open (the reference returns only vt / ps); layouts as hobbit_elastic_open_out */
 struct hobbit_host_elastic_transcript {
     int queries = 0, rounds = 0, reply_len = 0, ncols = 0;

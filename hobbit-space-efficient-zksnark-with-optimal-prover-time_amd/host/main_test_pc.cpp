@@ -1,5 +1,6 @@
 // main_test_pc.cpp -- the reference's commented-out CLI hook `./pigeon <logN> <option> <K>` (option 4: RS x expander, option 1: RS x RS,
-// option 3: the Brakedown baseline, K unused)
+// option 3: the Brakedown baseline, K unused) and `elastic <logN> <logB> <opt>` (Elastic_PC options 1 and 2; option 3: the streaming
+// Brakedown baseline, which sets its own buffer size, so <logB> is ignored there as in the reference)
 // (src/main.cpp:1176: test_PC(1ULL<<atoi(argv[1]), atoi(argv[2]), atoi(argv[3]))) over the
 // device-backed host mirror.  Build: see __graft_entry__.build_host().
 #include <cstdio>

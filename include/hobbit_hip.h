@@ -40,6 +40,8 @@ typedef struct hobbit_commitment hobbit_commitment;
 typedef struct hobbit_elastic hobbit_elastic;
 typedef struct hobbit_elastic_open hobbit_elastic_open;
 typedef struct hobbit_brakedown hobbit_brakedown;
+typedef struct hobbit_brakedown_stream hobbit_brakedown_stream;
+typedef struct hobbit_brakedown_stream_open hobbit_brakedown_stream_open;
 typedef struct { uint64_t re, im; } hobbit_F;
 
 /* ---- context, memory, timing ------------------------------------------------------------- */
@@ -190,6 +192,39 @@ int hobbit_brakedown_tensor(hobbit_ctx *ctx, const hobbit_brakedown *c, size_t c
  *   h_paths (nq x log2(2B) x 32 B): open_tree_blake(MT, {0, I[q]}, 0), i.e. the path of leaf (I[q]/4)*0 + 0 = 0 for every query, as built. */
 int hobbit_brakedown_open(hobbit_ctx *ctx, const hobbit_brakedown *c, const hobbit_F *h_x, const hobbit_F *h_r, const uint64_t *h_I, size_t nq,
                           hobbit_F *h_aggr_beta, hobbit_F *h_aggr_r, hobbit_F *h_reply, uint8_t *h_paths);
+
+/* ---- streaming Brakedown baseline (src/Elastic_PC.cpp:112-172 commit_brakedown_stream, 287-313 aggregate_brakedown / compute_reply,
+ * 561-623 open_brakedown_stream, 784-806 test_Elastic_PC option 3) --------------------------------------------------------------------- */
+/* The prover is handed the polynomial as a stream and keeps O(sqrt N) of it.  Shape for N = 2^n, 16 <= n <= 30 (else HOBBIT_EINVAL):
+ * B = 2^((n-1)/2 + 6), chunks = N/B (8 ... 1024).  Not hobbit_brakedown_shape: at even n the rows are half as long. */
+int hobbit_brakedown_stream_shape(size_t N, size_t *B, uint32_t *chunks);
+/* Commit.  The host owns the stream and pushes B-element device chunks; graphs for n = B must be finalized.  Every 4th chunk the group of
+ * four is encoded and hashed into the 2B running leaves: leaf[j] = H(H(c0[j'] | c1[j'] | c2[j] | c3[j]) | leaf[j]).  gcc_arg_order=1 is the
+ * reference as built by GCC (j' = j+1, see hobbit_elastic_begin; the operands leaf 2B-1 would read past the arrays are zero), 0 is j' = j.
+ * finish builds create_tree_blake over the leaves into d_levels ((4B-1)*32 B, device): left_left_quirk=1 parents are H(left | left), 0
+ * H(left | right).  finish with a chunk count that is not a multiple of 4 or is <= 4, and a push after finish, are HOBBIT_EINVAL.
+ * The object's device memory is O(B) and does not depend on the number of chunks pushed (device_bytes).  Calls return once queued.
+ * As with hobbit_elastic_*, a NULL handle is undefined in every call here and in the open calls below, except the two free calls (no-op). */
+int hobbit_brakedown_stream_begin(hobbit_ctx *ctx, size_t B, int gcc_arg_order, hobbit_brakedown_stream **out);
+int hobbit_brakedown_stream_push(hobbit_ctx *ctx, hobbit_brakedown_stream *s, const hobbit_F *d_chunk);
+int hobbit_brakedown_stream_finish(hobbit_ctx *ctx, hobbit_brakedown_stream *s, int left_left_quirk, uint8_t *d_levels);
+size_t hobbit_brakedown_stream_device_bytes(const hobbit_brakedown_stream *s);
+void hobbit_brakedown_stream_free(hobbit_brakedown_stream *s);
+/* Open, prover side.  The host passes the draws: h_beta (chunks F: precompute_beta of the first log2(chunks) coordinates of the point),
+ * h_rv (chunks F: the powers of the drawn r), h_I (nq indices < 2B, else HOBBIT_EINVAL).  Two more passes over the stream:
+ *   aggregate_push (chunks times): aggr_beta[j] += beta[i] chunk_i[j], aggr_r[j] += rv[i] chunk_i[j];
+ *   reply_push (chunks times): every chunk is encoded again, reply[q][i] = codeword_i[I[q]].
+ * finish waits and copies out (any output may be NULL): h_aggr_beta / h_aggr_r (B F), h_reply (nq x chunks F), h_paths (nq x log2(2B) x 32 B
+ * from d_levels: open_tree_blake(MT, {0, I[q]}, 0), the path of leaf 0 for every query, as built).  An output whose pass is incomplete is
+ * HOBBIT_EINVAL.  Device memory is O(B + nq * chunks), all of it allocated by open_begin. */
+int hobbit_brakedown_stream_open_begin(hobbit_ctx *ctx, size_t B, size_t chunks, const hobbit_F *h_beta, const hobbit_F *h_rv, const uint64_t *h_I, size_t nq,
+                                       hobbit_brakedown_stream_open **out);
+int hobbit_brakedown_stream_open_aggregate_push(hobbit_ctx *ctx, hobbit_brakedown_stream_open *o, const hobbit_F *d_chunk);
+int hobbit_brakedown_stream_open_reply_push(hobbit_ctx *ctx, hobbit_brakedown_stream_open *o, const hobbit_F *d_chunk);
+int hobbit_brakedown_stream_open_finish(hobbit_ctx *ctx, hobbit_brakedown_stream_open *o, const uint8_t *d_levels, hobbit_F *h_aggr_beta, hobbit_F *h_aggr_r,
+                                        hobbit_F *h_reply, uint8_t *h_paths);
+size_t hobbit_brakedown_stream_open_device_bytes(const hobbit_brakedown_stream_open *o);
+void hobbit_brakedown_stream_open_free(hobbit_brakedown_stream_open *o);
 
 /* ---- Elastic_PC streaming commit (src/Elastic_PC.cpp:174-285 commit) ------------------------- */
 /* The stream stays with the host (read_stream_PC); each B-element chunk is pushed as a device

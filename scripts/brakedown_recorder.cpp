@@ -1,5 +1,7 @@
 // scripts/brakedown_recorder.cpp -- TEST INFRASTRUCTURE ONLY: built by scripts/gen_brakedown_golden.py into a temporary directory and loaded
 // (dlopen RTLD_GLOBAL) in FRONT of the real reference (oracle/_ref/libhobbit_ref.so), in a child process that runs test_PC(N, 3, K).
+// scripts/gen_brakedown_stream_golden.py uses it the same way around test_Elastic_PC(N, 3): commit_brakedown_stream and
+// open_brakedown_stream (src/Elastic_PC.cpp:112-172, 561-623) go through the same four entry points in the same order.
 //
 // Call-through interposers on the reference's Merkle entry points (src/merkle_tree.cpp) record what commit_standard_brakedown and
 // open_brakedown_standard (src/Our_PC.cpp:197-236, 432-520) produce:
