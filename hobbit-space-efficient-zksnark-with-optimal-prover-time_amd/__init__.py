@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "hobbit_malloc", "hobbit_free", "hobbit_memcpy_h2d", "hobbit_memcpy_d2h", "hobbit_memset", "hobbit_timer_begin", "hobbit_timer_end_ms",
     "hobbit_profile_enable", "hobbit_profile_reset", "hobbit_profile_get", "hobbit_profile_names",
     "hobbit_mimc", "hobbit_f_mul_host", "hobbit_f_inv_host", "hobbit_f_binop",
-    "hobbit_graph_reset", "hobbit_graph_upload", "hobbit_graph_finalize", "hobbit_encode_batch", "hobbit_fft_batch",
+    "hobbit_graph_reset", "hobbit_graph_upload", "hobbit_graph_finalize", "hobbit_encode_batch", "hobbit_fft_batch", "hobbit_fft_any",
     "hobbit_blake3_64", "hobbit_hash_md", "hobbit_mt_commit_blake", "hobbit_merkle_levels", "hobbit_merkle_path", "hobbit_merkle_paths",
     "hobbit_eq_table", "hobbit_eval_vector", "hobbit_tensorcode",
     "hobbit_commit_standard", "hobbit_commit_standard_host", "hobbit_commitment_free", "hobbit_commitment_num_leaves", "hobbit_commitment_levels_dev",
@@ -101,7 +101,7 @@ def load_library(path=LIB_PATH):
         "hobbit_profile_enable": [V, I], "hobbit_profile_reset": [V], "hobbit_profile_get": [V, ctypes.c_char_p, V, V],
         "hobbit_profile_names": [V, V, S], "hobbit_mimc": [V, V, V], "hobbit_f_mul_host": [V, V, V, S], "hobbit_f_inv_host": [V, V, S],
         "hobbit_f_binop": [V, I, V, V, V, S], "hobbit_graph_reset": [V], "hobbit_graph_upload": [V, I, I, L, L, I, V, V],
-        "hobbit_graph_finalize": [V, L, V], "hobbit_encode_batch": [V, V, V, L, S, S, S], "hobbit_fft_batch": [V, V, I, S, S, I],
+        "hobbit_graph_finalize": [V, L, V], "hobbit_encode_batch": [V, V, V, L, S, S, S], "hobbit_fft_batch": [V, V, I, S, S, I], "hobbit_fft_any": [V, V, I, S, S, I],
         "hobbit_blake3_64": [V, V, V, S], "hobbit_hash_md": [V, V, V, V, S], "hobbit_mt_commit_blake": [V, V, S, V],
         "hobbit_merkle_levels": [V, V, S, I], "hobbit_merkle_path": [V, V, S, S, V], "hobbit_merkle_paths": [V, V, S, V, S, V],
         "hobbit_eq_table": [V, V, I, V], "hobbit_eval_vector": [V, V, S, V, V], "hobbit_tensorcode": [V, V, S, I, I, V],
@@ -456,6 +456,24 @@ class Hobbit:
         self._chk(self.lib.hobbit_fft_batch(self.ctx, c_vp(d.ptr), c_int(ln.bit_length() - 1), c_sz(batch), c_sz(ln), c_int(int(inverse))))
         out = self.to_host(d, a.shape, np.uint64)
         return out[0] if single else out
+
+    def fft_any(self, arr, inverse=False):
+        """fft at every length up to 2^28 and in both directions (hobbit_fft_any); host arrays in and out"""
+        a = Fh(arr)
+        single = a.ndim == 2
+        if single:
+            a = a[None]
+        batch, ln = a.shape[0], a.shape[1]
+        d = self.to_device(a)
+        self.fft_any_dev(d, ln.bit_length() - 1, batch, inverse)
+        out = self.to_host(d, a.shape, np.uint64)
+        return out[0] if single else out
+
+    def fft_any_dev(self, ptr, logn, batch=1, inverse=False):
+        """in place on `batch` contiguous rows of 2^logn elements at a device address (a DeviceBuffer, a raw pointer or a torch data_ptr()):
+        nothing is copied.  The work is queued on the context's stream; sync() before another stream reads the result."""
+        p = ptr.ptr if isinstance(ptr, DeviceBuffer) else int(ptr)
+        self._chk(self.lib.hobbit_fft_any(self.ctx, c_vp(p), c_int(logn), c_sz(batch), c_sz(1 << logn), c_int(int(inverse))))
 
     # ---- hashes / Merkle
     def blake3_64(self, blocks):

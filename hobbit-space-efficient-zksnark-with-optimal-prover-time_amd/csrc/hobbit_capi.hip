@@ -107,13 +107,14 @@ static int get_tw8(hobbit_ctx *ctx, bool inverse) {
 }
 // tables of k_fft_r8 for N = 2^logn = 8^P * R: per pass p = 1 .. P-1 (h = 8^p): [7][h] = w_N2^(rev3(t) k N2 / (8h)), w_N2 = w_N^R; then the tail
 // [R-1][N2] = w_N^(q k)
-static int get_tw_r8(hobbit_ctx *ctx, int logn, const F **out) {
-    auto it = ctx->tw_r8.find(logn);
+static int get_tw_r8(hobbit_ctx *ctx, int logn, bool inverse, const F **out) {
+    const int key = logn + (inverse ? 64 : 0);
+    auto it = ctx->tw_r8.find(key);
     if (it != ctx->tw_r8.end()) { *out = it->second; return 0; }
     const uint32_t N = 1u << logn, P = (uint32_t)logn / 3, R = 1u << (logn % 3), N2 = N / R;
     std::vector<F> w(N);
     w[0] = fmake(1);
-    const F w1 = root_of_unity(logn);
+    F w1 = root_of_unity(logn); if (inverse) w1 = finv(w1);
     for (uint32_t i = 1; i < N; i++) w[i] = fmul(w[i - 1], w1);
     static const uint32_t rev3[8] = {0, 4, 2, 6, 1, 5, 3, 7};
     std::vector<F> t;
@@ -125,7 +126,29 @@ static int get_tw_r8(hobbit_ctx *ctx, int logn, const F **out) {
     F *d = nullptr;
     if (hipMalloc((void **)&d, t.size() * sizeof(F)) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
     HB_CHECK(ctx, hipMemcpy(d, t.data(), t.size() * sizeof(F), hipMemcpyHostToDevice));
-    ctx->tw_r8[logn] = d; *out = d;
+    ctx->tw_r8[key] = d; *out = d;
+    return 0;
+}
+// The twiddles of a length 2^25 .. 2^28 as two small tables, w^(a 2^14 + b) = hi[a] lo[b]: [lo: 2^14 | hi: 2^(logn-14)] entries, at most
+// 512 KB together, each built by its own short chain of products (the full table would be 2^27 dependent products and a 2 GiB upload).
+static int get_tw_split(hobbit_ctx *ctx, int logn, bool inverse, const F **lo, const F **hi) {
+    const int key = logn + (inverse ? 64 : 0);
+    auto it = ctx->tw_split.find(key);
+    if (it == ctx->tw_split.end()) {
+        const size_t nlo = (size_t)1 << 14, nhi = (size_t)1 << (logn - 14);
+        std::vector<F> t(nlo + nhi);
+        F w1 = root_of_unity(logn); if (inverse) w1 = finv(w1);
+        t[0] = fmake(1);
+        for (size_t i = 1; i < nlo; i++) t[i] = fmul(t[i - 1], w1);
+        const F wh = fmul(t[nlo - 1], w1);                            // w^(2^14)
+        t[nlo] = fmake(1);
+        for (size_t i = 1; i < nhi; i++) t[nlo + i] = fmul(t[nlo + i - 1], wh);
+        F *d = nullptr;
+        if (hipMalloc((void **)&d, t.size() * sizeof(F)) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
+        HB_CHECK(ctx, hipMemcpy(d, t.data(), t.size() * sizeof(F), hipMemcpyHostToDevice));
+        it = ctx->tw_split.emplace(key, d).first;
+    }
+    *lo = it->second; *hi = it->second + ((size_t)1 << 14);
     return 0;
 }
 // FFT dispatch: the 4096-point kernel when it applies, the generic LDS kernel otherwise
@@ -150,34 +173,41 @@ static void free_code(DeviceCode &c) {
     c = DeviceCode();
 }
 
-static int fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, bool inverse,
-                    uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs) {
-    F scale = fmake(1);
-    if (inverse) scale = finv(fmake((uint64_t)1 << logn));          // src/utils.cpp:663-671
+// the transform with an explicit factor on the way out (do_scale == 0: none)
+static int fft_rows_scaled(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, bool inverse,
+                           F scale, int do_scale, uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs) {
     if (logn == 12 && (src_len == 2048 || src_len == 4096)) {
         HB_TRY(get_tw8(ctx, inverse));
         const int d = inverse ? 1 : 0;
         const F *t = ctx->tw8[d];
         return launch_fft4096(ctx, src, src_ld, 1, src_len, dst, dst_ld, dst_es, t, t + 7 * 8, t + 7 * 8 + 7 * 64, ctx->tw8_w8[d], ctx->tw8_w83[d],
-                              ctx->tw8_w4_plus_i[d], scale, inverse ? 1 : 0, groups, rows_per_group, src_gs, dst_gs);
+                              ctx->tw8_w4_plus_i[d], scale, do_scale, groups, rows_per_group, src_gs, dst_gs);
     }
     static const int r8_mode = [] { const char *e = getenv("HOBBIT_FFT_R8"); return e ? atoi(e) : 1; }();
     if (r8_mode && !inverse && logn >= 6 && logn <= 11 && (src_len == (1u << logn) || src_len == (1u << (logn - 1)))) {
         HB_TRY(get_tw8(ctx, false));                                  // (the direction of w_4: the same element for every length)
-        const F *tabs; HB_TRY(get_tw_r8(ctx, logn, &tabs));
+        const F *tabs; HB_TRY(get_tw_r8(ctx, logn, false, &tabs));
         return launch_fft_r8(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, logn, tabs, ctx->tw8_w4_plus_i[0], groups, rows_per_group, src_gs, dst_gs);
     }
     const F *tw; HB_TRY(get_twiddles(ctx, logn, inverse, &tw));
-    return launch_fft_rows(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, logn, tw, scale, inverse ? 1 : 0, groups, rows_per_group, src_gs, dst_gs);
+    return launch_fft_rows(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, logn, tw, scale, do_scale, groups, rows_per_group, src_gs, dst_gs);
+}
+static int fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, bool inverse,
+                    uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs) {
+    F scale = fmake(1);
+    if (inverse) scale = finv(fmake((uint64_t)1 << logn));          // src/utils.cpp:663-671
+    return fft_rows_scaled(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, logn, inverse, scale, inverse ? 1 : 0, groups, rows_per_group, src_gs, dst_gs);
 }
 
 // Long forward/inverse transform of `batch` rows: row b of src (src_len nonzero elements, the rest of the 2^logn
 // transform length zero) -> row b of dst (2^logn elements, contiguous).  13 <= logn <= 24.  src may equal dst.
-static int fft_long(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *dst, int logn, bool inverse, uint32_t batch) {
+// do_scale: every result is multiplied by `scale`, fused into the last arithmetic pass (the inverse's 1/len; a nested call of a longer
+// transform passes none).  An inverse transform takes full-length sources only.
+static int fft_long(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *dst, int logn, bool inverse, uint32_t batch, F scale, int do_scale) {
     const size_t len = (size_t)1 << logn; const int lr = logn - 12; const uint32_t R = 1u << lr;
-    if (lr < 1 || lr > 12) return ctx->fail(HOBBIT_EINVAL, "fft_long: logn must be in [13,24]");
-    if (inverse) return ctx->fail(HOBBIT_EINVAL, "fft_long: only forward transforms are built");
-    if (src_len != len && src_len != len / 2) return ctx->fail(HOBBIT_EINVAL, "fft_long: source must be the full length or its zero-padded half");
+    if (lr < 1 || lr > 12) return ctx->fail(HOBBIT_EINVAL, "fft_long: the two-factor form serves logn in [13,24]");
+    if (src_len != len && (inverse || src_len != len / 2)) return ctx->fail(HOBBIT_EINVAL, "fft_long: source must be the full length or, forward, its zero-padded half");
+    if ((size_t)batch * 4096 >> 32) return ctx->fail(HOBBIT_EINVAL, "fft_long: too many rows");
     F *t1, *t2;
     HB_TRY(ctx->workspace((size_t)batch * len * sizeof(F), (void **)&t1));
     HB_TRY(ctx->workspace2((size_t)batch * len * sizeof(F), (void **)&t2));
@@ -195,32 +225,72 @@ static int fft_long(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len
     HB_TRY(launch_fft4096(ctx, t1, 4096, 1, src_len == len ? 4096u : 2048u, t1, 4096, 1, t8, t8 + 7 * 8, t8 + 7 * 8 + 7 * 64, ctx->tw8_w8[d], ctx->tw8_w83[d],
                           ctx->tw8_w4_plus_i[d], fmake(1), 0, batch, R, len, len));
     }
-    // inter-stage twiddles as a 2-D table (len entries, built once per length, <= 32 MB)
+    // inter-stage twiddles as a 2-D table (len entries, built once per length and direction, <= 32 MB)
     const F *tw2 = nullptr;
     if (logn <= 21) {
-        auto it = ctx->tw2d_fwd.find(logn);
-        if (it == ctx->tw2d_fwd.end()) {
+        const int key = logn + (inverse ? 64 : 0);
+        auto it = ctx->tw2d.find(key);
+        if (it == ctx->tw2d.end()) {
             F *d2 = nullptr;
             if (hipMalloc((void **)&d2, len * sizeof(F)) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "twiddle table alloc failed");
             HB_TRY(launch_build_tw2d(ctx, twl, (uint32_t)(len / 2), R, d2));
-            it = ctx->tw2d_fwd.emplace(logn, d2).first;
+            it = ctx->tw2d.emplace(key, d2).first;
         }
         tw2 = it->second;
     }
     if (tw2 && lr >= 2 && lr <= 8 && batch <= 65535) {
         // one pass: twiddle on load, 16 columns x R rows per workgroup, final order on store (t1 -> dst; src was consumed above)
         static const int r8_cols = [] { const char *e = getenv("HOBBIT_FFT_COLS_R8"); return e ? atoi(e) : 1; }();
-        if (r8_cols && lr >= 5 && !inverse) {
-            const F *tabs; HB_TRY(get_tw_r8(ctx, lr, &tabs));
-            return launch_fft_cols_r8(ctx, t1, len, lr, dst, tw2, tabs, ctx->tw8_w4_plus_i[0], batch);
+        if (r8_cols && lr >= 5) {
+            const F *tabs; HB_TRY(get_tw_r8(ctx, lr, inverse, &tabs));
+            return launch_fft_cols_r8(ctx, t1, len, lr, dst, tw2, tabs, ctx->tw8_w4_plus_i[d], scale, do_scale, batch);
         }
         const F *twr; HB_TRY(get_twiddles(ctx, lr, inverse, &twr));
-        return launch_fft_cols(ctx, t1, len, lr, dst, tw2, twr, batch);
+        return launch_fft_cols(ctx, t1, len, lr, dst, tw2, twr, scale, do_scale, batch);
     }
     HB_TRY(launch_transpose_tw(ctx, t1, len, R, t2, twl, (uint32_t)(len / 2), tw2, batch));
-    HB_TRY(fft_rows(ctx, t2, R, R, t2, R, 1, lr, inverse, 1, (uint32_t)((size_t)batch * 4096), 0, 0));       // scale applied below, not here
+    // (forward, the R-point rows run as before: radix-8 where it is built; the inverse's 1/len rides on this pass, the last with arithmetic)
+    HB_TRY(fft_rows_scaled(ctx, t2, R, R, t2, R, 1, lr, inverse, scale, do_scale, 1, (uint32_t)((size_t)batch * 4096), 0, 0));
     HB_TRY(launch_transpose_ld(ctx, t2, len, R, 4096, R, dst, len, 4096, batch));
     return 0;
+}
+static int fft_long(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *dst, int logn, bool inverse, uint32_t batch) {
+    return fft_long(ctx, src, src_ld, src_len, dst, logn, inverse, batch, inverse ? finv(fmake((uint64_t)1 << logn)) : fmake(1), inverse ? 1 : 0);
+}
+
+// 2^25 <= len <= 2^28 as three factors, len = 256 * S = 256 * (4096 * R'), in place on `batch` contiguous rows (one row at a time: a row alone
+// fills the chip).  x[256 m + n1] is moved to y[n1][m] (workspace5), the 256 rows of S = 2^17 .. 2^20 points are transformed by the two-factor
+// form above (one batched call, workspace / workspace2), and the 256-point last factor takes its twiddle W_len^(n1 k2) from the split tables and
+// writes X[k1 S + k2] back over the input.  Sweeps over the data: transpose, (transpose for S >= 2^19,) FFT-4096, S-columns, 256-columns = 4 or 5.
+static int fft_wide(hobbit_ctx *ctx, F *data, int logn, bool inverse, size_t batch) {
+    if (logn < 25 || logn > 28) return ctx->fail(HOBBIT_EINVAL, "fft_wide: the three-factor form serves logn in [25,28]");
+    const size_t len = (size_t)1 << logn, S = len >> 8;
+    F *y; HB_TRY(ctx->workspace5(len * sizeof(F), (void **)&y));
+    const F *lo, *hi; HB_TRY(get_tw_split(ctx, logn, inverse, &lo, &hi));
+    const F *tabs; HB_TRY(get_tw_r8(ctx, 8, inverse, &tabs));
+    HB_TRY(get_tw8(ctx, inverse));
+    const F scale = inverse ? finv(fmake((uint64_t)1 << logn)) : fmake(1);
+    for (size_t b = 0; b < batch; b++) {
+        F *x = data + b * len;
+        HB_TRY(launch_transpose_ld(ctx, x, 0, 256, (uint32_t)S, 256, y, 0, S, 1));
+        HB_TRY(fft_long(ctx, y, S, S, y, logn - 8, inverse, 256, fmake(1), 0));
+        HB_TRY(launch_fft_cols_wide(ctx, y, S, x, lo, hi, tabs, ctx->tw8_w4_plus_i[inverse ? 1 : 0], scale, inverse ? 1 : 0));
+    }
+    return 0;
+}
+// every length: rows of src_len (the full length, or forward its zero-padded half) elements, src_ld apart -> contiguous rows of dst
+static int fft_any_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *dst, int logn, bool inverse, size_t batch) {
+    const size_t len = (size_t)1 << logn;
+    if (logn <= 12) return fft_rows(ctx, src, src_ld, (uint32_t)src_len, dst, len, 1, logn, inverse, 1, (uint32_t)batch, 0, 0);
+    if (logn <= 24) return fft_long(ctx, src, src_ld, src_len, dst, logn, inverse, (uint32_t)batch);
+    if (src == dst && (src_len != len || src_ld != len)) return ctx->fail(HOBBIT_EINVAL, "fft: in place, rows of 2^25 and more must be full and contiguous");
+    if (src != dst) {
+        for (size_t b = 0; b < batch; b++) {
+            HB_TRY(launch_copy(ctx, dst + b * len, src + b * src_ld, src_len * sizeof(F)));
+            if (src_len < len) HB_TRY(launch_zero(ctx, dst + b * len + src_len, (len - src_len) * sizeof(F)));
+        }
+    }
+    return fft_wide(ctx, dst, logn, inverse, batch);
 }
 
 namespace hobbit { TranscriptRec &transcript_rec() { static thread_local TranscriptRec t; return t; } }
@@ -270,7 +340,8 @@ void hobbit_ctx_destroy(hobbit_ctx *ctx) {
     ctx->prof_collect();
     for (auto &kv : ctx->tw_fwd) hipFree(kv.second);
     for (auto &kv : ctx->tw_inv) hipFree(kv.second);
-    for (auto &kv : ctx->tw2d_fwd) hipFree(kv.second);
+    for (auto &kv : ctx->tw2d) hipFree(kv.second);
+    for (auto &kv : ctx->tw_split) hipFree(kv.second);
     for (auto &kv : ctx->tw_r8) hipFree(kv.second);
     ctx->pool_drain();
     for (int d = 0; d < 2; d++) if (ctx->tw8[d]) hipFree(ctx->tw8[d]);
@@ -284,6 +355,7 @@ void hobbit_ctx_destroy(hobbit_ctx *ctx) {
     for (hipEvent_t e : ctx->ev_pool) hipEventDestroy(e);
     if (ctx->ws3) hipFree(ctx->ws3);
     if (ctx->ws4) hipFree(ctx->ws4);
+    if (ctx->ws5) hipFree(ctx->ws5);
     if (ctx->pinc) hipHostFree(ctx->pinc);
     if (ctx->spare_tensor) hipFree(ctx->spare_tensor);
     if (ctx->spare_levels) hipFree(ctx->spare_levels);
@@ -769,6 +841,17 @@ int hobbit_fft_batch(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, 
     }
     return fft_rows(ctx, cF(d_data), ld, 1u << logn, mF(d_data), ld, 1, logn, inverse != 0, 1, (uint32_t)batch, 0, 0);
 }
+int hobbit_fft_any(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, size_t ld, int inverse) {
+    if (logn < 1 || logn > 28) return ctx->fail(HOBBIT_EINVAL, "fft_any: logn must be in [1,28]");
+    const size_t len = (size_t)1 << logn;
+    if (!d_data) return ctx->fail(HOBBIT_EINVAL, "fft_any: null data");
+    if (batch > (((size_t)1 << 30) >> logn)) return ctx->fail(HOBBIT_EINVAL, "fft_any: batch * 2^logn must not exceed 2^30");
+    if (ld < len) return ctx->fail(HOBBIT_EINVAL, "fft_any: ld < 2^logn");
+    if (logn > 12 && ld != len) return ctx->fail(HOBBIT_EINVAL, "fft_any: rows longer than 4096 must be contiguous");
+    if (batch == 0) return 0;
+    if (logn <= 12) return fft_rows(ctx, cF(d_data), ld, (uint32_t)len, mF(d_data), ld, 1, logn, inverse != 0, 1, (uint32_t)batch, 0, 0);
+    return fft_any_rows(ctx, cF(d_data), len, len, mF(d_data), logn, inverse != 0, batch);
+}
 
 // ---- BLAKE3 / Merkle --------------------------------------------------------------------------
 int hobbit_blake3_64(hobbit_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, size_t n) { return launch_blake3_64(ctx, d_in, d_out, n); }
@@ -1125,8 +1208,8 @@ void hobbit_elastic_free(hobbit_elastic *e) {
 static int rs_rows(hobbit_ctx *ctx, const F *d_poly, size_t w, int k, F *d_enc) {
     const size_t W = 2 * w; const int lg = ilog2_exact(W);
     if (lg < 1) return ctx->fail(HOBBIT_EINVAL, "row length must be a power of two");
-    if (lg <= 12) return fft_rows(ctx, d_poly, w, (uint32_t)w, d_enc, W, 1, lg, false, 1, (uint32_t)k, 0, 0);
-    return fft_long(ctx, d_poly, w, w, d_enc, lg, false, (uint32_t)k);
+    if (lg > 27) return ctx->fail(HOBBIT_EINVAL, "rs_rows: encoded rows of at most 2^27 points");
+    return fft_any_rows(ctx, d_poly, w, w, d_enc, lg, false, (size_t)k);
 }
 int hobbit_shockwave_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int k, hobbit_F *d_enc, uint8_t *d_levels) {
     if (k < 4 || k > 64 || ilog2_exact((size_t)k) < 0 || N % (size_t)k) return ctx->fail(HOBBIT_EINVAL, "shockwave_commit: k must be a power of two in [4,64] dividing N");
@@ -1148,7 +1231,7 @@ int hobbit_change_form(hobbit_ctx *ctx, hobbit_F *d_poly, int logn) {
 }
 int hobbit_whir_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, hobbit_F *d_com, uint8_t *d_levels) {
     const int logn = ilog2_exact(N);
-    if (logn < 4 || logn > 23) return ctx->fail(HOBBIT_EINVAL, "whir_commit: N must be a power of two in [16, 2^23]");
+    if (logn < 4 || logn > 26) return ctx->fail(HOBBIT_EINVAL, "whir_commit: N must be a power of two in [16, 2^26]");
     const size_t L = 2 * N;
     F *pc; HB_TRY(ctx->workspace4(2 * L * sizeof(F), (void **)&pc));      // (the open arena, workspace3, may hold d_poly)
     F *enc = pc + L;

@@ -184,8 +184,10 @@ struct hobbit_ctx {
     hipEvent_t t0 = nullptr, t1 = nullptr;
     // twiddles: logn -> device table of 2^(logn-1) forward (and inverse) roots
     std::map<int, hobbit::F *> tw_fwd, tw_inv;
-    std::map<int, hobbit::F *> tw2d_fwd;          // inter-stage twiddles of the long transforms, [n1][k2] = w^(n1 k2), read coalesced
-    std::map<int, hobbit::F *> tw_r8;             // tables of k_fft_r8 per log2(N) (forward): radix-8 passes, then the radix-R tail
+    // the next three are keyed by log2(N) + 64 * (inverse ? 1 : 0)
+    std::map<int, hobbit::F *> tw2d;              // inter-stage twiddles of the long transforms, [n1][k2] = w^(n1 k2), read coalesced
+    std::map<int, hobbit::F *> tw_r8;             // tables of k_fft_r8 per log2(N): radix-8 passes, then the radix-R tail
+    std::map<int, hobbit::F *> tw_split;          // lengths 2^25 .. 2^28: [lo: w^b, b < 2^14 | hi: w^(a 2^14), a < 2^(logn-14)], w^(a 2^14 + b) = hi[a] lo[b]
     // radix-8 per-pass tables of the FFT-4096 kernel ([7][8] | [7][64] | [7][512]), fwd / inv
     hobbit::F *tw8[2] = {nullptr, nullptr};
     hobbit::F tw8_w8[2], tw8_w83[2]; int tw8_w4_plus_i[2] = {0, 0};
@@ -286,6 +288,16 @@ struct hobbit_ctx {
             ws4_bytes = bytes;
         }
         *p = ws4; return 0;
+    }
+    // the caller's buffer of a three-factor transform (2^25 .. 2^28): its nested long transforms own workspace / workspace2
+    void *ws5 = nullptr; size_t ws5_bytes = 0;
+    int workspace5(size_t bytes, void **p) {
+        if (bytes > ws5_bytes) {
+            if (ws5) { hipStreamSynchronize(stream); hipFree(ws5); ws5 = nullptr; ws5_bytes = 0; }
+            if (hipMalloc(&ws5, bytes) != hipSuccess) { err = "workspace5 hipMalloc failed"; return HOBBIT_ENOMEM; }
+            ws5_bytes = bytes;
+        }
+        *p = ws5; return 0;
     }
     // one retired commitment's buffers, kept for the next commit of the same shape (a 2^28 commit
     // owns 16.5 GiB; re-allocating it per call would dominate a repeated-commit loop)

@@ -166,8 +166,10 @@ k_fft_rows(const F *__restrict__ src, size_t src_ld, uint32_t src_len, F *__rest
 // A workgroup owns C = 16 adjacent k2 for all n1: loads and stores are 256-byte segments, the twiddles come from the 2-D table
 // tw2[n1][k2] with the same pattern, each of the C columns is one length-R transform in LDS (row stride odd: the column-major
 // fill and drain are bank-conflict-free).
+// SCALE: every result leaves multiplied by `scale` (the inverse transform's 1/len); the forward instantiation is the kernel as it was.
+template <bool SCALE>
 __global__ void __launch_bounds__(512)
-k_fft_cols(const F *__restrict__ y, size_t gs, int logr, F *__restrict__ out, const F *__restrict__ tw2, const F *__restrict__ twr) {
+k_fft_cols(const F *__restrict__ y, size_t gs, int logr, F *__restrict__ out, const F *__restrict__ tw2, const F *__restrict__ twr, F scale) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     F *s = reinterpret_cast<F *>(lds_raw);
     constexpr uint32_t C = 16;
@@ -185,15 +187,23 @@ k_fft_cols(const F *__restrict__ y, size_t gs, int logr, F *__restrict__ out, co
     fft_lds_stages(s, logr, twr, C * R, ldr);
     for (uint32_t e = threadIdx.x; e < C * R; e += blockDim.x) {
         const uint32_t k1 = e / C, t = e % C;
-        stF(dst + (size_t)k1 * 4096 + k20 + t, ldF(&s[t * ldr + fft_slot(k1)]));
+        F v = ldF(&s[t * ldr + fft_slot(k1)]);
+        if (SCALE) v = fmul(v, scale);
+        stF(dst + (size_t)k1 * 4096 + k20 + t, v);
     }
 }
-int launch_fft_cols(hobbit_ctx *ctx, const F *y, size_t gs, int logr, F *out, const F *tw2, const F *twr, uint32_t batch) {
+int launch_fft_cols(hobbit_ctx *ctx, const F *y, size_t gs, int logr, F *out, const F *tw2, const F *twr, F scale, int do_scale, uint32_t batch) {
     if (logr < 2 || logr > 8) return ctx->fail(HOBBIT_EINVAL, "fft_cols: R must be in [4, 256]");
     const size_t lds = (size_t)16 * (fft_row_slots(1u << logr) + 1) * 16;
     static std::atomic<uint64_t> attr_set{0};
-    set_lds_limit_once(ctx, (const void *)k_fft_cols, 16 * 289 * 16, attr_set);
-    HB_LAUNCH(ctx, "k_fft_cols", k_fft_cols, dim3(4096 / 16, batch), dim3(512), lds, y, gs, logr, out, tw2, twr);
+    static std::atomic<uint64_t> attr_set_scaled{0};
+    if (do_scale) {
+        set_lds_limit_once(ctx, (const void *)k_fft_cols<true>, 16 * 289 * 16, attr_set_scaled);
+        HB_LAUNCH(ctx, "k_fft_cols", k_fft_cols<true>, dim3(4096 / 16, batch), dim3(512), lds, y, gs, logr, out, tw2, twr, scale);
+        return 0;
+    }
+    set_lds_limit_once(ctx, (const void *)k_fft_cols<false>, 16 * 289 * 16, attr_set);
+    HB_LAUNCH(ctx, "k_fft_cols", k_fft_cols<false>, dim3(4096 / 16, batch), dim3(512), lds, y, gs, logr, out, tw2, twr, scale);
     return 0;
 }
 
@@ -526,9 +536,16 @@ int launch_fft_r8(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len
 // the fastest thread index, so global loads and stores are C * 16-byte runs and -- with an odd LDS row stride -- the butterflies of the 64 lanes
 // of a wave fall on different banks.  Products per element: 1 (twiddle) + 7/8 per radix-8 pass after the first + 1/2 or 3/4 for the tail,
 // against 1 + log2(N)/2 in the radix-2/4 stages of k_fft_cols.
-template <int LOGN>
+// SCALE: the result leaves multiplied by `scale` (the inverse transform's 1/len; a product is canonical, so it replaces the final fold).
+// WIDE: the last factor of a three-factor transform of 2^25 .. 2^28 points: the N rows are `rs` = len / N apart instead of 4096,
+// a workgroup still owns C adjacent columns, and the twiddle W_len^(n1 k2), n1 k2 < 2^28, is composed from two cache-resident tables:
+// tw2 = lo[b] = W^b (b < 2^14), twhi[a] = W^(a 2^14).
+template <bool SCALE> __device__ __forceinline__ F fft_cols_out(const F &a, const F &scale) { return SCALE ? fmul_lz(ffold(a), scale) : fcanon(a); }
+template <int LOGN, bool SCALE, bool WIDE>
 __global__ void __launch_bounds__(512)
-k_fft_cols_r8(const F *__restrict__ y, size_t gs, F *__restrict__ out, const F *__restrict__ tw2, const F *__restrict__ tabs, int plus_i) {
+k_fft_cols_r8(const F *__restrict__ y, size_t gs, F *__restrict__ out, const F *__restrict__ tw2, const F *__restrict__ tabs, int plus_i, F scale,
+              size_t rs_wide, const F *__restrict__ twhi) {
+    const size_t rs = WIDE ? rs_wide : (size_t)4096;
     constexpr uint32_t N = 1u << LOGN, P = LOGN / 3, T = 1u << (LOGN % 3), N2 = N / T, TPR = N / 8, C = 4096 / N, LDR = N + N / 8 + 1, OCT = N2 / 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     F *s = reinterpret_cast<F *>(lds_raw);
@@ -537,9 +554,12 @@ k_fft_cols_r8(const F *__restrict__ y, size_t gs, F *__restrict__ out, const F *
     F *dst = out + (size_t)blockIdx.y * gs;
     for (uint32_t e = tid; e < C * N; e += 512) {
         const uint32_t n1 = e / C, t = e % C;
-        const size_t at = (size_t)n1 * 4096 + k20 + t;
+        const size_t at = (size_t)n1 * rs + k20 + t;
         F v = ldF(src + at);
-        if (n1) v = fmul(v, ldF(tw2 + at));                               // W_len^(n1 k2); row 0 of the table is all ones
+        if (WIDE) {
+            const uint32_t m = n1 * (k20 + t);                            // < len <= 2^28
+            if (n1) v = fmul(v, fmul(ldF(twhi + (m >> 14)), ldF(tw2 + (m & 16383u))));
+        } else if (n1) v = fmul(v, ldF(tw2 + at));                        // W_len^(n1 k2); row 0 of the table is all ones
         stF(&s[t * LDR + fft_phys(n1)], v);
     }
     __syncthreads();
@@ -557,7 +577,7 @@ k_fft_cols_r8(const F *__restrict__ y, size_t gs, F *__restrict__ out, const F *
         __syncthreads();
         if (P == 1 && T == 1) {
 #pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) stF(dst + (size_t)t8 * 4096 + k20 + t, fcanon(a[t8]));
+            for (int t8 = 0; t8 < 8; t8++) stF(dst + (size_t)t8 * rs + k20 + t, fft_cols_out<SCALE>(a[t8], scale));
             return;
         }
         const uint32_t o = fft_phys(q * N2 + 8 * b);
@@ -578,7 +598,7 @@ k_fft_cols_r8(const F *__restrict__ y, size_t gs, F *__restrict__ out, const F *
         dft8_tail(a, plus_i);
         if (T == 1 && pass == P - 1) {
 #pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) stF(dst + (size_t)(i0 + t8 * h) * 4096 + k20 + t, fcanon(a[t8]));
+            for (int t8 = 0; t8 < 8; t8++) stF(dst + (size_t)(i0 + t8 * h) * rs + k20 + t, fft_cols_out<SCALE>(a[t8], scale));
         } else {
 #pragma unroll
             for (int t8 = 0; t8 < 8; t8++) stF(&sr[fft_phys(i0 + t8 * h)], ffold(a[t8]));
@@ -592,8 +612,8 @@ k_fft_cols_r8(const F *__restrict__ y, size_t gs, F *__restrict__ out, const F *
         for (uint32_t c = 0; c < N2 / TPR; c++) {
             const uint32_t k = u + TPR * c;
             const F x = ldF(&sr[fft_phys(k)]), yv = fmul_lz(ldF(&sr[fft_phys(N2 + k)]), ldF(tw + k));
-            stF(dst + (size_t)k * 4096 + k20 + t, fcanon(faddl(x, yv)));
-            stF(dst + (size_t)(k + N2) * 4096 + k20 + t, fcanon(fsubl<1>(x, yv)));
+            stF(dst + (size_t)k * rs + k20 + t, fft_cols_out<SCALE>(faddl(x, yv), scale));
+            stF(dst + (size_t)(k + N2) * rs + k20 + t, fft_cols_out<SCALE>(fsubl<1>(x, yv), scale));
         }
     } else {
 #pragma unroll
@@ -604,29 +624,44 @@ k_fft_cols_r8(const F *__restrict__ y, size_t gs, F *__restrict__ out, const F *
             const F y2 = fmul_lz(ldF(&sr[fft_phys(2 * N2 + k)]), ldF(tw + N2 + k));
             const F y3 = fmul_lz(ldF(&sr[fft_phys(3 * N2 + k)]), ldF(tw + 2 * N2 + k));
             const F t0 = faddl(y0, y2), t1 = fsubl<1>(y0, y2), t2 = faddl(y1, y3), t3 = fmul_w4<2>(fsubl<1>(y1, y3), plus_i);
-            stF(dst + (size_t)k * 4096 + k20 + t, fcanon(faddl(t0, t2)));
-            stF(dst + (size_t)(k + N2) * 4096 + k20 + t, fcanon(faddl(t1, t3)));
-            stF(dst + (size_t)(k + 2 * N2) * 4096 + k20 + t, fcanon(fsubl<2>(t0, t2)));
-            stF(dst + (size_t)(k + 3 * N2) * 4096 + k20 + t, fcanon(fsubl<2>(t1, t3)));
+            stF(dst + (size_t)k * rs + k20 + t, fft_cols_out<SCALE>(faddl(t0, t2), scale));
+            stF(dst + (size_t)(k + N2) * rs + k20 + t, fft_cols_out<SCALE>(faddl(t1, t3), scale));
+            stF(dst + (size_t)(k + 2 * N2) * rs + k20 + t, fft_cols_out<SCALE>(fsubl<2>(t0, t2), scale));
+            stF(dst + (size_t)(k + 3 * N2) * rs + k20 + t, fft_cols_out<SCALE>(fsubl<2>(t1, t3), scale));
         }
     }
 }
-template <int LOGN>
-static int launch_fft_cols_r8_n(hobbit_ctx *ctx, const F *y, size_t gs, F *out, const F *tw2, const F *tabs, int plus_i, uint32_t batch) {
+template <int LOGN, bool SCALE, bool WIDE>
+static int launch_fft_cols_r8_n(hobbit_ctx *ctx, const F *y, size_t gs, F *out, const F *tw2, const F *tabs, int plus_i, F scale, size_t rs, const F *twhi,
+                                uint32_t batch) {
     constexpr uint32_t N = 1u << LOGN, C = 4096 / N, LDR = N + N / 8 + 1;
     const size_t lds = (size_t)C * LDR * 16;
-    hipFuncSetAttribute((const void *)k_fft_cols_r8<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    HB_LAUNCH(ctx, "k_fft_cols", (k_fft_cols_r8<LOGN>), dim3(4096 / C, batch), dim3(512), lds, y, gs, out, tw2, tabs, plus_i);
+    hipFuncSetAttribute((const void *)k_fft_cols_r8<LOGN, SCALE, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    HB_LAUNCH(ctx, WIDE ? "k_fft_cols_wide" : "k_fft_cols", (k_fft_cols_r8<LOGN, SCALE, WIDE>), dim3((unsigned)(rs / C), batch), dim3(512), lds, y, gs, out, tw2,
+              tabs, plus_i, scale, rs, twhi);
     return 0;
 }
-int launch_fft_cols_r8(hobbit_ctx *ctx, const F *y, size_t gs, int logr, F *out, const F *tw2, const F *tabs, int plus_i, uint32_t batch) {
+template <bool SCALE>
+static int launch_fft_cols_r8_s(hobbit_ctx *ctx, const F *y, size_t gs, int logr, F *out, const F *tw2, const F *tabs, int plus_i, F scale, uint32_t batch) {
     switch (logr) {
-        case 5: return launch_fft_cols_r8_n<5>(ctx, y, gs, out, tw2, tabs, plus_i, batch);
-        case 6: return launch_fft_cols_r8_n<6>(ctx, y, gs, out, tw2, tabs, plus_i, batch);
-        case 7: return launch_fft_cols_r8_n<7>(ctx, y, gs, out, tw2, tabs, plus_i, batch);
-        case 8: return launch_fft_cols_r8_n<8>(ctx, y, gs, out, tw2, tabs, plus_i, batch);
+        case 5: return launch_fft_cols_r8_n<5, SCALE, false>(ctx, y, gs, out, tw2, tabs, plus_i, scale, 4096, nullptr, batch);
+        case 6: return launch_fft_cols_r8_n<6, SCALE, false>(ctx, y, gs, out, tw2, tabs, plus_i, scale, 4096, nullptr, batch);
+        case 7: return launch_fft_cols_r8_n<7, SCALE, false>(ctx, y, gs, out, tw2, tabs, plus_i, scale, 4096, nullptr, batch);
+        case 8: return launch_fft_cols_r8_n<8, SCALE, false>(ctx, y, gs, out, tw2, tabs, plus_i, scale, 4096, nullptr, batch);
     }
     return ctx->fail(HOBBIT_EINVAL, "fft_cols_r8: R must be in [32, 256]");
+}
+int launch_fft_cols_r8(hobbit_ctx *ctx, const F *y, size_t gs, int logr, F *out, const F *tw2, const F *tabs, int plus_i, F scale, int do_scale,
+                       uint32_t batch) {
+    return do_scale ? launch_fft_cols_r8_s<true>(ctx, y, gs, logr, out, tw2, tabs, plus_i, scale, batch)
+                    : launch_fft_cols_r8_s<false>(ctx, y, gs, logr, out, tw2, tabs, plus_i, scale, batch);
+}
+// The 256-point last factor of a len = 256 * rs transform (2^25 <= len <= 2^28): y[n1][k2], rows rs apart -> X[k1 * rs + k2].  (A workgroup
+// reads its 16 columns whole before it writes them and shares no address with another workgroup, so out may be y.)
+int launch_fft_cols_wide(hobbit_ctx *ctx, const F *y, size_t rs, F *out, const F *twlo, const F *twhi, const F *tabs, int plus_i, F scale, int do_scale) {
+    if (rs < ((size_t)1 << 17) || rs > ((size_t)1 << 20) || (rs & (rs - 1))) return ctx->fail(HOBBIT_EINVAL, "fft_cols_wide: row stride must be 2^17 .. 2^20");
+    if (do_scale) return launch_fft_cols_r8_n<8, true, true>(ctx, y, 0, out, twlo, tabs, plus_i, scale, rs, twhi, 1);
+    return launch_fft_cols_r8_n<8, false, true>(ctx, y, 0, out, twlo, tabs, plus_i, scale, rs, twhi, 1);
 }
 
 // The R sub-transforms run in k_fft4096 (strided source); this kernel applies the twiddles and

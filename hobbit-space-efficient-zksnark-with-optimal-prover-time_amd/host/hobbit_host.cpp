@@ -130,9 +130,10 @@ void _fft(F *arr, int logn, bool flag) {                            // src/utils
     // of the same length reuses FORWARD twiddles.  This mirror always uses the twiddles of
     // the requested direction; the commit path only ever calls the forward transform.
     size_t len = (size_t)1 << logn;
-    if (logn > 12) { printf("Error: _fft length 2^%d not supported on the device yet\n", logn); exit(-1); }
+    if (logn > 28) { printf("Error: _fft length 2^%d not supported on the device yet\n", logn); exit(-1); }
     DevBuf d(arr, len * sizeof(F));
-    HCHK(hobbit_fft_batch(hobbit_host_ctx(), (hobbit_F *)d.p, logn, 1, len, flag ? 1 : 0));
+    if (logn <= 12) HCHK(hobbit_fft_batch(hobbit_host_ctx(), (hobbit_F *)d.p, logn, 1, len, flag ? 1 : 0));
+    else HCHK(hobbit_fft_any(hobbit_host_ctx(), (hobbit_F *)d.p, logn, 1, len, flag ? 1 : 0));
     d.to_host(arr, len * sizeof(F));
 }
 void fft(vector<F> &arr, int logn, bool flag) { _fft(arr.data(), logn, flag); }   // src/utils.cpp:467-527
@@ -1418,6 +1419,12 @@ void test_PC(size_t N, int option, int K) {
 
 // ---- extern "C" hooks so tests can drive the C++ mirror through ctypes -------------------------------
 extern "C" {
+// _fft on a caller's array of 2^logn elements (two uint64 each), in place
+int hobbit_host_fft(uint64_t *arr, int logn, int flag) {
+    if (logn < 1 || logn > 28) return -1;
+    _fft(reinterpret_cast<F *>(arr), logn, flag != 0);
+    return 0;
+}
 int hobbit_host_test_pc_root(size_t N, int K, uint8_t *root_out) {
     srandom(1);
     vector<F> poly = generate_randomness((int)N);

@@ -104,8 +104,15 @@ int hobbit_encode_batch(hobbit_ctx *ctx, const hobbit_F *d_src, hobbit_F *d_dst,
 /* in place on `batch` rows of 2^logn F, row b at d_data + b*ld (logn <= 12; forward transforms up to 2^24 on
  * contiguous rows).  inverse!=0 scales by 1/len.
  * Twiddles are always those of the requested direction (the reference's length-keyed cache quirk,
- * SURVEY.md 1, is NOT reproduced here; the host mirror documents where it matters). */
+ * SURVEY.md 1, is NOT reproduced here; the host mirror documents where it matters).
+ * Longer or long inverse transforms: hobbit_fft_any below; this call keeps refusing them. */
 int hobbit_fft_batch(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, size_t ld, int inverse);
+/* _fft / fft (src/utils.cpp:605-673, 467-527) at every length and direction: 1 <= logn <= 28, `batch` rows in place, row b at d_data + b*ld,
+ * natural order in and out, inverse != 0 scales by 1/len.  logn > 12 needs contiguous rows (ld == 2^logn).  batch * 2^logn <= 2^30.
+ * Bit-identical to hobbit_fft_batch on every shape that call accepts.  Anything else is HOBBIT_EINVAL before any allocation or launch.
+ * Twiddles are those of the requested direction here too (the reference's length-keyed cache quirk is not reproduced).
+ * logn >= 25 keeps three scratch buffers of one row (2^logn F) each in the context. */
+int hobbit_fft_any(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, size_t ld, int inverse);
 
 /* ---- BLAKE3 / Merkle (src/Blake3_hash.cpp:5-10; src/merkle_tree.cpp:62-87,193-221,255-324) -- */
 int hobbit_blake3_64(hobbit_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, size_t n);      /* blake3_hash x n */
@@ -244,11 +251,14 @@ void hobbit_elastic_free(hobbit_elastic *e);
 
 /* ---- inner PCS commitments of the opening (src/Virgo.cpp:104-178) ------------------------------ */
 /* shockwave_commit: poly as k rows of N/k, rows RS-encoded to 2N/k (d_enc: k x 2N/k row-major), column digests
- * (MT_commit_Blake over the k entries of a column) and the tree over them (d_levels: (2*(2N/k)-1) hashes) */
+ * (MT_commit_Blake over the k entries of a column) and the tree over them (d_levels: (2*(2N/k)-1) hashes).  Encoded rows (2N/k) of at most
+ * 2^27 points: the sizes the reference's baselines use; no further limit of this call was met up to there */
 int hobbit_shockwave_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int k, hobbit_F *d_enc, uint8_t *d_levels);
 /* change_form (src/Virgo.cpp:104-118), in place on 2^logn elements */
 int hobbit_change_form(hobbit_ctx *ctx, hobbit_F *d_poly, int logn);
-/* whir_commit: change_form, zero-pad x2, FFT, 16-way regroup (d_com: 2N F), MT_commit_Blake (d_levels: N - 1 hashes... (2N/4)*2-1) */
+/* whir_commit: change_form, zero-pad x2, FFT, 16-way regroup (d_com: 2N F), MT_commit_Blake (d_levels: N - 1 hashes... (2N/4)*2-1).
+ * 16 <= N <= 2^26 (a 2^27-point transform): standalone WHIR at the reference's sizes; no further limit of this call was met up to there.
+ * hobbit_whir_prove keeps its own, lower limit. */
 int hobbit_whir_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, hobbit_F *d_com, uint8_t *d_levels);
 
 /* _whir_prove (src/Virgo.cpp:519-686), prover side.  The verifier emulation inside it (fold of the replies,
