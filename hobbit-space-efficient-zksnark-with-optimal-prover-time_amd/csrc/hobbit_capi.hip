@@ -356,7 +356,6 @@ void hobbit_ctx_destroy(hobbit_ctx *ctx) {
     if (ctx->ws3) hipFree(ctx->ws3);
     if (ctx->ws4) hipFree(ctx->ws4);
     if (ctx->ws5) hipFree(ctx->ws5);
-    if (ctx->pinc) hipHostFree(ctx->pinc);
     if (ctx->spare_tensor) hipFree(ctx->spare_tensor);
     if (ctx->spare_levels) hipFree(ctx->spare_levels);
     hipEventDestroy(ctx->t0); hipEventDestroy(ctx->t1);
@@ -927,7 +926,9 @@ struct Uploader {
         const unsigned char *src = h + (size_t)g * group_bytes; unsigned char *dst = d + (size_t)g * group_bytes;
         for (size_t off = 0; off < group_bytes; off += hobbit_ctx::UP_PIECE, piece_no++) {
             const size_t n = std::min(hobbit_ctx::UP_PIECE, group_bytes - off); const int b = piece_no & 1;
-            if (piece_no >= 2 && hipEventSynchronize(ctx->up_done[b]) != hipSuccess) return ctx->fail(HOBBIT_EHIP, "upload: staging buffer wait failed");
+            // every refill waits for the piece's last transfer, the first two of a call included: an earlier hobbit_commit_standard_host on this
+            // context returns with its last pieces still on the bus (an event that was never recorded returns at once)
+            if (hipEventSynchronize(ctx->up_done[b]) != hipSuccess) return ctx->fail(HOBBIT_EHIP, "upload: staging buffer wait failed");
             unsigned char *pin = (unsigned char *)ctx->up_pin[b];
             par_memcpy(pin, src + off, n);
             HB_CHECK(ctx, hipMemcpyAsync(dst + off, pin, n, hipMemcpyHostToDevice, ctx->up_stream));

@@ -1949,15 +1949,16 @@ int launch_eq_table(hobbit_ctx *ctx, CHP h_r, int k, F *d_out) {
     return 0;
 }
 // aggr[j] = sum_i beta[i] * poly[i*M + j]   (src/Our_PC.cpp:258-272)
-__global__ void k_aggregate_dev(const F *__restrict__ poly, size_t M, int K, const F *__restrict__ beta, F *__restrict__ aggr) {
+// K <= 64 coefficients passed by value in the kernel arguments (1 KB): no host buffer, no copy, no synchronisation
+struct AggCoef { F b[64]; };
+// a later slice of a sum over more than 64 chunks: aggr[j] += sum_i beta[i] * poly[i*M + j], continuing from what aggr holds
+__global__ void k_aggregate_arg_acc(const F *__restrict__ poly, size_t M, int K, AggCoef beta, F *__restrict__ aggr) {
     for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < M; j += (size_t)gridDim.x * blockDim.x) {
-        F acc = fmake(0);
-        for (int i = 0; i < K; i++) acc = fadd(acc, fmul(ldF(beta + i), ldF(poly + (size_t)i * M + j)));
+        F acc = ldF(aggr + j);
+        for (int i = 0; i < K; i++) acc = fadd(acc, fmul(beta.b[i], ldF(poly + (size_t)i * M + j)));
         stF(aggr + j, acc);
     }
 }
-// the same with the K <= 64 coefficients passed by value in the kernel arguments (1 KB): no host buffer, no copy, no synchronisation
-struct AggCoef { F b[64]; };
 __global__ void k_aggregate_arg(const F *__restrict__ poly, size_t M, int K, AggCoef beta, F *__restrict__ aggr) {
     for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < M; j += (size_t)gridDim.x * blockDim.x) {
         F acc = fmake(0);
@@ -1972,11 +1973,16 @@ int launch_aggregate(hobbit_ctx *ctx, const F *poly, size_t M, int K, CHP h_beta
         HB_LAUNCH(ctx, "k_aggregate", k_aggregate_arg, dim3(grid_for(M, 256)), dim3(256), 0, poly, M, K, cf, aggr);
         return 0;
     }
-    // more chunks than fit the argument block: the coefficients are read by the kernel straight from a small pinned
-    // (device-visible) host buffer
-    F *pc; HB_TRY(ctx->pinned_const((size_t)K * sizeof(F), (void **)&pc));
-    for (int i = 0; i < K; i++) pc[i] = h_beta[i];
-    HB_LAUNCH(ctx, "k_aggregate", k_aggregate_dev, dim3(grid_for(M, 256)), dim3(256), 0, poly, M, K, pc, aggr);
+    // more chunks than fit the argument block: slices of 64, each with its coefficients in its own launch's arguments, the later ones continuing
+    // the sum the earlier ones left in aggr -- the same additions in the same order i = 0 .. K-1 (canonical values survive the round trip through
+    // memory unchanged).  Nothing the kernels read lives in a buffer a later call on this context could rewrite while they are still queued.
+    for (int i0 = 0; i0 < K; i0 += 64) {
+        const int k = K - i0 < 64 ? K - i0 : 64;
+        AggCoef cf;
+        for (int i = 0; i < 64; i++) cf.b[i] = i < k ? h_beta[i0 + i] : fmake(0);
+        if (i0 == 0) HB_LAUNCH(ctx, "k_aggregate", k_aggregate_arg, dim3(grid_for(M, 256)), dim3(256), 0, poly, M, k, cf, aggr);
+        else HB_LAUNCH(ctx, "k_aggregate", k_aggregate_arg_acc, dim3(grid_for(M, 256)), dim3(256), 0, poly + (size_t)i0 * M, M, k, cf, aggr);
+    }
     return 0;
 }
 // reply[q*K + i] = tensor[i][col_q][row_q]   (src/Our_PC.cpp:291-305, codeword-major tensor)

@@ -16,7 +16,9 @@
  *     describes the most recent failure on the context.  Nothing falls back to the CPU: without
  *     a HIP device hobbit_ctx_create fails with HOBBIT_ENODEV.
  *   - work is enqueued on the context's stream; calls that return data to h_* pointers
- *     synchronise that stream, all others are asynchronous.
+ *     synchronise that stream, all others are asynchronous.  h_* INPUTS are consumed before a call returns: the caller may overwrite or
+ *     free them at once, also while the work that uses their values is still queued.  A caller's stream (hobbit_ctx_create_on_stream) may
+ *     be non-blocking (torch's are): the library orders its own streams against it with events, not through the NULL stream.
  *   - not re-entrant per context (like the reference: global scratch, global RNG); use one context
  *     per thread / per GPU.
  */
