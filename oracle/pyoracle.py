@@ -413,6 +413,13 @@ class Oracle(_Base):
         d = f(_p(lv), c_sz(n_leaves), c_sz(col), c_sz(row), c_sz(columns), _p(path))
         return path[:d]
 
+    def batch_prod_terms(self, b1, b2, b3, f1, f2, f3):
+        """the three sums of one batch of batch_prod (K1_temp, K2_temp, K3[j]; src/sumcheck.cpp:1093-1111)"""
+        a = [F(x).reshape(-1, 2) for x in (b1, b2, b3, f1, f2, f3)]
+        K = np.zeros((3, 2), np.uint64)
+        self.lib.orc_batch_prod_terms(*[_p(x) for x in a], c_sz(a[0].shape[0]), _p(K))
+        return K
+
     def aggregate(self, poly, beta):
         p = F(poly).reshape(-1, 2); b = F(beta).reshape(-1, 2)
         K = b.shape[0]

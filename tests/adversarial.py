@@ -146,6 +146,156 @@ def from_py(v):
     return np.array(v, dtype=np.uint64).reshape(-1, 2)
 
 
+# ---- big-integer restatements of the circuit prover's element-wise operations (tests/test_circuit_refs_cpu.py proves them against the
+# oracle; tests/test_circuit_prover_shapes.py holds the device to them).  Tables are lists of (re, im) Python integers (to_py).
+ONE, ZERO = (1, 0), (0, 0)
+
+
+def py_sum(terms):
+    s = ZERO
+    for t in terms:
+        s = py_add(s, t)
+    return s
+
+
+def py_gate3(s, lookup_rand=None):
+    """compute3p_error_terms' gate: F(selector) without lookups; with them 0 and 4 -> 1, 2 -> lookup_rand[0], 3 -> lookup_rand[1], else 0"""
+    s = int(s)
+    if lookup_rand is None:
+        return (s % P, 0)
+    return ONE if s in (0, 4) else lookup_rand[0] if s == 2 else lookup_rand[1] if s == 3 else ZERO
+
+
+def py_gate4(s, lookups=False):
+    """compute4p_error_terms' gate: 1 - F(selector) without lookups, [selector == 1] with them"""
+    s = int(s)
+    return (1 if s == 1 else 0, 0) if lookups else py_sub(ONE, (s % P, 0))
+
+
+def py_err2p(b1, b2, f1, f2):
+    """K1 = sum b1 f2 + b2 f1, K2 = sum b1 b2 (src/sumcheck.cpp:374-379)"""
+    n = len(b1)
+    return [py_sum(py_add(py_mul(b1[i], f2[i]), py_mul(b2[i], f1[i])) for i in range(n)), py_sum(py_mul(b1[i], b2[i]) for i in range(n))]
+
+
+def py_err3p(b1, gate, f1, f2, f3, beta, lookup_rand=None):
+    """with g = the gate: K1 = sum f3 (b1 f2 + g f1) + beta f1 f2, K2 = sum beta (b1 f2 + g f1) + f3 b1 g, K3 = sum b1 g beta (:407-432)"""
+    K = [ZERO, ZERO, ZERO]
+    for j in range(len(b1)):
+        g = py_gate3(gate[j], lookup_rand)
+        t1 = py_add(py_mul(b1[j], f2[j]), py_mul(g, f1[j])); t2 = py_mul(b1[j], g)
+        K[0] = py_add(K[0], py_add(py_mul(f3[j], t1), py_mul(py_mul(beta[j], f1[j]), f2[j])))
+        K[1] = py_add(K[1], py_add(py_mul(beta[j], t1), py_mul(f3[j], t2)))
+        K[2] = py_add(K[2], py_mul(t2, beta[j]))
+    return K
+
+
+def py_err4p(b1, b2, b3, gate, f1, f2, f3, f4, lookups=False):
+    """the four coefficients of sum (f1 + x b1)(f2 + x b2)(f3 + x b3)(f4 + x g) above the constant one, lowest first (:381-405)"""
+    K = [ZERO] * 4
+    for i in range(len(b1)):
+        g = py_gate4(gate[i], lookups)
+        t1 = py_add(py_mul(f1[i], b2[i]), py_mul(f2[i], b1[i])); t2 = py_add(py_mul(f3[i], g), py_mul(f4[i], b3[i]))
+        t3 = py_mul(b1[i], b2[i]); t4 = py_mul(g, b3[i]); t5 = py_mul(f1[i], f2[i]); t6 = py_mul(f3[i], f4[i])
+        K[0] = py_add(K[0], py_add(py_mul(t1, t6), py_mul(t2, t5)))
+        K[1] = py_add(K[1], py_add(py_add(py_mul(t1, t2), py_mul(t3, t6)), py_mul(t4, t5)))
+        K[2] = py_add(K[2], py_add(py_mul(t1, t4), py_mul(t2, t3)))
+        K[3] = py_add(K[3], py_mul(t3, t4))
+    return K
+
+
+def py_batch_terms(b1, b2, b3, f1, f2, f3):
+    """the three sums of one batch_prod batch (:1093-1111): compute3p's with the third chunk b3 in beta's place and b2 in the gate's"""
+    K = [ZERO, ZERO, ZERO]
+    for k in range(len(b1)):
+        t1 = py_add(py_mul(b1[k], f2[k]), py_mul(b2[k], f1[k])); t2 = py_mul(b1[k], b2[k])
+        K[0] = py_add(K[0], py_add(py_mul(f3[k], t1), py_mul(py_mul(b3[k], f1[k]), f2[k])))
+        K[1] = py_add(K[1], py_add(py_mul(b3[k], t1), py_mul(f3[k], t2)))
+        K[2] = py_add(K[2], py_mul(t2, b3[k]))
+    return K
+
+
+def py_axpy(y, a, x):
+    """y + a x"""
+    return [py_add(y[i], py_mul(a, x[i])) for i in range(len(y))]
+
+
+def py_axpy_i32(y, a, sel, one_minus=False):
+    """y + a F(sel), or y + a (1 - F(sel))"""
+    v = [py_sub(ONE, (int(s) % P, 0)) if one_minus else (int(s) % P, 0) for s in sel]
+    return py_axpy(y, a, v)
+
+
+def py_fingerprint(addr, value, a, freq=None, b=None):
+    """addr + 1 + a value (+ b freq)"""
+    out = [py_add(py_add(addr[i], ONE), py_mul(a, value[i])) for i in range(len(addr))]
+    return out if freq is None else [py_add(out[i], py_mul(b, freq[i])) for i in range(len(out))]
+
+
+def py_fold_rows(rows, r):
+    """adjacent rows folded with r: row j = row 2j + r (row 2j+1 - row 2j)"""
+    return [[py_add(a, py_mul(r, py_sub(b, a))) for a, b in zip(rows[2 * j], rows[2 * j + 1])] for j in range(len(rows) // 2)]
+
+
+def py_prepare_matrix_cols(M, r):
+    """M: (rows, cols, 2); the rows folded len(r) times (r[0] first), then row 0: column c's multilinear evaluation over the row index
+    when len(r) = log2 rows, the first entry of its partial fold otherwise"""
+    rows = [to_py(row) for row in np.asarray(M, np.uint64)]
+    for rt in to_py(r) if len(r) else []:
+        rows = py_fold_rows(rows, rt)
+    return rows[0]
+
+
+def py_phi_g(rx, w, scale=ONE, ifft=False):
+    """phiGInit by its doubling recurrence: g[0] = scale; level i = 1, 2, ... with half = 2^(i-1), m = n - i and c = rx[m]:
+    g[b ^ half] = g[b] ((1 - c) - c w^(b 2^m)), g[b] = g[b] ((1 - c) + c w^(b 2^m)) for b < half.  The inverse table (w -> 1 / w) runs
+    levels 1 .. n; the forward table runs 1 .. n - 1 and closes with level n updating g[b] alone, so its upper half stays zero.
+    w: the 2^n-th root of unity (oracle.root_of_unity(n))."""
+    n = len(rx); N = 1 << n
+    if ifft:
+        w = py_pow(w, N - 1)
+    pm = [ONE] * N
+    for t in range(1, N):
+        pm[t] = py_mul(pm[t - 1], w)
+    g = [ZERO] * N; g[0] = scale
+    for i in range(1, n + 1):
+        half, m = 1 << (i - 1), n - i
+        t1 = py_sub(ONE, rx[m])
+        left_only = (i == n) and not ifft
+        for b in range(half):
+            t2 = py_mul(rx[m], pm[b << m])
+            if not left_only:
+                g[b ^ half] = py_mul(g[b], py_sub(t1, t2))
+            g[b] = py_mul(g[b], py_add(t1, t2))
+    return g
+
+
+def py_cubic_claim(t1, t2, t3, lens, a):
+    """sum_j a_j sum_i t1 t2 t3 over table j of the concatenated tables: round 0's p(0) + p(1) of the batched cubic sumcheck"""
+    s, o = ZERO, 0
+    for j, ln in enumerate(lens):
+        s = py_add(s, py_mul(a[j], py_sum(py_mul(py_mul(t1[i], t2[i]), t3[i]) for i in range(o, o + int(ln)))))
+        o += int(ln)
+    return s
+
+
+LK_VALUES = (-1, 0, 1, 2, 3, 4)        # every selector prove_gate_consistency_lookups hands the error terms over its three rewrites
+
+
+def selectors(n, lookups=False):
+    """{name: (n,) int32} gate selectors.  Without lookups they are 0 / 1 (the gate is F(s) or 1 - F(s)); lookups=True adds the lookup
+    prover's values: all six in turn, and each alone (one branch of the selector map per array)."""
+    i = np.arange(n)
+    last = np.zeros(n, np.int32); last[-1] = 1
+    out = {"zeros": np.zeros(n, np.int32), "ones": np.ones(n, np.int32), "alternate": (i % 2).astype(np.int32), "only_last": last,
+           "thirds": (i % 3 == 0).astype(np.int32)}
+    if lookups:
+        out["lk_cycle"] = (i % 6 - 1).astype(np.int32)
+        for v in LK_VALUES:
+            out["lk_all_%s" % (("m%d" % -v) if v < 0 else v)] = np.full(n, v, np.int32)
+    return out
+
+
 def graphs_from(oracle, n):
     """the oracle's current expander graphs for message length n, {(dep, kind): dict(L, R, degree, nbr, w)} (Hobbit.upload_graphs' form)"""
     lv, dep, m = {}, 0, n
