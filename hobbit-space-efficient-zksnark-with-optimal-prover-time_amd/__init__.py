@@ -59,6 +59,12 @@ ABI_SYMBOLS = [
     "hobbit_brakedown_stream_open_device_bytes", "hobbit_brakedown_stream_open_free",
 ]
 
+# every symbol include/hobbit_parity.h declares (checked by tests/test_parity_matrix.py)
+PARITY_SYMBOLS = [
+    "hobbit_parity_commit", "hobbit_parity_commitment_free", "hobbit_parity_dims", "hobbit_parity_dev", "hobbit_parity_root", "hobbit_parity_levels",
+    "hobbit_parity_lists", "hobbit_parity_open", "hobbit_prove_linear_code_batch",
+]
+
 
 
 class _OpenOut(ctypes.Structure):
@@ -146,7 +152,13 @@ def load_library(path=LIB_PATH):
         "hobbit_brakedown_stream_open_begin": [V, S, S, V, V, V, S, V], "hobbit_brakedown_stream_open_aggregate_push": [V, V, V],
         "hobbit_brakedown_stream_open_reply_push": [V, V, V], "hobbit_brakedown_stream_open_finish": [V, V, V, V, V, V, V],
         "hobbit_brakedown_stream_open_device_bytes": [V], "hobbit_brakedown_stream_open_free": [V],
+        # include/hobbit_parity.h
+        "hobbit_parity_commit": [V, L, V], "hobbit_parity_commitment_free": [V], "hobbit_parity_dims": [V, V, V, V, V], "hobbit_parity_dev": [V, I],
+        "hobbit_parity_root": [V, V, V], "hobbit_parity_levels": [V, V, V], "hobbit_parity_lists": [V, V, V, V, V, V, V, V, V],
+        "hobbit_parity_open": [V, V, V, V, I, V], "hobbit_prove_linear_code_batch": [V, V, S, S, S, L, V, V, V, V, V, V],
     }
+    lib.hobbit_parity_commitment_free.restype = None
+    lib.hobbit_parity_dev.restype = c_vp
     for name, args in protos.items():
         getattr(lib, name).argtypes = args
     lib.hobbit_transcript_count.restype = c_sz; lib.hobbit_transcript_read.restype = c_sz; lib.hobbit_transcript_record.restype = None
@@ -275,6 +287,47 @@ class BrakedownCommitment:
     def free(self):
         if self.h and self.hb.ctx:
             self.hb.lib.hobbit_brakedown_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class ParityCommitment:
+    """Handle on a device-resident commitment to the code's parity matrix (hobbit_parity_commit): the access lists and C_p."""
+
+    def __init__(self, hb, handle):
+        self.hb, self.h = hb, handle
+        n, m, P, sec = c_ll(), c_sz(), c_sz(), ctypes.c_double()
+        hb.lib.hobbit_parity_dims(handle, ctypes.byref(n), ctypes.byref(m), ctypes.byref(P), ctypes.byref(sec))
+        self.n, self.m, self.P, self.list_seconds = n.value, m.value, P.value, sec.value
+
+    def dev(self, which):
+        return self.hb.lib.hobbit_parity_dev(self.h, c_int(which))
+
+    def root(self):
+        out = np.zeros(32, np.uint8)
+        self.hb._chk(self.hb.lib.hobbit_parity_root(self.hb.ctx, self.h, _hp(out)))
+        return out
+
+    def levels(self):
+        out = np.zeros((2 * self.P - 1, 32), np.uint8)
+        self.hb._chk(self.hb.lib.hobbit_parity_levels(self.hb.ctx, self.h, _hp(out)))
+        return out
+
+    def lists(self):
+        """d2h read of the lists: idx1, idx2, cnt1, cnt2 (P x u32), weight (P F), acc1, acc2 (2n F)"""
+        u = [np.zeros(self.P, np.uint32) for _ in range(4)]
+        w = np.zeros((self.P, 2), np.uint64); a1 = np.zeros((2 * self.n, 2), np.uint64); a2 = np.zeros((2 * self.n, 2), np.uint64)
+        self.hb._chk(self.hb.lib.hobbit_parity_lists(self.hb.ctx, self.h, _hp(u[0]), _hp(u[1]), _hp(u[2]), _hp(u[3]), _hp(w), _hp(a1), _hp(a2)))
+        return dict(idx1=u[0], idx2=u[1], cnt1=u[2], cnt2=u[3], weight=w, acc1=a1, acc2=a2)
+
+    def free(self):
+        if self.h and self.hb.ctx:
+            self.hb.lib.hobbit_parity_commitment_free(self.h)
         self.h = None
 
     def __del__(self):
@@ -893,6 +946,50 @@ class Hobbit:
                                            _hp(final_r), _hp(oe), _hp(fe), ctypes.byref(layers)))
         L = layers.value
         return dict(layers=np.array([L]), poly=q, r=r, vr=vr[:L], fin=fin[:L], final_r=final_r, out_eval=oe, final_eval=fe)
+
+    # ---- the code's parity matrix, committed and opened (include/hobbit_parity.h; src/sumcheck.cpp:2671-2885, 3201-3221)
+    def commit_parity_matrix(self, n):
+        h = c_vp()
+        self._chk(self.lib.hobbit_parity_commit(self.ctx, c_ll(n), ctypes.byref(h)))
+        return ParityCommitment(self, h)
+
+    def open_parity_matrix(self, pc, r1, r2):
+        """prover side of open_parity_matrix(r1, r2, n) for the commitment pc; libc draws on the host in the reference's order"""
+        r1 = Fh(r1).reshape(-1, 2); r2 = Fh(r2).reshape(-1, 2)
+        P, S = pc.P, 2 * pc.n
+        Z = lambda *s: np.zeros(s + (2,), np.uint64)  # noqa: E731
+
+        def tree(size):
+            lt = (4 * size).bit_length() - 1; depth = size.bit_length() - 1; nr = sum(range(lt)) + 1
+            return dict(poly=Z(nr, 4), r=Z(nr), vr=Z(depth, 3), fin=Z(depth), final_r=Z(lt), evals=Z(2), layers=np.zeros(1, np.int32))
+        L = P.bit_length() - 1
+        t1, t2 = tree(P), tree(S)
+        out = dict(p2=dict(poly=Z(L, 4), r=Z(L), vr=Z(3), fin=Z(1)), p3=dict(poly=Z(L + 1, 3), r=Z(L + 1), vr=Z(2), fin=Z(1)),
+                   p4=dict(poly=Z(L + 3, 3), r=Z(L + 3), vr=Z(2), fin=Z(1)), cw_root=np.zeros(32, np.uint8), scalars=Z(4), partial=Z(7), acc_y=Z(2),
+                   checks=np.zeros(2, np.int32))
+        sp_p, o_p = self._sp_buffers(8 * P, 16); sp_w, o_w = self._sp_buffers(2 * P, 16)
+        ptrs = [t[k].ctypes.data for t in (t1, t2) for k in ("poly", "r", "vr", "fin", "final_r", "evals", "layers")]
+        ptrs += [out[p][k].ctypes.data for p in ("p2", "p3", "p4") for k in ("poly", "r", "vr", "fin")]
+        out["stage_ms"] = np.zeros(6, np.float64)
+        ptrs += [out[k].ctypes.data for k in ("cw_root", "scalars", "partial", "acc_y", "checks")] + [ctypes.addressof(o_p), ctypes.addressof(o_w), out["stage_ms"].ctypes.data]
+        o = (c_vp * len(ptrs))(*ptrs)
+        self._chk(self.lib.hobbit_parity_open(self.ctx, pc.h, _hp(r1), _hp(r2), c_int(r1.shape[0]), o))
+        for name, t in (("t1", t1), ("t2", t2)):
+            lay = int(t["layers"][0])
+            out[name] = dict(layers=np.array([lay]), poly=t["poly"], r=t["r"], vr=t["vr"][:lay], fin=t["fin"][:lay], final_r=t["final_r"], out_eval=t["evals"][0],
+                             final_eval=t["evals"][1])
+        for p in ("p2", "p3", "p4"):
+            out[p]["fin"] = out[p]["fin"][0]
+        out["sp_p"] = self._sp_trim(sp_p, 8 * P, 16); out["sp_w"] = self._sp_trim(sp_w, 2 * P, 16)
+        return out
+
+    def prove_linear_code_batch(self, codewords, n, r1, r2):
+        """codewords (count, len, 2); the challenges r1 (log2 2n), r2 (log2 count) come from the caller"""
+        cw = Fh(codewords); count, ln = cw.shape[0], cw.shape[1]; r1 = Fh(r1).reshape(-1, 2); r2 = Fh(r2).reshape(-1, 2)
+        q, r, vr, fin = self._proof2((2 * n).bit_length() - 1)
+        d = self.to_device(cw)
+        self._chk(self.lib.hobbit_prove_linear_code_batch(self.ctx, d.ptr, count, ln, ln, n, _hp(r1), _hp(r2), _hp(q), _hp(r), _hp(vr), _hp(fin)))
+        return dict(poly=q, r=r, vr=vr, fin=fin)
 
     # ---- streaming-sumcheck error terms / folds (reference names: src/sumcheck.cpp:374-432, 1093-1136)
     def err2p(self, b1, b2, f1, f2):

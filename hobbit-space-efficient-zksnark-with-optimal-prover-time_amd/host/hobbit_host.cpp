@@ -60,6 +60,7 @@ struct PhaseTimer {
 #define TIMED_READ(stmt) do { double t__ = now_s(); stmt; g_t_read += now_s() - t__; } while (0)
 #define TIMED_UP(stmt) do { double t__ = now_s(); stmt; g_t_up += now_s() - t__; } while (0)
 
+static hobbit_parity_commitment *g_parity = nullptr;             // device residents behind the global C_p (commit_parity_matrix)
 hobbit_ctx *hobbit_host_ctx() {
     if (!g_ctx) {
         const char *d = getenv("HOBBIT_DEVICE");
@@ -72,6 +73,7 @@ void hobbit_host_shutdown() {
     if (g_ctx) free_prev();
     if (g_commit) { hobbit_commitment_free(g_commit); g_commit = nullptr; }
     if (g_bd) { hobbit_brakedown_free(g_bd); g_bd = nullptr; }
+    if (g_parity) { hobbit_parity_commitment_free(g_parity); g_parity = nullptr; }
     if (g_bds_levels) { hobbit_free(g_ctx, g_bds_levels); g_bds_levels = nullptr; }
     if (g_poly_dev) { hobbit_free(g_ctx, g_poly_dev); g_poly_dev = nullptr; g_poly_n = 0; }
     if (g_ctx) { hobbit_ctx_destroy(g_ctx); g_ctx = nullptr; }
@@ -854,7 +856,7 @@ void _compute_tensorcode(F *message, F **tensor, int size) {                    
     for (size_t i = 0; i < t.size(); i++) memcpy((void *)tensor[i], t[i].data(), t[i].size() * sizeof(F));
 }
 shockwave_data::~shockwave_data() {
-    if (k > 0) { for (int i = 0; i < k; i++) { delete[] encoded_matrix[i]; delete[] matrix[i]; } delete[] encoded_matrix; delete[] matrix; }
+    if (k > 0 && matrix) { for (int i = 0; i < k; i++) { delete[] encoded_matrix[i]; delete[] matrix[i]; } delete[] encoded_matrix; delete[] matrix; }
     for (void *p : {d_matrix, d_enc, d_levels}) if (p && g_ctx) hobbit_free(g_ctx, p);
 }
 shockwave_data *shockwave_commit(vector<F> &poly, int k) {                                                     // src/Virgo.cpp:120-157
@@ -882,6 +884,67 @@ void shockwave_prove(shockwave_data *data, vector<F> x, double &vt, double &ps) 
     if (g_sw.iters && !(g_sw.wchecks[0] && g_sw.wchecks[1])) { printf("Error in final verification step\n"); exit(-1); }               // src/Virgo.cpp:562-565, 648-651
     shockwave_ps(g_sw, (size_t)data->N, data->k, ps); (void)vt;
     delete data;                                                                                                                      // (:515)
+}
+// ---- the code's parity matrix, committed and opened (src/sumcheck.cpp:2671-2885, 3201-3221; include/hobbit_parity.h) ---------------------------
+shockwave_data *C_p = nullptr;                                                                                  // src/sumcheck.cpp:25
+static hobbit_host_parity_transcript g_popen;
+hobbit_host_parity_transcript &hobbit_host_last_parity_open() { return g_popen; }
+void commit_parity_matrix(int n) {                                                                              // src/sumcheck.cpp:2671-2706
+    if (g_parity) { hobbit_parity_commitment_free(g_parity); g_parity = nullptr; }
+    HCHK(hobbit_parity_commit(hobbit_host_ctx(), n, &g_parity));
+    size_t P = 0; HCHK(hobbit_parity_dims(g_parity, nullptr, nullptr, &P, nullptr));
+    // C_p as the reference's global: N, k and the column tree.  The matrix and its encoded rows stay with the device object (matrix /
+    // encoded_matrix are left null); above 2^20 leaves only the root level is brought to the host.
+    delete C_p; C_p = new shockwave_data; C_p->k = 16; C_p->N = (int)(8 * P);
+    const int levels = (int)log2((double)P) + 1; C_p->MT.resize(levels);
+    if (P <= ((size_t)1 << 20)) {
+        vector<uint8_t> lv(32 * (2 * P - 1)); HCHK(hobbit_parity_levels(g_ctx, g_parity, lv.data()));
+        size_t off = 0; for (int l = 0, sz = (int)P; l < levels; l++, sz /= 2) { C_p->MT[l].resize(sz); memcpy(C_p->MT[l].data(), lv.data() + 32 * off, 32 * (size_t)sz); off += sz; }
+    } else { C_p->MT[levels - 1].resize(1); HCHK(hobbit_parity_root(g_ctx, g_parity, C_p->MT[levels - 1][0].arr)); }
+}
+static void sumcheck3_ps(int rounds, double &ps) { ps += ((size_t)rounds * 5 + 3) * sizeof(F) / 1024.0; }      // src/sumcheck.cpp:2031, 2048
+void open_parity_matrix(vector<F> r1, vector<F> r2, int n, double &vt, double &ps) {                             // src/sumcheck.cpp:2708-2885
+    long long cn = 0; size_t P = 0;
+    if (!g_parity || hobbit_parity_dims(g_parity, &cn, nullptr, &P, nullptr) || cn != n) { printf("Error: open_parity_matrix without commit_parity_matrix(%d)\n", n); exit(-1); }
+    const size_t S = 2 * (size_t)n; const int L = (int)log2((double)P), l = (int)log2((double)S);
+    hobbit_host_parity_transcript &t = g_popen; t.n = n; t.P = P;
+    auto tree = [](hobbit_host_parity_transcript::tree &T, size_t size) {
+        const int lt = (int)log2((double)(4 * size)), depth = lt - 2; size_t nr = 1; for (int i = 0; i < lt; i++) nr += (size_t)i;
+        T.cpoly.assign(4 * nr, F(0)); T.r.assign(nr, F(0)); T.vr.assign(3 * (size_t)depth, F(0)); T.fin.assign(depth, F(0)); T.final_r.assign(lt, F(0)); T.layers = 0;
+    };
+    tree(t.t1, P); tree(t.t2, S);
+    t.p2.assign(4 * (size_t)L, F(0)); t.p2_r.assign(L, F(0)); t.p3.assign(3 * (size_t)(L + 1), F(0)); t.p3_r.assign(L + 1, F(0)); t.p4.assign(3 * (size_t)(L + 3), F(0)); t.p4_r.assign(L + 3, F(0));
+    SpBuffers bp(t.sp_p, 8 * P, 16), bw(t.sp_w, 2 * P, 16);
+    hobbit_parity_open_out o = {hF(t.t1.cpoly.data()), hF(t.t1.r.data()), hF(t.t1.vr.data()), hF(t.t1.fin.data()), hF(t.t1.final_r.data()), hF(t.t1.evals), &t.t1.layers,
+                                hF(t.t2.cpoly.data()), hF(t.t2.r.data()), hF(t.t2.vr.data()), hF(t.t2.fin.data()), hF(t.t2.final_r.data()), hF(t.t2.evals), &t.t2.layers,
+                                hF(t.p2.data()), hF(t.p2_r.data()), hF(t.p2_vr), hF(&t.p2_fin), hF(t.p3.data()), hF(t.p3_r.data()), hF(t.p3_vr), hF(&t.p3_fin),
+                                hF(t.p4.data()), hF(t.p4_r.data()), hF(t.p4_vr), hF(&t.p4_fin), t.cw_root, hF(t.scalars), hF(t.partial), hF(t.acc_y), t.checks, &bp.o, &bw.o};
+    HCHK(hobbit_parity_open(hobbit_host_ctx(), g_parity, hF(r1.data()), hF(r2.data()), (int)r1.size(), &o));
+    if (!t.checks[0]) { printf("Error 1\n"); exit(-1); }                                                        // (:2838-2841)
+    if (!t.checks[1]) { printf("Error 2\n"); exit(-1); }                                                        // (:2876-2879)
+    for (auto *sp : {&t.sp_p, &t.sp_w}) if (sp->iters && !(sp->wchecks[0] && sp->wchecks[1])) { printf("Error in final verification step\n"); exit(-1); }
+    // ps in the reference's order: the first tree's layers (2, 3, .. rounds), the second's, P2, P3, P4, the two shockwave proofs
+    for (int k = 0; k < t.t1.layers; k++) sumcheck3_ps(2 + k, ps);
+    for (int k = 0; k < t.t2.layers; k++) sumcheck3_ps(2 + k, ps);
+    sumcheck3_ps(L, ps); sumcheck2_ps(L + 1, ps); sumcheck2_ps(L + 3, ps);
+    shockwave_ps(t.sp_p, 8 * P, 16, ps); shockwave_ps(t.sp_w, 2 * P, 16, ps);
+    delete C_p; C_p = nullptr; (void)vt; (void)l;                                                                // shockwave_prove deletes its argument (src/Virgo.cpp:515)
+}
+proof prove_linear_code_batch(vector<vector<F>> &codewords, int n, double &vt, double &ps) {                     // src/sumcheck.cpp:3201-3221
+    const size_t count = codewords.size(), S = 2 * (size_t)n; const int k = (int)log2((double)S), kc = (int)log2((double)count);
+    if (count < 2 || ((size_t)1 << kc) != count) { printf("Error: prove_linear_code_batch needs a power-of-two number of codewords\n"); exit(-1); }
+    vector<F> r1 = generate_randomness(k), r2 = generate_randomness(kc);
+    size_t len = 0; for (auto &c : codewords) len = c.size() > len ? c.size() : len;
+    vector<F> flat(count * len, F(0));
+    for (size_t i = 0; i < count; i++) memcpy((void *)(flat.data() + i * len), codewords[i].data(), codewords[i].size() * sizeof(F));
+    DevBuf cw(flat.data(), flat.size() * sizeof(F));
+    vector<F> q(3 * (size_t)k), r(k); F vr[2], fin;
+    HCHK(hobbit_prove_linear_code_batch(hobbit_host_ctx(), (const hobbit_F *)cw.p, count, len, len, n, hF(r1.data()), hF(r2.data()), hF(q.data()), hF(r.data()), hF(vr), hF(&fin)));
+    proof P = proof_from2(k, q, r, vr, fin);
+    sumcheck2_ps(k, ps); (void)vt;
+    if (P.q_poly[0].eval(0) + P.q_poly[0].eval(1) != F(0)) printf("Error in codeword\n");
+    P.randomness.push_back(r1); P.randomness.push_back(r2);
+    return P;
 }
 // the streaming multiplication-tree prover over read_stream: the stream is re-generated on the host exactly as the reference does, every
 // read is uploaded and handed to the library as a chunk source
@@ -1713,6 +1776,28 @@ int hobbit_host_mul_tree_stream(size_t B, int vectors, size_t size, int distance
     vector<F> o = prove_multiplication_tree_stream_shallow(fd, vectors, (int)size, F(32), distance, px, naive != 0, vt, ps);
     memcpy(out, o.data(), o.size() * sizeof(F)); *ps_out = ps;
     return (int)o.size();
+}
+// commit_parity_matrix + open_parity_matrix through the mirror on the stream of a fresh process: srandom(1), expander_init_store(n), commit, r1 and r2
+// (generate_randomness(log2 2n) each), then -- after srandom(seed) when seed != 0 -- the opening.  roots: C_p, C_w, whir_p, whir_w; polys: P2 (4 F per
+// round), P3, P4 (3 F per round) back to back; scal: a, b, r, _a, the seven partial evaluations, accesses1_y, accesses2_y.  Returns P4's rounds.
+int hobbit_host_parity_open(int n, unsigned seed, uint8_t *roots, uint64_t *polys, uint64_t *scal, int *checks4, double *ps_out) {
+    srandom(1);
+    expander_init_store(n);
+    commit_parity_matrix(n);
+    memcpy(roots, C_p->MT.back()[0].arr, 32);
+    const int l = (int)log2((double)(2 * n));
+    vector<F> r1 = generate_randomness(l), r2 = generate_randomness(l);
+    if (seed) srandom(seed);
+    double vt = 0, ps = 0;
+    open_parity_matrix(r1, r2, n, vt, ps);
+    hobbit_host_parity_transcript &t = hobbit_host_last_parity_open();
+    memcpy(roots + 32, t.cw_root, 32); memcpy(roots + 64, t.sp_p.whir_root, 32); memcpy(roots + 96, t.sp_w.whir_root, 32);
+    uint64_t *p = polys;
+    for (const vector<F> *v : {&t.p2, &t.p3, &t.p4}) { memcpy(p, v->data(), 16 * v->size()); p += 2 * v->size(); }
+    memcpy(scal, t.scalars, 64); memcpy(scal + 8, t.partial, 112); memcpy(scal + 22, t.acc_y, 32);
+    checks4[0] = t.checks[0]; checks4[1] = t.checks[1]; checks4[2] = t.sp_p.wchecks[0] & t.sp_p.wchecks[1]; checks4[3] = t.sp_w.wchecks[0] & t.sp_w.wchecks[1];
+    *ps_out = ps;
+    return (int)t.p4_r.size();
 }
 void hobbit_host_close(void) { hobbit_host_shutdown(); }
 }

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 #include "hobbit_hip.h"
+#include "hobbit_parity.h"
 
 using std::vector;
 
@@ -227,6 +228,25 @@ hobbit_host_shockwave_transcript &hobbit_host_last_shockwave();           /* the
  * compatibility only (the device encode has no host scratch); routine_time accumulates the time spent re-generating streams, sc_vt is
  * never written on the prover side. */
 extern shockwave_data *C_f, *C_c;
+/* src/sumcheck.cpp:25, 2671, 2708, 3201 (defined there without header declarations): the succinct opening of the code's parity matrix.
+ * commit_parity_matrix(n) needs expander_init_store(n) and sets the global C_p (N = 8P, k = 16, the column tree; the matrix and its encoded
+ * rows stay on the device, matrix / encoded_matrix are null).  open_parity_matrix draws from libc in the reference's order, exits on the
+ * reference's "Error 1" / "Error 2", accumulates ps piece by piece and, like the reference (shockwave_prove deletes its argument), leaves C_p
+ * deleted.  Index padding is 0 (include/hobbit_parity.h).  prove_linear_code_batch draws r1, r2 itself; a power-of-two number of codewords. */
+extern shockwave_data *C_p;
+void commit_parity_matrix(int n);
+void open_parity_matrix(vector<F> r1, vector<F> r2, int n, double &vt, double &ps);
+proof prove_linear_code_batch(vector<vector<F>> &codewords, int n, double &vt, double &ps);
+/* the messages of the last open_parity_matrix (the reference returns none); layouts as hobbit_parity_open_out */
+struct hobbit_host_parity_transcript {
+    struct tree { vector<F> cpoly, r, vr, fin, final_r; F evals[2]; int layers = 0; };
+    int n = 0; size_t P = 0;
+    tree t1, t2;
+    vector<F> p2, p2_r, p3, p3_r, p4, p4_r; F p2_vr[3], p3_vr[2], p4_vr[2], p2_fin, p3_fin, p4_fin;
+    uint8_t cw_root[32]; F scalars[4], partial[7], acc_y[2]; int checks[2] = {0, 0};
+    hobbit_host_shockwave_transcript sp_p, sp_w;
+};
+hobbit_host_parity_transcript &hobbit_host_last_parity_open();
 extern F *scratch[2][100];
 extern bool __encode_initialized;
 extern double routine_time, sc_vt;

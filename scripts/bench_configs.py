@@ -23,6 +23,46 @@ def timed(fn, reps=3, warm=1):
     for _ in range(reps): fn()
     hb.sync(); return (time.perf_counter() - t0) / reps
 
+# PM  the code's parity matrix (include/hobbit_parity.h): commit_parity_matrix and open_parity_matrix at n = 4096, 2^17 and 2^20.  Per stage
+#     (host wall times of hobbit_parity_open, every stage ends synchronised), the host seconds of the list building, the launch count of
+#     one opening and the gather kernel's achieved bytes per second (16 B of lists read and 96 B written per entry, the 32 B of gathered
+#     table entries not counted) from the library's event brackets, next to the 8 TB/s this repository uses as peak.  The reference's CPU
+#     seconds are those of tests/golden/parity_matrix.npz (n = 4096 only: commit, and the opening up to its first SHA3 call).
+#     `python scripts/bench_configs.py parity [n ...]` runs this entry alone; `parity-gather n` one commit and one opening without
+#     the event brackets, for a kernel trace of its own.
+def parity_entry(ns=(4096, 1 << 17, 1 << 20), bare=False):
+    res = {}
+    gold = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "parity_matrix.npz"))
+    for n in ns:
+        hb.rng_reset(); t0 = time.perf_counter(); hb.expander_init_store(n); t_graphs = time.perf_counter() - t0
+        l = (2 * n).bit_length() - 1
+        r1, r2 = hb.generate_randomness(l), hb.generate_randomness(l)
+        pc = hb.commit_parity_matrix(n); hb.sync(); pc.free()                                  # warm: workspaces, tables
+        t0 = time.perf_counter(); pc = hb.commit_parity_matrix(n); hb.sync(); t_commit = time.perf_counter() - t0
+        g = hb.open_parity_matrix(pc, r1, r2)                                                  # warm
+        if not bare:
+            hb.profile(True); hb.profile_reset()
+        t0 = time.perf_counter(); g = hb.open_parity_matrix(pc, r1, r2); t_open = time.perf_counter() - t0
+        assert g["checks"].tolist() == [1, 1]
+        e = dict(m=pc.m, P=pc.P, graphs_host_draw_s=t_graphs, lists_host_s=pc.list_seconds, commit_ms=1e3 * t_commit, open_ms=1e3 * t_open,
+                 stage_ms=dict(zip(("gather_and_Cw", "tree1", "eval_and_tree2", "sumchecks_P2_P3_P4", "shockwave_prove_Cp", "shockwave_prove_Cw"), g["stage_ms"].tolist())))
+        if not bare:
+            rep = hb.profile_report(); hb.profile(False)
+            e["launches"] = int(sum(v[1] for v in rep.values()))
+            ms = rep.get("k_parity_gather", (0.0, 0))[0]
+            e["gather_ms"] = ms
+            if ms:
+                e["gather_bytes_per_s"] = 112.0 * pc.P / (1e-3 * ms); e["gather_fraction_of_8TBs"] = e["gather_bytes_per_s"] / 8e12
+        if "ref_seconds_%d" % n in gold:
+            e["reference_cpu_s"] = dict(commit=float(gold["ref_seconds_%d" % n][0]), open_child_until_first_sha3=float(gold["ref_seconds_%d" % n][1]))
+        res["PM_n%d" % n] = e
+        pc.free()
+    return res
+
+if len(sys.argv) > 1 and sys.argv[1] in ("parity", "parity-gather"):
+    print(json.dumps(parity_entry(tuple(int(a) for a in sys.argv[2:]) or (4096, 1 << 17, 1 << 20), bare=sys.argv[1] == "parity-gather")))
+    hb.close(); sys.exit(0)
+
 # C2
 n = 1 << 24
 d1 = hb.fill_splitmix(n, 1); d2 = hb.precompute_beta(splitmix_field(24, 9), keep_on_device=True)
@@ -129,5 +169,6 @@ for logN in (26, 30):
         assert r["checks"].tolist() == [1]
     out["C5_elastic_open_2e%d_B2e20_opt2_s" % logN] = timed(c5_open2, reps=2, warm=1)
     del lvd
+out.update(parity_entry())
 print(json.dumps(out))
 hb.close()
