@@ -1417,8 +1417,9 @@ __global__ void k_blake3_64(const uint8_t *__restrict__ in, uint8_t *__restrict_
         load16w(in + 64 * i, m); blake3_compress64(m, h); store8w(out + 32 * i, h);
     }
 }
-// out[i] = H( H(xyzw[i]) | prev[i] )   (src/merkle_tree.cpp:62-87)
-__global__ void k_hash_md(const F *__restrict__ xyzw, const uint8_t *__restrict__ prev, uint8_t *__restrict__ out, size_t n) {
+// out[i] = H( H(xyzw[i]) | prev[i] )   (src/merkle_tree.cpp:62-87).  out may be prev (the streaming commits update their state in place): a
+// thread reads prev[i] before it writes out[i] and touches no other entry, so neither of the two is declared __restrict__
+__global__ void k_hash_md(const F *__restrict__ xyzw, const uint8_t *prev, uint8_t *out, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         uint32_t m[16], h[8];
         load16w(xyzw + 4 * i, m); blake3_compress64(m, h);

@@ -118,7 +118,8 @@ int hobbit_fft_any(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, si
 
 /* ---- BLAKE3 / Merkle (src/Blake3_hash.cpp:5-10; src/merkle_tree.cpp:62-87,193-221,255-324) -- */
 int hobbit_blake3_64(hobbit_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, size_t n);      /* blake3_hash x n */
-/* hash_double_field_element_merkle_damgard_blake x n: out[i] = H(H(xyzw[i]) | prev[i]); in place ok */
+/* hash_double_field_element_merkle_damgard_blake x n: out[i] = H(H(xyzw[i]) | prev[i]).  In place is allowed: d_out may equal d_prev
+ * (entry i is read before it is written, and no other entry is touched); any other overlap of the two is not. */
 int hobbit_hash_md(hobbit_ctx *ctx, const hobbit_F *d_xyzw, const uint8_t *d_prev, uint8_t *d_out, size_t n);
 /* MT_commit_Blake: leaves H(4 consecutive F) into d_levels[0..N/4), then the tree */
 int hobbit_mt_commit_blake(hobbit_ctx *ctx, const hobbit_F *d_leafs, size_t N, uint8_t *d_levels);

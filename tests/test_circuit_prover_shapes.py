@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 from adversarial import (families, selectors, graphs_from, set_weights, to_py, from_py, py_mul, py_add, py_err2p, py_err3p, py_err4p,
                          py_batch_terms, py_axpy, py_axpy_i32, py_fingerprint, py_prepare_matrix_cols, py_phi_g, py_cubic_claim, P)
+from commit_refs import paths as expected_paths      # the sibling gather lives with the other commitment references
 from oracle.pyoracle import splitmix_field
 from test_sumcheck_eq import point_families
 from test_sumcheck_shapes import open_case
@@ -609,12 +610,6 @@ def test_shockwave_prove_witness_like_polynomials(hb, oracle):
 
 
 # ---- h. every Merkle path ------------------------------------------------------------------------------------------------------------
-def expected_paths(levels, n, pos):
-    """sibling paths of leaves `pos` of a flat tree over n leaves, in one gather: level l starts at sum_{t<l} n >> t"""
-    depth = n.bit_length() - 1
-    off = np.concatenate([[0], np.cumsum([n >> t for t in range(depth)])])[:depth].astype(np.int64)
-    pos = np.asarray(pos, np.int64)
-    return levels[off[None, :] + ((pos[:, None] >> np.arange(depth)[None, :]) ^ 1)]
 
 
 def test_merkle_paths_direct(hb, oracle):
