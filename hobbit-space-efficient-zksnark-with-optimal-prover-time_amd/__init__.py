@@ -65,6 +65,9 @@ PARITY_SYMBOLS = [
     "hobbit_parity_lists", "hobbit_parity_open", "hobbit_prove_linear_code_batch",
 ]
 
+# every symbol include/hobbit_whir.h declares (checked by tests/test_whir_long.py)
+WHIR_SYMBOLS = ["hobbit_whir_ood", "hobbit_whir_prove_any"]
+
 
 
 class _OpenOut(ctypes.Structure):
@@ -156,6 +159,8 @@ def load_library(path=LIB_PATH):
         "hobbit_parity_commit": [V, L, V], "hobbit_parity_commitment_free": [V], "hobbit_parity_dims": [V, V, V, V, V], "hobbit_parity_dev": [V, I],
         "hobbit_parity_root": [V, V, V], "hobbit_parity_levels": [V, V, V], "hobbit_parity_lists": [V, V, V, V, V, V, V, V, V],
         "hobbit_parity_open": [V, V, V, V, I, V], "hobbit_prove_linear_code_batch": [V, V, S, S, S, L, V, V, V, V, V, V],
+        # include/hobbit_whir.h
+        "hobbit_whir_ood": [V, V, V, I, V, V, I, V], "hobbit_whir_prove_any": [V, V, S, V, V, V, V],
     }
     lib.hobbit_parity_commitment_free.restype = None
     lib.hobbit_parity_dev.restype = c_vp
@@ -895,8 +900,31 @@ class Hobbit:
         return dict(qn=nq, qidx=b["qidx"][:tot].copy(), qreply=b["qreply"][:tot].copy(), qpaths=b["qpaths"][:pbytes].copy(), final_pb=b["final_pb"][:2 * rem].copy())
 
     def whir_prove(self, poly, x, com=None, com_levels=None):
-        """_whir_prove (src/Virgo.cpp:519-686), prover side; com / com_levels: device buffers from whir_commit (computed here if None)"""
-        p = Fh(poly).reshape(-1, 2); x = Fh(x).reshape(-1, 2); N = p.shape[0]; logN = N.bit_length() - 1
+        """_whir_prove (src/Virgo.cpp:519-686), prover side, N <= 2^24; com / com_levels: device buffers from whir_commit (computed here if None)"""
+        return self._whir_prove(self.lib.hobbit_whir_prove, poly, x, com, com_levels)
+
+    def whir_prove_any(self, poly, x, com=None, com_levels=None):
+        """hobbit_whir_prove_any (include/hobbit_whir.h): the same proof for 2^9 <= N <= 2^26.  poly: host array (N,2), or (DeviceBuffer / int
+        pointer, N); com / com_levels: device buffers (or int pointers) of hobbit_whir_commit, computed here if None"""
+        return self._whir_prove(self.lib.hobbit_whir_prove_any, poly, x, com, com_levels)
+
+    def whir_ood(self, poly, beta, z, pw):
+        """hobbit_whir_ood: the out-of-domain step for the R points z (R, v, 2) with weights pw (R, 2) over poly, beta of 2^v elements (host
+        arrays); returns (y (R, 2), the updated beta)"""
+        p = Fh(poly).reshape(-1, 2); b = Fh(beta).reshape(-1, 2); z = Fh(z); pw = Fh(pw).reshape(-1, 2)
+        R, v = z.shape[0], z.shape[1]
+        assert z.ndim == 3 and pw.shape[0] == R and p.shape[0] == (1 << v) and b.shape[0] == (1 << v)
+        dp, db, dy = self.to_device(p), self.to_device(b), self.alloc(16 * R)
+        self._chk(self.lib.hobbit_whir_ood(self.ctx, dp.ptr, db.ptr, v, _hp(z), _hp(pw), R, dy.ptr))
+        return self.to_host(dy, (R, 2), np.uint64), self.to_host(db, p.shape, np.uint64)
+
+    def _whir_prove(self, fn, poly, x, com, com_levels):
+        x = Fh(x).reshape(-1, 2)
+        if isinstance(poly, tuple):
+            d, N = poly
+        else:
+            p = Fh(poly).reshape(-1, 2); N = p.shape[0]; d = None
+        logN = max(N.bit_length() - 1, 1)
         out = dict(qpoly=np.zeros((logN + 8, 3, 2), np.uint64), a=np.zeros((logN + 8, 2), np.uint64), fri_roots=np.zeros((logN, 32), np.uint8),
                    scal=np.zeros((2, 2), np.uint64), checks=np.zeros(2, np.int32), iters=np.zeros(1, np.int32))
         out.update(self._wq_buffers())
@@ -905,10 +933,13 @@ class Hobbit:
         class Out(ctypes.Structure):
             _fields_ = [(n, c_vp) for n in names]
         o = Out(*[out[n].ctypes.data for n in names])
-        d = self.to_device(p)
-        dc, dl = self.alloc(16 * 2 * N), self.alloc(32 * N)
-        self._chk(self.lib.hobbit_whir_commit(self.ctx, d.ptr, N, dc.ptr, dl.ptr))
-        self._chk(self.lib.hobbit_whir_prove(self.ctx, d.ptr, N, dc.ptr, dl.ptr, _hp(x), ctypes.byref(o)))
+        if d is None:
+            d = self.to_device(p)
+        ptr = lambda b: b.ptr if isinstance(b, DeviceBuffer) else int(b)
+        if com is None or com_levels is None:
+            com, com_levels = self.alloc(16 * 2 * max(N, 1)), self.alloc(32 * max(N, 1))
+            self._chk(self.lib.hobbit_whir_commit(self.ctx, ptr(d), N, com.ptr, com_levels.ptr))
+        self._chk(fn(self.ctx, ptr(d), N, ptr(com), ptr(com_levels), _hp(x), ctypes.byref(o)))
         it = int(out["iters"][0])
         res = dict(iters=np.array([it]), poly=out["qpoly"][:4 * it], a=out["a"][:4 * it], roots=out["fri_roots"][:it], scal=out["scal"], checks=out["checks"])
         res.update(self._wq_trim(out, N, it))

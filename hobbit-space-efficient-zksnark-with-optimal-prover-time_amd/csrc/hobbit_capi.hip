@@ -10,6 +10,7 @@
 #include <functional>
 #include "hobbit_kernels.hpp"
 #include "hobbit_blake3.hpp"
+#include "../../include/hobbit_whir.h"
 
 using namespace hobbit;
 
@@ -1252,9 +1253,7 @@ static int whir_fri_layer(hobbit_ctx *ctx, const F *d_poly, size_t cur, size_t f
     HB_TRY(launch_zero(ctx, fp, fsz * sizeof(F)));
     HB_TRY(launch_copy(ctx, fp, d_poly, cur * sizeof(F)));
     HB_TRY(hobbit_change_form(ctx, reinterpret_cast<hobbit_F *>(fp), ilog2_exact(cur)));
-    const int lg = ilog2_exact(fsz);
-    if (lg <= 12) HB_TRY(fft_rows(ctx, fp, fsz, (uint32_t)fsz, fp, fsz, 1, lg, false, 1, 1, 0, 0));
-    else HB_TRY(fft_long(ctx, fp, fsz, fsz, fp, lg, false, 1));
+    HB_TRY(fft_any_rows(ctx, fp, fsz, fsz, fp, ilog2_exact(fsz), false, 1));         // (2^25, 2^26: the first layer of hobbit_whir_prove_any)
     HB_TRY(launch_transpose_ld(ctx, fp, 0, fsz / 16, 16, (uint32_t)(fsz / 16), buf, 0, 16, 1));
     HB_TRY(hobbit_mt_commit_blake(ctx, reinterpret_cast<hobbit_F *>(buf), fsz, lv));
     HB_TRY(launch_copy(ctx, d_root, lv + 32 * (2 * (fsz / 4) - 2), 32));
@@ -1270,18 +1269,30 @@ static void compute_zetas_host(std::vector<F> &z, std::vector<uint64_t> &ridx, i
 }
 // scratch elements hobbit_whir_prove carves from workspace4 AFTER the first 4N (left to a whir_commit of the same polynomial)
 static constexpr size_t WHIR_DIN = 2048 + 128 + 64, WHIR_DRES = 1024;       // F elements: z (100 x <= 20) | pows (<= 100) | indices (<= 128 u64)
-static size_t whir_scratch_elems(size_t N) {
-    return 2 * N /* poly, beta */ + 2 * 100 * (N >> 4) /* batched eq tables */ + N /* fp */ + 2 * N + N /* two kept layers */ + 64
-           + 3 * 1024 /* partials */ + WHIR_DIN * 6 /* per-iteration inputs z | pows | query indices */ + WHIR_DRES /* coefficients, roots, y, finals */
+// The two forms of the proof.  hobbit_whir_prove: N <= 2^24, the out-of-domain step over `repeats` materialised eq tables.
+// hobbit_whir_prove_any: N <= 2^26, that step from the two halves of every table (hobbit_whir.hip); its staging slot holds
+// z (100 x <= 22) | pows | indices | the low halves of z (100 x WHIR_OOD_VL).  Plan, query answering and replay are shared.
+struct WhirCfg {
+    int max_log; bool split; const char *range;
+    constexpr size_t zcap() const { return split ? 2304 : 2048; }
+    constexpr size_t din() const { return zcap() + 128 + 64 + (split ? 128 * WHIR_OOD_VL : 0); }
+    size_t ood_elems(size_t N) const { return split ? whir_ood_scratch_elems(std::max(ilog2_exact(N) - 4, 1), 100) : 2 * 100 * (N >> 4); }
+};
+static constexpr WhirCfg WHIR_TABLES = {24, false, "whir_prove: N must be a power of two in [2^9, 2^24]"},
+                         WHIR_ANY = {26, true, "whir_prove_any: N must be a power of two in [2^9, 2^26]"};
+static_assert(WHIR_TABLES.din() == WHIR_DIN, "hobbit_whir_prove's staging slot is what open_impl sizes the pinned buffer for");
+static size_t whir_scratch_elems(size_t N, const WhirCfg &cfg = WHIR_TABLES) {
+    return 2 * N /* poly, beta */ + cfg.ood_elems(N) /* out-of-domain step */ + N /* fp */ + 2 * N + N /* two kept layers */ + 64
+           + 3 * 1024 /* partials */ + cfg.din() * 6 /* per-iteration inputs z | pows | query indices */ + WHIR_DRES /* coefficients, roots, y, finals */
            + 256 * 16 /* query replies */ + 8192 /* query paths: < 4096 hashes */ + 64;
 }
 // Every host-drawn input of one _whir_prove, taken from libc in the reference's order BEFORE anything is queued (none depends on device
 // data): a caller can draw the plan of one proof, hand the proof to another thread / context and go on drawing for the next.
 struct WhirIterPlan { F a[4]; bool last = false; int repeats = 0; std::vector<F> z, pw; std::vector<uint64_t> ridx; };
 struct WhirPlan { std::vector<WhirIterPlan> it; int final_repeats = 0; size_t remaining = 0; bool final_round = false; std::vector<uint64_t> final_ridx; };
-static int whir_plan(size_t N, WhirPlan &P) {
+static int whir_plan(size_t N, WhirPlan &P, const WhirCfg &cfg = WHIR_TABLES) {
     const int k = 4, logN = ilog2_exact(N);
-    if (logN < 9 || logN > 24) return HOBBIT_EINVAL;
+    if (logN < 9 || logN > cfg.max_log) return HOBBIT_EINVAL;
     int iter = 0, repeats = 100;
     for (;;) {
         if (iter >= 6) return HOBBIT_EINVAL;
@@ -1313,22 +1324,23 @@ static int whir_plan(size_t N, WhirPlan &P) {
 // proof is queued without a single synchronisation -- host-drawn inputs go through one pinned staging slot per iteration (one
 // async copy each), every result lands in a device result area -- and is read back once at the end, where the checks are replayed.
 static int whir_prove_run(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_F *d_com, const uint8_t *d_com_levels, const hobbit_F *h_x, hobbit_whir_out *o,
-                         const WhirPlan &plan) {
+                         const WhirPlan &plan, const WhirCfg &cfg = WHIR_TABLES) {
     const int k = 4, logN = ilog2_exact(N);
-    if (logN < 9 || logN > 24 || !o) return ctx->fail(HOBBIT_EINVAL, "whir_prove: N must be a power of two in [2^9, 2^24]");
+    if (logN < 9 || logN > cfg.max_log || !o) return ctx->fail(HOBBIT_EINVAL, cfg.range);
+    const size_t DIN = cfg.din(), ZCAP = cfg.zcap();
     hobbit_F *h_qpoly = o->qpoly, *h_a = o->a, *h_scal = o->scal; uint8_t *h_fri_roots = o->fri_roots; int *h_checks = o->checks;
     StageScope sc(ctx);
-    const size_t curmax = N >> k, sz_front = 4 * N, sz_E = 100 * curmax;
-    F *base; HB_TRY(ctx->workspace4((sz_front + whir_scratch_elems(N)) * sizeof(F), (void **)&base));
-    F *poly = base + sz_front, *beta = poly + N, *E0 = beta + N, *E1 = E0 + sz_E, *fp = E1 + sz_E, *keepA = fp + N, *keepB = keepA + 2 * N, *part = keepB + N + 64,
-      *din = part + 3 * 1024, *dres = din + WHIR_DIN * 6, *d_rep = dres + WHIR_DRES;
+    const size_t sz_front = 4 * N, sz_E = cfg.ood_elems(N) / 2;                  // (tables: two buffers of 100 N/16; split: one area, E0 onwards)
+    F *base; HB_TRY(ctx->workspace4((sz_front + whir_scratch_elems(N, cfg)) * sizeof(F), (void **)&base));
+    F *poly = base + sz_front, *beta = poly + N, *E0 = beta + N, *E1 = E0 + sz_E, *fp = E0 + cfg.ood_elems(N), *keepA = fp + N, *keepB = keepA + 2 * N, *part = keepB + N + 64,
+      *din = part + 3 * 1024, *dres = din + DIN * 6, *d_rep = dres + WHIR_DRES;
     uint8_t *d_paths = reinterpret_cast<uint8_t *>(d_rep + 256 * 16);
     // result area: [0] eval0 | per iteration t (stride 128): 12 coefficients, root (2 F), y (100 F) | [900] final sum | [904..) final poly | beta
     auto res_it = [&](int t) { return dres + 8 + (size_t)t * 128; };
     F *res_fin = dres + 900;
     // pinned staging: one slot per iteration, laid out exactly like its device twin (z | pows | indices), then the read-back area
-    uint8_t *pinb; HB_TRY(ctx->pinned((WHIR_DIN * 6 + WHIR_DRES) * sizeof(F), (void **)&pinb));
-    F *pin_in = reinterpret_cast<F *>(pinb), *pin_res = pin_in + WHIR_DIN * 6;
+    uint8_t *pinb; HB_TRY(ctx->pinned((DIN * 6 + WHIR_DRES) * sizeof(F), (void **)&pinb));
+    F *pin_in = reinterpret_cast<F *>(pinb), *pin_res = pin_in + DIN * 6;
     HB_TRY(launch_copy(ctx, poly, d_poly, N * sizeof(F)));
     HB_TRY(hobbit_eq_table(ctx, h_x, logN, reinterpret_cast<hobbit_F *>(beta)));
     HB_TRY(launch_dot(ctx, beta, poly, N, part, dres));                          // eval = <beta, poly> (:535-538)
@@ -1376,19 +1388,26 @@ static int whir_prove_run(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
         const std::vector<F> &pw = ip.pw;
         pw_all.push_back(pw);
         // stage z | pows | indices of this iteration and ship them with one asynchronous copy
-        F *pslot = pin_in + (size_t)(iter - 1) * WHIR_DIN, *dslot = din + (size_t)(iter - 1) * WHIR_DIN;
-        if (z.size() > 2048 || (size_t)repeats > 128 || ridx.size() > 128) return ctx->fail(HOBBIT_EINVAL, "whir_prove: staging slot too small");
-        memcpy(pslot, z.data(), z.size() * sizeof(F)); memcpy(pslot + 2048, pw.data(), pw.size() * sizeof(F)); memcpy(pslot + 2048 + 128, ridx.data(), ridx.size() * 8);
-        HB_CHECK(ctx, hipMemcpyAsync(dslot, pslot, WHIR_DIN * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
-        const F *dz = dslot, *dpw = dslot + 2048; const uint64_t *d_idx = reinterpret_cast<const uint64_t *>(dslot + 2048 + 128);
-        // the `repeats` eq tables side by side, then y = E poly, beta += pows^T E (:613-633)
-        F *cE = E0, *nE = E1;
-        const int hd = v < 11 ? v : 11;                                           // levels 0..hd-1 of every table in one launch
-        HB_TRY(launch_eq_head_batched(ctx, cE, cur, dz, v, hd, repeats));
-        for (int l = hd; l < v; l++) { HB_TRY(launch_eq_step_batched(ctx, cE, nE, (size_t)1 << l, cur, dz, v, l, repeats)); std::swap(cE, nE); }
-        HB_TRY(launch_matvec_rows(ctx, cE, (size_t)repeats, cur, poly, res_it(iter - 1) + 16));
-        HB_TRY(launch_vecmat(ctx, cE, (size_t)repeats, cur, dpw, nE));          // nE[0..cur) = sum_i pow_i E[i]   (uses ctx->workspace for partials)
-        HB_TRY(launch_axpy(ctx, beta, nE, fmake(1), cur));
+        F *pslot = pin_in + (size_t)(iter - 1) * DIN, *dslot = din + (size_t)(iter - 1) * DIN;
+        if (z.size() > ZCAP || (size_t)repeats > 128 || ridx.size() > 128) return ctx->fail(HOBBIT_EINVAL, "whir_prove: staging slot too small");
+        memcpy(pslot, z.data(), z.size() * sizeof(F)); memcpy(pslot + ZCAP, pw.data(), pw.size() * sizeof(F)); memcpy(pslot + ZCAP + 128, ridx.data(), ridx.size() * 8);
+        const int vl = v < WHIR_OOD_VL ? v : WHIR_OOD_VL;
+        if (cfg.split) for (int i = 0; i < repeats; i++) memcpy(pslot + ZCAP + 192 + (size_t)i * vl, z.data() + (size_t)i * v, (size_t)vl * sizeof(F));
+        HB_CHECK(ctx, hipMemcpyAsync(dslot, pslot, DIN * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+        const F *dz = dslot, *dpw = dslot + ZCAP; const uint64_t *d_idx = reinterpret_cast<const uint64_t *>(dslot + ZCAP + 128);
+        if (cfg.split) {
+            // y = E poly, beta += pows^T E (:613-633) from the halves of the tables: poly and beta cross memory once each
+            HB_TRY(launch_whir_ood(ctx, poly, beta, v, dz, dslot + ZCAP + 192, dpw, repeats, E0, res_it(iter - 1) + 16));
+        } else {
+            // the `repeats` eq tables side by side, then y = E poly, beta += pows^T E (:613-633)
+            F *cE = E0, *nE = E1;
+            const int hd = v < 11 ? v : 11;                                       // levels 0..hd-1 of every table in one launch
+            HB_TRY(launch_eq_head_batched(ctx, cE, cur, dz, v, hd, repeats));
+            for (int l = hd; l < v; l++) { HB_TRY(launch_eq_step_batched(ctx, cE, nE, (size_t)1 << l, cur, dz, v, l, repeats)); std::swap(cE, nE); }
+            HB_TRY(launch_matvec_rows(ctx, cE, (size_t)repeats, cur, poly, res_it(iter - 1) + 16));
+            HB_TRY(launch_vecmat(ctx, cE, (size_t)repeats, cur, dpw, nE));      // nE[0..cur) = sum_i pow_i E[i]   (uses ctx->workspace for partials)
+            HB_TRY(launch_axpy(ctx, beta, nE, fmake(1), cur));
+        }
         HB_TRY(answer(d_idx));                                                    // _verify_iteration(data, a, r, repeats, iter) (:634)
         prev = keep; prev_lv = reinterpret_cast<const uint8_t *>(keep + fsz); prev_sz = fsz;
         repeats = queries;
@@ -1403,10 +1422,10 @@ static int whir_prove_run(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
         if (plan.final_round) {
             ridx = plan.final_ridx;
             if (ridx.size() > 128) return ctx->fail(HOBBIT_EINVAL, "whir_prove: staging slot too small");
-            F *pslot = pin_in + (size_t)5 * WHIR_DIN, *dslot = din + (size_t)5 * WHIR_DIN;     // the last slot: only indices
-            memcpy(pslot + 2048 + 128, ridx.data(), ridx.size() * 8);
-            HB_CHECK(ctx, hipMemcpyAsync(dslot + 2048 + 128, pslot + 2048 + 128, 128 * 8, hipMemcpyHostToDevice, ctx->stream));
-            HB_TRY(answer(reinterpret_cast<const uint64_t *>(dslot + 2048 + 128)));
+            F *pslot = pin_in + (size_t)5 * DIN, *dslot = din + (size_t)5 * DIN;               // the last slot: only indices
+            memcpy(pslot + ZCAP + 128, ridx.data(), ridx.size() * 8);
+            HB_CHECK(ctx, hipMemcpyAsync(dslot + ZCAP + 128, pslot + ZCAP + 128, 128 * 8, hipMemcpyHostToDevice, ctx->stream));
+            HB_TRY(answer(reinterpret_cast<const uint64_t *>(dslot + ZCAP + 128)));
         }
     }
     // the one read-back
@@ -1439,6 +1458,12 @@ int hobbit_whir_prove(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const h
     WhirPlan plan;
     if (whir_plan(N, plan) != 0) return ctx->fail(HOBBIT_EINVAL, "whir_prove: N must be a power of two in [2^9, 2^24]");
     return whir_prove_run(ctx, d_poly, N, d_com, d_com_levels, h_x, o, plan);
+}
+int hobbit_whir_prove_any(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_F *d_com, const uint8_t *d_com_levels, const hobbit_F *h_x, hobbit_whir_out *o) {
+    WhirPlan plan;
+    if (!o) return ctx->fail(HOBBIT_EINVAL, "whir_prove_any: NULL out");                                 // (before the plan: nothing is drawn)
+    if (whir_plan(N, plan, WHIR_ANY) != 0) return ctx->fail(HOBBIT_EINVAL, WHIR_ANY.range);
+    return whir_prove_run(ctx, d_poly, N, d_com, d_com_levels, h_x, o, plan, WHIR_ANY);
 }
 // shockwave_prove (src/Virgo.cpp:435-517), prover side
 // workspace4 elements of one shockwave_prove: [0, nested) belongs to the nested whir_commit / whir_prove calls, its own vectors follow

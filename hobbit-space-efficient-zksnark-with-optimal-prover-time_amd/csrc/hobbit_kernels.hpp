@@ -77,6 +77,10 @@ int launch_change_form_level(hobbit_ctx *ctx, const F *in, F *out, size_t n, siz
 int launch_whir_round(hobbit_ctx *ctx, F *poly, F *beta, size_t L, F a, F *part, F *coef);
 int launch_eq_step_batched(hobbit_ctx *ctx, const F *old, F *nw, size_t m, size_t ld, const F *z, int v, int level, int reps);
 int launch_eq_head_batched(hobbit_ctx *ctx, F *out, size_t ld, const F *z, int v, int h, int reps);
+// hobbit_whir.hip: the out-of-domain step from the two halves of every eq table (low half: WHIR_OOD_VL variables, in LDS)
+static constexpr int WHIR_OOD_VL = 4;
+size_t whir_ood_scratch_elems(int v, int R);
+int launch_whir_ood(hobbit_ctx *ctx, const F *poly, F *beta, int v, const F *dz, const F *dzlo, const F *dpw, int R, F *scratch, F *d_y);
 int launch_fill_F(hobbit_ctx *ctx, F *p, size_t stride, size_t n, F v);
 int launch_sumcheck2(hobbit_ctx *ctx, const F *v1, const F *v2, size_t n, F prev_r, MHP h_qpoly, MHP h_r, MHP h_vr, MHP h_final);
 int launch_sumcheck2_eq(hobbit_ctx *ctx, int T, CHP h_r1, CHP h_r2, CHP h_a, const F *v2, size_t n, F prev_r, MHP h_qpoly, MHP h_r, MHP h_vr, MHP h_final);

@@ -334,27 +334,31 @@ struct SpBuffers {   // host buffers behind one hobbit_shockwave_out
                                  hF(t.reply.data()), t.paths.data(), t.wqidx.data(), hF(t.wqreply.data()), t.wqpaths.data(), hF(t.wfinal.data()), t.wqn.data()};
     }
 };
+// ps of one _whir_prove (src/Virgo.cpp:519-686) on w coefficients in the reference's order of accumulation: per iteration the four round
+// polynomials (:557), then _verify_iteration's replies and paths (:262); the last iteration adds the final polynomial and beta first (:643)
+static void whir_ps(const vector<int32_t> &qn, const vector<int32_t> &qidx, int iters, size_t w, double &ps) {
+    size_t q = 0;
+    for (int it = 1; it <= iters; it++) {
+        for (int i = 0; i < 4; i++) ps += (3 * sizeof(F)) / 1024.0;
+        size_t size = it == 1 ? 2 * w : (2 * w) >> (it - 1);                              // layer the queries of this round read
+        auto answer = [&](int round) {
+            int n = qn[round];
+            ps += 16.0 * n * sizeof(F) / 1024.0;
+            vector<size_t> pos(qidx.begin() + q, qidx.begin() + q + n);
+            path_ps(size / 4, (int)log2((double)(size / 4)), pos, ps);
+            q += n;
+        };
+        if (it < iters) answer(it - 1);
+        else { ps += (w >> (4 * iters)) * 2 * sizeof(F) / 1024.0; answer(it - 1); }
+    }
+}
 // ps of one shockwave_prove (src/Virgo.cpp:435-517) in the reference's order of accumulation
 static void shockwave_ps(const hobbit_host_shockwave_transcript &t, size_t N, int k, double &ps) {
     size_t w = N / k, W = 2 * w; int lgW = (int)log2((double)W);
     sumcheck2_ps(lgW, ps); sumcheck2_ps(lgW, ps);                                         // P1, prove_fft
     // :479 tests aggr.size()/2 after prove_fft doubled aggr in place (src/sumcheck.cpp:2984-2985): the original width, and :482 adds the doubled one
-    if (w > 256) {                                                                        // _whir_prove (:519-686)
-        size_t q = 0;
-        for (int it = 1; it <= t.iters; it++) {
-            for (int i = 0; i < 4; i++) ps += (3 * sizeof(F)) / 1024.0;
-            size_t size = it == 1 ? 2 * w : (2 * w) >> (it - 1);                          // layer the queries of this round read
-            auto answer = [&](int round) {
-                int n = t.wqn[round];
-                ps += 16.0 * n * sizeof(F) / 1024.0;
-                vector<size_t> pos(t.wqidx.begin() + q, t.wqidx.begin() + q + n);
-                path_ps(size / 4, (int)log2((double)(size / 4)), pos, ps);
-                q += n;
-            };
-            if (it < t.iters) answer(it - 1);
-            else { ps += (w >> (4 * t.iters)) * 2 * sizeof(F) / 1024.0; answer(it - 1); }
-        }
-    } else ps += 2 * w * sizeof(F) / 1024.0;
+    if (w > 256) whir_ps(t.wqn, t.wqidx, t.iters, w, ps);                                 // _whir_prove (:519-686)
+    else ps += 2 * w * sizeof(F) / 1024.0;
     ps += 240.0 * k * sizeof(F) / 1024.0;
     vector<size_t> pos(t.I.begin(), t.I.end());
     path_ps(W, lgW, pos, ps);
@@ -885,6 +889,60 @@ void shockwave_prove(shockwave_data *data, vector<F> x, double &vt, double &ps) 
     shockwave_ps(g_sw, (size_t)data->N, data->k, ps); (void)vt;
     delete data;                                                                                                                      // (:515)
 }
+// ---- the standalone WHIR baseline (src/Virgo.cpp:160-178, 519-686; src/Our_PC.cpp:843-859; include/hobbit_whir.h) --------------------------------
+#ifndef HOBBIT_HOST_REFERENCE_BUILD
+Whir_data::~Whir_data() { for (void *p : {d_poly, d_com, d_levels}) if (p && g_ctx) hobbit_free(g_ctx, p); }
+void whir_commit(vector<F> &poly, Whir_data &data) {                                                           // src/Virgo.cpp:160-178
+    const size_t N = poly.size();
+    data.k = 4; data.poly = poly;
+    for (void **p : {&data.d_poly, &data.d_com, &data.d_levels}) if (*p) { hobbit_free(hobbit_host_ctx(), *p); *p = nullptr; }
+    HCHK(hobbit_malloc(hobbit_host_ctx(), N * sizeof(F), &data.d_poly)); HCHK(hobbit_malloc(g_ctx, 2 * N * sizeof(F), &data.d_com)); HCHK(hobbit_malloc(g_ctx, 32 * N, &data.d_levels));
+    HCHK(hobbit_memcpy_h2d(g_ctx, data.d_poly, poly.data(), N * sizeof(F)));
+    HCHK(hobbit_whir_commit(g_ctx, (const hobbit_F *)data.d_poly, N, (hobbit_F *)data.d_com, (uint8_t *)data.d_levels));
+    // MT_commit_Blake over 2N elements: N/2 leaves, N - 1 hashes, leaves first
+    data.MT.clear(); size_t off = 0;
+    for (size_t sz = N / 2; sz >= 1; sz /= 2) {
+        data.MT.emplace_back(sz);
+        HCHK(hobbit_memcpy_d2h(g_ctx, data.MT.back().data(), (const char *)data.d_levels + 32 * off, 32 * sz)); off += sz;
+    }
+}
+static hobbit_host_whir_transcript g_whir;
+hobbit_host_whir_transcript &hobbit_host_last_whir() { return g_whir; }
+void _whir_prove(Whir_data &data, vector<F> x, double &vt, double &ps) {                                       // src/Virgo.cpp:519-686
+    const size_t N = data.poly.size(); const int lw = (int)log2((double)N);
+    hobbit_host_whir_transcript &t = g_whir;
+    t.qpoly.assign(3 * (lw + 8), F(0)); t.a.assign(lw + 8, F(0)); t.fri_roots.assign(32 * (lw + 1), 0); t.scal.assign(2, F(0));
+    t.qidx.assign(256, 0); t.qreply.assign(256 * 16, F(0)); t.qpaths.assign(256 * 24 * 32, 0); t.final_pb.assign(32, F(0)); t.qn.assign(8, 0);
+    t.checks[0] = t.checks[1] = 0; t.iters = 0;
+    hobbit_whir_out o{hF(t.qpoly.data()), hF(t.a.data()), t.fri_roots.data(), hF(t.scal.data()), t.checks, &t.iters, t.qidx.data(), hF(t.qreply.data()), t.qpaths.data(),
+                      hF(t.final_pb.data()), t.qn.data()};
+    HCHK(hobbit_whir_prove_any(hobbit_host_ctx(), (const hobbit_F *)data.d_poly, N, (const hobbit_F *)data.d_com, (const uint8_t *)data.d_levels, hF(x.data()), &o));
+    if (!t.checks[0]) { printf("Error in %d\n", 0); exit(-1); }                                                  // (:562-565)
+    if (!t.checks[1]) { printf("Error in final verification step\n"); exit(-1); }                                // (:648-651)
+    auto t1 = std::chrono::steady_clock::now();
+    whir_ps(t.qn, t.qidx, t.iters, N, ps);
+    vt += std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t1).count();
+    t.ps = ps; t.vt = vt;
+}
+void test_whir(size_t N) {                                                                                       // src/Our_PC.cpp:757-761, 843-859
+    vector<F> poly = generate_randomness((int)N);
+    auto start = std::chrono::steady_clock::now();
+    Whir_data C;
+    whir_commit(poly, C);
+    auto end = std::chrono::steady_clock::now();
+    double elapsed_seconds = std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    std::cout << "Commit time: " << elapsed_seconds << " seconds" << std::endl;
+    printf("root ");
+    for (int i = 0; i < 32; i++) printf("%02x", C.MT.back()[0].arr[i]);
+    printf("\n");
+    start = std::chrono::steady_clock::now();
+    double ps = 0.0, vt = 0.0;
+    _whir_prove(C, generate_randomness((int)log2((double)N)), vt, ps);
+    end = std::chrono::steady_clock::now();
+    elapsed_seconds += std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    printf("PC Total: pt = %lf, ps = %lf, vt = %lf\n", elapsed_seconds, ps, vt);
+}
+#endif
 // ---- the code's parity matrix, committed and opened (src/sumcheck.cpp:2671-2885, 3201-3221; include/hobbit_parity.h) ---------------------------
 shockwave_data *C_p = nullptr;                                                                                  // src/sumcheck.cpp:25
 static hobbit_host_parity_transcript g_popen;

@@ -15,6 +15,7 @@
 #include <vector>
 #include "hobbit_hip.h"
 #include "hobbit_parity.h"
+#include "hobbit_whir.h"
 
 using std::vector;
 
@@ -223,6 +224,34 @@ shockwave_data *shockwave_commit(vector<F> &poly, int k);
 void shockwave_prove(shockwave_data *data, vector<F> x, double &vt, double &ps);
 struct hobbit_host_shockwave_transcript;
 hobbit_host_shockwave_transcript &hobbit_host_last_shockwave();           /* the messages of the last shockwave_prove (the reference returns none) */
+/* src/Virgo.h:52-60, src/Virgo.cpp:160-178, 519-686: the standalone WHIR baseline (test_PC's last branch, src/Our_PC.cpp:843-859), on the
+ * device through hobbit_whir_commit / hobbit_whir_prove_any (include/hobbit_whir.h), 2^9 <= N <= 2^26.  whir_commit keeps the polynomial, the
+ * regrouped codeword and the tree on the device (d_poly, d_com, d_levels); MT is read back, poly_com and the FRI members stay empty on the
+ * host.  _whir_prove draws from libc in the reference's order, exits on the reference's two checks and accumulates ps as the reference does.
+ * Left out of the build that sits in front of the reference's objects: there a caller's Whir_data has the reference's layout. */
+#ifndef HOBBIT_HOST_REFERENCE_BUILD
+struct Whir_data {
+    int k = 0;
+    vector<F> poly, poly_com;
+    vector<vector<_hash>> MT;
+    vector<vector<vector<_hash>>> FRI_MT;
+    vector<vector<F>> FRI_poly;
+    void *d_poly = nullptr, *d_com = nullptr, *d_levels = nullptr;         /* not in the reference: device residents of the same data */
+    Whir_data() = default;
+    Whir_data(const Whir_data &) = delete;
+    Whir_data &operator=(const Whir_data &) = delete;
+    ~Whir_data();
+};
+void whir_commit(vector<F> &poly, Whir_data &data);
+void _whir_prove(Whir_data &data, vector<F> x, double &vt, double &ps);
+/* the messages of the last _whir_prove (the reference returns none); layouts as hobbit_whir_out */
+struct hobbit_host_whir_transcript {
+    vector<F> qpoly, a, scal, qreply, final_pb; vector<uint8_t> fri_roots, qpaths; vector<int32_t> qidx, qn; int checks[2] = {0, 0}, iters = 0;
+    double ps = 0, vt = 0;
+};
+hobbit_host_whir_transcript &hobbit_host_last_whir();
+void test_whir(size_t N);                                                 /* test_PC's last branch; `host/test_pc whir <logN>` */
+#endif
 /* src/PC_utils.cpp:6-7 ; src/linear_code_encode.cpp:3-4 ; src/sumcheck.cpp:27,29 : globals of the reference ABI.  C_f / C_c are set by
  * this mirror's shockwave users as the reference's _aggregate / aggregate do; scratch / __encode_initialized exist for source
  * compatibility only (the device encode has no host scratch); routine_time accumulates the time spent re-generating streams, sc_vt is

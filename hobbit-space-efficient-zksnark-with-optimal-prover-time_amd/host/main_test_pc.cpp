@@ -1,6 +1,7 @@
 // main_test_pc.cpp -- the reference's commented-out CLI hook `./pigeon <logN> <option> <K>` (option 4: RS x expander, option 1: RS x RS,
 // option 3: the Brakedown baseline, K unused) and `elastic <logN> <logB> <opt>` (Elastic_PC options 1 and 2; option 3: the streaming
-// Brakedown baseline, which sets its own buffer size, so <logB> is ignored there as in the reference)
+// Brakedown baseline, which sets its own buffer size, so <logB> is ignored there as in the reference) and `whir <logN>` (the standalone WHIR
+// baseline: test_PC's last branch, which test_PC itself keeps refusing)
 // (src/main.cpp:1176: test_PC(1ULL<<atoi(argv[1]), atoi(argv[2]), atoi(argv[3]))) over the
 // device-backed host mirror.  Build: see __graft_entry__.build_host().
 #include <cstdio>
@@ -8,8 +9,14 @@
 #include <string>
 #include "hobbit_host.hpp"
 int main(int argc, char **argv) {
-    if (argc < 4) { printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>\n", argv[0], argv[0]); return 1; }
+    const bool whir = argc == 3 && std::string(argv[1]) == "whir";
+    if (argc < 4 && !whir) { printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>\n", argv[0], argv[0], argv[0]); return 1; }
     init_hash();
+    if (whir) {                                       // src/Our_PC.cpp:843-859
+        const int logn = atoi(argv[2]);
+        if (logn < 9 || logn > 26) { printf("Error: the standalone WHIR baseline takes 9 <= logN <= 26\n"); return 255; }
+        test_whir(1ULL << logn);
+    } else
     if (std::string(argv[1]) == "elastic") {          // src/main.cpp:1177-1178: BUFFER_SPACE = 1<<argv[2]; test_Elastic_PC(1<<argv[1], argv[3])
         BUFFER_SPACE = 1ULL << atoi(argv[3]);
         test_Elastic_PC(1ULL << atoi(argv[2]), argc > 4 ? atoi(argv[4]) : 1);

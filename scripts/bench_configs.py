@@ -59,6 +59,51 @@ def parity_entry(ns=(4096, 1 << 17, 1 << 20), bare=False):
         pc.free()
     return res
 
+# WH  the standalone WHIR baseline (include/hobbit_whir.h; test_PC's last branch): hobbit_whir_commit and hobbit_whir_prove_any at 2^20, 2^22,
+#     2^24, 2^26 between device events, warmed, the profiler off; at sizes hobbit_whir_prove serves, the two proofs alternated in one process
+#     (materialised eq tables against the table-free out-of-domain step); then one run with the library's event brackets for the two new
+#     kernels, against their products (R cur each per iteration) and their bytes (poly once; beta read and written once; the high tables).
+#     `python scripts/bench_configs.py whir [logN ...]` runs this entry alone; `whir-bare logN` one warmed commit + proof and nothing else,
+#     for a kernel trace of its own.
+def whir_entry(logs=(20, 22, 24, 26), reps=5, bare=False):
+    res = {}
+    stat = lambda v: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)), runs=[float(t) for t in v])
+    for logN in logs:
+        N = 1 << logN
+        d = hb.fill_splitmix(N, 5); x = splitmix_field(logN, 6); com, lv = hb.alloc(32 * N), hb.alloc(32 * N)
+        commit = lambda: hb._chk(hb.lib.hobbit_whir_commit(hb.ctx, d.ptr, N, com.ptr, lv.ptr))
+        def ev(fn):
+            hb.timer_begin(); fn(); return hb.timer_end_ms()
+        commit(); r = hb.whir_prove_any((d, N), x, com, lv); assert r["checks"].tolist() == [1, 1]           # warm: workspaces, twiddles
+        if bare:
+            hb.sync(); commit(); hb.whir_prove_any((d, N), x, com, lv); continue
+        e = dict(commit_ms=stat([ev(commit) for _ in range(reps)]), iters=int(r["iters"][0]))
+        if logN <= 24:
+            hb.whir_prove((d, N), x, com, lv)                                                               # warm the other form's scratch
+            ta, tb = [], []
+            for _ in range(reps):
+                ta.append(ev(lambda: hb.whir_prove((d, N), x, com, lv))); tb.append(ev(lambda: hb.whir_prove_any((d, N), x, com, lv)))
+            e["prove_tables_ms"] = stat(ta); e["prove_any_ms"] = stat(tb)
+        else:
+            e["prove_any_ms"] = stat([ev(lambda: hb.whir_prove_any((d, N), x, com, lv)) for _ in range(reps)])
+        hb.profile(True); hb.profile_reset(); hb.whir_prove_any((d, N), x, com, lv); rep = hb.profile_report(); hb.profile(False); hb.profile_reset()
+        prod = by_y = by_b = 0; R, t = 100, 1
+        while logN - 4 * t > 4:
+            cur = N >> (4 * t); prod += R * cur; by_y += 16 * (cur + R * (cur >> 4)); by_b += 16 * (2 * cur + R * (cur >> 4)); R = int(100 / (1 + 3 * t)); t += 1
+        for k, b in (("k_whir_ood_y", by_y), ("k_whir_ood_beta", by_b)):
+            ms = rep.get(k, (0.0, 0))[0]
+            e[k] = dict(ms=ms, launches=int(rep.get(k, (0.0, 0))[1]), products=prod, products_per_s=prod / (1e-3 * ms) if ms else None, bytes=b,
+                        bytes_per_s=b / (1e-3 * ms) if ms else None)
+        e["bracketed_kernel_ms"] = {k: v[0] for k, v in sorted(rep.items(), key=lambda kv: -kv[1][0])[:8]}
+        res["WH_2e%d" % logN] = e
+        for b in (d, com, lv):
+            b.free()
+    return res
+
+if len(sys.argv) > 1 and sys.argv[1] in ("whir", "whir-bare"):
+    print(json.dumps(whir_entry(tuple(int(a) for a in sys.argv[2:]) or (20, 22, 24, 26), bare=sys.argv[1] == "whir-bare")))
+    hb.close(); sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] in ("parity", "parity-gather"):
     print(json.dumps(parity_entry(tuple(int(a) for a in sys.argv[2:]) or (4096, 1 << 17, 1 << 20), bare=sys.argv[1] == "parity-gather")))
     hb.close(); sys.exit(0)
@@ -170,5 +215,6 @@ for logN in (26, 30):
     out["C5_elastic_open_2e%d_B2e20_opt2_s" % logN] = timed(c5_open2, reps=2, warm=1)
     del lvd
 out.update(parity_entry())
+out.update(whir_entry())
 print(json.dumps(out))
 hb.close()
