@@ -60,4 +60,17 @@ HB3_HD void blake3_compress64(const uint32_t m[16], uint32_t out[8]) {
     out[4] = v4 ^ v12; out[5] = v5 ^ v13; out[6] = v6 ^ v14; out[7] = v7 ^ v15;
 }
 
+// Z_K: the Our_PC leaf of a group of four rows that are zero in every one of the K chunks.  Its chain starts from the zero state and absorbs the
+// same inner digest H(0^64) K times, st_{i+1} = H(H(0^64) | st_i), so it depends on K alone (host side: the commit's launcher computes it once
+// and k_leaf_chain stores it; tests/zero_chain_check.cpp compares it with a table-driven BLAKE3).
+inline void blake3_zero_group_leaf(int K, uint32_t out[8]) {
+    uint32_t m[16] = {0}, zdig[8], st[8] = {0};
+    blake3_compress64(m, zdig);
+    for (int i = 0; i < K; i++) {
+        for (int q = 0; q < 8; q++) { m[q] = zdig[q]; m[8 + q] = st[q]; }
+        blake3_compress64(m, st);
+    }
+    for (int q = 0; q < 8; q++) out[q] = st[q];
+}
+
 }  // namespace hobbit

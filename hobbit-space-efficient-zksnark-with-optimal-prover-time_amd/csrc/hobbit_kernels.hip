@@ -1509,49 +1509,48 @@ __global__ void __launch_bounds__(1024) k_merkle_sub(const uint8_t *__restrict__
 // ([chunk][col][2 trs]), so the 4 field elements of leaf (j, col) are 64 contiguous bytes.  One
 // thread owns one leaf and keeps its Merkle-Damgard state in registers across the chunk loop:
 // the tensor is read exactly once and the leaf array is written exactly once.
-// Rows at or beyond the codeword length are zero in every chunk (the expander code fills 1.72 n of the 2 n rows), so for the groups
-// j >= zero_from the inner digest is the constant H(0^64) (passed in as zdig): one compression per chunk instead of two for those
-// leaves (14 % of them at n = 4096).  A wavefront covers 64 consecutive j of one column, so the branch is wave-uniform but for one wave
-// per column.
+// Rows at or beyond the codeword length are zero in every chunk (the expander code fills 1.72 n of the 2 n rows), so the groups j >= zf
+// (14 % of them at n = 4096) are neither read nor hashed here: the commit's chain starts from the zero state, so every such leaf is the same
+// 32 bytes Z_K = blake3_zero_group_leaf(K), computed on the host and passed in as zk.  In leaf order j * cols + c those leaves are one
+// contiguous tail of the leaf array, and every workgroup stores a slice of it with 16-byte stores before it starts hashing.
+// The chain runs over the dense index idx in [0, cols * zf) of the other groups, c = idx / zf, j = idx % zf: a wavefront may straddle two
+// columns, each lane still reads its own 64 contiguous bytes per chunk, and every workgroup costs the same, so no block order has to be
+// arranged around the 8 XCDs.  (k_leaf_chain_relay below does NOT take this shortcut: it continues from a state its caller hands in, and
+// what the chain of a zero group has absorbed before is not its to assume.)
 struct ZeroDig { uint32_t w[8]; };
 template <int NL>
 __global__ void __launch_bounds__(256)
-k_leaf_chain(const F *__restrict__ tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *__restrict__ leaves, uint32_t zero_from, ZeroDig zdig) {
+k_leaf_chain(const F *__restrict__ tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *__restrict__ leaves, uint32_t zf, ZeroDig zk) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    // the leaves of the zero groups: 2 (half_trs - zf) cols stores of 16 bytes, ending exactly at the end of the leaf array
+    {
+        const size_t fill16 = 2 * (size_t)(half_trs - zf) * cols;
+        uint4 *tail = reinterpret_cast<uint4 *>(leaves + 32 * (size_t)zf * cols);
+        const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;     // stride is even: a thread stores the same half of Z_K every time
+        const uint4 v = (t & 1) ? make_uint4(zk.w[4], zk.w[5], zk.w[6], zk.w[7]) : make_uint4(zk.w[0], zk.w[1], zk.w[2], zk.w[3]);
+        for (size_t u = t; u < fill16; u += stride) tail[u] = v;
+    }
     // NL leaves per thread (independent hash chains interleaved for instruction-level parallelism)
-    const size_t total = (size_t)cols * half_trs, per = (total + NL - 1) / NL;
-    // Blocks are dealt round-robin over the 8 XCDs, and with 8 blocks per column the all-zero groups of EVERY column would land on one
-    // XCD (b % 8 == 7): that XCD would idle while the other seven set the kernel's time (measured: skipping 6 % of the compressions
-    // bought 0.5 %).  Rotating the block index inside each run of 8 by the run's number spreads the cheap blocks evenly.
-    // The grid is capped (launch_leaf_chain): a block walks several runs of 8, and the pass number joins the rotation, or it would meet the same
-    // position of every column it visits.  (The rotation permutes whole runs of 8 blocks: only when the block count is a multiple of 8.)
-    const bool rot = (gridDim.x & 7) == 0 && (((per + blockDim.x - 1) / blockDim.x) & 7) == 0;
-    uint32_t pass = 0;
-    for (size_t vb = blockIdx.x; vb * (size_t)blockDim.x < per; vb += gridDim.x, pass++) {
-        const size_t bid = rot ? (vb & ~(size_t)7) | ((vb + (vb >> 3) + pass) & 7) : vb;
-        const size_t g0 = bid * (size_t)blockDim.x + threadIdx.x;
+    const uint32_t total = cols * zf, per = (total + NL - 1) / NL;
+    for (uint32_t b0 = blockIdx.x * blockDim.x; b0 < per; b0 += stride) {
+        const uint32_t g0 = b0 + threadIdx.x;
         if (g0 >= per) continue;
         uint32_t st[NL][8];
         const F *p[NL];
-        size_t g[NL];
-        bool zero[NL];
+        uint32_t g[NL], c[NL], j[NL];
 #pragma unroll
         for (int l = 0; l < NL; l++) {
-            g[l] = g0 + (size_t)l * per;
-            const size_t gg = g[l] < total ? g[l] : total - 1;      // tail lanes recompute the last leaf (not stored)
+            g[l] = g0 + (uint32_t)l * per;
+            const uint32_t gg = g[l] < total ? g[l] : total - 1;    // tail lanes recompute the last leaf (not stored)
 #pragma unroll
             for (int q = 0; q < 8; q++) st[l][q] = 0;
-            p[l] = tensor + gg * 4;                                   // (c * 2trs + 4j) with gg = c*half_trs + j
-            zero[l] = (uint32_t)(gg % half_trs) >= zero_from;
+            c[l] = gg / zf; j[l] = gg - c[l] * zf;
+            p[l] = tensor + ((size_t)c[l] * half_trs + j[l]) * 4;     // (c * 2trs + 4j)
         }
         for (int i = 0; i < K; i++) {
             uint32_t m[NL][16], h[NL][8];
 #pragma unroll
-            for (int l = 0; l < NL; l++) {
-                if (zero[l]) {
-#pragma unroll
-                    for (int q = 0; q < 8; q++) h[l][q] = zdig.w[q];
-                } else { load16w(p[l] + (size_t)i * chunk_stride, m[l]); blake3_compress64(m[l], h[l]); }
-            }
+            for (int l = 0; l < NL; l++) { load16w(p[l] + (size_t)i * chunk_stride, m[l]); blake3_compress64(m[l], h[l]); }
 #pragma unroll
             for (int l = 0; l < NL; l++) {
 #pragma unroll
@@ -1562,10 +1561,7 @@ k_leaf_chain(const F *__restrict__ tensor, size_t chunk_stride, int K, uint32_t 
         }
 #pragma unroll
         for (int l = 0; l < NL; l++)
-            if (g[l] < total) {
-                const uint32_t c = (uint32_t)(g[l] / half_trs), j = (uint32_t)(g[l] % half_trs);
-                store8w(leaves + 32 * ((size_t)j * cols + c), st[l]);
-            }
+            if (g[l] < total) store8w(leaves + 32 * ((size_t)j[l] * cols + c[l]), st[l]);
     }
 }
 // Multi-GPU commit by chain relay: the same chain over the K_local chunks of a rank's tensor shard, for the leaf slots
@@ -1576,7 +1572,12 @@ k_leaf_chain(const F *__restrict__ tensor, size_t chunk_stride, int K, uint32_t 
 __global__ void __launch_bounds__(256)
 k_leaf_chain_relay(const F *__restrict__ tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, size_t g_begin, size_t g_count,
                    const uint8_t *__restrict__ state_in, uint8_t *__restrict__ state_out, uint8_t *leaves, uint32_t zero_from, ZeroDig zdig, int leaves_inout) {
-    // capped grid + per-pass rotation of the block order inside each run of 8, as in k_leaf_chain
+    // This kernel still visits the all-zero groups (one compression per chunk for them, with the constant inner digest zdig = H(0^64), instead
+    // of two).  Blocks are dealt round-robin over the 8 XCDs, and with 8 blocks per column the cheap all-zero groups of EVERY column would land
+    // on one XCD (b % 8 == 7), which would idle while the other seven set the kernel's time.  Rotating the block index inside each run of 8 by
+    // the run's number spreads the cheap blocks evenly.  The grid is capped: a block walks several runs of 8, and the pass number joins the
+    // rotation, or it would meet the same position of every column it visits.  (The rotation permutes whole runs of 8 blocks: only when the
+    // block count is a multiple of 8.)
     const bool rot = (gridDim.x & 7) == 0 && (((g_count + blockDim.x - 1) / blockDim.x) & 7) == 0;
     uint32_t pass = 0;
     for (size_t vb = blockIdx.x; vb * (size_t)blockDim.x < g_count; vb += gridDim.x, pass++) {
@@ -1868,15 +1869,20 @@ int launch_merkle_levels(hobbit_ctx *ctx, uint8_t *levels, size_t n, int quirk) 
     }
     return 0;
 }
-// zero_rows_from: first row index that is zero in EVERY chunk (the expander codeword length; 2*half_trs = none)
+// zero_rows_from: first row index that is zero in EVERY chunk (the expander codeword length; 2*half_trs = none).  The chain starts from the
+// zero state -- the commit, its one caller, always does -- and only that makes the leaves of the all-zero groups the constant Z_K.
 int launch_leaf_chain(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from) {
-    size_t total = (size_t)cols * half_trs;
     constexpr int NL = 1;   // 2 interleaved chains measured no faster: the kernel sits at the VALU issue limit (profiles/r01_microbench.txt)
-    ZeroDig zd; { uint32_t z[16] = {0}; blake3_compress64(z, zd.w); }
-    // 4096 resident-ish workgroups walking the leaves instead of one workgroup per 256 leaves (32 768 at 2^28): 10.15 -> 9.65 ms, same call
-    // (2048: 9.7, 8192: 9.7) -- fewer dispatches, and the per-pass rotation spreads the cheap all-zero groups evenly
-    HB_LAUNCH(ctx, "k_leaf_chain", k_leaf_chain<NL>, dim3(grid_for((total + NL - 1) / NL, 256, 4096)), dim3(256), 0, tensor, chunk_stride, K, cols,
-              half_trs, leaves, (zero_rows_from + 3) / 4, zd);
+    if (((size_t)cols * half_trs) >> 32) return ctx->fail(HOBBIT_EINVAL, "leaf chain: more than 2^32 leaves");
+    const uint32_t zf = std::min((zero_rows_from + 3) / 4, half_trs);
+    ZeroDig zk = {};
+    if (zf < half_trs) blake3_zero_group_leaf(K, zk.w);      // no zero group (RS x RS, or graphs not finalised for this trs): nothing is filled
+    // Workgroups of 256 leaves over the dense range (28 192 at 2^28, K = 32), walked by a grid capped at 4096.  Measured in one job, kernel ms
+    // per step, mean of three interleaved runs: 4096 8.74, 8192 8.73, 14 096 8.79, uncapped 8.71 -- one within the run-to-run
+    // spread of the other -- and 4028 (7 equal passes) 8.84; in an earlier job 2048 9.04 and 3524 (8 equal passes) 9.00 against 4096 8.89.
+    // Equal passes buy nothing: the hardware hands the next workgroup to whichever CU is free, so the cap stays where it was.
+    HB_LAUNCH(ctx, "k_leaf_chain", k_leaf_chain<NL>, dim3(grid_for(((size_t)cols * zf + NL - 1) / NL, 256, 4096)), dim3(256), 0, tensor, chunk_stride, K, cols,
+              half_trs, leaves, zf, zk);
     return 0;
 }
 int launch_merkle_paths(hobbit_ctx *ctx, const uint8_t *levels, size_t n, const uint64_t *d_pos, size_t nq, int depth, uint8_t *d_paths) {

@@ -35,6 +35,7 @@ int launch_fft_r8(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len
                   uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs);
 int launch_leaf_chain_relay(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, size_t g_begin, size_t g_count,
                             const uint8_t *state_in, uint8_t *state_out, uint8_t *leaves, uint32_t zero_rows_from, int leaves_inout = 0);
+// the commit's chain: starts from the zero state, so the leaves of the groups at or past zero_rows_from are written as one host-computed constant
 int launch_leaf_chain(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from);
 int launch_inner_digests(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int nchunks, uint32_t cols, uint32_t half_trs, uint8_t *out);
 int launch_chain_digests(hobbit_ctx *ctx, const uint8_t *digests, size_t stride_bytes, int K, size_t m, uint8_t *leaves);
