@@ -68,6 +68,13 @@ PARITY_SYMBOLS = [
 # every symbol include/hobbit_whir.h declares (checked by tests/test_whir_long.py)
 WHIR_SYMBOLS = ["hobbit_whir_ood", "hobbit_whir_prove_any"]
 
+# every symbol include/hobbit_brakingbase.h declares (checked by tests/test_brakingbase.py)
+BRAKINGBASE_SYMBOLS = [
+    "hobbit_brakingbase_shape", "hobbit_brakingbase_commit", "hobbit_brakingbase_free", "hobbit_brakingbase_dims", "hobbit_brakingbase_matrix_dev",
+    "hobbit_brakingbase_levels_dev", "hobbit_brakingbase_levels", "hobbit_brakingbase_root", "hobbit_brakingbase_tensor", "hobbit_brakingbase_open",
+]
+BRAKINGBASE_QUERIES = 2935
+_PARITY_P = {}          # n -> P of hobbit_parity_commit (Hobbit.brakingbase_open)
 
 
 class _OpenOut(ctypes.Structure):
@@ -161,7 +168,15 @@ def load_library(path=LIB_PATH):
         "hobbit_parity_open": [V, V, V, V, I, V], "hobbit_prove_linear_code_batch": [V, V, S, S, S, L, V, V, V, V, V, V],
         # include/hobbit_whir.h
         "hobbit_whir_ood": [V, V, V, I, V, V, I, V], "hobbit_whir_prove_any": [V, V, S, V, V, V, V],
+        # include/hobbit_brakingbase.h
+        "hobbit_brakingbase_shape": [S, S, V], "hobbit_brakingbase_commit": [V, V, S, S, I, V], "hobbit_brakingbase_free": [V],
+        "hobbit_brakingbase_dims": [V, V, V, V, V], "hobbit_brakingbase_matrix_dev": [V], "hobbit_brakingbase_levels_dev": [V],
+        "hobbit_brakingbase_levels": [V, V, V], "hobbit_brakingbase_root": [V, V, V], "hobbit_brakingbase_tensor": [V, V, S, S, V],
+        "hobbit_brakingbase_open": [V, V, V, V],
     }
+    lib.hobbit_brakingbase_free.restype = None
+    lib.hobbit_brakingbase_matrix_dev.restype = c_vp
+    lib.hobbit_brakingbase_levels_dev.restype = c_vp
     lib.hobbit_parity_commitment_free.restype = None
     lib.hobbit_parity_dev.restype = c_vp
     for name, args in protos.items():
@@ -292,6 +307,49 @@ class BrakedownCommitment:
     def free(self):
         if self.h and self.hb.ctx:
             self.hb.lib.hobbit_brakedown_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class BrakingbaseCommitment:
+    """Handle on a device-resident Braking base commitment (hobbit_brakingbase_commit): K rows of trs = N / K, encoded, rows-innermost, and the
+    Merkle levels over the 2 trs column digests."""
+
+    def __init__(self, hb, handle):
+        self.hb, self.h = hb, handle
+        N, K, trs, ln = c_sz(), c_sz(), c_sz(), c_ll()
+        hb.lib.hobbit_brakingbase_dims(handle, ctypes.byref(N), ctypes.byref(K), ctypes.byref(trs), ctypes.byref(ln))
+        self.N, self.K, self.trs, self.len = N.value, K.value, trs.value, ln.value
+        self.W = 2 * self.trs                   # columns = leaves of the tree
+
+    def levels(self):
+        out = np.zeros((2 * self.W - 1, 32), np.uint8)
+        self.hb._chk(self.hb.lib.hobbit_brakingbase_levels(self.hb.ctx, self.h, _hp(out)))
+        return out
+
+    def root(self):
+        out = np.zeros(32, np.uint8)
+        self.hb._chk(self.hb.lib.hobbit_brakingbase_root(self.hb.ctx, self.h, _hp(out)))
+        return out
+
+    def tensor(self, col_lo=0, ncols=None):
+        """the reference's tensor[0][i][c] for every row i and c in [col_lo, col_lo + ncols): shape (K, ncols, 2)"""
+        ncols = self.W - col_lo if ncols is None else ncols
+        out = np.zeros((self.K, ncols, 2), np.uint64)
+        self.hb._chk(self.hb.lib.hobbit_brakingbase_tensor(self.hb.ctx, self.h, c_sz(col_lo), c_sz(ncols), _hp(out)))
+        return out
+
+    def open(self, x):
+        return self.hb.brakingbase_open(self, x)
+
+    def free(self):
+        if self.h and self.hb.ctx:
+            self.hb.lib.hobbit_brakingbase_free(self.h)
         self.h = None
 
     def __del__(self):
@@ -984,10 +1042,9 @@ class Hobbit:
         self._chk(self.lib.hobbit_parity_commit(self.ctx, c_ll(n), ctypes.byref(h)))
         return ParityCommitment(self, h)
 
-    def open_parity_matrix(self, pc, r1, r2):
-        """prover side of open_parity_matrix(r1, r2, n) for the commitment pc; libc draws on the host in the reference's order"""
-        r1 = Fh(r1).reshape(-1, 2); r2 = Fh(r2).reshape(-1, 2)
-        P, S = pc.P, 2 * pc.n
+    def _parity_buffers(self, P, n):
+        """host buffers behind one hobbit_parity_open_out: (the struct as an array of pointers, what keeps its targets alive)"""
+        S = 2 * n
         Z = lambda *s: np.zeros(s + (2,), np.uint64)  # noqa: E731
 
         def tree(size):
@@ -1003,15 +1060,82 @@ class Hobbit:
         ptrs += [out[p][k].ctypes.data for p in ("p2", "p3", "p4") for k in ("poly", "r", "vr", "fin")]
         out["stage_ms"] = np.zeros(6, np.float64)
         ptrs += [out[k].ctypes.data for k in ("cw_root", "scalars", "partial", "acc_y", "checks")] + [ctypes.addressof(o_p), ctypes.addressof(o_w), out["stage_ms"].ctypes.data]
-        o = (c_vp * len(ptrs))(*ptrs)
-        self._chk(self.lib.hobbit_parity_open(self.ctx, pc.h, _hp(r1), _hp(r2), c_int(r1.shape[0]), o))
-        for name, t in (("t1", t1), ("t2", t2)):
-            lay = int(t["layers"][0])
+        return (c_vp * len(ptrs))(*ptrs), dict(out=out, t1=t1, t2=t2, sp_p=sp_p, sp_w=sp_w, o_p=o_p, o_w=o_w, P=P)
+
+    def _parity_result(self, keep):
+        out, P = keep["out"], keep["P"]
+        for name in ("t1", "t2"):
+            t = keep[name]; lay = int(t["layers"][0])
             out[name] = dict(layers=np.array([lay]), poly=t["poly"], r=t["r"], vr=t["vr"][:lay], fin=t["fin"][:lay], final_r=t["final_r"], out_eval=t["evals"][0],
                              final_eval=t["evals"][1])
         for p in ("p2", "p3", "p4"):
             out[p]["fin"] = out[p]["fin"][0]
-        out["sp_p"] = self._sp_trim(sp_p, 8 * P, 16); out["sp_w"] = self._sp_trim(sp_w, 2 * P, 16)
+        out["sp_p"] = self._sp_trim(keep["sp_p"], 8 * P, 16); out["sp_w"] = self._sp_trim(keep["sp_w"], 2 * P, 16)
+        return out
+
+    def open_parity_matrix(self, pc, r1, r2):
+        """prover side of open_parity_matrix(r1, r2, n) for the commitment pc; libc draws on the host in the reference's order"""
+        r1 = Fh(r1).reshape(-1, 2); r2 = Fh(r2).reshape(-1, 2)
+        o, keep = self._parity_buffers(pc.P, pc.n)
+        self._chk(self.lib.hobbit_parity_open(self.ctx, pc.h, _hp(r1), _hp(r2), c_int(r1.shape[0]), o))
+        return self._parity_result(keep)
+
+    # ---- the Braking base baseline (include/hobbit_brakingbase.h; src/Our_PC.cpp:114-144, 238-256, 355-429)
+    @staticmethod
+    def brakingbase_shape(N, K):
+        """trs = N / K of test_PC(N, 5, K): N, K powers of two, 4 <= K <= 512, 128 <= trs <= 2^20"""
+        lib = load_library()
+        trs = c_sz()
+        if lib.hobbit_brakingbase_shape(c_sz(N), c_sz(K), ctypes.byref(trs)) != 0:
+            raise HobbitError("brakingbase: (N, K) = (%d, %d) is not served: powers of two, 4 <= K <= 512, 128 <= N / K <= 2^20" % (N, K))
+        return trs.value
+
+    def brakingbase_commit(self, poly, K, quirk=1, sync=True):
+        """commit_brakingbase: poly is a host array (N, 2) or (DeviceBuffer/ptr, N); the graphs for n = N / K must be finalized.  Returns a
+        BrakingbaseCommitment; sync=False leaves the work queued on the context's stream."""
+        if isinstance(poly, tuple):
+            ptr, N = poly
+            ptr = ptr.ptr if isinstance(ptr, DeviceBuffer) else int(ptr)
+        else:
+            p = Fh(poly).reshape(-1, 2)
+            N = p.shape[0]
+            keep = self.to_device(p); ptr = keep.ptr
+        h = c_vp()
+        self._chk(self.lib.hobbit_brakingbase_commit(self.ctx, c_vp(ptr), c_sz(N), c_sz(K), c_int(quirk), ctypes.byref(h)))
+        if not h.value:
+            raise HobbitError("hobbit_brakingbase_commit returned no handle")
+        if sync or not isinstance(poly, tuple):
+            self.sync()                         # (a host polynomial's device copy is released when this returns)
+        return BrakingbaseCommitment(self, h)
+
+    def brakingbase_open(self, c, x):
+        """open_brakingbase's prover side: x holds at least log2 K F.  libc draws on the host in the reference's order.  Returns dict(I, reply
+        (2935, K, 2), paths (2935, log2 2 trs, 32), aggr, cc_root, cp_root, p1 (poly, r, vr, fin, r1), parity (as open_parity_matrix), sp_c (as
+        shockwave_prove), checks, ps, stage_ms)"""
+        lk = c.K.bit_length() - 1; l = c.W.bit_length() - 1; Q = BRAKINGBASE_QUERIES
+        x = Fh(x).reshape(-1, 2)[:lk].copy()
+        assert x.shape[0] == lk
+        # the parity buffers are sized by P, the padded list length of the code of n = trs, which the graphs' dimensions decide and those n
+        # alone: a throw-away commit_parity_matrix tells it once per n (it draws nothing from libc)
+        pcn = c.trs
+        if pcn not in _PARITY_P:
+            probe = self.commit_parity_matrix(pcn); _PARITY_P[pcn] = probe.P; probe.free()
+        P = _PARITY_P[pcn]
+        po, keep = self._parity_buffers(P, pcn)
+        sp_c, o_c = self._sp_buffers(2 * c.trs, 32)
+        q, r, vr, fin = self._proof2(l)
+        out = dict(I=np.zeros(Q, np.uint32), reply=np.zeros((Q, c.K, 2), np.uint64), paths=np.zeros((Q, l, 32), np.uint8), aggr=np.zeros((c.trs, 2), np.uint64),
+                   cc_root=np.zeros(32, np.uint8), cp_root=np.zeros(32, np.uint8), ps=np.zeros(1, np.float64), stage_ms=np.zeros(6, np.float64))
+        r1 = np.zeros((l, 2), np.uint64)
+        ptrs = [out[k].ctypes.data for k in ("I", "reply", "paths", "aggr", "cc_root", "cp_root")] + [a.ctypes.data for a in (q, r, vr, fin, r1)]
+        ptrs += [ctypes.addressof(po), ctypes.addressof(o_c), out["ps"].ctypes.data, out["stage_ms"].ctypes.data]
+        o = (c_vp * len(ptrs))(*ptrs)
+        self._chk(self.lib.hobbit_brakingbase_open(self.ctx, c.h, _hp(x), o))
+        out["p1"] = dict(poly=q, r=r, vr=vr, fin=fin, r1=r1)
+        out["parity"] = self._parity_result(keep)
+        out["sp_c"] = self._sp_trim(sp_c, 2 * c.trs, 32)
+        out["checks"] = out["parity"]["checks"]
+        out["ps"] = float(out["ps"][0])
         return out
 
     def prove_linear_code_batch(self, codewords, n, r1, r2):

@@ -3150,19 +3150,19 @@ void hobbit_brakedown_free(hobbit_brakedown *c) {
     if (c->d_levels) hipFree(c->d_levels);
     delete c;
 }
-int hobbit_brakedown_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int left_left_quirk, hobbit_brakedown **out) {
+}  // extern "C"
+// commit_standard_brakedown's body for `rows` messages of B elements (graphs for n = B finalized: the callers check); hobbit_brakedown_commit
+// takes the shape from N, hobbit_brakingbase_commit (hobbit_brakingbase.hip) hands in B = N / K, rows = K
+int hobbit::brakedown_commit_shape(hobbit_ctx *ctx, const F *d_poly, size_t B, uint32_t rows, int left_left_quirk, hobbit_brakedown **out) {
     *out = nullptr;
-    size_t B; uint32_t rows;
-    if (hobbit_brakedown_shape(N, &B, &rows)) return ctx->fail(HOBBIT_EINVAL, "brakedown_commit: N must be 2^n with 16 <= n <= 29");
-    if (ctx->code.n != (long long)B) return ctx->fail(HOBBIT_ESTATE, "brakedown_commit: graphs for n = B are not finalized (expander_init_store(B))");
     HB_TRY(ensure_ilv(ctx));
     const size_t W = 2 * B;
-    hobbit_brakedown *c = new hobbit_brakedown{ctx, N, B, rows, ctx->code.len, left_left_quirk ? 1 : 0, nullptr, nullptr};
+    hobbit_brakedown *c = new hobbit_brakedown{ctx, B * rows, B, rows, ctx->code.len, left_left_quirk ? 1 : 0, nullptr, nullptr};
     if (hipMalloc((void **)&c->d_mat, W * rows * sizeof(F)) != hipSuccess || hipMalloc((void **)&c->d_levels, (2 * W - 1) * 32) != hipSuccess) {
         hobbit_brakedown_free(c); return ctx->fail(HOBBIT_ENOMEM, "brakedown_commit: device allocation failed");
     }
     // row i of the message (poly[i B .. (i + 1) B)) becomes entry i of columns 0 .. B - 1; every row is then encoded in place (tensor[0][i])
-    int r = launch_transpose(ctx, cF(d_poly), 0, rows, (uint32_t)B, c->d_mat, 0, rows, 1);
+    int r = launch_transpose(ctx, d_poly, 0, rows, (uint32_t)B, c->d_mat, 0, rows, 1);
     if (!r) r = launch_encode_ilv(ctx, c->d_mat, c->d_mat, rows);
     // MT_commit_Blake of every column -> level 0 (columns [len, 2B) are zero), then create_tree_blake over the 2B digests
     if (!r) r = launch_brakedown_digests(ctx, c->d_mat, rows, (size_t)c->len, W - (size_t)c->len, c->quirk, c->d_levels);
@@ -3170,6 +3170,14 @@ int hobbit_brakedown_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, i
     if (r) { hobbit_brakedown_free(c); return r; }
     *out = c;
     return 0;
+}
+extern "C" {
+int hobbit_brakedown_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int left_left_quirk, hobbit_brakedown **out) {
+    *out = nullptr;
+    size_t B; uint32_t rows;
+    if (hobbit_brakedown_shape(N, &B, &rows)) return ctx->fail(HOBBIT_EINVAL, "brakedown_commit: N must be 2^n with 16 <= n <= 29");
+    if (ctx->code.n != (long long)B) return ctx->fail(HOBBIT_ESTATE, "brakedown_commit: graphs for n = B are not finalized (expander_init_store(B))");
+    return brakedown_commit_shape(ctx, cF(d_poly), B, rows, left_left_quirk, out);
 }
 int hobbit_brakedown_dims(const hobbit_brakedown *c, size_t *B, uint32_t *rows, long long *len) {
     if (B) *B = c->B;

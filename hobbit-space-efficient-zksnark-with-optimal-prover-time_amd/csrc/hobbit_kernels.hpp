@@ -7,6 +7,8 @@ namespace hobbit {
 int ensure_tiled(hobbit_ctx *ctx);
 int ensure_ilv(hobbit_ctx *ctx);
 int launch_encode_ilv(hobbit_ctx *ctx, const F *src, F *dst, uint32_t rows);
+// the body of hobbit_brakedown_commit for `rows` messages of B elements (hobbit_capi.hip); the caller has checked the shape and the graphs
+int brakedown_commit_shape(hobbit_ctx *ctx, const F *d_poly, size_t B, uint32_t rows, int left_left_quirk, hobbit_brakedown **out);
 int launch_brakedown_digests(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t ncols, size_t nz, int quirk, uint8_t *out);
 int launch_brakedown_aggr(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t B, const F *beta, const F *r, F *aggr_beta, F *aggr_r);
 int launch_brakedown_reply(hobbit_ctx *ctx, const F *mat, uint32_t rows, const uint32_t *d_I, size_t nq, F *reply);

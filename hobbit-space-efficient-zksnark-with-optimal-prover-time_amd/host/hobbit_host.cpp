@@ -18,6 +18,7 @@ graph _C[100], D[100];
 static hobbit_ctx *g_ctx = nullptr;
 static hobbit_commitment *g_commit = nullptr;
 static hobbit_brakedown *g_bd = nullptr;                            // the last commit_standard_brakedown's matrix and tree
+static hobbit_brakingbase *g_bb = nullptr;                          // the last commit_brakingbase's
 static void *g_bds_levels = nullptr;                                // the last commit_brakedown_stream's levels
 static int g_commit_K = 0, g_commit_trs = 0; static size_t g_commit_cols = 0;
 static void *g_poly_dev = nullptr; static size_t g_poly_n = 0;      // device copy of the committed polynomial, kept for open_standard
@@ -73,6 +74,7 @@ void hobbit_host_shutdown() {
     if (g_ctx) free_prev();
     if (g_commit) { hobbit_commitment_free(g_commit); g_commit = nullptr; }
     if (g_bd) { hobbit_brakedown_free(g_bd); g_bd = nullptr; }
+    if (g_bb) { hobbit_brakingbase_free(g_bb); g_bb = nullptr; }
     if (g_parity) { hobbit_parity_commitment_free(g_parity); g_parity = nullptr; }
     if (g_bds_levels) { hobbit_free(g_ctx, g_bds_levels); g_bds_levels = nullptr; }
     if (g_poly_dev) { hobbit_free(g_ctx, g_poly_dev); g_poly_dev = nullptr; g_poly_n = 0; }
@@ -1371,6 +1373,112 @@ void open_brakedown_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>>
     printf("PC Open: pt = %lf, ps = %lf KB, vt = %lf sec\n", pt, ps, vt);
 }
 
+// ---- Braking base baseline (src/Our_PC.cpp:114-144, 238-256, 355-429, 827-842; src/PC_utils.cpp:389-394; include/hobbit_brakingbase.h) --------
+#ifndef HOBBIT_HOST_REFERENCE_BUILD
+static hobbit_host_brakingbase_transcript g_bb_open;
+hobbit_host_brakingbase_transcript &hobbit_host_last_brakingbase() { return g_bb_open; }
+void commit_brakingbase(vector<F> &poly, vector<vector<_hash>> &MT_hashes) {                                     // (:114-144)
+    BUFFER_SPACE = tensor_row_size;
+    const size_t N = poly.size(), trs = (size_t)tensor_row_size, K = N / trs;
+    printf("%d,%d\n", (int)BUFFER_SPACE, (int)K);
+    if (g_bb) { hobbit_brakingbase_free(g_bb); g_bb = nullptr; }
+    DevBuf d(poly.data(), N * sizeof(F));
+    HCHK(hobbit_brakingbase_commit(hobbit_host_ctx(), (const hobbit_F *)d.p, N, K, 1, &g_bb));
+    // MT_hashes: level 0 = the 2 trs column digests (MT_commit_Blake of every column), then create_tree_blake (:127-143)
+    const size_t W = 2 * trs, levels = (size_t)log2((double)W) + 1;
+    vector<_hash> flat(2 * W - 1);
+    HCHK(hobbit_brakingbase_levels(g_ctx, g_bb, flat.data()->arr));
+    MT_hashes.assign(levels, vector<_hash>());
+    for (size_t l = 0, off = 0, sz = W; l < levels; l++, off += sz, sz /= 2) MT_hashes[l].assign(flat.begin() + off, flat.begin() + off + sz);
+}
+void _aggregate_brakingbase(vector<F> &poly, vector<F> beta1, vector<F> random_points, vector<F> &codeword) {    // (:238-256)
+    (void)random_points;                                             // the reference never reads it either
+    const size_t trs = (size_t)tensor_row_size;
+    vector<F> aggregated_vector;
+    _aggregate_axpy(poly, beta1, aggregated_vector, (int)(poly.size() / trs));
+    codeword.assign(2 * trs, F(0));
+    encode_monolithic(aggregated_vector.data(), codeword.data(), (long long)trs);
+    C_c = shockwave_commit(codeword, 32);
+}
+void recursive_prover_brakingbase(vector<F> &codeword, vector<size_t> I, double &vt, double &ps) {              // src/PC_utils.cpp:389-394
+    (void)I;
+    const int n = (int)(codeword.size() / 2);
+    commit_parity_matrix(n);
+    proof P1 = prove_linear_code(codeword, n, vt, ps);
+    open_parity_matrix(P1.randomness[0], P1.randomness[1], n, vt, ps);
+    shockwave_prove(C_c, P1.randomness[0], vt, ps);
+    C_c = nullptr;                                                   // shockwave_prove deleted it (src/Virgo.cpp:515)
+}
+void open_brakingbase(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_hashes) {                          // (:355-429)
+    (void)MT_hashes;
+    if (!g_bb) { printf("Error: open_brakingbase without commit_brakingbase\n"); exit(-1); }
+    size_t N = 0, K = 0, trs = 0;
+    hobbit_brakingbase_dims(g_bb, &N, &K, &trs, nullptr);
+    if (poly.size() != N || (size_t)tensor_row_size != trs) { printf("Error: open_brakingbase on a polynomial of another shape\n"); exit(-1); }
+    BUFFER_SPACE = tensor_row_size; aggregation_queries = HOBBIT_BRAKINGBASE_QUERIES;
+    const size_t S = 2 * trs, Q = HOBBIT_BRAKINGBASE_QUERIES; const int lk = (int)log2((double)K), l = (int)log2((double)S);
+    if ((int)x.size() < lk) { printf("Error: open_brakingbase needs log2(K) coordinates\n"); exit(-1); }
+    // the parity transcript's buffers are sized by P, which the list length of the code decides: a throw-away commitment tells it (no draws)
+    size_t P = 0;
+    { hobbit_parity_commitment *pc = nullptr; HCHK(hobbit_parity_commit(hobbit_host_ctx(), (long long)trs, &pc)); hobbit_parity_dims(pc, nullptr, nullptr, &P, nullptr); hobbit_parity_commitment_free(pc); }
+    const int L = (int)log2((double)P);
+    hobbit_host_brakingbase_transcript &t = g_bb_open;
+    hobbit_host_parity_transcript &pt = hobbit_host_last_parity_open(); pt.n = (int)trs; pt.P = P;
+    auto tree = [](hobbit_host_parity_transcript::tree &T, size_t size) {
+        const int lt = (int)log2((double)(4 * size)), depth = lt - 2; size_t nr = 1; for (int i = 0; i < lt; i++) nr += (size_t)i;
+        T.cpoly.assign(4 * nr, F(0)); T.r.assign(nr, F(0)); T.vr.assign(3 * (size_t)depth, F(0)); T.fin.assign(depth, F(0)); T.final_r.assign(lt, F(0)); T.layers = 0;
+    };
+    tree(pt.t1, P); tree(pt.t2, S);
+    pt.p2.assign(4 * (size_t)L, F(0)); pt.p2_r.assign(L, F(0)); pt.p3.assign(3 * (size_t)(L + 1), F(0)); pt.p3_r.assign(L + 1, F(0)); pt.p4.assign(3 * (size_t)(L + 3), F(0)); pt.p4_r.assign(L + 3, F(0));
+    SpBuffers bp(pt.sp_p, 8 * P, 16), bw(pt.sp_w, 2 * P, 16), bc(t.sp_c, S, 32);
+    hobbit_parity_open_out po = {hF(pt.t1.cpoly.data()), hF(pt.t1.r.data()), hF(pt.t1.vr.data()), hF(pt.t1.fin.data()), hF(pt.t1.final_r.data()), hF(pt.t1.evals), &pt.t1.layers,
+                                 hF(pt.t2.cpoly.data()), hF(pt.t2.r.data()), hF(pt.t2.vr.data()), hF(pt.t2.fin.data()), hF(pt.t2.final_r.data()), hF(pt.t2.evals), &pt.t2.layers,
+                                 hF(pt.p2.data()), hF(pt.p2_r.data()), hF(pt.p2_vr), hF(&pt.p2_fin), hF(pt.p3.data()), hF(pt.p3_r.data()), hF(pt.p3_vr), hF(&pt.p3_fin),
+                                 hF(pt.p4.data()), hF(pt.p4_r.data()), hF(pt.p4_vr), hF(&pt.p4_fin), pt.cw_root, hF(pt.scalars), hF(pt.partial), hF(pt.acc_y), pt.checks, &bp.o, &bw.o,
+                                 nullptr};
+    t.I.assign(Q, 0); t.reply.assign(Q * K, F(0)); t.paths.assign(Q * (size_t)l * 32, 0); t.aggr.assign(trs, F(0));
+    t.p1_q.assign(3 * (size_t)l, F(0)); t.p1_r.assign(l, F(0)); t.p1_r1.assign(l, F(0));
+    hobbit_brakingbase_open_out o = {t.I.data(), hF(t.reply.data()), t.paths.data(), hF(t.aggr.data()), t.cc_root, t.cp_root, hF(t.p1_q.data()), hF(t.p1_r.data()), hF(t.p1_vr),
+                                     hF(&t.p1_fin), hF(t.p1_r1.data()), &po, &bc.o, &t.ps, t.stage_ms};
+    vector<F> xs(x.begin(), x.begin() + lk);
+    HCHK(hobbit_brakingbase_open(g_ctx, g_bb, hF(xs.data()), &o));
+    if (t.p1_q[0] + t.p1_q[1] + t.p1_q[2] + t.p1_q[2] != F(0)) printf("Error in codeword\n");                   // q(0) + q(1) of P1's first round (src/sumcheck.cpp:3231)
+    if (!pt.checks[0]) { printf("Error 1\n"); exit(-1); }
+    if (!pt.checks[1]) { printf("Error 2\n"); exit(-1); }
+    for (auto *sp : {&pt.sp_p, &pt.sp_w, &t.sp_c}) if (sp->iters && !(sp->wchecks[0] && sp->wchecks[1])) { printf("Error in final verification step\n"); exit(-1); }
+    // (:403-427) the reference re-hashes the replies and sums them against beta (its loop bounds read past both), then verify_claim_opt_blake:
+    // only the accounting is kept, inside the library's ps; vt is what remains of the verifier here
+    t.vt = 0.0;
+    printf("Ps : %lf, Vt : %lf \n", t.ps, t.vt);
+}
+void test_brakingbase(size_t N, int K) {                                                                         // (:757-761, 827-842)
+    size_t trs = 0;
+    if (K <= 0 || hobbit_brakingbase_shape(N, (size_t)K, &trs) != 0) {
+        if (K >= 4 && K <= 512 && (K & (K - 1)) == 0 && N / (size_t)K > ((size_t)1 << 20))
+            printf("Error: Braking base at N / K = %zu needs a code longer than 2^20, which the code proof and the parity opening do not build\n", N / (size_t)K);
+        else printf("Error: Braking base takes N, K powers of two with 4 <= K <= 512 and 128 <= N / K <= 2^20\n");
+        exit(-1);
+    }
+    vector<F> poly = generate_randomness((int)N);
+    vector<vector<_hash>> MT_hashes;
+    tensor_row_size = (int)trs;
+    expander_init_store(tensor_row_size);
+    auto start = std::chrono::steady_clock::now();
+    commit_brakingbase(poly, MT_hashes);
+    auto end = std::chrono::steady_clock::now();
+    double elapsed_seconds = std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    std::cout << "Commit time: " << elapsed_seconds << " seconds" << std::endl;
+    printf("root ");
+    for (int i = 0; i < 32; i++) printf("%02x", MT_hashes.back()[0].arr[i]);
+    printf("\n");
+    start = std::chrono::steady_clock::now();
+    open_brakingbase(poly, generate_randomness((int)log2((double)poly.size())), MT_hashes);
+    end = std::chrono::steady_clock::now();
+    elapsed_seconds += std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    std::cout << "Total time: " << elapsed_seconds << " seconds" << std::endl;
+}
+#endif
+
 // ---- streaming Brakedown baseline (src/Elastic_PC.cpp:112-172, 287-313, 561-623) ------------------
 // The stream is read on the host, chunk by chunk, with the descriptor by value as in the reference (three passes: commit, aggregate, reply);
 // the device keeps one group of four chunks.  The commitment's levels also stay on the device for the paths of the opening.
@@ -1857,5 +1965,41 @@ int hobbit_host_parity_open(int n, unsigned seed, uint8_t *roots, uint64_t *poly
     *ps_out = ps;
     return (int)t.p4_r.size();
 }
+#ifndef HOBBIT_HOST_REFERENCE_BUILD
+// test_PC(N, 5, K)'s flow on the stream of a fresh process (srandom(1), polynomial, graphs, commit, x), the opening either as open_brakingbase
+// (by_steps == 0: one hobbit_brakingbase_open) or as the reference sequences it from _aggregate_brakingbase and recursive_prover_brakingbase
+// over host vectors (by_steps != 0: src/Our_PC.cpp:368-401, 417-424).  roots: the commitment's, C_c's.  Returns the number of queries.
+int hobbit_host_brakingbase(size_t N, int K, int by_steps, uint8_t *roots, double *ps_out) {
+    size_t trs = 0;
+    if (K <= 0 || hobbit_brakingbase_shape(N, (size_t)K, &trs) != 0) return -1;
+    srandom(1);
+    vector<F> poly = generate_randomness((int)N);
+    vector<vector<_hash>> MT_hashes;
+    tensor_row_size = (int)trs;
+    expander_init_store(tensor_row_size);
+    commit_brakingbase(poly, MT_hashes);
+    memcpy(roots, MT_hashes.back()[0].arr, 32);
+    vector<F> x = generate_randomness((int)log2((double)N));
+    if (!by_steps) {
+        open_brakingbase(poly, x, MT_hashes);
+        memcpy(roots + 32, g_bb_open.cc_root, 32); *ps_out = g_bb_open.ps;
+        return (int)g_bb_open.I.size();
+    }
+    double vt = 0.0, ps = 0.0;
+    const int queries = HOBBIT_BRAKINGBASE_QUERIES;
+    vector<F> x1(x.begin(), x.begin() + (int)log2((double)K)), beta, codeword;
+    precompute_beta(x1, beta);
+    vector<F> r_v(beta.size()); r_v[0] = generate_randomness(1)[0];
+    _aggregate_brakingbase(poly, beta, r_v, codeword);
+    memcpy(roots + 32, C_c->MT.back()[0].arr, 32);
+    vector<size_t> I(queries);
+    for (int i = 0; i < queries; i++) I[i] = (size_t)(rand() % (int)(2 * trs));
+    ps += (double)((size_t)K * queries * sizeof(F)) / 1024.0;
+    recursive_prover_brakingbase(codeword, I, vt, ps);
+    path_ps(2 * trs, (int)log2((double)(2 * trs)), I, ps);
+    *ps_out = ps;
+    return queries;
+}
+#endif
 void hobbit_host_close(void) { hobbit_host_shutdown(); }
 }

@@ -16,6 +16,7 @@
 #include "hobbit_hip.h"
 #include "hobbit_parity.h"
 #include "hobbit_whir.h"
+#include "hobbit_brakingbase.h"
 
 using std::vector;
 
@@ -251,6 +252,28 @@ struct hobbit_host_whir_transcript {
 };
 hobbit_host_whir_transcript &hobbit_host_last_whir();
 void test_whir(size_t N);                                                 /* test_PC's last branch; `host/test_pc whir <logN>` */
+#endif
+/* src/Our_PC.cpp:114-144, 238-256, 355-429, 827-842 ; src/PC_utils.cpp:389-394: the Braking base comparison baseline (test_PC option 5), on the
+ * device through include/hobbit_brakingbase.h.  tensor_row_size is the row length (N / K) and expander_init_store(tensor_row_size) has run, as
+ * in the reference's driver.  commit_brakingbase prints the reference's "%d,%d" line and keeps the encoded matrix on the device;
+ * open_brakingbase is one hobbit_brakingbase_open (libc draws in the reference's order), exits on the reference's checks and prints its
+ * "Ps : .., Vt : .." line; the verifier emulation behind it is reduced to its proof-size accounting.  _aggregate_brakingbase and
+ * recursive_prover_brakingbase are the reference's two steps over this mirror's own entry points (host vectors in, C_c set / consumed).
+ * test_PC itself keeps refusing option 5: the driver is test_brakingbase, reached as `host/test_pc brakingbase <logN> <K>`; a shape the
+ * library does not serve prints an error and exits with -1 before anything is drawn.
+ * Left out of the build that sits in front of the reference's objects, which has the reference's own. */
+#ifndef HOBBIT_HOST_REFERENCE_BUILD
+void commit_brakingbase(vector<F> &poly, vector<vector<_hash>> &MT_hashes);
+void _aggregate_brakingbase(vector<F> &poly, vector<F> beta1, vector<F> random_points, vector<F> &codeword);
+void open_brakingbase(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_hashes);
+void recursive_prover_brakingbase(vector<F> &codeword, vector<size_t> I, double &vt, double &ps);
+/* the messages of the last open_brakingbase (the reference returns none); layouts as hobbit_brakingbase_open_out */
+struct hobbit_host_brakingbase_transcript {
+    vector<uint32_t> I; vector<F> reply, aggr, p1_q, p1_r, p1_r1; F p1_vr[2], p1_fin; vector<uint8_t> paths; uint8_t cc_root[32], cp_root[32];
+    hobbit_host_shockwave_transcript sp_c; double stage_ms[6] = {0, 0, 0, 0, 0, 0}, ps = 0, vt = 0;
+};
+hobbit_host_brakingbase_transcript &hobbit_host_last_brakingbase();       /* the parity part: hobbit_host_last_parity_open() */
+void test_brakingbase(size_t N, int K);
 #endif
 /* src/PC_utils.cpp:6-7 ; src/linear_code_encode.cpp:3-4 ; src/sumcheck.cpp:27,29 : globals of the reference ABI.  C_f / C_c are set by
  * this mirror's shockwave users as the reference's _aggregate / aggregate do; scratch / __encode_initialized exist for source

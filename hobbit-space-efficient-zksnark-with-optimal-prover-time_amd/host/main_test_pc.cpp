@@ -1,7 +1,8 @@
 // main_test_pc.cpp -- the reference's commented-out CLI hook `./pigeon <logN> <option> <K>` (option 4: RS x expander, option 1: RS x RS,
 // option 3: the Brakedown baseline, K unused) and `elastic <logN> <logB> <opt>` (Elastic_PC options 1 and 2; option 3: the streaming
 // Brakedown baseline, which sets its own buffer size, so <logB> is ignored there as in the reference) and `whir <logN>` (the standalone WHIR
-// baseline: test_PC's last branch, which test_PC itself keeps refusing)
+// baseline: test_PC's last branch, which test_PC itself keeps refusing) and `brakingbase <logN> <K>` (the Braking base baseline: test_PC's
+// option 5, which test_PC itself keeps refusing; shapes outside 4 <= K <= 512, 128 <= N / K <= 2^20 print an error and return 255)
 // (src/main.cpp:1176: test_PC(1ULL<<atoi(argv[1]), atoi(argv[2]), atoi(argv[3]))) over the
 // device-backed host mirror.  Build: see __graft_entry__.build_host().
 #include <cstdio>
@@ -10,8 +11,17 @@
 #include "hobbit_host.hpp"
 int main(int argc, char **argv) {
     const bool whir = argc == 3 && std::string(argv[1]) == "whir";
-    if (argc < 4 && !whir) { printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>\n", argv[0], argv[0], argv[0]); return 1; }
+    const bool bbase = argc == 4 && std::string(argv[1]) == "brakingbase";
+    if (argc < 4 && !whir) {
+        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>\n", argv[0], argv[0], argv[0], argv[0]);
+        return 1;
+    }
     init_hash();
+    if (bbase) {                                      // src/Our_PC.cpp:827-842
+        const int logn = atoi(argv[2]);
+        if (logn < 1 || logn > 40) { printf("Error: Braking base takes N, K powers of two with 4 <= K <= 512 and 128 <= N / K <= 2^20\n"); return 255; }
+        test_brakingbase(1ULL << logn, atoi(argv[3]));
+    } else
     if (whir) {                                       // src/Our_PC.cpp:843-859
         const int logn = atoi(argv[2]);
         if (logn < 9 || logn > 26) { printf("Error: the standalone WHIR baseline takes 9 <= logN <= 26\n"); return 255; }

@@ -100,6 +100,82 @@ def whir_entry(logs=(20, 22, 24, 26), reps=5, bare=False):
             b.free()
     return res
 
+# BB  the Braking base baseline (include/hobbit_brakingbase.h; test_PC option 5) at (log2 N, K) = (26, 64), (26, 128), (28, 256): commit
+#     between device events and the host-returning open by wall time with its six stage times (median of `reps` after one warm-up), and in
+#     the same process hobbit_brakedown_commit + _open and Our_PC's commit_standard + open_standard at the same N.  The commit runs
+#     Brakedown's kernels at another shape: its per-launch times (the library's event brackets, one extra step) stand next to Brakedown's.
+#     Stage 0 encodes ONE codeword of n = trs: the rows-innermost encode at rows = 1 (what the opening uses) against hobbit_encode_batch at
+#     batch 1 on the same message.  `python scripts/bench_configs.py brakingbase [logN:K ...]` runs this entry alone.
+def brakingbase_entry(shapes=((26, 64), (26, 128), (28, 256)), reps=3):
+    import ctypes
+    res = {}
+    med = lambda v: float(np.median(v))
+    def ev(fn):
+        hb.timer_begin(); r = fn(); return r, hb.timer_end_ms()
+    def wall(fn):
+        hb.sync(); t0 = time.perf_counter(); r = fn(); return r, 1e3 * (time.perf_counter() - t0)
+    def prof(fn):
+        hb.profile(True); hb.profile_reset(); fn(); rep = hb.profile_report(); hb.profile(False); hb.profile_reset()
+        return {k: dict(ms=round(v[0], 3), launches=int(v[1])) for k, v in sorted(rep.items(), key=lambda kv: -kv[1][0])}
+    for logN, K in shapes:
+        N = 1 << logN; trs = mod.Hobbit.brakingbase_shape(N, K)
+        d = hb.fill_splitmix(N, 1000); x = splitmix_field(logN, 8)
+        e = dict(N=N, K=K, trs=trs)
+        # ---- Braking base
+        hb.rng_reset(); t0 = time.perf_counter(); hb.expander_init_store(trs); e["graphs_host_draw_s"] = time.perf_counter() - t0
+        c = hb.brakingbase_commit((d, N), K); g = c.open(x); assert g["checks"].tolist() == [1, 1]; c.free()          # warm: plans, workspaces, tables
+        tc, to, st = [], [], []
+        for _ in range(reps):
+            c, t = ev(lambda: hb.brakingbase_commit((d, N), K)); tc.append(t)
+            g, t = wall(lambda: c.open(x)); to.append(t); st.append(g["stage_ms"].tolist())
+            assert g["checks"].tolist() == [1, 1]
+            root = bytes(c.root()).hex(); c.free()
+        e["brakingbase"] = dict(commit_ms=med(tc), open_ms=med(to), commit_runs=tc, open_runs=to, root=root, ps_KB=g["ps"],
+                                stage_ms=dict(zip(("aggregate_encode_Cc", "replies_paths", "commit_parity_matrix", "prove_linear_code", "open_parity_matrix", "shockwave_prove_Cc"),
+                                                  np.median(np.array(st), axis=0).tolist())))
+        e["brakingbase"]["commit_kernels"] = prof(lambda: hb.brakingbase_commit((d, N), K).free())
+        src1, dst1 = hb.fill_splitmix(trs, 5), hb.alloc(32 * trs)
+        one = dict(interleaved_rows1=lambda: hb._chk(hb.lib.hobbit_encode_interleaved(hb.ctx, ctypes.c_void_p(src1.ptr), ctypes.c_void_p(dst1.ptr), ctypes.c_longlong(trs), ctypes.c_uint32(1))),
+                   encode_batch_1=lambda: hb._chk(hb.lib.hobbit_encode_batch(hb.ctx, ctypes.c_void_p(src1.ptr), ctypes.c_void_p(dst1.ptr), ctypes.c_longlong(trs), ctypes.c_size_t(1),
+                                                                             ctypes.c_size_t(trs), ctypes.c_size_t(2 * trs))))
+        e["encode_one_codeword_ms"] = {}
+        for name, fn in one.items():
+            try:
+                fn(); hb.sync()
+                e["encode_one_codeword_ms"][name] = med([ev(fn)[1] for _ in range(5)])
+            except mod.HobbitError as err:
+                e["encode_one_codeword_ms"][name] = "refused: %s" % err
+        src1.free(); dst1.free()
+        # ---- Brakedown at the same N
+        B, rows = mod.Hobbit.brakedown_shape(N)
+        hb.rng_reset(); hb.expander_init_store(B)
+        rng = np.random.default_rng(logN)
+        r = np.zeros((rows, 2), np.uint64); r[:, 0] = rng.integers(0, 1 << 31, rows); I = rng.integers(0, 2 * B, 2900).astype(np.uint64)
+        c = hb.brakedown_commit((d, N)); hb.brakedown_open(c, x, r, I); c.free()
+        tc, to = [], []
+        for _ in range(reps):
+            c, t = ev(lambda: hb.brakedown_commit((d, N))); tc.append(t)
+            _, t = wall(lambda: hb.brakedown_open(c, x, r, I)); to.append(t); c.free()
+        e["brakedown"] = dict(B=B, rows=rows, commit_ms=med(tc), open_ms=med(to), commit_runs=tc, open_runs=to)
+        e["brakedown"]["commit_kernels"] = prof(lambda: hb.brakedown_commit((d, N)).free())
+        e["commit_time_per_encoded_element_over_brakedowns"] = e["brakingbase"]["commit_ms"] / e["brakedown"]["commit_ms"]        # 2 N elements both
+        # ---- Our_PC at the same N (bench.py's shape: K = 32, trs = N / (K 2^11), 5900 queries)
+        Kh = 32; th = N // (Kh << 11)
+        hb.rng_reset(); hb.expander_init_store(th)
+        c = hb.commit_standard((d, N), Kh, th, 1); hb.open_standard((d, N), c, x, 5900, want_paths=False); c.free()
+        tc, to = [], []
+        for _ in range(reps):
+            c, t = ev(lambda: hb.commit_standard((d, N), Kh, th, 1)); tc.append(t)
+            _, t = wall(lambda: hb.open_standard((d, N), c, x, 5900, want_paths=False)); to.append(t); c.free()
+        e["our_pc"] = dict(K=Kh, trs=th, commit_ms=med(tc), open_ms=med(to), commit_runs=tc, open_runs=to)
+        res["BB_2e%d_K%d" % (logN, K)] = e
+        d.free()
+    return res
+
+if len(sys.argv) > 1 and sys.argv[1] == "brakingbase":
+    print(json.dumps(brakingbase_entry(tuple(tuple(int(v) for v in a.split(":")) for a in sys.argv[2:]) or ((26, 64), (26, 128), (28, 256)))))
+    hb.close(); sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] in ("whir", "whir-bare"):
     print(json.dumps(whir_entry(tuple(int(a) for a in sys.argv[2:]) or (20, 22, 24, 26), bare=sys.argv[1] == "whir-bare")))
     hb.close(); sys.exit(0)
@@ -216,5 +292,6 @@ for logN in (26, 30):
     del lvd
 out.update(parity_entry())
 out.update(whir_entry())
+out.update(brakingbase_entry())
 print(json.dumps(out))
 hb.close()
