@@ -65,6 +65,9 @@ PARITY_SYMBOLS = [
     "hobbit_parity_lists", "hobbit_parity_open", "hobbit_prove_linear_code_batch",
 ]
 
+# every symbol include/hobbit_parity_lists.h declares (checked by tests/test_parity_lists_device.py)
+PARITY_LISTS_SYMBOLS = ["hobbit_parity_commit_device", "hobbit_parity_shape"]
+
 # every symbol include/hobbit_whir.h declares (checked by tests/test_whir_long.py)
 WHIR_SYMBOLS = ["hobbit_whir_ood", "hobbit_whir_prove_any"]
 
@@ -74,7 +77,6 @@ BRAKINGBASE_SYMBOLS = [
     "hobbit_brakingbase_levels_dev", "hobbit_brakingbase_levels", "hobbit_brakingbase_root", "hobbit_brakingbase_tensor", "hobbit_brakingbase_open",
 ]
 BRAKINGBASE_QUERIES = 2935
-_PARITY_P = {}          # n -> P of hobbit_parity_commit (Hobbit.brakingbase_open)
 
 
 class _OpenOut(ctypes.Structure):
@@ -166,6 +168,8 @@ def load_library(path=LIB_PATH):
         "hobbit_parity_commit": [V, L, V], "hobbit_parity_commitment_free": [V], "hobbit_parity_dims": [V, V, V, V, V], "hobbit_parity_dev": [V, I],
         "hobbit_parity_root": [V, V, V], "hobbit_parity_levels": [V, V, V], "hobbit_parity_lists": [V, V, V, V, V, V, V, V, V],
         "hobbit_parity_open": [V, V, V, V, I, V], "hobbit_prove_linear_code_batch": [V, V, S, S, S, L, V, V, V, V, V, V],
+        # include/hobbit_parity_lists.h
+        "hobbit_parity_commit_device": [V, L, V], "hobbit_parity_shape": [V, L, V, V],
         # include/hobbit_whir.h
         "hobbit_whir_ood": [V, V, V, I, V, V, I, V], "hobbit_whir_prove_any": [V, V, S, V, V, V, V],
         # include/hobbit_brakingbase.h
@@ -360,7 +364,7 @@ class BrakingbaseCommitment:
 
 
 class ParityCommitment:
-    """Handle on a device-resident commitment to the code's parity matrix (hobbit_parity_commit): the access lists and C_p."""
+    """Handle on a device-resident commitment to the code's parity matrix (hobbit_parity_commit / hobbit_parity_commit_device): the access lists and C_p."""
 
     def __init__(self, hb, handle):
         self.hb, self.h = hb, handle
@@ -1042,6 +1046,18 @@ class Hobbit:
         self._chk(self.lib.hobbit_parity_commit(self.ctx, c_ll(n), ctypes.byref(h)))
         return ParityCommitment(self, h)
 
+    # the same commitment with the access lists built by kernels (include/hobbit_parity_lists.h)
+    def commit_parity_matrix_device(self, n):
+        h = c_vp()
+        self._chk(self.lib.hobbit_parity_commit_device(self.ctx, c_ll(n), ctypes.byref(h)))
+        return ParityCommitment(self, h)
+
+    def parity_shape(self, n):
+        """(m, P) of the parity commitment of the code finalized for n: host only, nothing allocated, launched or drawn"""
+        m, P = c_sz(), c_sz()
+        self._chk(self.lib.hobbit_parity_shape(self.ctx, c_ll(n), ctypes.byref(m), ctypes.byref(P)))
+        return m.value, P.value
+
     def _parity_buffers(self, P, n):
         """host buffers behind one hobbit_parity_open_out: (the struct as an array of pointers, what keeps its targets alive)"""
         S = 2 * n
@@ -1116,11 +1132,9 @@ class Hobbit:
         x = Fh(x).reshape(-1, 2)[:lk].copy()
         assert x.shape[0] == lk
         # the parity buffers are sized by P, the padded list length of the code of n = trs, which the graphs' dimensions decide and those n
-        # alone: a throw-away commit_parity_matrix tells it once per n (it draws nothing from libc)
+        # alone: hobbit_parity_shape tells it on the host
         pcn = c.trs
-        if pcn not in _PARITY_P:
-            probe = self.commit_parity_matrix(pcn); _PARITY_P[pcn] = probe.P; probe.free()
-        P = _PARITY_P[pcn]
+        P = self.parity_shape(pcn)[1]
         po, keep = self._parity_buffers(P, pcn)
         sp_c, o_c = self._sp_buffers(2 * c.trs, 32)
         q, r, vr, fin = self._proof2(l)

@@ -7,6 +7,7 @@
 #include <vector>
 #include "hobbit_kernels.hpp"
 #include "../../include/hobbit_brakingbase.h"
+#include "../../include/hobbit_parity_lists.h"
 
 using namespace hobbit;
 
@@ -192,7 +193,7 @@ int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const 
     HB_TRY(stage(1));
 
     // ---- recursive_prover_brakingbase (src/PC_utils.cpp:389-394) ----------------------------------------------------------------------------------
-    HB_TRY(hobbit_parity_commit(ctx, (long long)trs, &sc.pc));
+    HB_TRY(hobbit_parity_commit_device(ctx, (long long)trs, &sc.pc));
     if (o->cp_root) HB_TRY(hobbit_parity_root(ctx, sc.pc, o->cp_root));
     HB_TRY(stage(2));
 

@@ -171,6 +171,7 @@ static void free_code(DeviceCode &c) {
     if (c.d_pm_w) hipFree(c.d_pm_w);
     for (void *q : {(void *)c.d_tile_ptr, (void *)c.d_tile_width, (void *)c.d_tile_out, (void *)c.d_tile_e32, (void *)c.d_tile_eidx, (void *)c.d_tile_ew}) if (q) hipFree(q);
     for (void *q : {(void *)c.d_ilv_ptr, (void *)c.d_ilv_e32, (void *)c.d_ilv_eidx, (void *)c.d_ilv_ew}) if (q) hipFree(q);
+    for (void *q : {(void *)c.d_fwd_segs, (void *)c.d_fwd_nbr, (void *)c.d_fwd_w32, (void *)c.d_fwd_w}) if (q) hipFree(q);
     c = DeviceCode();
 }
 
@@ -359,6 +360,7 @@ void hobbit_ctx_destroy(hobbit_ctx *ctx) {
     if (ctx->ws5) hipFree(ctx->ws5);
     if (ctx->spare_tensor) hipFree(ctx->spare_tensor);
     if (ctx->spare_levels) hipFree(ctx->spare_levels);
+    ctx->spare_parity_release();
     hipEventDestroy(ctx->t0); hipEventDestroy(ctx->t1);
     if (ctx->up_stream) {
         hipStreamSynchronize(ctx->up_stream);
@@ -741,6 +743,67 @@ int ensure_ilv(hobbit_ctx *ctx) {
     if (c.small_weights) HB_TRY(upload(ctx, &c.d_ilv_e32, e32));
     else { HB_TRY(upload(ctx, &c.d_ilv_eidx, eidx)); HB_TRY(upload(ctx, &c.d_ilv_ew, ew)); }
     c.ilv_built = true;
+    return 0;
+}
+// The segment table of the parity matrix' access lists (hobbit_ctx.hpp ParitySeg) from the finalized plan: the recursion of
+// generate_access_idx (src/sumcheck.cpp:2622-2669) unrolled -- C-edges(d), C-identity(d) for d = 0 .. D-1, then D-edges(d), D-identity(d) for
+// d = D-1 .. 0.  Depth d adds lvl_d = R_C(0) + .. + R_C(d-1) to every idx1 of its four segments (the reference's *lvl of depth d: the
+// `+= R` at the end of a call reaches no list entry) and starts its idx2 at the plan's offsets.  Host only; *m: the entry count.
+int parity_segments(hobbit_ctx *ctx, std::vector<ParitySeg> &segs, size_t *m) {
+    const DeviceCode &c = ctx->code;
+    if (c.graph_gen != ctx->graph_gen) return ctx->fail(HOBBIT_ESTATE, "parity_commit: the graphs changed after hobbit_graph_finalize");
+    const size_t D = c.plan.size() / 2;
+    std::vector<long long> lvl(D + 1, 0);
+    for (size_t d = 0; d < D; d++) lvl[d + 1] = lvl[d] + c.plan[d].g->R;
+    size_t base = 0, src = 0;
+    bool fits = true;
+    segs.clear();
+    auto put = [&](const PlanStep &p, size_t d) {
+        const HostGraph &g = *p.g;
+        const size_t E = (size_t)g.L * (size_t)g.degree;
+        fits = fits && base + E + (size_t)g.R < ((size_t)1 << 31) && lvl[d] < (1LL << 31) && p.out_off < (1LL << 31);
+        segs.push_back({(uint32_t)base, (uint32_t)E, (uint32_t)g.degree, (uint32_t)lvl[d], (uint32_t)p.in_off, 0u, (uint32_t)src, (uint32_t)g.L});
+        base += E; src += E;
+        segs.push_back({(uint32_t)base, (uint32_t)g.R, 1u, (uint32_t)lvl[d], (uint32_t)p.out_off, 1u, 0u, (uint32_t)g.R});
+        base += (size_t)g.R;
+    };
+    for (size_t d = 0; d < D; d++) put(c.plan[d], d);
+    for (size_t d = D; d-- > 0;) put(c.plan[2 * D - 1 - d], d);
+    if (!fits) return ctx->fail(HOBBIT_EINVAL, "parity_commit: list length outside the public witness' 8P layout");
+    *m = base;
+    return 0;
+}
+// The forward form behind hobbit_parity_commit_device, built by the first such commit of the finalized code: every level's neighbours (u32) and
+// weights (u32 under small_weights, else F) in list order, and the segment table.  The index ranges are checked here from the table, in
+// O(levels): hobbit_graph_upload bounds every neighbour by R.
+int ensure_fwd(hobbit_ctx *ctx) {
+    DeviceCode &c = ctx->code;
+    if (c.fwd_built) return 0;
+    std::vector<ParitySeg> segs; size_t m = 0;
+    HB_TRY(parity_segments(ctx, segs, &m));
+    const size_t S = 2 * (size_t)c.n;
+    for (size_t s = 0; s < segs.size(); s += 2) {
+        const size_t R = segs[s + 1].count;                     // the level's R: bound of its neighbours, length of its identity run
+        if (segs[s].lvl + R > S || (size_t)segs[s].off + segs[s].cells > S || (size_t)segs[s + 1].off + R > S)
+            return ctx->fail(HOBBIT_EINVAL, "parity_commit: list index beyond the 2n cells");
+    }
+    size_t total = 0;
+    for (const PlanStep &p : c.plan) total += (size_t)p.g->L * (size_t)p.g->degree;
+    std::vector<uint32_t> nbr(total), w32; std::vector<F> w;
+    if (c.small_weights) w32.resize(total); else w.resize(total);
+    size_t at = 0;
+    for (const PlanStep &p : c.plan) {
+        const HostGraph &g = *p.g;
+        const size_t E = (size_t)g.L * (size_t)g.degree;
+        for (size_t e = 0; e < E; e++) nbr[at + e] = (uint32_t)g.nbr[e];
+        if (c.small_weights) for (size_t e = 0; e < E; e++) w32[at + e] = (uint32_t)g.w[e].re;
+        else for (size_t e = 0; e < E; e++) w[at + e] = g.w[e];
+        at += E;
+    }
+    HB_TRY(upload(ctx, &c.d_fwd_segs, segs));
+    HB_TRY(upload(ctx, &c.d_fwd_nbr, nbr));
+    if (c.small_weights) HB_TRY(upload(ctx, &c.d_fwd_w32, w32)); else HB_TRY(upload(ctx, &c.d_fwd_w, w));
+    c.fwd_segs = segs; c.fwd_m = m; c.fwd_built = true;
     return 0;
 }
 }  // namespace hobbit

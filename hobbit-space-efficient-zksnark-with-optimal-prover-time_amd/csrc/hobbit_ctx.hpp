@@ -108,6 +108,12 @@ struct IlvStep { uint32_t in_off, out_off, out_len, ptr_base; };
 
 struct PlanStep { const HostGraph *g; long long in_off, out_off; };
 
+// One segment of the parity matrix' access lists (generate_access_idx, src/sumcheck.cpp:2622-2669; hobbit_parity_commit_device): entries
+// [base, base + count) of the lists.  kind 0, the edges of one level: entry base + j is edge j of the level's forward records (record src + j
+// of the forward form), idx1 = nbr + lvl, idx2 = j / degree + off.  kind 1, an identity run: idx1 = j + lvl, idx2 = j + off, weight p - 1,
+// degree 1.  `cells`: the idx2 cells the segment covers (each `degree` times), [off, off + cells).
+struct ParitySeg { uint32_t base, count, degree, lvl, off, kind, src, cells; };
+
 struct DeviceCode {         // finalized code for one message length n
     long long n = 0, len = 0;
     bool small_weights = true;               // all weights real and < 2^32
@@ -135,6 +141,13 @@ struct DeviceCode {         // finalized code for one message length n
     uint32_t *d_ilv_ptr = nullptr;
     uint2 *d_ilv_e32 = nullptr;              // {index relative to in_off, w32}   (small_weights)
     uint32_t *d_ilv_eidx = nullptr; F *d_ilv_ew = nullptr;   // general weights
+    // The code's forward form (hobbit_parity_commit_device: ensure_fwd), built on first use: the neighbours and weights of every plan step
+    // in list order (C_0 .. C_{D-1}, D_{D-1} .. D_0), and the segment table of the access lists (m entries in all)
+    bool fwd_built = false;
+    std::vector<ParitySeg> fwd_segs; size_t fwd_m = 0;
+    ParitySeg *d_fwd_segs = nullptr;
+    uint32_t *d_fwd_nbr = nullptr, *d_fwd_w32 = nullptr;   // w32 under small_weights
+    F *d_fwd_w = nullptr;                                    // general weights
     // H^T in CSR (evaluate_parity_matrix), built on first use
     uint32_t *d_pm_rowptr = nullptr, *d_pm_idx = nullptr; F *d_pm_w = nullptr; size_t pm_rows = 0;
 };
@@ -291,6 +304,13 @@ struct hobbit_ctx {
     // owns 16.5 GiB; re-allocating it per call would dominate a repeated-commit loop)
     void *spare_tensor = nullptr; size_t spare_tensor_bytes = 0;
     void *spare_levels = nullptr; size_t spare_levels_bytes = 0;
+    // likewise one retired parity commitment's five device buffers (12.6 GiB at n = 2^20), for the next hobbit_parity_commit_device of the same
+    // (P, n): the runtime releases freed buffers of this size in bursts, seconds long, inside a later allocation
+    void *spare_parity[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t spare_parity_P = 0; long long spare_parity_n = 0;
+    void spare_parity_release() {
+        for (void *&q : spare_parity) { if (q) hipFree(q); q = nullptr; }
+        spare_parity_P = 0; spare_parity_n = 0;
+    }
 
     int fail(int code, const std::string &msg) { err = msg; return code; }
     int hip(hipError_t e, const char *what) {

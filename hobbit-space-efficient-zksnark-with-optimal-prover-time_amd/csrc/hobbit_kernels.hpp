@@ -6,6 +6,9 @@ namespace hobbit {
 // plans built on first use (hobbit_capi.hip): the tiled steps of a long code, the CSR steps of the rows-innermost encode
 int ensure_tiled(hobbit_ctx *ctx);
 int ensure_ilv(hobbit_ctx *ctx);
+// the access lists of the parity matrix: their segment table from the finalized plan (host only), and the forward form on the device
+int parity_segments(hobbit_ctx *ctx, std::vector<ParitySeg> &segs, size_t *m);
+int ensure_fwd(hobbit_ctx *ctx);
 int launch_encode_ilv(hobbit_ctx *ctx, const F *src, F *dst, uint32_t rows);
 // the body of hobbit_brakedown_commit for `rows` messages of B elements (hobbit_capi.hip); the caller has checked the shape and the graphs
 int brakedown_commit_shape(hobbit_ctx *ctx, const F *d_poly, size_t B, uint32_t rows, int left_left_quirk, hobbit_brakedown **out);

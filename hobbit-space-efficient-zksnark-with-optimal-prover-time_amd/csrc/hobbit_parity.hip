@@ -1,13 +1,17 @@
 // hobbit_parity.hip -- the C ABI of include/hobbit_parity.h: commit_parity_matrix, open_parity_matrix and prove_linear_code_batch
 // (src/sumcheck.cpp:2622-2885, 3201-3221).  The sub-provers (multiplication tree, sumchecks, shockwave commit / prove, eq tables) are the
-// library's own entry points; this file adds what lies between them: the access lists (host, once per commitment: public data of the graphs),
-// and the kernels that turn lists and challenges into the provers' inputs.  No list goes back to the host during an opening.
+// library's own entry points; this file adds what lies between them: the access lists (public data of the graphs: on the host in
+// hobbit_parity_commit, by kernels in hobbit_parity_commit_device of include/hobbit_parity_lists.h), and the kernels that turn lists and
+// challenges into the provers' inputs.  No list goes back to the host during an opening.
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "hobbit_ctx.hpp"
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include "hobbit_kernels.hpp"
 #include "../../include/hobbit_parity.h"
+#include "../../include/hobbit_parity_lists.h"
 
 using namespace hobbit;
 
@@ -116,6 +120,76 @@ __global__ void __launch_bounds__(PB) k_parity_batch_rows(const F *__restrict__ 
     }
 }
 
+// ---- the access lists built on the device (hobbit_parity_commit_device) -------------------------------------------------------------------------
+// The lists are a function of the code's forward form and its segment table (hobbit_ctx.hpp ParitySeg; hobbit_capi.hip ensure_fwd).  One fill
+// pass writes idx1, idx2, weight and cnt2; cnt1 -- the rank of an entry among the entries of the same idx1 cell, in list order -- comes from
+// one stable sort of the m positions by cell (rocprim's radix sort over log2 2n key bits): the sorted run of a cell lists its entries in list
+// order whatever the graphs' in-degrees are, so the rank is the place in the run and the run's length is the cell's access count.
+constexpr uint32_t MAX_SEGS = 400;            // four per depth; hobbit_graph_upload takes depths below 100
+
+// occurrences of the idx2 cell c in segments [0, upto): a segment covers an interval of cells, each `degree` times
+__device__ __forceinline__ uint32_t cell_count2(const ParitySeg *sg, uint32_t upto, uint32_t c) {
+    uint32_t k = 0;
+    for (uint32_t s = 0; s < upto; s++) if (c - sg[s].off < sg[s].cells) k += sg[s].degree;
+    return k;
+}
+// Four consecutive entries per lane: the three u32 lists go out 16 B per lane, the weights 64 B per lane.  Entries from m on are zero.
+__global__ void __launch_bounds__(PB) k_parity_fill(const ParitySeg *__restrict__ segs, uint32_t nseg, const uint32_t *__restrict__ nbr, const uint32_t *__restrict__ w32,
+                                                    const F *__restrict__ wF, size_t m, size_t P, uint32_t *__restrict__ idx1, uint32_t *__restrict__ idx2,
+                                                    uint32_t *__restrict__ cnt2, F *__restrict__ weight) {
+    __shared__ ParitySeg sg[MAX_SEGS];
+    for (uint32_t i = threadIdx.x; i < nseg; i += PB) sg[i] = segs[i];
+    __syncthreads();
+    const F minus1 = fmake(P61 - 1), zero = fmake(0);
+    for (size_t q = blockIdx.x * (size_t)PB + threadIdx.x; q < P / 4; q += (size_t)gridDim.x * PB) {
+        const size_t e0 = 4 * q;
+        uint32_t s = 0, hi = nseg;                                   // the last segment that starts at or before e0
+        while (hi - s > 1) { const uint32_t mid = (s + hi) / 2; if (sg[mid].base <= e0) s = mid; else hi = mid; }
+        uint32_t a[4], b[4], c2[4]; F w[4];
+        for (int k = 0; k < 4; k++) {
+            const size_t e = e0 + k;
+            a[k] = b[k] = c2[k] = 0; w[k] = zero;
+            if (e >= m) continue;
+            while (e - sg[s].base >= sg[s].count) s++;
+            const uint32_t j = (uint32_t)(e - sg[s].base);
+            uint32_t in_seg = 1;
+            if (sg[s].kind == 0) {
+                const size_t r = (size_t)sg[s].src + j;
+                const uint32_t row = j / sg[s].degree;
+                a[k] = nbr[r] + sg[s].lvl; b[k] = row + sg[s].off; in_seg = j - row * sg[s].degree + 1;
+                w[k] = w32 ? fmake(w32[r]) : wF[r];
+            } else { a[k] = j + sg[s].lvl; b[k] = j + sg[s].off; w[k] = minus1; }
+            c2[k] = cell_count2(sg, s, b[k]) + in_seg;
+        }
+        reinterpret_cast<uint4 *>(idx1)[q] = make_uint4(a[0], a[1], a[2], a[3]);
+        reinterpret_cast<uint4 *>(idx2)[q] = make_uint4(b[0], b[1], b[2], b[3]);
+        reinterpret_cast<uint4 *>(cnt2)[q] = make_uint4(c2[0], c2[1], c2[2], c2[3]);
+        for (int k = 0; k < 4; k++) weight[e0 + k] = w[k];
+    }
+}
+// per cell c < S = 2n: where its run starts in the sorted keys, the run's length (acc1) and the closed-form count of the idx2 cell (acc2)
+__global__ void __launch_bounds__(PB) k_parity_cells(const ParitySeg *__restrict__ segs, uint32_t nseg, const uint32_t *__restrict__ skeys, size_t m, size_t S,
+                                                     uint32_t *__restrict__ start, F *__restrict__ acc1, F *__restrict__ acc2) {
+    __shared__ ParitySeg sg[MAX_SEGS];
+    for (uint32_t i = threadIdx.x; i < nseg; i += PB) sg[i] = segs[i];
+    __syncthreads();
+    for (size_t c = blockIdx.x * (size_t)PB + threadIdx.x; c < S; c += (size_t)gridDim.x * PB) {
+        size_t b[2];
+        for (int t = 0; t < 2; t++) {                                // first sorted place whose key is >= c + t
+            size_t lo = 0, hi = m;
+            while (lo < hi) { const size_t mid = (lo + hi) / 2; if (skeys[mid] < (uint32_t)c + t) lo = mid + 1; else hi = mid; }
+            b[t] = lo;
+        }
+        start[c] = (uint32_t)b[0];
+        acc1[c] = fmake((uint32_t)(b[1] - b[0]));
+        acc2[c] = fmake(cell_count2(sg, nseg, (uint32_t)c));
+    }
+}
+__global__ void __launch_bounds__(PB) k_parity_cnt1(const uint32_t *__restrict__ skeys, const uint32_t *__restrict__ spos, const uint32_t *__restrict__ start, size_t m,
+                                                    uint32_t *__restrict__ cnt1) {
+    for (size_t j = blockIdx.x * (size_t)PB + threadIdx.x; j < m; j += (size_t)gridDim.x * PB) cnt1[spos[j]] = (uint32_t)j - start[skeys[j]] + 1;
+}
+
 // the libc generator is part of the transcript; loading this file's code object (its first launch) must not draw from it (see hobbit_ctx_create)
 struct LibcRngGuard {
     char tmp[256]; char *prev;
@@ -171,11 +245,12 @@ void hobbit_parity_commitment_free(hobbit_parity_commitment *c) {
     if (!c) return;
     hipSetDevice(c->ctx->device);
     hipStreamSynchronize(c->ctx->stream);
-    if (c->d_u32) hipFree(c->d_u32);
-    if (c->d_F) hipFree(c->d_F);
-    if (c->d_pw) hipFree(c->d_pw);
-    if (c->d_enc) hipFree(c->d_enc);
-    if (c->d_levels) hipFree(c->d_levels);
+    void *bufs[5] = {c->d_u32, c->d_F, c->d_pw, c->d_enc, c->d_levels};
+    if (bufs[0] && bufs[1] && bufs[2] && bufs[3] && bufs[4] && !c->ctx->spare_parity[0]) {       // park a whole set for the next device-built commit
+        for (int k = 0; k < 5; k++) c->ctx->spare_parity[k] = bufs[k];
+        c->ctx->spare_parity_P = c->P; c->ctx->spare_parity_n = c->n;
+    } else
+        for (void *q : bufs) if (q) hipFree(q);
     if (c->h_u32) hipHostFree(c->h_u32);
     if (c->h_F) hipHostFree(c->h_F);
     delete c;
@@ -404,6 +479,87 @@ int hobbit_prove_linear_code_batch(hobbit_ctx *ctx, const hobbit_F *d_codewords,
     ctx->prof_end("k_parity_batch_rows");
     HB_CHECK(ctx, hipGetLastError());
     return hobbit_sumcheck2(ctx, aF(A), aF(B), S, h_r1 + (l - 1), h_qpoly, h_r, h_vr, h_final);
+}
+
+// ---- include/hobbit_parity_lists.h ----------------------------------------------------------------------------------------------------------------
+int hobbit_parity_shape(hobbit_ctx *ctx, long long n, size_t *m_out, size_t *P_out) {
+    if (n < 16 || n > (1LL << 20) || (n & (n - 1))) return ctx->fail(HOBBIT_EINVAL, "parity_commit: n must be a power of two in [16, 2^20]");
+    if (ctx->code.n != n) return ctx->fail(HOBBIT_ESTATE, "parity_commit: graphs for this n are not finalized (hobbit_graph_finalize)");
+    std::vector<ParitySeg> segs; size_t m = 0;
+    HB_TRY(parity_segments(ctx, segs, &m));
+    const size_t S = 2 * (size_t)n;
+    size_t P = 1; while (P < m) P <<= 1;
+    if (m == 0 || segs.size() > MAX_SEGS || 5 * P + 2 * S > 8 * P) return ctx->fail(HOBBIT_EINVAL, "parity_commit: list length outside the public witness' 8P layout");
+    if (m_out) *m_out = m;
+    if (P_out) *P_out = P;
+    return 0;
+}
+
+int hobbit_parity_commit_device(hobbit_ctx *ctx, long long n, hobbit_parity_commitment **out) {
+    if (!out) return ctx->fail(HOBBIT_EINVAL, "parity_commit: null output");
+    *out = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    size_t m = 0, P = 0;
+    HB_TRY(hobbit_parity_shape(ctx, n, &m, &P));
+    LibcRngGuard guard;
+    hipSetDevice(ctx->device);
+    HB_TRY(ensure_fwd(ctx));
+    const DeviceCode &code = ctx->code;
+    const size_t S = 2 * (size_t)n, W = P;
+    const uint32_t nseg = (uint32_t)code.fwd_segs.size();
+    Scratch sc(ctx);
+    uint32_t *skeys, *spos, *start; void *tmp = nullptr; size_t tmp_bytes = 0;
+    hobbit_parity_commitment *c = new hobbit_parity_commitment();
+    c->ctx = ctx; c->n = n; c->m = m; c->P = P;
+    auto bail = [&](int rc) { hobbit_parity_commitment_free(c); return rc; };
+    if (ctx->spare_parity[0] && ctx->spare_parity_P == P && ctx->spare_parity_n == n) {             // the buffers of a retired commitment of this shape
+        c->d_u32 = (uint32_t *)ctx->spare_parity[0]; c->d_F = (F *)ctx->spare_parity[1]; c->d_pw = (F *)ctx->spare_parity[2]; c->d_enc = (F *)ctx->spare_parity[3];
+        c->d_levels = (uint8_t *)ctx->spare_parity[4];
+        for (void *&q : ctx->spare_parity) q = nullptr;
+    } else {
+        if (ctx->spare_parity[0]) { hipStreamSynchronize(ctx->stream); ctx->spare_parity_release(); }  // another shape: release it before allocating
+        if (hipMalloc((void **)&c->d_u32, 4 * P * sizeof(uint32_t)) != hipSuccess || hipMalloc((void **)&c->d_F, (P + 2 * S) * sizeof(F)) != hipSuccess ||
+            hipMalloc((void **)&c->d_pw, 8 * P * sizeof(F)) != hipSuccess || hipMalloc((void **)&c->d_enc, 16 * W * sizeof(F)) != hipSuccess ||
+            hipMalloc((void **)&c->d_levels, 64 * W) != hipSuccess)
+            return bail(ctx->fail(HOBBIT_ENOMEM, "parity_commit: device allocation failed"));
+    }
+    uint32_t *idx1 = c->d_u32, *idx2 = idx1 + P, *cnt1 = idx2 + P, *cnt2 = cnt1 + P;
+    int rc = sc.get((2 * m + S) * sizeof(uint32_t), (void **)&skeys);
+    if (rc) return bail(rc);
+    spos = skeys + m; start = spos + m;
+    const rocprim::counting_iterator<uint32_t> places(0);
+    const unsigned key_bits = (unsigned)ilog2x(S);                  // every idx1 is below 2n (ensure_fwd)
+    rc = ctx->hip(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const uint32_t *)idx1, skeys, places, spos, m, 0u, key_bits, ctx->stream), "parity_commit: sort scratch");
+    if (!rc) rc = sc.get(tmp_bytes, &tmp);
+    if (rc) return bail(rc);
+    rc = ctx->hip(hipMemsetAsync(cnt1 + m, 0, (P - m) * sizeof(uint32_t), ctx->stream), "parity_commit: cnt1 padding");
+    if (rc) return bail(rc);
+    ctx->prof_begin("k_parity_fill");
+    hipLaunchKernelGGL(k_parity_fill, dim3(pgrid(P / 4)), dim3(PB), 0, ctx->stream, code.d_fwd_segs, nseg, code.d_fwd_nbr, code.d_fwd_w32, code.d_fwd_w, m, P, idx1, idx2, cnt2,
+                       c->d_F);
+    ctx->prof_end("k_parity_fill");
+    rc = ctx->hip(hipGetLastError(), "k_parity_fill");
+    if (rc) return bail(rc);
+    ctx->prof_begin("k_parity_sort");
+    rc = ctx->hip(rocprim::radix_sort_pairs(tmp, tmp_bytes, (const uint32_t *)idx1, skeys, places, spos, m, 0u, key_bits, ctx->stream), "parity_commit: sort");
+    ctx->prof_end("k_parity_sort");
+    if (rc) return bail(rc);
+    ctx->prof_begin("k_parity_cnt1");
+    hipLaunchKernelGGL(k_parity_cells, dim3(pgrid(S)), dim3(PB), 0, ctx->stream, code.d_fwd_segs, nseg, skeys, m, S, start, c->d_F + P, c->d_F + P + S);
+    hipLaunchKernelGGL(k_parity_cnt1, dim3(pgrid(m)), dim3(PB), 0, ctx->stream, skeys, spos, start, m, cnt1);
+    ctx->prof_end("k_parity_cnt1");
+    rc = ctx->hip(hipGetLastError(), "k_parity_cnt1");
+    if (rc) return bail(rc);
+    c->list_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    ctx->prof_begin("k_parity_witness");
+    hipLaunchKernelGGL(k_parity_witness, dim3(pgrid(8 * P)), dim3(PB), 0, ctx->stream, c->idx1(), c->idx2(), c->cnt1(), c->cnt2(), c->weight(), c->acc1(), c->acc2(), m, P, m, S,
+                       c->d_pw);
+    ctx->prof_end("k_parity_witness");
+    rc = ctx->hip(hipGetLastError(), "k_parity_witness");
+    if (!rc) rc = hobbit_shockwave_commit(ctx, aF(c->d_pw), 8 * P, 16, aF(c->d_enc), c->d_levels);
+    if (rc) return bail(rc);
+    *out = c;
+    return 0;
 }
 
 }  // extern "C"

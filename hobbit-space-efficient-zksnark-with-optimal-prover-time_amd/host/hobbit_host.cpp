@@ -951,7 +951,7 @@ static hobbit_host_parity_transcript g_popen;
 hobbit_host_parity_transcript &hobbit_host_last_parity_open() { return g_popen; }
 void commit_parity_matrix(int n) {                                                                              // src/sumcheck.cpp:2671-2706
     if (g_parity) { hobbit_parity_commitment_free(g_parity); g_parity = nullptr; }
-    HCHK(hobbit_parity_commit(hobbit_host_ctx(), n, &g_parity));
+    HCHK(hobbit_parity_commit_device(hobbit_host_ctx(), n, &g_parity));
     size_t P = 0; HCHK(hobbit_parity_dims(g_parity, nullptr, nullptr, &P, nullptr));
     // C_p as the reference's global: N, k and the column tree.  The matrix and its encoded rows stay with the device object (matrix /
     // encoded_matrix are left null); above 2^20 leaves only the root level is brought to the host.
@@ -1418,9 +1418,9 @@ void open_brakingbase(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_ha
     BUFFER_SPACE = tensor_row_size; aggregation_queries = HOBBIT_BRAKINGBASE_QUERIES;
     const size_t S = 2 * trs, Q = HOBBIT_BRAKINGBASE_QUERIES; const int lk = (int)log2((double)K), l = (int)log2((double)S);
     if ((int)x.size() < lk) { printf("Error: open_brakingbase needs log2(K) coordinates\n"); exit(-1); }
-    // the parity transcript's buffers are sized by P, which the list length of the code decides: a throw-away commitment tells it (no draws)
+    // the parity transcript's buffers are sized by P, which the list length of the code decides: hobbit_parity_shape tells it on the host (no draws)
     size_t P = 0;
-    { hobbit_parity_commitment *pc = nullptr; HCHK(hobbit_parity_commit(hobbit_host_ctx(), (long long)trs, &pc)); hobbit_parity_dims(pc, nullptr, nullptr, &P, nullptr); hobbit_parity_commitment_free(pc); }
+    HCHK(hobbit_parity_shape(hobbit_host_ctx(), (long long)trs, nullptr, &P));
     const int L = (int)log2((double)P);
     hobbit_host_brakingbase_transcript &t = g_bb_open;
     hobbit_host_parity_transcript &pt = hobbit_host_last_parity_open(); pt.n = (int)trs; pt.P = P;

@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 #include "hobbit_hip.h"
-#include "hobbit_parity.h"
+#include "hobbit_parity_lists.h"
 #include "hobbit_whir.h"
 #include "hobbit_brakingbase.h"
 

@@ -48,7 +48,8 @@ int hobbit_brakingbase_tensor(hobbit_ctx *ctx, const hobbit_brakingbase *c, size
  *   0  beta = precompute_beta(x), aggr[j] = sum_i beta[i] poly[i trs + j] (from the matrix' message columns), codeword =
  *      encode_monolithic(aggr), C_c = shockwave_commit(codeword, 32);
  *   1  reply[q][i] = T[i][I[q]] and open_tree_blake(MT, {0, I[q]}, 0): as in Brakedown, every path is leaf 0's;
- *   2  commit_parity_matrix(trs) (inside the opening, as in the reference);
+ *   2  commit_parity_matrix(trs) (inside the opening, as in the reference), the access lists built on the device
+ *      (hobbit_parity_commit_device, hobbit_parity_lists.h);
  *   3  P1 = prove_linear_code(codeword, trs);
  *   4  open_parity_matrix(P1.randomness[0], P1.randomness[1], trs);
  *   5  shockwave_prove(C_c, P1.randomness[0]).

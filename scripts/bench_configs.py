@@ -29,7 +29,25 @@ def timed(fn, reps=3, warm=1):
 #     table entries not counted) from the library's event brackets, next to the 8 TB/s this repository uses as peak.  The reference's CPU
 #     seconds are those of tests/golden/parity_matrix.npz (n = 4096 only: commit, and the opening up to its first SHA3 call).
 #     `python scripts/bench_configs.py parity [n ...]` runs this entry alone; `parity-gather n` one commit and one opening without
-#     the event brackets, for a kernel trace of its own.
+#     the event brackets, for a kernel trace of its own.  "commit_builders": the commit with the lists built on the host and by kernels
+#     (include/hobbit_parity_lists.h), same graphs, same process.
+def parity_builders(n, reps=3):
+    """the parity commitment of the finalized code of n with the lists built on the host (hobbit_parity_commit) and by kernels
+    (hobbit_parity_commit_device): wall time from the call to a synchronised stream, median of `reps` after one warm-up; the device builder's
+    first call after the finalize (it uploads the code's forward form) on its own"""
+    def wall(fn):
+        hb.sync(); t0 = time.perf_counter(); pc = fn(n); hb.sync(); t = 1e3 * (time.perf_counter() - t0)
+        root, sec = bytes(pc.root()).hex(), pc.list_seconds; pc.free()
+        return t, root, sec
+    wall(hb.commit_parity_matrix)
+    host = [wall(hb.commit_parity_matrix) for _ in range(reps)]
+    first = wall(hb.commit_parity_matrix_device)
+    dev = [wall(hb.commit_parity_matrix_device) for _ in range(reps)]
+    assert len(set(r[1] for r in host + [first] + dev)) == 1, "the two builders' roots differ"
+    return dict(host_built=dict(ms=float(np.median([r[0] for r in host])), runs=[r[0] for r in host], lists_host_s=host[-1][2]),
+                device_built=dict(first_call_ms=first[0], first_call_until_queued_s=first[2], ms=float(np.median([r[0] for r in dev])), runs=[r[0] for r in dev],
+                                  until_queued_s=dev[-1][2]))
+
 def parity_entry(ns=(4096, 1 << 17, 1 << 20), bare=False):
     res = {}
     gold = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "parity_matrix.npz"))
@@ -44,6 +62,9 @@ def parity_entry(ns=(4096, 1 << 17, 1 << 20), bare=False):
             hb.profile(True); hb.profile_reset()
         t0 = time.perf_counter(); g = hb.open_parity_matrix(pc, r1, r2); t_open = time.perf_counter() - t0
         assert g["checks"].tolist() == [1, 1]
+        if bare:                                                                               # the list kernels, for the same trace: first call and a later one
+            for _ in range(2):
+                pd = hb.commit_parity_matrix_device(n); hb.sync(); pd.free()
         e = dict(m=pc.m, P=pc.P, graphs_host_draw_s=t_graphs, lists_host_s=pc.list_seconds, commit_ms=1e3 * t_commit, open_ms=1e3 * t_open,
                  stage_ms=dict(zip(("gather_and_Cw", "tree1", "eval_and_tree2", "sumchecks_P2_P3_P4", "shockwave_prove_Cp", "shockwave_prove_Cw"), g["stage_ms"].tolist())))
         if not bare:
@@ -53,6 +74,7 @@ def parity_entry(ns=(4096, 1 << 17, 1 << 20), bare=False):
             e["gather_ms"] = ms
             if ms:
                 e["gather_bytes_per_s"] = 112.0 * pc.P / (1e-3 * ms); e["gather_fraction_of_8TBs"] = e["gather_bytes_per_s"] / 8e12
+            e["commit_builders"] = parity_builders(n)
         if "ref_seconds_%d" % n in gold:
             e["reference_cpu_s"] = dict(commit=float(gold["ref_seconds_%d" % n][0]), open_child_until_first_sha3=float(gold["ref_seconds_%d" % n][1]))
         res["PM_n%d" % n] = e
@@ -105,7 +127,8 @@ def whir_entry(logs=(20, 22, 24, 26), reps=5, bare=False):
 #     the same process hobbit_brakedown_commit + _open and Our_PC's commit_standard + open_standard at the same N.  The commit runs
 #     Brakedown's kernels at another shape: its per-launch times (the library's event brackets, one extra step) stand next to Brakedown's.
 #     Stage 0 encodes ONE codeword of n = trs: the rows-innermost encode at rows = 1 (what the opening uses) against hobbit_encode_batch at
-#     batch 1 on the same message.  `python scripts/bench_configs.py brakingbase [logN:K ...]` runs this entry alone.
+#     batch 1 on the same message.  "parity_commit_ms": stage 2's commit on its own, host-built and device-built lists.
+#     `python scripts/bench_configs.py brakingbase [logN:K ...]` runs this entry alone.
 def brakingbase_entry(shapes=((26, 64), (26, 128), (28, 256)), reps=3):
     import ctypes
     res = {}
@@ -123,6 +146,7 @@ def brakingbase_entry(shapes=((26, 64), (26, 128), (28, 256)), reps=3):
         e = dict(N=N, K=K, trs=trs)
         # ---- Braking base
         hb.rng_reset(); t0 = time.perf_counter(); hb.expander_init_store(trs); e["graphs_host_draw_s"] = time.perf_counter() - t0
+        e["parity_commit_ms"] = parity_builders(trs)                                                                      # stage 2 alone, both builders
         c = hb.brakingbase_commit((d, N), K); g = c.open(x); assert g["checks"].tolist() == [1, 1]; c.free()          # warm: plans, workspaces, tables
         tc, to, st = [], [], []
         for _ in range(reps):
