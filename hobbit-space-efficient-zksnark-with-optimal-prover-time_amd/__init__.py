@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "hobbit_malloc", "hobbit_free", "hobbit_memcpy_h2d", "hobbit_memcpy_d2h", "hobbit_memset", "hobbit_timer_begin", "hobbit_timer_end_ms",
     "hobbit_profile_enable", "hobbit_profile_reset", "hobbit_profile_get", "hobbit_profile_names",
     "hobbit_mimc", "hobbit_f_mul_host", "hobbit_f_inv_host", "hobbit_f_binop",
-    "hobbit_graph_reset", "hobbit_graph_upload", "hobbit_graph_finalize", "hobbit_encode_batch", "hobbit_fft_batch", "hobbit_fft_any",
+    "hobbit_graph_reset", "hobbit_graph_upload", "hobbit_graph_finalize", "hobbit_encode_forms", "hobbit_encode_batch", "hobbit_fft_batch", "hobbit_fft_any",
     "hobbit_blake3_64", "hobbit_hash_md", "hobbit_mt_commit_blake", "hobbit_merkle_levels", "hobbit_merkle_path", "hobbit_merkle_paths",
     "hobbit_eq_table", "hobbit_eval_vector", "hobbit_tensorcode",
     "hobbit_commit_standard", "hobbit_commit_standard_host", "hobbit_commitment_free", "hobbit_commitment_num_leaves", "hobbit_commitment_levels_dev",
@@ -119,7 +119,7 @@ def load_library(path=LIB_PATH):
         "hobbit_profile_enable": [V, I], "hobbit_profile_reset": [V], "hobbit_profile_get": [V, ctypes.c_char_p, V, V],
         "hobbit_profile_names": [V, V, S], "hobbit_mimc": [V, V, V], "hobbit_f_mul_host": [V, V, V, S], "hobbit_f_inv_host": [V, V, S],
         "hobbit_f_binop": [V, I, V, V, V, S], "hobbit_graph_reset": [V], "hobbit_graph_upload": [V, I, I, L, L, I, V, V],
-        "hobbit_graph_finalize": [V, L, V], "hobbit_encode_batch": [V, V, V, L, S, S, S], "hobbit_fft_batch": [V, V, I, S, S, I], "hobbit_fft_any": [V, V, I, S, S, I],
+        "hobbit_graph_finalize": [V, L, V], "hobbit_encode_forms": [V, V, V], "hobbit_encode_batch": [V, V, V, L, S, S, S], "hobbit_fft_batch": [V, V, I, S, S, I], "hobbit_fft_any": [V, V, I, S, S, I],
         "hobbit_blake3_64": [V, V, V, S], "hobbit_hash_md": [V, V, V, V, S], "hobbit_mt_commit_blake": [V, V, S, V],
         "hobbit_merkle_levels": [V, V, S, I], "hobbit_merkle_path": [V, V, S, S, V], "hobbit_merkle_paths": [V, V, S, V, S, V],
         "hobbit_eq_table": [V, V, I, V], "hobbit_eval_vector": [V, V, S, V, V], "hobbit_tensorcode": [V, V, S, I, I, V],
@@ -544,6 +544,16 @@ class Hobbit:
         ln = c_ll()
         self._chk(self.lib.hobbit_graph_finalize(self.ctx, c_ll(n), ctypes.byref(ln)))
         return ln.value
+
+    def encode_forms(self):
+        """the kernel forms the finalized code runs in (hobbit_encode_forms): small_weights, fatA, fatC1, fatD, narrow as booleans;
+        tiled_depth once a long code's tiled steps are built (its first encode), else 0 with tiled_pending set"""
+        fl, td = ctypes.c_uint(), ctypes.c_uint()
+        self._chk(self.lib.hobbit_encode_forms(self.ctx, ctypes.byref(fl), ctypes.byref(td)))
+        names = ("small_weights", "fatA", "fatC1", "fatD", "narrow", "tiled_pending")
+        out = {k: bool(fl.value >> i & 1) for i, k in enumerate(names)}
+        out["tiled_depth"] = td.value
+        return out
 
     def encode_monolithic(self, src, in_place=False):
         """src: (batch, n, 2) or (n, 2) -> (batch, 2n, 2).  in_place: the messages are laid out at the head of their 2n-element codewords and

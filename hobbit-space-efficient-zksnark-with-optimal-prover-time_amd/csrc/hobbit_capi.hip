@@ -885,6 +885,16 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
     if (len_out) *len_out = c.len;
     return 0;
 }
+// Which kernel forms hobbit_graph_finalize chose for the finalized code (include/hobbit_hip.h).  Host only: reads the code's flags.
+int hobbit_encode_forms(hobbit_ctx *ctx, unsigned *flags, unsigned *tiled_depth) {
+    const DeviceCode &c = ctx->code;
+    if (!c.n || c.graph_gen != ctx->graph_gen) return ctx->fail(HOBBIT_ESTATE, "encode_forms: no finalized code (hobbit_graph_finalize)");
+    const bool pending = (size_t)c.len * 16 > 160 * 1024 && !c.tiled_built;
+    if (flags) *flags = (c.small_weights ? HOBBIT_FORM_SMALL_WEIGHTS : 0u) | (c.fatA.ok ? HOBBIT_FORM_FAT_A : 0u) | (c.fatC1.ok ? HOBBIT_FORM_FAT_C1 : 0u) |
+                        (c.fatD.ok ? HOBBIT_FORM_FAT_D : 0u) | (c.narrow.ok ? HOBBIT_FORM_NARROW : 0u) | (pending ? HOBBIT_FORM_TILED_PENDING : 0u);
+    if (tiled_depth) *tiled_depth = c.tiled_built ? c.tiled_depth : 0u;
+    return 0;
+}
 int hobbit_encode_batch(hobbit_ctx *ctx, const hobbit_F *d_src, hobbit_F *d_dst, long long n, size_t batch, size_t ld_src, size_t ld_dst) {
     if (n <= 0 || ld_src < (size_t)n || ld_dst < (size_t)(2 * n)) return ctx->fail(HOBBIT_EINVAL, "encode_batch: bad n / leading dimensions");
     // in place (the messages already sit at the head of their codewords): nothing to copy, and the deep-code kernels apply

@@ -97,6 +97,17 @@ int hobbit_graph_upload(hobbit_ctx *ctx, int dep, int kind, long long L, long lo
                         const long long *h_nbr, const hobbit_F *h_w);
 /* call after all levels for code length n are uploaded; returns codeword length via *len */
 int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len);
+/* which kernel forms the finalized code runs in (chosen at finalize from the graphs' shape and in-degrees).  *flags: the bits below; a fat or
+ * narrow bit says that the step's register-resident tables were built, so an in-place encode runs k_enc_fat / k_enc_narrow there.
+ * *tiled_depth: outer steps per side in tiled form, once they are built (a long code's first encode builds them: until then 0 and
+ * HOBBIT_FORM_TILED_PENDING); 0 for a code that fits in LDS.  Host only, launches nothing. */
+#define HOBBIT_FORM_SMALL_WEIGHTS 1u   /* every weight real and < 2^32; else the general-weight (_fullw) kernels */
+#define HOBBIT_FORM_FAT_A 2u           /* C_0 */
+#define HOBBIT_FORM_FAT_C1 4u          /* C_1 */
+#define HOBBIT_FORM_FAT_D 8u           /* D_0 */
+#define HOBBIT_FORM_NARROW 16u         /* C_2 .. D_1, one wave per column */
+#define HOBBIT_FORM_TILED_PENDING 32u  /* a long code whose tiled steps are not built yet */
+int hobbit_encode_forms(hobbit_ctx *ctx, unsigned *flags, unsigned *tiled_depth);
 /* encode_monolithic on `batch` messages; message b at d_src + b*ld_src (n F, contiguous), its
  * codeword written to d_dst + b*ld_dst (2n F: codeword then zeros).  d_src may alias d_dst. */
 int hobbit_encode_batch(hobbit_ctx *ctx, const hobbit_F *d_src, hobbit_F *d_dst, long long n,

@@ -203,6 +203,16 @@ void orc_graph_set_weights(int dep, int kind, const oF *w) {
     ograph *g = kind ? &gD[dep] : &gC[dep];
     memcpy(g->w, w, sizeof(oF) * (size_t)(g->L * g->degree));
 }
+/* any graph of the drawn shape: L, R and degree stay, neighbours (each in [0, R)) and weights are replaced; -1 and nothing changed if a
+ * neighbour is out of range */
+int orc_graph_set_edges(int dep, int kind, const long long *nbr, const oF *w) {
+    ograph *g = kind ? &gD[dep] : &gC[dep];
+    size_t m = (size_t)(g->L * g->degree);
+    for (size_t e = 0; e < m; e++) if (nbr[e] < 0 || nbr[e] >= g->R) return -1;
+    memcpy(g->nbr, nbr, sizeof(long long) * m);
+    memcpy(g->w, w, sizeof(oF) * m);
+    return 0;
+}
 
 /* src/linear_code_encode.h:62-119: codeword = [x | Enc(C x) | D Enc(C x)] by scatter-add */
 static long long encode_rec(const oF *src, oF *dst, long long n, int dep) {

@@ -49,6 +49,7 @@ long long orc_expander_init_store(long long n);
 long long orc_graph_dims(int dep, int kind, long long *R, int *degree);
 void orc_graph_edges(int dep, int kind, long long *nbr, oF *w);
 void orc_graph_set_weights(int dep, int kind, const oF *w);
+int orc_graph_set_edges(int dep, int kind, const long long *nbr, const oF *w);
 int orc_encode_monolithic(const oF *src, oF *dst, long long n);
 
 /* FFT / eq table / evaluation */

@@ -145,6 +145,15 @@ class _Base:
         w = F(w)
         self.fn("graph_set_weights")(ctypes.c_int(dep), ctypes.c_int(kind), _p(w))
 
+    def graph_set_edges(self, dep, kind, nbr, w):
+        """neighbours and weights of a drawn level replaced (L, R and degree stay)"""
+        nbr = np.ascontiguousarray(nbr, np.int64).reshape(-1); w = F(w).reshape(-1, 2)
+        g = self.graph(dep, kind)
+        assert nbr.size == g["L"] * g["degree"] == w.shape[0], "graph_set_edges: not the drawn shape"
+        f = self.fn("graph_set_edges"); f.restype = ctypes.c_int
+        if f(ctypes.c_int(dep), ctypes.c_int(kind), _p(nbr), _p(w)) != 0:
+            raise ValueError("graph_set_edges: neighbour out of range")
+
     def encode_monolithic(self, src):
         s = F(src).reshape(-1, 2)
         n = s.shape[0]

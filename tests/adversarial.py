@@ -443,3 +443,390 @@ def gate_sumcheck_inputs(n):
     add = splitmix_field(n, 801); mul = splitmix_field(n, 802)
     tabs = [add, splitmix_field(n, 803), splitmix_field(n, 804), splitmix_field(n, 805), splitmix_field(n, 806), mul]
     return tabs, splitmix_field(4, 807), splitmix_field(1, 808)[0]
+
+
+# ---- the expander encode on graphs other than the drawn one (tests/test_encode_graphs.py, tests/test_encode_graph_families_cpu.py) -----------
+# hobbit_graph_finalize chooses every kernel form of the encode from the shape and the in-degrees of the uploaded graphs.  expected_forms
+# restates that choice in plain Python, expected_chain the launches launch_encode / launch_encode_long make of it, and the builders below put
+# graphs at, just below and just above every rule in front of both.
+def ctx_constants():
+    """{name: [values]} of csrc/hobbit_ctx.hpp's NARROW_*, FAT_*, TILE_* tables and ENC_WIDE_MIN"""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, "hobbit-space-efficient-zksnark-with-optimal-prover-time_amd", "csrc", "hobbit_ctx.hpp")).read()
+    out = {}
+    for name, val in re.findall(r"\b((?:NARROW|FAT|TILE)_[A-Z0-9_]+|ENC_WIDE_MIN)(?:\[[A-Z_]+\])? = (\{[0-9, ]+\}|[0-9]+)[,;]", src):
+        out[name] = [int(v) for v in re.findall(r"[0-9]+", val)]
+    return out
+
+
+CTX = ctx_constants()
+FAT = {   # step -> (level key, outputs per lane, consumer waves, register slots per position)
+    "fatA": ((0, 0), CTX["FAT_A_NOUT"][0], CTX["FAT_A_CONS"][0], [CTX["FAT_A_CAP0"][0], CTX["FAT_A_CAP1"][0]]),
+    "fatC1": ((1, 0), CTX["FAT_C1_NOUT"][0], CTX["FAT_C1_CONS"][0], [CTX["FAT_C1_CAP0"][0]]),
+    "fatD": ((0, 1), CTX["FAT_D_NOUT"][0], CTX["FAT_D_CONS"][0], [CTX["FAT_D_CAP0"][0], CTX["FAT_D_CAP1"][0], CTX["FAT_D_CAP2"][0]]),
+}
+assert all(len(cap) == nout for _, nout, _, cap in FAT.values())
+LEVEL_NAMES = {"C0": (0, 0), "C1": (1, 0), "C2": (2, 0), "C3": (3, 0), "D3": (3, 1), "D2": (2, 1), "D1": (1, 1), "D0": (0, 1)}
+
+
+NARROW_LEVELS = [(2, 0), (3, 0), (3, 1), (2, 1), (1, 1)]              # C_2, C_3, D_3, D_2, D_1: steps 0 .. 4 of k_enc_narrow
+
+
+def in_degrees(g):
+    return np.bincount(np.asarray(g["nbr"], np.int64).reshape(-1), minlength=g["R"])
+
+
+def code_plan(lv, n):
+    """hobbit_graph_finalize's plan: the steps C_0 .. C_{D-1}, D_{D-1} .. D_0 as (level key, in_off, out_off), and cwlen[d], the length of
+    the sub-codeword of depth d (cwlen[0]: the codeword)"""
+    nd, off, D = [n], [0], 0
+    while nd[D] > 13:
+        g = lv[(D, 0)]
+        assert g["L"] == nd[D]
+        off.append(off[D] + nd[D]); nd.append(g["R"]); D += 1
+    cwlen = [0] * (D + 1); cwlen[D] = nd[D]
+    for d in range(D - 1, -1, -1):
+        assert lv[(d, 1)]["L"] == cwlen[d + 1]
+        cwlen[d] = nd[d] + cwlen[d + 1] + lv[(d, 1)]["R"]
+    plan = [((d, 0), off[d], off[d] + nd[d]) for d in range(D)]
+    plan += [((d, 1), off[d + 1], off[d + 1] + cwlen[d + 1]) for d in range(D - 1, -1, -1)]
+    return plan, cwlen
+
+
+def fat_verdict(g, nout, ncons, cap):
+    """build_fat_step's decision for one level: (accepted, why, heaviest in-degree per position).  why: "ok", "shape" (more outputs than
+    nout x lanes, or an input window over 64 KB) or "cap" (an output with more in-edges than its position has register slots: the outputs
+    sorted heaviest first fill position 0 lane by lane, position 1 backwards, position 2 forwards)"""
+    lanes = ncons * 64
+    if g["R"] > nout * lanes or g["L"] * 16 > 65536:
+        return False, "shape", None
+    deg = np.sort(in_degrees(g))[::-1]
+    top = [int(deg[j * lanes:(j + 1) * lanes].max()) if deg[j * lanes:(j + 1) * lanes].size else 0 for j in range(nout)]
+    ok = all(top[j] <= cap[j] for j in range(nout))
+    return ok, "ok" if ok else "cap", top
+
+
+def narrow_verdict(lv, n):
+    """build_narrow's decision: (accepted, why).  The code must have the five-step shape between C_1 and D_0 that the kernel was compiled
+    for; then per step the outputs sorted heaviest first fill the step's positions, 64 / LPO outputs each, and none may have more in-edges
+    than LPO x CAP"""
+    plan, _ = code_plan(lv, n)
+    S = CTX["NARROW_STEPS"][0]
+    if len(plan) != S + 3:
+        return False, "shape"
+    x2 = plan[2][1]
+    for s in range(S):
+        key, in_off, out_off = plan[2 + s]
+        if (lv[key]["L"], lv[key]["R"], in_off - x2, out_off - x2) != (CTX["NARROW_L"][s], CTX["NARROW_R"][s], CTX["NARROW_IN"][s], CTX["NARROW_OUT"][s]):
+            return False, "shape"
+    for s in range(S):
+        deg = np.sort(in_degrees(lv[plan[2 + s][0]]))[::-1]
+        nxt = 0
+        for pos in range(CTX["NARROW_POS"][0]):
+            if CTX["NARROW_STEP_OF"][pos] != s:
+                continue
+            lpo, cap = CTX["NARROW_LPO"][pos], CTX["NARROW_CAP"][pos]
+            part = deg[nxt:nxt + 64 // lpo]
+            if part.size and int(part.max()) > cap * lpo:
+                return False, "cap at position %d" % pos
+            nxt = min(deg.size, nxt + 64 // lpo)
+        if nxt < deg.size:
+            return False, "more outputs than positions"
+    return True, "ok"
+
+
+class Forms(dict):
+    """expected_forms' result: equal to Hobbit.encode_forms() as a dict; size_class, nsteps and why ride along for expected_chain and the guards"""
+    size_class = None; nsteps = 0; why = None
+
+
+def expected_forms(lv, n):
+    """what hobbit_graph_finalize decides for the graphs lv of message length n (and ensure_tiled at the first encode of a long code):
+    Hobbit.encode_forms()'s dict after that encode.  .size_class: "single" (codeword <= 80 KB: one k_encode pass), "deep" (<= 160 KB: two
+    passes, or the fat / narrow chain in place) or "tiled"; .why: per fat step and for narrow, the reason of the verdict; .top: per fat
+    step the heaviest in-degree of each position"""
+    plan, cwlen = code_plan(lv, n)
+    ln = cwlen[0]
+    small = all(not np.asarray(lv[k]["w"])[:, 1].any() and not (np.asarray(lv[k]["w"], np.uint64)[:, 0] >> U(32)).any() for k, _, _ in plan)
+    f = Forms(small_weights=small, fatA=False, fatC1=False, fatD=False, narrow=False, tiled_pending=False, tiled_depth=0)
+    f.nsteps = len(plan)
+    f.size_class = "single" if ln * 16 <= 80 * 1024 else "deep" if ln * 16 <= 160 * 1024 else "tiled"
+    f.why, f.top = {}, {}
+    if small and len(plan) >= 4 and f.size_class == "deep":
+        for name, (key, nout, ncons, cap) in FAT.items():
+            f[name], f.why[name], f.top[name] = fat_verdict(lv[key], nout, ncons, cap)
+        f["narrow"], f.why["narrow"] = narrow_verdict(lv, n)
+    if f.size_class == "tiled":
+        d = 0
+        while d < len(cwlen) - 1 and cwlen[d] > CTX["TILE_MID_MAX"][0]:
+            d += 1
+        f["tiled_depth"] = d
+    return f
+
+
+def expected_chain(forms, in_place):
+    """the profile names launch_encode / launch_encode_long run under for a code with these forms (csrc/hobbit_kernels.hip)"""
+    fw = "" if forms["small_weights"] else "fullw_"
+    if forms.size_class == "tiled":
+        return {"k_enc_tiled_%sC" % fw, "k_encode_%slong_M" % fw, "k_enc_tiled_%sD" % fw}
+    if forms.size_class == "single" or forms.nsteps < 2:
+        return {"k_encode" if forms["small_weights"] else "k_encode_fullw"}
+    if not forms["small_weights"]:
+        return {"k_encode_fullw_A", "k_encode_fullw_B"}
+    if not (forms["fatA"] and in_place):
+        return {"k_encode_A", "k_encode_B"}
+    if not forms["fatD"] or forms.nsteps < 5:
+        return {"k_enc_fat_A", "k_encode_B"}
+    return {"k_enc_fat_A", "k_enc_fat_C1" if forms["fatC1"] else "k_encode_C1", "k_encode_M2", "k_enc_fat_D"}
+
+
+def encode_kernel_names():
+    """every profile name in launch_encode_long and launch_encode (csrc/hobbit_kernels.hip), read from the source"""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = open(os.path.join(root, "hobbit-space-efficient-zksnark-with-optimal-prover-time_amd", "csrc", "hobbit_kernels.hip")).read()
+    a = src.index("static int launch_encode_long("); b = src.index("int launch_encode(", a); e = src.index("\n}\n", b)
+    return set(re.findall(r'"(k_enc[a-zA-Z0-9_]*)"', src[a:e]))
+
+
+def drawn_graphs(oracle, n, skip=None):
+    """the graphs libc draws for message length n straight after rng_reset() -- or after generate_randomness(skip) -- on the oracle"""
+    oracle.rng_reset()
+    if skip is not None:
+        oracle.generate_randomness(skip)
+    oracle.expander_init_store(n)
+    return graphs_from(oracle, n)
+
+
+def set_graphs(oracle, lv):
+    """the oracle's current graphs (same shapes) replaced by lv's edges"""
+    for (dep, kind), g in lv.items():
+        oracle.graph_set_edges(dep, kind, g["nbr"], g["w"])
+
+
+def with_in_degrees(g, deg, seed):
+    """g with the same L, R, degree and weights and its neighbours re-dealt: output t gets exactly deg[t] in-edges"""
+    deg = np.asarray(deg, np.int64)
+    assert deg.shape == (g["R"],) and (deg >= 0).all() and int(deg.sum()) == g["L"] * g["degree"], (deg.shape, int(deg.sum()))
+    nbr = np.repeat(np.arange(g["R"], dtype=np.int64), deg)
+    np.random.default_rng(seed).shuffle(nbr)
+    return dict(g, nbr=nbr)
+
+
+def heavy_degrees(R, E, k, h, seed, empty=()):
+    """in-degrees summing to E: k outputs at h, the outputs in `empty` at 0, the rest as even as possible; which outputs are the heavy ones
+    is drawn from seed"""
+    free = np.setdiff1d(np.arange(R), np.asarray(empty, np.int64))
+    free = free[np.random.default_rng(seed).permutation(free.size)]
+    deg = np.zeros(R, np.int64)
+    deg[free[:k]] = h
+    rest, m = E - k * h, free.size - k
+    assert rest >= 0 and m > 0
+    deg[free[k:]] = rest // m
+    deg[free[k:k + rest % m]] += 1
+    return deg
+
+
+def fitted_degrees(R, E, empty, room, seed):
+    """in-degrees summing to E with the outputs in `empty` at 0, fitted to room[r], the register slots of the r-th heaviest output
+    (non-increasing): every fed output gets the same share of its slots, so a step whose slots hold E edges at all accepts the graph"""
+    free = np.setdiff1d(np.arange(R), np.asarray(empty, np.int64))
+    free = free[np.random.default_rng(seed).permutation(free.size)]
+    room = np.asarray(room, np.int64)[:free.size]
+    assert room.size == free.size and (np.diff(room) <= 0).all() and E < int(room.sum())
+    per = E * room // int(room.sum())
+    per[:E - int(per.sum())] += 1
+    assert (per <= room).all() and int(per.sum()) == E
+    deg = np.zeros(R, np.int64); deg[free] = per
+    return deg
+
+
+def fat_room(step):
+    """register slots by rank of in-degree for a fat step: cap[0] for the heaviest `lanes` outputs, cap[1] for the next, ..."""
+    _, nout, ncons, cap = FAT[step]
+    return np.repeat(cap, ncons * 64)
+
+
+def narrow_room(s):
+    """the same for narrow step s: LPO x CAP for the 64 / LPO outputs of each of its positions"""
+    return np.concatenate([np.full(64 // CTX["NARROW_LPO"][p], CTX["NARROW_LPO"][p] * CTX["NARROW_CAP"][p])
+                           for p in range(CTX["NARROW_POS"][0]) if CTX["NARROW_STEP_OF"][p] == s])
+
+
+def empty_set(R):
+    """outputs 0, R - 1 and every 7th"""
+    return np.union1d(np.arange(0, R, 7), [R - 1])
+
+
+def _hub(nbr, w, degree, i, a, b=None):
+    """all edges of input i on output a; with b, the last one on b with weight 0"""
+    nbr[i * degree:(i + 1) * degree] = a
+    if b is not None:
+        nbr[(i + 1) * degree - 1] = b; w[(i + 1) * degree - 1] = 0
+
+
+def hubs(g, seed):
+    """input 0: all edges but one on one output a, the last one with weight 0 on an output b that has no other in-edge (b's only record is
+    (index 0, weight 0), what a padding slot looks like); input L - 1 the same on outputs c, d (the largest record offset); input L // 2
+    with all its edges on one output e (a multi-edge).  a, c, e are the lightest outputs of g, so that the step keeps its form."""
+    L, R, d = g["L"], g["R"], g["degree"]
+    nbr = np.array(g["nbr"], np.int64).reshape(-1); w = np.array(g["w"], np.uint64).reshape(-1, 2)
+    order = np.argsort(in_degrees(g), kind="stable")
+    a, c, e, b, dd = (int(t) for t in order[:5])
+    others = order[5:]
+    for t in (b, dd):                                   # nobody else feeds b and d
+        idx = np.flatnonzero(nbr == t)
+        nbr[idx] = others[np.random.default_rng(seed + t).integers(0, others.size, idx.size)]
+    _hub(nbr, w, d, 0, a, b); _hub(nbr, w, d, L - 1, c, dd); _hub(nbr, w, d, L // 2, e)
+    out = dict(g, nbr=nbr, w=w)
+    deg = in_degrees(out)
+    assert deg[b] == 1 and deg[dd] == 1
+    return out
+
+
+def bank_clash(g):
+    """input i sends all its edges to outputs t with (t // 16) % 16 == i % 16, dealt evenly: every record of such an output reads the bank
+    quad i % 16, so the lanes of a 16-lane LDS group that own outputs of one class find no conflict-free slot order"""
+    L, R, d = g["L"], g["R"], g["degree"]
+    nbr = np.zeros((L, d), np.int64)
+    for c in range(16):
+        outs = np.flatnonzero((np.arange(R) // 16) % 16 == c); ins = np.arange(c, L, 16)
+        E = ins.size * d
+        deg = np.full(outs.size, E // outs.size, np.int64); deg[:E % outs.size] += 1
+        tg = np.repeat(outs, deg)
+        np.random.default_rng(160 + c).shuffle(tg)
+        nbr[ins] = tg.reshape(ins.size, d)
+    return dict(g, nbr=nbr.reshape(-1))
+
+
+def tile_split(g, tile):
+    """outputs below R / 2 fed only by inputs < tile, the others only by inputs >= tile (every slice of a tiled step has a tile without an
+    edge); inputs 0 and tile - 1 with all their edges on one output each of the lower half, tile and L - 1 of the upper half"""
+    L, R, d = g["L"], g["R"], g["degree"]
+    assert tile < L
+    rng = np.random.default_rng(5955)
+    nbr = np.empty((L, d), np.int64)
+    nbr[:tile] = rng.integers(0, R // 2, (tile, d)); nbr[tile:] = rng.integers(R // 2, R, (L - tile, d))
+    nbr[0] = 3; nbr[tile - 1] = R // 2 - 1; nbr[tile] = R // 2; nbr[L - 1] = R - 1
+    return dict(g, nbr=nbr.reshape(-1))
+
+
+def _swap(lv, levels):
+    """lv with the levels {key: graph} replaced"""
+    out = dict(lv); out.update(levels)
+    return out
+
+
+def _set_weight(g, e, w):
+    ww = np.array(g["w"], np.uint64).reshape(-1, 2); ww[e] = w
+    return dict(g, w=ww)
+
+
+# the six caps of the fat steps: family name -> (level, position, outputs at the cap so that the position's heaviest output sits on it)
+CAP_CASES = {"C0_pos0": ("C0", "fatA", 0), "C0_pos1": ("C0", "fatA", 1), "C1_pos0": ("C1", "fatC1", 0),
+             "D0_pos0": ("D0", "fatD", 0), "D0_pos1": ("D0", "fatD", 1), "D0_pos2": ("D0", "fatD", 2)}
+
+
+FAMILIES_4096 = ["cap_exact_" + c for c in CAP_CASES] + ["cap_plus_one_" + c for c in CAP_CASES] + [
+    "bank_clash", "empty_outputs", "narrow_empty_outputs", "hubs", "zero_weights", "one_big_weight_2^32", "one_big_weight_(1,1)"]       # graph_families(., 4096)
+
+
+def cap_graph(g, step, pos, over, seed):
+    """g's level re-dealt so that position pos of the fat step has its heaviest output exactly at the cap (over = 0) or one above (over = 1):
+    pos x lanes + 1 outputs at that in-degree, the rest as even as possible -- or, where the rest would then be heavier than that (D_0's last
+    position: its cap is below the mean in-degree), every output from that position on at it and the earlier ones as even as possible"""
+    _, nout, ncons, cap = FAT[step]
+    R, E, h, before = g["R"], g["L"] * g["degree"], cap[pos] + over, pos * ncons * 64
+    if (E - (before + 1) * h) <= h * (R - before - 1):
+        deg = heavy_degrees(R, E, before + 1, h, seed)
+    else:
+        deg = heavy_degrees(R, E, R - before, h, seed)
+    assert np.sort(deg)[::-1][before] == h
+    return with_in_degrees(g, deg, seed + 1)
+
+
+def graph_families(lv0, n):
+    """{name: (graphs, what the family is meant to select)} for the drawn graphs lv0 of n = 4096 (every family but tile_split) or n = 5955
+    (tile_split).  Each family changes the levels it names and keeps the others as drawn.  The second entry: {form: value} that
+    expected_forms must give (tests/test_encode_graph_families_cpu.py)."""
+    lv0 = {k: dict(g) for k, g in lv0.items()}
+    out = {}
+    if n == 5955:
+        out["tile_split"] = (_swap(lv0, {(0, 0): tile_split(lv0[(0, 0)], CTX["TILE_ELEMS"][0])}), {"tiled_depth": 1, "small_weights": True})
+        return out
+    assert n == 4096
+    asdrawn = {"small_weights": True, "fatA": True, "fatC1": True, "fatD": True, "narrow": True}
+    for i, (name, (lvl, step, pos)) in enumerate(CAP_CASES.items()):
+        key = LEVEL_NAMES[lvl]
+        out["cap_exact_" + name] = (_swap(lv0, {key: cap_graph(lv0[key], step, pos, 0, 100 + 10 * i)}), dict(asdrawn))
+        out["cap_plus_one_" + name] = (_swap(lv0, {key: cap_graph(lv0[key], step, pos, 1, 105 + 10 * i)}), dict(asdrawn, **{step: False}))
+    out["bank_clash"] = (_swap(lv0, {(0, 0): bank_clash(lv0[(0, 0)])}), dict(asdrawn))
+    lv = {}
+    for key, g in lv0.items():
+        E, empty = g["L"] * g["degree"], empty_set(g["R"])
+        fat = [k for k, v in FAT.items() if v[0] == key]
+        deg = fitted_degrees(g["R"], E, empty, fat_room(fat[0]), 300) if fat else heavy_degrees(g["R"], E, 0, 0, 300, empty)
+        lv[key] = with_in_degrees(g, deg, 301 + key[0] + 10 * key[1])
+    out["empty_outputs"] = (lv, dict(asdrawn, narrow=False))       # (C_2's 31 fed outputs cannot hold its 1638 edges in the narrow slots)
+    lv = dict(lv0)
+    for st, key in enumerate(NARROW_LEVELS):                        # the narrow kernel's own zero outputs: the first and the last of every step
+        g = lv0[key]
+        lv[key] = with_in_degrees(g, fitted_degrees(g["R"], g["L"] * g["degree"], [0, g["R"] - 1], narrow_room(st), 320 + st), 330 + st)
+    out["narrow_empty_outputs"] = (lv, dict(asdrawn))
+    out["hubs"] = (_swap(lv0, {LEVEL_NAMES[k]: hubs(lv0[LEVEL_NAMES[k]], 400) for k in ("C0", "C1", "D0")}), dict(asdrawn))
+    lv = {}
+    for key, g in lv0.items():
+        w = np.array(g["w"], np.uint64).reshape(-1, 2); w[0::3] = 0
+        lv[key] = dict(g, w=w)
+    out["zero_weights"] = (lv, dict(asdrawn))
+    c2 = lv0[(2, 0)]
+    nofat = {"small_weights": False, "fatA": False, "fatC1": False, "fatD": False, "narrow": False}
+    out["one_big_weight_2^32"] = (_swap(lv0, {(2, 0): _set_weight(c2, 777, [1 << 32, 0])}), dict(nofat))
+    out["one_big_weight_(1,1)"] = (_swap(lv0, {(2, 0): _set_weight(c2, 778, [1, 1])}), dict(nofat))
+    return out
+
+
+def encode_messages(n, nb, seed):
+    """nb messages: the families (all_pm1 first: a batch of one is the worst case of the 96-bit sums, not the zero message), then uniform ones"""
+    fam = families(n, seed=seed)
+    fam = np.stack([fam["all_pm1"]] + [v for k, v in fam.items() if k != "all_pm1"])
+    if nb <= len(fam):
+        return np.ascontiguousarray(fam[:nb])
+    return np.concatenate([fam, _splitmix((nb - len(fam)) * n, 6000 + seed).reshape(nb - len(fam), n, 2)])
+
+
+# natural draws: (n, skip) -- the graphs libc draws for n after rng_reset() and generate_randomness(skip) (None: straight after the reset).
+# 2977 / 2978 and 5954 / 5955 are the two sides of the LDS size classes; n = 4096 after two draws is a code with the narrow plan refused.
+NATURAL = [(2977, None), (2978, None), (3000, None), (3333, None), (3500, None), (4000, None), (4095, None), (4097, None), (5954, None),
+           (5955, None), (4096, 2)]
+# the same draws with one weight of C_1 set to 2^32: the single-pass and the tiled chain in their general-weight forms
+NATURAL_FULLW = [(2977, None, "2^32"), (5955, None, "2^32")]
+
+
+def natural_graphs(oracle, case):
+    lv = drawn_graphs(oracle, case[0], case[1])
+    if len(case) > 2:
+        lv = _swap(lv, {(1, 0): _set_weight(lv[(1, 0)], 5, [1 << 32, 0])})
+    return lv
+
+
+def natural_guard(forms):
+    """forms: {case: expected_forms} over NATURAL.  The list as a whole still holds every kind of case it was chosen for (a libc whose
+    draws differ would change which n is which)"""
+    have = {"A refused by cap": False, "A refused by shape": False, "C1 refused": False, "a step exactly at a cap": False,
+            "narrow refused with the fat steps accepted": False, "single pass": False, "tiled": False, "every fat step refused, two passes": False}
+    for f in forms.values():
+        have["single pass"] |= f.size_class == "single"
+        have["tiled"] |= f.size_class == "tiled"
+        if f.size_class != "deep":
+            continue
+        have["A refused by cap"] |= f.why["fatA"] == "cap"
+        have["A refused by shape"] |= f.why["fatA"] == "shape"
+        have["C1 refused"] |= f["fatA"] and f["fatD"] and not f["fatC1"]
+        have["a step exactly at a cap"] |= any(f[s] and f.top[s][j] == FAT[s][3][j] for s in FAT if f.top[s] for j in range(FAT[s][1]))
+        have["narrow refused with the fat steps accepted"] |= f["fatA"] and f["fatC1"] and f["fatD"] and not f["narrow"]
+        have["every fat step refused, two passes"] |= not (f["fatA"] or f["fatC1"] or f["fatD"])
+    assert all(have.values()), [k for k, v in have.items() if not v]

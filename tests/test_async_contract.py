@@ -57,7 +57,7 @@ HOST_RETURNING = {
     "hobbit_sumcheck2_sparse", "hobbit_sumcheck2_eq", "hobbit_gate_sumcheck", "hobbit_sumcheck3", "hobbit_prove_linear_code", "hobbit_prove_fft",
     "hobbit_prove_fft_matrix", "hobbit_batch_3product_sumcheck", "hobbit_mul_tree", "hobbit_compute2p_error_terms", "hobbit_compute3p_error_terms",
     "hobbit_compute4p_error_terms", "hobbit_batch_prod", "hobbit_generate_claims_opt", "hobbit_sumcheck3_stream_batch",
-    "hobbit_mul_tree_stream_shallow", "hobbit_gate_consistency_stream", "hobbit_gate_consistency_lookups_stream", "hobbit_sync",
+    "hobbit_mul_tree_stream_shallow", "hobbit_gate_consistency_stream", "hobbit_gate_consistency_lookups_stream", "hobbit_sync", "hobbit_encode_forms",
 }
 EXEMPT = {
     "hobbit_ctx_create": "creates a context; nothing is queued yet",

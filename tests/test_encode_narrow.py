@@ -67,6 +67,7 @@ def test_narrow_batch_sizes(hb, oracle, big, batch):
     x, out = big
     nb = {"1": 1, "W-1": W - 1, "W": W, "W+1": W + 1, "3W+5": 3 * W + 5}[batch]
     hb.upload_graphs(N, _drawn(oracle))
+    assert hb.encode_forms()["narrow"] is True                   # k_encode_M2 below is k_enc_narrow, not its one-workgroup fallback
     got, ran = encode_with_kernels(hb, x[:nb], in_place=True)
     assert ran == FAT_CHAIN_4096, (batch, ran)
     bad = np.flatnonzero((got != out[:nb]).any(axis=(1, 2)))
@@ -84,6 +85,7 @@ def test_narrow_families_and_weights(hb, oracle, wname):
     if WEIGHTS[wname] is not None:
         lv = set_weights(oracle, lv, WEIGHTS[wname])
     hb.upload_graphs(N, lv)
+    assert hb.encode_forms()["narrow"] is (wname != "full_p-1"), wname
     fams = families(N, seed=N)
     names, x = list(fams), np.stack(list(fams.values()))
     out, ran = encode_with_kernels(hb, x, in_place=False)
@@ -127,6 +129,8 @@ def test_narrow_cap_overflow_falls_back(hb, oracle, case):
     lv = _drawn(oracle)
     lv[key] = _raise_in_degree(lv[key], 0, _first_position_room(step) + 1)
     hb.upload_graphs(N, lv)
+    forms = hb.encode_forms()
+    assert forms["narrow"] is False and forms["fatA"] and forms["fatC1"] and forms["fatD"], (case, forms)
     x = np.concatenate([np.stack(list(families(N, seed=N).values())), splitmix_field(100 * N, 4098).reshape(100, N, 2)])
     got, ran = encode_with_kernels(hb, x, in_place=True)
     assert ran == FAT_CHAIN_4096, (case, ran)
@@ -145,6 +149,7 @@ def test_narrow_no_stale_window(hb, oracle):
     ref, _ = encode_with_kernels(hb, two, in_place=False)
     assert not ref[0].any() and ref[1].any()
     nb = W + 1
+    assert hb.encode_forms()["narrow"] is True
     a, ran = encode_with_kernels(hb, np.broadcast_to(two[1], (nb, N, 2)), in_place=True)
     assert ran == FAT_CHAIN_4096, ran
     b, _ = encode_with_kernels(hb, np.broadcast_to(two[0], (nb, N, 2)), in_place=True)
