@@ -78,6 +78,13 @@ BRAKINGBASE_SYMBOLS = [
 ]
 BRAKINGBASE_QUERIES = 2935
 
+# every symbol include/hobbit_orion.h declares (checked by tests/test_orion.py)
+ORION_SYMBOLS = [
+    "hobbit_encode_interleaved_ld", "hobbit_encode_interleaved_ld_order", "hobbit_orion_gather", "hobbit_orion_grid_paths", "hobbit_orion_shape",
+    "hobbit_orion_commit", "hobbit_orion_free", "hobbit_orion_dims", "hobbit_orion_tensor_dev", "hobbit_orion_levels_dev", "hobbit_orion_root",
+    "hobbit_orion_open", "hobbit_orion_proof_size",
+]
+
 
 class _OpenOut(ctypes.Structure):
     """hobbit_open_out (include/hobbit_hip.h)"""
@@ -177,7 +184,15 @@ def load_library(path=LIB_PATH):
         "hobbit_brakingbase_dims": [V, V, V, V, V], "hobbit_brakingbase_matrix_dev": [V], "hobbit_brakingbase_levels_dev": [V],
         "hobbit_brakingbase_levels": [V, V, V], "hobbit_brakingbase_root": [V, V, V], "hobbit_brakingbase_tensor": [V, V, S, S, V],
         "hobbit_brakingbase_open": [V, V, V, V],
+        # include/hobbit_orion.h
+        "hobbit_encode_interleaved_ld": [V, V, L, S, S], "hobbit_encode_interleaved_ld_order": [V, V, L, S, S, ctypes.c_uint32],
+        "hobbit_orion_gather": [V, V, S, S, V, S, V], "hobbit_orion_grid_paths": [V, V, S, S, V, V, S, V], "hobbit_orion_shape": [S, V, V],
+        "hobbit_orion_commit": [V, V, S, V], "hobbit_orion_free": [V], "hobbit_orion_dims": [V, V, V, V, V], "hobbit_orion_tensor_dev": [V],
+        "hobbit_orion_levels_dev": [V], "hobbit_orion_root": [V, V, V], "hobbit_orion_open": [V, V, V, I, V], "hobbit_orion_proof_size": [V, V, S, V],
     }
+    lib.hobbit_orion_free.restype = None
+    lib.hobbit_orion_tensor_dev.restype = c_vp
+    lib.hobbit_orion_levels_dev.restype = c_vp
     lib.hobbit_brakingbase_free.restype = None
     lib.hobbit_brakingbase_matrix_dev.restype = c_vp
     lib.hobbit_brakingbase_levels_dev.restype = c_vp
@@ -311,6 +326,46 @@ class BrakedownCommitment:
     def free(self):
         if self.h and self.hb.ctx:
             self.hb.lib.hobbit_brakedown_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class OrionCommitment:
+    """Handle on a device-resident Orion commitment (hobbit_orion_commit): the 2B x 2B row-major tensor and the Merkle levels over its N leaves."""
+
+    def __init__(self, hb, handle):
+        self.hb, self.h = hb, handle
+        N, B, Q, ln = c_sz(), c_sz(), c_sz(), c_ll()
+        hb.lib.hobbit_orion_dims(handle, ctypes.byref(N), ctypes.byref(B), ctypes.byref(Q), ctypes.byref(ln))
+        self.N, self.B, self.Q, self.len = N.value, B.value, Q.value, ln.value
+        self.W = 2 * self.B
+        self.tensor_ptr = hb.lib.hobbit_orion_tensor_dev(handle)
+        self.levels_ptr = hb.lib.hobbit_orion_levels_dev(handle)
+
+    def levels(self):
+        return self.hb.to_host(self.levels_ptr, (2 * self.N - 1, 32), np.uint8)
+
+    def root(self):
+        out = np.zeros(32, np.uint8)
+        self.hb._chk(self.hb.lib.hobbit_orion_root(self.hb.ctx, self.h, _hp(out)))
+        return out
+
+    def tensor(self, row_lo=0, nrows=None):
+        """rows [row_lo, row_lo + nrows) of the 2B x 2B tensor: shape (nrows, 2B, 2)"""
+        nrows = self.W - row_lo if nrows is None else nrows
+        return self.hb.to_host(self.tensor_ptr, (nrows, self.W, 2), np.uint64, offset=row_lo * self.W * 16)
+
+    def open(self, x, **kw):
+        return self.hb.orion_open(self, x, **kw)
+
+    def free(self):
+        if self.h and self.hb.ctx:
+            self.hb.lib.hobbit_orion_free(self.h)
         self.h = None
 
     def __del__(self):
@@ -1160,6 +1215,98 @@ class Hobbit:
         out["sp_c"] = self._sp_trim(sp_c, 2 * c.trs, 32)
         out["checks"] = out["parity"]["checks"]
         out["ps"] = float(out["ps"][0])
+        return out
+
+    # ---- the Orion baseline (include/hobbit_orion.h; src/Our_PC.cpp:28-65, 173-195, 523-602; src/PC_utils.cpp:150-166)
+    def encode_interleaved_ld(self, mat, n, width, strip=None):
+        """hobbit_encode_interleaved_ld in place on mat (2n, ld, 2): the messages i < width; strip: the grid order (None: the library's)"""
+        m = Fh(mat); assert m.shape[0] == 2 * n
+        d = self.to_device(m)
+        if strip is None:
+            self._chk(self.lib.hobbit_encode_interleaved_ld(self.ctx, c_vp(d.ptr), c_ll(n), c_sz(width), c_sz(m.shape[1])))
+        else:
+            self._chk(self.lib.hobbit_encode_interleaved_ld_order(self.ctx, c_vp(d.ptr), c_ll(n), c_sz(width), c_sz(m.shape[1]), ctypes.c_uint32(strip)))
+        return self.to_host(d, m.shape, np.uint64)
+
+    def orion_gather(self, T, I):
+        """arr[q][c] = T[c][I[q]]: T a host array (nrows, ld, 2) or (ptr, nrows, ld)"""
+        if isinstance(T, tuple):
+            ptr, nrows, ld = T
+        else:
+            t = Fh(T); nrows, ld = t.shape[0], t.shape[1]; keep = self.to_device(t); ptr = keep.ptr
+        I = np.ascontiguousarray(I, np.uint32)
+        out = self.alloc(max(len(I) * nrows * 16, 16))
+        self._chk(self.lib.hobbit_orion_gather(self.ctx, c_vp(ptr), c_sz(nrows), c_sz(ld), _hp(I), c_sz(len(I)), c_vp(out.ptr)))
+        return self.to_host(out, (len(I), nrows, 2), np.uint64)
+
+    def orion_grid_paths(self, levels, n, cols, I, J):
+        """the len(I)^2 paths of leaves (J[j] / 4) cols + I[i], i outer: levels a host array ((2n - 1), 32) or a device pointer.  Returns the
+        DeviceBuffer (nq^2 x log2 n x 32 B)"""
+        if isinstance(levels, np.ndarray):
+            keep = self.to_device(np.ascontiguousarray(levels, np.uint8)); ptr = keep.ptr
+        else:
+            ptr = int(levels)
+        I = np.ascontiguousarray(I, np.uint32); J = np.ascontiguousarray(J, np.uint32); nq = len(I)
+        out = self.alloc(max(nq * nq * (n.bit_length() - 1) * 32, 16))
+        self._chk(self.lib.hobbit_orion_grid_paths(self.ctx, c_vp(ptr), c_sz(n), c_sz(cols), _hp(I), _hp(J), c_sz(nq), c_vp(out.ptr)))
+        return out
+
+    @staticmethod
+    def orion_shape(N):
+        """(B, Q) of test_PC(N, 2, .): N = 2^n, n even, 14 <= n <= 28"""
+        lib = load_library()
+        B, Q = c_sz(), c_sz()
+        if lib.hobbit_orion_shape(c_sz(N), ctypes.byref(B), ctypes.byref(Q)) != 0:
+            raise HobbitError("orion: N = %d is not served: N = 2^n, n even, 14 <= n <= 28" % N)
+        return B.value, Q.value
+
+    def orion_commit(self, poly, sync=True):
+        """commit_standard_orion: poly is a host array (N, 2) or (DeviceBuffer/ptr, N); the graphs for n = sqrt(N) must be finalized.  Returns an
+        OrionCommitment; sync=False leaves the work queued on the context's stream."""
+        if isinstance(poly, tuple):
+            ptr, N = poly
+            ptr = ptr.ptr if isinstance(ptr, DeviceBuffer) else int(ptr)
+        else:
+            p = Fh(poly).reshape(-1, 2)
+            N = p.shape[0]
+            keep = self.to_device(p); ptr = keep.ptr
+        h = c_vp()
+        self._chk(self.lib.hobbit_orion_commit(self.ctx, c_vp(ptr), c_sz(N), ctypes.byref(h)))
+        if not h.value:
+            raise HobbitError("hobbit_orion_commit returned no handle")
+        if sync or not isinstance(poly, tuple):
+            self.sync()                         # (a host polynomial's device copy is released when this returns)
+        return OrionCommitment(self, h)
+
+    def orion_open(self, c, x, want_paths=True, want_ps=True):
+        """open_orion_standard's prover side.  libc draws on the host in the reference's order.  Returns dict(I, J, c_root, cp_root, p1 (poly, r,
+        vr, fin, r1, r2), parity (as open_parity_matrix), sp_c (as shockwave_prove), checks, paths (a DeviceBuffer of Q^2 x log2 N x 32 B, or
+        None), ps (hobbit_orion_proof_size, or None), stage_ms)"""
+        x = Fh(x).reshape(-1, 2).copy()
+        l = c.W.bit_length() - 1; lq = c.Q.bit_length() - 1; ln = c.N.bit_length() - 1
+        P = self.parity_shape(c.B)[1]
+        po, keep = self._parity_buffers(P, c.B)
+        sp_c, o_c = self._sp_buffers(c.Q * c.W, 32)
+        q, r, vr, fin = self._proof2(l)
+        out = dict(I=np.zeros(c.Q, np.uint32), J=np.zeros(c.Q, np.uint32), c_root=np.zeros(32, np.uint8), cp_root=np.zeros(32, np.uint8),
+                   stage_ms=np.zeros(6, np.float64))
+        r1 = np.zeros((l, 2), np.uint64); r2 = np.zeros((lq, 2), np.uint64)
+        paths = self.alloc(c.Q * c.Q * ln * 32) if want_paths else None
+        ptrs = [out[k].ctypes.data for k in ("I", "J", "c_root", "cp_root")] + [a.ctypes.data for a in (q, r, vr, fin, r1, r2)]
+        ptrs += [ctypes.addressof(po), ctypes.addressof(o_c), paths.ptr if paths else None, out["stage_ms"].ctypes.data]
+        o = (c_vp * len(ptrs))(*ptrs)
+        self._chk(self.lib.hobbit_orion_open(self.ctx, c.h, _hp(x), c_int(x.shape[0]), o))
+        ps = np.zeros(1, np.float64)
+        if want_ps:
+            if self.lib.hobbit_orion_proof_size(c.h, o, c_sz(P), _hp(ps)) != 0:
+                raise HobbitError("hobbit_orion_proof_size refused a finished opening")
+        out["p1"] = dict(poly=q, r=r, vr=vr, fin=fin, r1=r1, r2=r2)
+        out["parity"] = self._parity_result(keep)
+        out["sp_c"] = self._sp_trim(sp_c, c.Q * c.W, 32)
+        out["checks"] = out["parity"]["checks"]
+        out["paths"] = paths
+        out["ps"] = float(ps[0]) if want_ps else None
+        out["P"] = P
         return out
 
     def prove_linear_code_batch(self, codewords, n, r1, r2):

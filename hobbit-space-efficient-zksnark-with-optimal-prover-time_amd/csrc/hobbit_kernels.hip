@@ -3455,6 +3455,73 @@ int launch_encode_ilv(hobbit_ctx *ctx, const F *src, F *dst, uint32_t rows) {
     return launch_zero(ctx, dst + (size_t)c.len * rows, (size_t)(2 * c.n - c.len) * rows * sizeof(F));    // the codewords' zero tail
 }
 
+// The same step on a matrix whose rows are `ld` apart, over its first `width` columns only (hobbit_encode_interleaved_ld): neither need be a
+// power of two, so the thread index is split by a division and not by a shift.  The columns are cut into strips of `strip` (a multiple of 64,
+// so a wave still owns one output and its edge records stay wave-uniform); the grid is STRIP-MAJOR: blocks [s * bps, (s + 1) * bps) walk every
+// output of the step over the columns of strip s, so the workgroups in flight together gather from a window of in_len x strip elements and not
+// from in_len x width.  strip >= width is the plain order of k_enc_ilv (all columns of a few outputs).  Arithmetic as k_enc_ilv, bit for bit.
+template <bool SMALLW>
+__global__ void __launch_bounds__(256)
+k_enc_ilv_ld(F *__restrict__ mat, size_t ld, uint32_t width, uint32_t strip, uint32_t bps, IlvStep st, const uint32_t *__restrict__ ptr,
+             const uint2 *__restrict__ e32, const uint32_t *__restrict__ eidx, const F *__restrict__ ew) {
+    const uint32_t s = blockIdx.x / bps, item = (blockIdx.x - s * bps) * 256 + threadIdx.x;      // out_len * strip < 2^31 (the launcher)
+    const uint32_t t = item / strip, col = s * strip + (item - t * strip);
+    if (t >= st.out_len || col >= width) return;
+    const F *in = mat + (size_t)st.in_off * ld + col;
+    const uint32_t beg = __builtin_amdgcn_readfirstlane(ptr[st.ptr_base + t]), end = __builtin_amdgcn_readfirstlane(ptr[st.ptr_base + t + 1]);
+    F out;
+    if (SMALLW) {
+        Acc96 rl = {0, 0}, rh = {0, 0}, il = {0, 0}, ih = {0, 0};
+        uint32_t e = beg;
+        for (; e + 4 <= end; e += 4) {
+            uint2 r[4]; uint4 x[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) r[u] = e32[e + u];
+#pragma unroll
+            for (int u = 0; u < 4; u++) x[u] = *reinterpret_cast<const uint4 *>(in + (size_t)r[u].x * ld);
+#pragma unroll
+            for (int u = 0; u < 4; u++) acc96_mad4(rl, rh, il, ih, r[u].y, x[u]);
+        }
+        for (; e < end; e++) {
+            const uint2 r = e32[e];
+            acc96_mad4(rl, rh, il, ih, r.y, *reinterpret_cast<const uint4 *>(in + (size_t)r.x * ld));
+        }
+        out = fmake(acc_fold(rl, rh), acc_fold(il, ih));
+    } else {
+        out = fmake(0);
+        for (uint32_t e = beg; e < end; e++) out = fadd(out, fmul(ldF(in + (size_t)eidx[e] * ld), ldF(ew + e)));
+    }
+    stF(mat + (size_t)(st.out_off + t) * ld + col, out);
+}
+// zeros into rows [row_lo, row_lo + nrows) x columns [col_lo, col_lo + ncols) of a matrix whose rows are ld apart
+__global__ void k_zero_rect(F *__restrict__ mat, size_t ld, size_t row_lo, size_t nrows, size_t col_lo, size_t ncols) {
+    const uint4 z = {0, 0, 0, 0};
+    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < nrows * ncols; g += (size_t)gridDim.x * blockDim.x)
+        *reinterpret_cast<uint4 *>(mat + (row_lo + g / ncols) * ld + col_lo + g % ncols) = z;
+}
+int launch_zero_rect(hobbit_ctx *ctx, F *mat, size_t ld, size_t row_lo, size_t nrows, size_t col_lo, size_t ncols) {
+    if (!nrows || !ncols) return 0;
+    HB_LAUNCH(ctx, "k_zero_rect", k_zero_rect, dim3(grid_for(nrows * ncols, 256, 1 << 16)), dim3(256), 0, mat, ld, row_lo, nrows, col_lo, ncols);
+    return 0;
+}
+// in place on the 2n x ld matrix, columns [0, width); strip = 0: the plain order.  The caller has checked 2 n roundup64(width) < 2^31.
+int launch_encode_ilv_ld(hobbit_ctx *ctx, F *mat, uint32_t width, size_t ld, uint32_t strip) {
+    const DeviceCode &c = ctx->code;
+    const uint32_t w64 = (width + 63) / 64 * 64;
+    if (!strip || strip > w64) strip = w64;
+    const uint32_t nstrips = (width + strip - 1) / strip;
+    for (const IlvStep &st : c.isteps) {
+        const uint32_t bps = (uint32_t)(((size_t)st.out_len * strip + 255) / 256);
+        if (c.small_weights)
+            HB_LAUNCH(ctx, "k_enc_ilv_ld", k_enc_ilv_ld<true>, dim3(nstrips * bps), dim3(256), 0, mat, ld, width, strip, bps, st, c.d_ilv_ptr, c.d_ilv_e32,
+                      c.d_ilv_eidx, c.d_ilv_ew);
+        else
+            HB_LAUNCH(ctx, "k_enc_ilv_ld_fullw", k_enc_ilv_ld<false>, dim3(nstrips * bps), dim3(256), 0, mat, ld, width, strip, bps, st, c.d_ilv_ptr,
+                      c.d_ilv_e32, c.d_ilv_eidx, c.d_ilv_ew);
+    }
+    return launch_zero_rect(ctx, mat, ld, (size_t)c.len, (size_t)(2 * c.n - c.len), 0, width);                // the codewords' zero tail
+}
+
 // Column digests of the matrix (MT_commit_Blake over the `rows` entries of column c, src/merkle_tree.cpp:193-221): leaf l = H(rows 4l..4l+3),
 // which is 64 contiguous bytes here.  quirk (create_tree_blake's parent H(left | left), src/merkle_tree.cpp:275-280): the digest is leaf 0
 // re-hashed log2(rows / 4) times, 1 + log2(rows / 4) compressions.  Otherwise the full tree over the rows / 4 leaves (rows <= 512), folded

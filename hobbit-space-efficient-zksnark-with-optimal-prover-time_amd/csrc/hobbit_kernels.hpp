@@ -10,6 +10,9 @@ int ensure_ilv(hobbit_ctx *ctx);
 int parity_segments(hobbit_ctx *ctx, std::vector<ParitySeg> &segs, size_t *m);
 int ensure_fwd(hobbit_ctx *ctx);
 int launch_encode_ilv(hobbit_ctx *ctx, const F *src, F *dst, uint32_t rows);
+// the rows-innermost encode in place on a 2n x ld matrix over its first `width` columns, strip-major (strip: columns per strip, 0 = plain order)
+int launch_encode_ilv_ld(hobbit_ctx *ctx, F *mat, uint32_t width, size_t ld, uint32_t strip);
+int launch_zero_rect(hobbit_ctx *ctx, F *mat, size_t ld, size_t row_lo, size_t nrows, size_t col_lo, size_t ncols);
 // the body of hobbit_brakedown_commit for `rows` messages of B elements (hobbit_capi.hip); the caller has checked the shape and the graphs
 int brakedown_commit_shape(hobbit_ctx *ctx, const F *d_poly, size_t B, uint32_t rows, int left_left_quirk, hobbit_brakedown **out);
 int launch_brakedown_digests(hobbit_ctx *ctx, const F *mat, uint32_t rows, size_t ncols, size_t nz, int quirk, uint8_t *out);

@@ -19,6 +19,7 @@ static hobbit_ctx *g_ctx = nullptr;
 static hobbit_commitment *g_commit = nullptr;
 static hobbit_brakedown *g_bd = nullptr;                            // the last commit_standard_brakedown's matrix and tree
 static hobbit_brakingbase *g_bb = nullptr;                          // the last commit_brakingbase's
+static hobbit_orion *g_or = nullptr;                                // the last commit_standard_orion's
 static void *g_bds_levels = nullptr;                                // the last commit_brakedown_stream's levels
 static int g_commit_K = 0, g_commit_trs = 0; static size_t g_commit_cols = 0;
 static void *g_poly_dev = nullptr; static size_t g_poly_n = 0;      // device copy of the committed polynomial, kept for open_standard
@@ -75,6 +76,7 @@ void hobbit_host_shutdown() {
     if (g_commit) { hobbit_commitment_free(g_commit); g_commit = nullptr; }
     if (g_bd) { hobbit_brakedown_free(g_bd); g_bd = nullptr; }
     if (g_bb) { hobbit_brakingbase_free(g_bb); g_bb = nullptr; }
+    if (g_or) { hobbit_orion_free(g_or); g_or = nullptr; }
     if (g_parity) { hobbit_parity_commitment_free(g_parity); g_parity = nullptr; }
     if (g_bds_levels) { hobbit_free(g_ctx, g_bds_levels); g_bds_levels = nullptr; }
     if (g_poly_dev) { hobbit_free(g_ctx, g_poly_dev); g_poly_dev = nullptr; g_poly_n = 0; }
@@ -1375,6 +1377,22 @@ void open_brakedown_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>>
 
 // ---- Braking base baseline (src/Our_PC.cpp:114-144, 238-256, 355-429, 827-842; src/PC_utils.cpp:389-394; include/hobbit_brakingbase.h) --------
 #ifndef HOBBIT_HOST_REFERENCE_BUILD
+// the host buffers behind one hobbit_parity_open_out, sized by the code length n and the padded list length P, in the last-opening transcript
+static hobbit_parity_open_out parity_open_buffers(hobbit_host_parity_transcript &pt, size_t n, size_t P, SpBuffers &bp, SpBuffers &bw) {
+    const size_t S = 2 * n; const int L = (int)log2((double)P);
+    pt.n = (int)n; pt.P = P;
+    auto tree = [](hobbit_host_parity_transcript::tree &T, size_t size) {
+        const int lt = (int)log2((double)(4 * size)), depth = lt - 2; size_t nr = 1; for (int i = 0; i < lt; i++) nr += (size_t)i;
+        T.cpoly.assign(4 * nr, F(0)); T.r.assign(nr, F(0)); T.vr.assign(3 * (size_t)depth, F(0)); T.fin.assign(depth, F(0)); T.final_r.assign(lt, F(0)); T.layers = 0;
+    };
+    tree(pt.t1, P); tree(pt.t2, S);
+    pt.p2.assign(4 * (size_t)L, F(0)); pt.p2_r.assign(L, F(0)); pt.p3.assign(3 * (size_t)(L + 1), F(0)); pt.p3_r.assign(L + 1, F(0)); pt.p4.assign(3 * (size_t)(L + 3), F(0)); pt.p4_r.assign(L + 3, F(0));
+    return hobbit_parity_open_out{hF(pt.t1.cpoly.data()), hF(pt.t1.r.data()), hF(pt.t1.vr.data()), hF(pt.t1.fin.data()), hF(pt.t1.final_r.data()), hF(pt.t1.evals), &pt.t1.layers,
+                                  hF(pt.t2.cpoly.data()), hF(pt.t2.r.data()), hF(pt.t2.vr.data()), hF(pt.t2.fin.data()), hF(pt.t2.final_r.data()), hF(pt.t2.evals), &pt.t2.layers,
+                                  hF(pt.p2.data()), hF(pt.p2_r.data()), hF(pt.p2_vr), hF(&pt.p2_fin), hF(pt.p3.data()), hF(pt.p3_r.data()), hF(pt.p3_vr), hF(&pt.p3_fin),
+                                  hF(pt.p4.data()), hF(pt.p4_r.data()), hF(pt.p4_vr), hF(&pt.p4_fin), pt.cw_root, hF(pt.scalars), hF(pt.partial), hF(pt.acc_y), pt.checks, &bp.o, &bw.o,
+                                  nullptr};
+}
 static hobbit_host_brakingbase_transcript g_bb_open;
 hobbit_host_brakingbase_transcript &hobbit_host_last_brakingbase() { return g_bb_open; }
 void commit_brakingbase(vector<F> &poly, vector<vector<_hash>> &MT_hashes) {                                     // (:114-144)
@@ -1421,21 +1439,10 @@ void open_brakingbase(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_ha
     // the parity transcript's buffers are sized by P, which the list length of the code decides: hobbit_parity_shape tells it on the host (no draws)
     size_t P = 0;
     HCHK(hobbit_parity_shape(hobbit_host_ctx(), (long long)trs, nullptr, &P));
-    const int L = (int)log2((double)P);
     hobbit_host_brakingbase_transcript &t = g_bb_open;
-    hobbit_host_parity_transcript &pt = hobbit_host_last_parity_open(); pt.n = (int)trs; pt.P = P;
-    auto tree = [](hobbit_host_parity_transcript::tree &T, size_t size) {
-        const int lt = (int)log2((double)(4 * size)), depth = lt - 2; size_t nr = 1; for (int i = 0; i < lt; i++) nr += (size_t)i;
-        T.cpoly.assign(4 * nr, F(0)); T.r.assign(nr, F(0)); T.vr.assign(3 * (size_t)depth, F(0)); T.fin.assign(depth, F(0)); T.final_r.assign(lt, F(0)); T.layers = 0;
-    };
-    tree(pt.t1, P); tree(pt.t2, S);
-    pt.p2.assign(4 * (size_t)L, F(0)); pt.p2_r.assign(L, F(0)); pt.p3.assign(3 * (size_t)(L + 1), F(0)); pt.p3_r.assign(L + 1, F(0)); pt.p4.assign(3 * (size_t)(L + 3), F(0)); pt.p4_r.assign(L + 3, F(0));
+    hobbit_host_parity_transcript &pt = hobbit_host_last_parity_open();
     SpBuffers bp(pt.sp_p, 8 * P, 16), bw(pt.sp_w, 2 * P, 16), bc(t.sp_c, S, 32);
-    hobbit_parity_open_out po = {hF(pt.t1.cpoly.data()), hF(pt.t1.r.data()), hF(pt.t1.vr.data()), hF(pt.t1.fin.data()), hF(pt.t1.final_r.data()), hF(pt.t1.evals), &pt.t1.layers,
-                                 hF(pt.t2.cpoly.data()), hF(pt.t2.r.data()), hF(pt.t2.vr.data()), hF(pt.t2.fin.data()), hF(pt.t2.final_r.data()), hF(pt.t2.evals), &pt.t2.layers,
-                                 hF(pt.p2.data()), hF(pt.p2_r.data()), hF(pt.p2_vr), hF(&pt.p2_fin), hF(pt.p3.data()), hF(pt.p3_r.data()), hF(pt.p3_vr), hF(&pt.p3_fin),
-                                 hF(pt.p4.data()), hF(pt.p4_r.data()), hF(pt.p4_vr), hF(&pt.p4_fin), pt.cw_root, hF(pt.scalars), hF(pt.partial), hF(pt.acc_y), pt.checks, &bp.o, &bw.o,
-                                 nullptr};
+    hobbit_parity_open_out po = parity_open_buffers(pt, trs, P, bp, bw);
     t.I.assign(Q, 0); t.reply.assign(Q * K, F(0)); t.paths.assign(Q * (size_t)l * 32, 0); t.aggr.assign(trs, F(0));
     t.p1_q.assign(3 * (size_t)l, F(0)); t.p1_r.assign(l, F(0)); t.p1_r1.assign(l, F(0));
     hobbit_brakingbase_open_out o = {t.I.data(), hF(t.reply.data()), t.paths.data(), hF(t.aggr.data()), t.cc_root, t.cp_root, hF(t.p1_q.data()), hF(t.p1_r.data()), hF(t.p1_vr),
@@ -1473,6 +1480,103 @@ void test_brakingbase(size_t N, int K) {                                        
     printf("\n");
     start = std::chrono::steady_clock::now();
     open_brakingbase(poly, generate_randomness((int)log2((double)poly.size())), MT_hashes);
+    end = std::chrono::steady_clock::now();
+    elapsed_seconds += std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    std::cout << "Total time: " << elapsed_seconds << " seconds" << std::endl;
+}
+
+// ---- Orion baseline (src/Our_PC.cpp:28-65, 173-195, 523-602, 780-793; src/PC_utils.cpp:150-166; include/hobbit_orion.h) ----------------------
+static hobbit_host_orion_transcript g_or_open;
+hobbit_host_orion_transcript &hobbit_host_last_orion() { return g_or_open; }
+static void orion_release() { if (g_or) { hobbit_orion_free(g_or); g_or = nullptr; } }
+void _compute_tensorcode_linear_code(vector<F> &message, vector<vector<F>> &tensor) {                            // (:28-65)
+    // the 2B x 2B tensor of a host message through the device: rows by the batch encode, columns by the strided rows-innermost encode
+    const size_t rows = tensor.empty() ? 2 * (size_t)tensor_row_size : tensor.size(), B = rows / 2;
+    const size_t S = tensor.empty() ? 2 * message.size() / (size_t)tensor_row_size : tensor[0].size();
+    if (S != rows || message.size() != B * B) { printf("Error: _compute_tensorcode_linear_code serves the square tensor of the Orion baseline\n"); exit(-1); }
+    tensor.resize(rows);
+    DevBuf m(message.data(), B * B * sizeof(F)), T(S * S * sizeof(F));
+    HCHK(hobbit_memset(g_ctx, T.p, 0, S * S * sizeof(F)));
+    HCHK(hobbit_encode_batch(g_ctx, (const hobbit_F *)m.p, (hobbit_F *)T.p, (long long)B, B, B, S));
+    HCHK(hobbit_encode_interleaved_ld(g_ctx, (hobbit_F *)T.p, (long long)B, S, S));
+    for (size_t i = 0; i < rows; i++) { tensor[i].resize(S); HCHK(hobbit_memcpy_d2h(g_ctx, tensor[i].data(), (const char *)T.p + i * S * sizeof(F), S * sizeof(F))); }
+    printf("OK\n");
+}
+void commit_standard_orion(vector<F> &poly, _hash &comm, vector<vector<_hash>> &MT_hashes) {                      // (:173-195)
+    (void)comm;                                                      // the reference never writes it either
+    const size_t N = poly.size(); size_t B = 0;
+    if (hobbit_orion_shape(N, &B, nullptr) != 0) { printf("Error: Orion takes N = 2^n with n even and 14 <= n <= 28\n"); exit(-1); }
+    BUFFER_SPACE = B;
+    expander_init_store((long long)B);                               // (:176-178: the graphs of the code, drawn here)
+    orion_release();
+    DevBuf d(poly.data(), N * sizeof(F));
+    HCHK(hobbit_orion_commit(hobbit_host_ctx(), (const hobbit_F *)d.p, N, &g_or));
+    HCHK(hobbit_sync(g_ctx));
+    printf("OK\n");                                                  // _compute_tensorcode_linear_code's line (:63)
+    // MT_hashes: the tensor and its N-leaf tree stay on the device (16 GB of levels at 2^28); the host gets the level sizes and the root
+    const size_t levels = (size_t)log2((double)N) + 1;
+    MT_hashes.assign(levels, vector<_hash>());
+    MT_hashes.back().resize(1);
+    HCHK(hobbit_orion_root(g_ctx, g_or, MT_hashes.back()[0].arr));
+}
+void recursive_prover_orion(vector<vector<F>> &codewords, double &vt, double &ps) {                             // src/PC_utils.cpp:150-166
+    printf("%d,%d\n", (int)codewords.size(), (int)codewords[0].size());
+    vector<F> arr;
+    for (auto &c : codewords) arr.insert(arr.end(), c.begin(), c.end());
+    auto t1 = std::chrono::steady_clock::now();
+    shockwave_data *C = shockwave_commit(arr, 32);
+    printf("%lf\n", std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t1).count());
+    const int n = (int)(codewords[0].size() / 2);
+    commit_parity_matrix(n);
+    proof P1 = prove_linear_code_batch(codewords, n, vt, ps);
+    open_parity_matrix(P1.randomness[0], P1.randomness[1], n, vt, ps);
+    vector<F> r = P1.randomness[0]; r.insert(r.end(), P1.randomness[2].begin(), P1.randomness[2].end());
+    shockwave_prove(C, r, vt, ps);
+}
+void open_orion_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>> &Commitment_MT) {                  // (:523-602)
+    (void)Commitment_MT;
+    if (!g_or) { printf("Error: open_orion_standard without commit_standard_orion\n"); exit(-1); }
+    size_t N = 0, B = 0, Q = 0;
+    hobbit_orion_dims(g_or, &N, &B, &Q, nullptr);
+    if (poly.size() != N) { printf("Error: open_orion_standard on a polynomial of another size\n"); exit(-1); }
+    BUFFER_SPACE = B;
+    const size_t S = 2 * B; const int l = (int)log2((double)S), lq = (int)log2((double)Q);
+    size_t P = 0;
+    HCHK(hobbit_parity_shape(hobbit_host_ctx(), (long long)B, nullptr, &P));
+    hobbit_host_orion_transcript &t = g_or_open;
+    hobbit_host_parity_transcript &pt = hobbit_host_last_parity_open();
+    SpBuffers bp(pt.sp_p, 8 * P, 16), bw(pt.sp_w, 2 * P, 16), bc(t.sp_c, Q * S, 32);
+    hobbit_parity_open_out po = parity_open_buffers(pt, B, P, bp, bw);
+    t.I.assign(Q, 0); t.J.assign(Q, 0); t.p1_q.assign(3 * (size_t)l, F(0)); t.p1_r.assign(l, F(0)); t.p1_r1.assign(l, F(0)); t.p1_r2.assign(lq, F(0));
+    // the Q^2 opening paths are not produced here: they are 15 GB at 2^28 and the reference only counts them (:582-595)
+    hobbit_orion_open_out o = {t.I.data(), t.J.data(), t.c_root, t.cp_root, hF(t.p1_q.data()), hF(t.p1_r.data()), hF(t.p1_vr), hF(&t.p1_fin), hF(t.p1_r1.data()),
+                               hF(t.p1_r2.data()), &po, &bc.o, nullptr, t.stage_ms};
+    printf("%d,%d\n", (int)Q, (int)S);                               // recursive_prover_orion's line (src/PC_utils.cpp:152)
+    HCHK(hobbit_orion_open(g_ctx, g_or, hF(x.data()), (int)x.size(), &o));
+    if (t.p1_q[0] + t.p1_q[1] + t.p1_q[2] + t.p1_q[2] != F(0)) printf("Error in codeword\n");                   // q(0) + q(1) of P1's first round (src/sumcheck.cpp:3214)
+    if (!pt.checks[0]) { printf("Error 1\n"); exit(-1); }
+    if (!pt.checks[1]) { printf("Error 2\n"); exit(-1); }
+    for (auto *sp : {&pt.sp_p, &pt.sp_w, &t.sp_c}) if (sp->iters && !(sp->wchecks[0] && sp->wchecks[1])) { printf("Error in final verification step\n"); exit(-1); }
+    // (:571-595) the accounting, `visited` all false at the start; vt is what remains of the verifier here
+    auto t1 = std::chrono::steady_clock::now();
+    if (hobbit_orion_proof_size(g_or, &o, P, &t.ps) != 0) { printf("Error: the proof size needs a finished opening\n"); exit(-1); }
+    t.vt = std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t1).count();
+    printf(" ps = %lf, vt = %lf\n", t.ps, t.vt);
+}
+void test_orion(size_t N) {                                                                                      // (:757-761, 780-793)
+    if (hobbit_orion_shape(N, nullptr, nullptr) != 0) { printf("Error: Orion takes N = 2^n with n even and 14 <= n <= 28\n"); exit(-1); }
+    vector<F> poly = generate_randomness((int)N);
+    vector<vector<_hash>> hashes; _hash comm;
+    auto start = std::chrono::steady_clock::now();
+    commit_standard_orion(poly, comm, hashes);
+    auto end = std::chrono::steady_clock::now();
+    double elapsed_seconds = std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    start = std::chrono::steady_clock::now();
+    std::cout << "Commit time: " << elapsed_seconds << " seconds" << std::endl;
+    printf("root ");
+    for (int i = 0; i < 32; i++) printf("%02x", hashes.back()[0].arr[i]);
+    printf("\n");
+    open_orion_standard(poly, generate_randomness((int)log2((double)N)), hashes);
     end = std::chrono::steady_clock::now();
     elapsed_seconds += std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
     std::cout << "Total time: " << elapsed_seconds << " seconds" << std::endl;

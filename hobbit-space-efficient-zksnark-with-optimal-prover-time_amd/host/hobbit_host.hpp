@@ -17,6 +17,7 @@
 #include "hobbit_parity_lists.h"
 #include "hobbit_whir.h"
 #include "hobbit_brakingbase.h"
+#include "hobbit_orion.h"
 
 using std::vector;
 
@@ -274,6 +275,28 @@ struct hobbit_host_brakingbase_transcript {
 };
 hobbit_host_brakingbase_transcript &hobbit_host_last_brakingbase();       /* the parity part: hobbit_host_last_parity_open() */
 void test_brakingbase(size_t N, int K);
+#endif
+/* src/Our_PC.cpp:28-65, 173-195, 523-602, 780-793 ; src/PC_utils.cpp:150-166: the Orion comparison baseline (test_PC option 2), on the device
+ * through include/hobbit_orion.h.  commit_standard_orion draws the graphs of n = sqrt(N) as the reference does, prints its "OK" line and keeps
+ * the tensor AND its tree on the device (the tree has N leaves: 16 GB of levels at 2^28); MT_hashes gets the level count and the root.
+ * open_orion_standard is one hobbit_orion_open (libc draws in the reference's order) without the Q^2 opening paths -- the reference only
+ * counts them, and this mirror never materialises them on the host -- then hobbit_orion_proof_size; it exits on the reference's checks and
+ * prints its " ps = .., vt = .." line.  recursive_prover_orion is the reference's sequence over this mirror's own entry points (host vectors
+ * in); _compute_tensorcode_linear_code returns the square tensor of a host message.  test_PC itself keeps refusing option 2: the driver is
+ * test_orion, reached as `host/test_pc orion <logN>`; a shape the library does not serve prints an error and exits with -1 before anything is
+ * drawn.  Left out of the build that sits in front of the reference's objects, which has the reference's own. */
+#ifndef HOBBIT_HOST_REFERENCE_BUILD
+void _compute_tensorcode_linear_code(vector<F> &message, vector<vector<F>> &tensor);
+void commit_standard_orion(vector<F> &poly, _hash &comm, vector<vector<_hash>> &MT_hashes);
+void open_orion_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>> &Commitment_MT);
+void recursive_prover_orion(vector<vector<F>> &codewords, double &vt, double &ps);
+/* the messages of the last open_orion_standard (the reference returns none); layouts as hobbit_orion_open_out */
+struct hobbit_host_orion_transcript {
+    vector<uint32_t> I, J; vector<F> p1_q, p1_r, p1_r1, p1_r2; F p1_vr[2], p1_fin; uint8_t c_root[32], cp_root[32];
+    hobbit_host_shockwave_transcript sp_c; double stage_ms[6] = {0, 0, 0, 0, 0, 0}, ps = 0, vt = 0;
+};
+hobbit_host_orion_transcript &hobbit_host_last_orion();                   /* the parity part: hobbit_host_last_parity_open() */
+void test_orion(size_t N);
 #endif
 /* src/PC_utils.cpp:6-7 ; src/linear_code_encode.cpp:3-4 ; src/sumcheck.cpp:27,29 : globals of the reference ABI.  C_f / C_c are set by
  * this mirror's shockwave users as the reference's _aggregate / aggregate do; scratch / __encode_initialized exist for source

@@ -2,7 +2,8 @@
 // option 3: the Brakedown baseline, K unused) and `elastic <logN> <logB> <opt>` (Elastic_PC options 1 and 2; option 3: the streaming
 // Brakedown baseline, which sets its own buffer size, so <logB> is ignored there as in the reference) and `whir <logN>` (the standalone WHIR
 // baseline: test_PC's last branch, which test_PC itself keeps refusing) and `brakingbase <logN> <K>` (the Braking base baseline: test_PC's
-// option 5, which test_PC itself keeps refusing; shapes outside 4 <= K <= 512, 128 <= N / K <= 2^20 print an error and return 255)
+// option 5, which test_PC itself keeps refusing; shapes outside 4 <= K <= 512, 128 <= N / K <= 2^20 print an error and return 255) and
+// `orion <logN>` (the Orion baseline: test_PC's option 2, which test_PC itself keeps refusing; logN even in [14, 28], else an error and 255)
 // (src/main.cpp:1176: test_PC(1ULL<<atoi(argv[1]), atoi(argv[2]), atoi(argv[3]))) over the
 // device-backed host mirror.  Build: see __graft_entry__.build_host().
 #include <cstdio>
@@ -12,11 +13,18 @@
 int main(int argc, char **argv) {
     const bool whir = argc == 3 && std::string(argv[1]) == "whir";
     const bool bbase = argc == 4 && std::string(argv[1]) == "brakingbase";
-    if (argc < 4 && !whir) {
-        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>\n", argv[0], argv[0], argv[0], argv[0]);
+    const bool orion = argc == 3 && std::string(argv[1]) == "orion";
+    if (argc < 4 && !whir && !orion) {
+        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>   |   %s orion <logN>\n", argv[0], argv[0], argv[0],
+               argv[0], argv[0]);
         return 1;
     }
     init_hash();
+    if (orion) {                                      // src/Our_PC.cpp:780-793
+        const int logn = atoi(argv[2]);
+        if (logn < 14 || logn > 28 || (logn & 1)) { printf("Error: Orion takes N = 2^n with n even and 14 <= n <= 28\n"); return 255; }
+        test_orion(1ULL << logn);
+    } else
     if (bbase) {                                      // src/Our_PC.cpp:827-842
         const int logn = atoi(argv[2]);
         if (logn < 1 || logn > 40) { printf("Error: Braking base takes N, K powers of two with 4 <= K <= 512 and 128 <= N / K <= 2^20\n"); return 255; }
