@@ -5,7 +5,9 @@
 #include <cstdio>
 #include <chrono>
 #include <cstring>
+#include <condition_variable>
 #include <map>
+#include <mutex>
 #include <thread>
 #include <functional>
 #include "hobbit_kernels.hpp"
@@ -964,10 +966,11 @@ int hobbit_eq_table(hobbit_ctx *ctx, const hobbit_F *h_r, int k, hobbit_F *d_out
     if (k < 0 || k > 34) return ctx->fail(HOBBIT_EINVAL, "eq_table: bad k");
     return launch_eq_table(ctx, cF(h_r), k, mF(d_out));
 }
-int hobbit_eval_vector(hobbit_ctx *ctx, const hobbit_F *d_v, size_t n, const hobbit_F *h_r, hobbit_F *h_out) {
+// the evaluation left on the device: *d_res points at it (in ctx->workspace, or d_v itself for n = 1), valid until the workspace's next user
+static int eval_vector_dev(hobbit_ctx *ctx, const hobbit_F *d_v, size_t n, const hobbit_F *h_r, const F **d_res) {
     int lg = ilog2_exact(n);
     if (lg < 0) return ctx->fail(HOBBIT_EINVAL, "eval_vector: n must be a power of two");
-    if (lg == 0) return hobbit_memcpy_d2h(ctx, h_out, d_v, sizeof(F));
+    if (lg == 0) { *d_res = cF(d_v); return 0; }
     F *ws; HB_TRY(ctx->workspace((n / 2 + n / 4 + 2) * sizeof(F), (void **)&ws));
     F *a = ws, *b = ws + n / 2;
     const F *src = cF(d_v);
@@ -984,7 +987,11 @@ int hobbit_eval_vector(hobbit_ctx *ctx, const hobbit_F *d_v, size_t n, const hob
         HB_TRY(launch_eval_tail(ctx, src, dst, n >> i, lg - i, rt.data()));
         src = dst;
     }
-    return hobbit_memcpy_d2h(ctx, h_out, src, sizeof(F));
+    *d_res = src; return 0;
+}
+int hobbit_eval_vector(hobbit_ctx *ctx, const hobbit_F *d_v, size_t n, const hobbit_F *h_r, hobbit_F *h_out) {
+    const F *d_res; HB_TRY(eval_vector_dev(ctx, d_v, n, h_r, &d_res));
+    return hobbit_memcpy_d2h(ctx, h_out, d_res, sizeof(F));       // a public call: h_out is final on return
 }
 
 // ---- tensor code / commit ---------------------------------------------------------------------
@@ -2873,7 +2880,8 @@ int hobbit_gate_consistency_lookups_stream(hobbit_ctx *ctx, hobbit_trace_source 
 //               them the query answers (which feed nothing) go to helper2's stream, P1 -> P2 -> P3 -> P4 stay on the caller's thread and stream;
 //               after P4, shockwave_prove(C_c) runs on the helper context from a second host thread beside P5 -> shockwave_prove(C_f).  Each
 //               chain is a sequence of small dependent launches and host round trips that leaves the GPU mostly idle on its own.
-//               Events: side_ev[62] tensor code final (main -> helper2), [63] inner commitments final, [60] query answers final (-> main).
+//               Events: side_ev[62] tensor code final (main -> helper2), [63] inner commitments final, [60] query answers final (-> main),
+//               [61] main stream at the end of P4 (-> helper: C).  The stream is never drained in mid-chain.
 struct OpenRun {
     hobbit_ctx *ctx; const hobbit_F *d_poly; size_t N; const hobbit_commitment *c; const hobbit_F *h_x; int queries; hobbit_open_out *o; bool full, overlapped;
     OpenTrace tr; StageScope sc;
@@ -2881,13 +2889,22 @@ struct OpenRun {
     F *d_aggr, *BIG, *Mp, *C, *Tcm, *d_s, *d_ev, *d_ac, *d_b1, *tmpv, *encf, *encc; uint64_t *tmpi; uint8_t *lvf, *lvc;       // device arena
     std::vector<F> beta, sv, r1; std::vector<uint32_t> qc, qr; std::vector<uint64_t> Iv; F s2, a; size_t nnz = 0;      // host: beta over the chunk variables, the libc draws, buff2's length
     hobbit_F *Q1, *Q2, *Q3, *Q4, *Q5, *Rr1, *Rr2, *Rr3, *Rr4, *Rr5;                                                    // the output cursors of P1..P5
-    std::thread q_thread, sp_thread; ShockPlan plan_c; int sp_rc = 0;      // overlapped only: the hand-over of the query answers, shockwave_prove(C_c) with its libc draws
+    F y1 = {}, *y1_pin = nullptr;                                          // y1 and the pinned slot its read-back lands in (y1_p5, finish)
+    ShockPlan plan_c, plan_f;                                              // the libc draws of shockwave_prove(C_c) and (C_f), taken in libc_draws
+    // overlapped only: the hand-over of the query answers; shockwave_prove(C_c) on the helper context.  Its thread is started in libc_draws,
+    // while the GPU is busy, and parks on sp_cv until start_prove_cc lets it run (sp_go = 1) or the destructor sends it home (-1).
+    std::thread q_thread, sp_thread; int sp_rc = 0;
+    std::mutex sp_mu; std::condition_variable sp_cv; int sp_go = 0; bool cc_on_helper = false;
+    void sp_signal(int go) { { std::lock_guard<std::mutex> lk(sp_mu); if (sp_go == 0) sp_go = go; } sp_cv.notify_one(); }
     OpenRun(hobbit_ctx *ctx_, const hobbit_F *d_poly_, size_t N_, const hobbit_commitment *c_, const hobbit_F *h_x_, int queries_, hobbit_open_out *o_, bool full_)
         : ctx(ctx_), d_poly(d_poly_), N(N_), c(c_), h_x(h_x_), queries(queries_), o(o_), full(full_), tr(ctx_), sc(ctx_) {
         const char *ot_env = getenv("HOBBIT_OPEN_THREADS");
         overlapped = full && o->sp_c && !(ot_env && ot_env[0] == '0') && ctx->prof_on != 1 && !tr.drain;
     }
-    ~OpenRun() { for (std::thread *t : {&sp_thread, &q_thread}) if (t->joinable()) t->join(); }       // every return path joins its threads
+    ~OpenRun() {            // every return path joins its threads; a worker still parked leaves without running
+        if (sp_thread.joinable()) sp_signal(-1);
+        for (std::thread *t : {&sp_thread, &q_thread}) if (t->joinable()) t->join();
+    }
     int dims_beta_first_draw(const int *dims) {
         tr.mark("entry (stream drain)");
         if (c && !c->lin) return ctx->fail(HOBBIT_EINVAL, "open_core: only the RS x expander (linear_time) code is built");
@@ -2976,8 +2993,11 @@ struct OpenRun {
     // Every libc draw of the opening after r_v[0], in the reference's order -- queries (:633-641), s (src/PC_utils.cpp:293), r1
     // (prove_linear_code's generate_randomness, src/sumcheck.cpp:3225), s2 (:331), a (:342) -- none depends on device data, and nothing between
     // them draws.  Taken here, while the GPU still works through the aggregate's tensor code and inner commitments queued above: the GPU
-    // never waits for the host later.  (shockwave_prove's own draws follow P4, where the reference runs that proof.)
-    void libc_draws() {
+    // never waits for the host later.  The reference's next draws after `a` are those of shockwave_prove(C_c) and then of shockwave_prove(C_f)
+    // (P3, P4 and P5 draw nothing, and nothing else in those two proofs draws), and they depend on sizes alone: both plans are drawn here
+    // too, in that order, under either schedule.  The overlapped schedule also starts the thread of shockwave_prove(C_c) here; it parks
+    // until P4 has returned, so that neither the plan nor a thread start stands between P4 and y1.
+    int libc_draws() {
         qc.resize(queries); qr.resize(queries); Iv.resize(queries); sv.resize(cols); r1.resize(R1);
         for (int q = 0; q < queries; q++) { qc[q] = (uint32_t)(rand() % (long)cols); qr[q] = (uint32_t)(rand() % (long)rows2); Iv[q] = qc[q] + cols * (uint64_t)qr[q]; }
         sv[0] = fmake((uint64_t)random()); o->scalars[1] = *reinterpret_cast<hobbit_F *>(&sv[0]);
@@ -2986,7 +3006,23 @@ struct OpenRun {
         a = fmake((uint64_t)random()); o->scalars[3] = *reinterpret_cast<const hobbit_F *>(&a);
         if (o->cols) memcpy(o->cols, qc.data(), 4 * (size_t)queries);
         if (o->rows) memcpy(o->rows, qr.data(), 4 * (size_t)queries);
+        if (full) {
+            if (shockwave_plan(nc_el, 32, plan_c) != 0) return ctx->fail(HOBBIT_EINVAL, "open: C_c has no shockwave plan");
+            if (shockwave_plan(M, 32, plan_f) != 0) return ctx->fail(HOBBIT_EINVAL, "open: C_f has no shockwave plan");
+        }
+        if (overlapped) {
+            hobbit_ctx *hc = ctx->helper;
+            try {       // (this object outlives the thread: its destructor releases and joins it)
+                sp_thread = std::thread([this, hc] {
+                    hipSetDevice(hc->device);
+                    { std::unique_lock<std::mutex> lk(sp_mu); sp_cv.wait(lk, [this] { return sp_go != 0; }); if (sp_go < 0) return; }
+                    sp_rc = shockwave_prove_run(hc, reinterpret_cast<hobbit_F *>(C), reinterpret_cast<hobbit_F *>(encc), lvc, nc_el, 32, Rr4, R3 - 1, o->sp_c, plan_c);
+                });
+                cc_on_helper = true;
+            } catch (const std::exception &) { /* no thread: the proof runs on this context where the serial schedule runs it */ }
+        }
         tr.mark("libc draws");
+        return 0;
     }
     // replies (:291-305) and Merkle paths (:645-647) at the drawn positions.  Without a commitment (multi-GPU open) they are the caller's business.
     int query_answers() {
@@ -3073,48 +3109,61 @@ struct OpenRun {
         tr.mark("betas, P4");
         return 0;
     }
-    int prove_cc() {        // shockwave_prove(C_c, P4.r minus its last entry) (src/PC_utils.cpp:368)
-        HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<hobbit_F *>(C), reinterpret_cast<hobbit_F *>(encc), lvc, nc_el, 32, Rr4, R3 - 1, o->sp_c));
+    int prove_cc() {        // shockwave_prove(C_c, P4.r minus its last entry) (src/PC_utils.cpp:368), its draws taken in libc_draws
+        HB_TRY(shockwave_prove_run(ctx, reinterpret_cast<hobbit_F *>(C), reinterpret_cast<hobbit_F *>(encc), lvc, nc_el, 32, Rr4, R3 - 1, o->sp_c, plan_c));
         tr.mark("shockwave_prove C_c");
         return 0;
     }
     // Overlapped, where the reference runs shockwave_prove(C_c): nothing after that proof depends on it and every challenge in it is a libc draw.
-    // So its draws are taken HERE, on the calling thread (ShockPlan); the proof runs on the helper context from a second host thread.
+    // Its draws were taken in libc_draws, on the calling thread (ShockPlan); the proof runs on the helper context from the second host thread
+    // parked there.  Nothing is drained: P4's challenges are host values, final when p4() has returned, and events order the device data for
+    // the helper's stream -- side_ev[61] for C (this stream's, recorded here), side_ev[63] for encc and lvc (the commitments ran on helper2's).
     int start_prove_cc() {
         if (overlapped) {
+            if (cc_on_helper) {
+                hobbit_ctx *hc = ctx->helper;
+                HB_CHECK(ctx, hipEventRecord(ctx->side_ev[61], ctx->stream)); HB_CHECK(ctx, hipStreamWaitEvent(hc->stream, ctx->side_ev[61], 0));
+                HB_CHECK(ctx, hipStreamWaitEvent(hc->stream, ctx->side_ev[63], 0));
+                sp_signal(1);
+            }
             if (c) HB_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[60], 0));      // the query answers (their read-back is staged) ...
             HB_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[63], 0));             // ... and the inner commitments are complete from here on
             HB_TRY(read_roots());
-            if (shockwave_plan(nc_el, 32, plan_c) != 0) return ctx->fail(HOBBIT_EINVAL, "open: C_c has no shockwave plan");
-            HB_TRY(ctx->sync());                                                             // C, encc, lvc and P4's challenges are final ...
-            hobbit_ctx *hc = ctx->helper;
-            HB_CHECK(ctx, hipStreamWaitEvent(hc->stream, ctx->side_ev[63], 0));              // ... for the helper's stream too (the commitments ran on helper2's)
-            try {       // (this object outlives the thread: its destructor joins)
-                sp_thread = std::thread([this, hc] {
-                    hipSetDevice(hc->device);
-                    sp_rc = shockwave_prove_run(hc, reinterpret_cast<hobbit_F *>(C), reinterpret_cast<hobbit_F *>(encc), lvc, nc_el, 32, Rr4, R3 - 1, o->sp_c, plan_c);
-                });
-            } catch (const std::exception &e) { return ctx->fail(HOBBIT_ESTATE, std::string("open: cannot start the helper thread: ") + e.what()); }
         }
-        tr.mark("  plan C_c, drain, helper thread started");
+        tr.mark("  helper released (events, no drain)");
         return 0;
     }
     // y1 = evaluate_vector(M', P4.r minus its last entry) (:372-373); P5 = prove_fft_matrix(initial tensor, r, y1) (:383)
+    // Nothing on the chain needs y1 on the host: P5 takes P4.r, and y1 feeds only scalars[4] and the check against P5's first polynomial.
+    // So it is read back like every other result of the opening -- a copy into the pinned staging arena queued behind the last fold, read
+    // after the closing synchronisation -- and the check is made there (finish): no copy into pageable memory and no drain between P4 and P5.
     int y1_p5() {
-        F y1;
-        HB_TRY(hobbit_eval_vector(ctx, reinterpret_cast<hobbit_F *>(Mp), nc_el, Rr4, reinterpret_cast<hobbit_F *>(&y1)));
-        o->scalars[4] = *reinterpret_cast<hobbit_F *>(&y1);
+        const F *d_y1;
+        HB_TRY(eval_vector_dev(ctx, reinterpret_cast<hobbit_F *>(Mp), nc_el, Rr4, &d_y1));
+        y1_pin = static_cast<F *>(ctx->stage_alloc(sizeof(F)));
+        if (y1_pin) HB_CHECK(ctx, hipMemcpyAsync(y1_pin, d_y1, sizeof(F), hipMemcpyDeviceToHost, ctx->stream));      // (in stream order before P5 re-uses the workspace d_y1 lies in)
+        else HB_TRY(hobbit_memcpy_d2h(ctx, reinterpret_cast<hobbit_F *>(&y1), d_y1, sizeof(F)));                    // arena full: the synchronous copy
         tr.mark("  y1 = evaluate_vector");
         HB_TRY(hobbit_prove_fft_matrix(ctx, reinterpret_cast<hobbit_F *>(d_aggr), (size_t)trs, cols / 2, Rr4, Q5, Rr5, o->vr + 8, o->fin + 4));
-        { CHP q5 = cF(Q5); F c5 = fadd(fadd(q5[0], q5[1]), fadd(q5[2], q5[2])); o->checks[2] = feq(c5, y1); }
-        tr.mark("y1, P5");   // src/sumcheck.cpp:3016-3019
+        tr.mark("y1, P5");
+        return 0;
+    }
+    // the closing synchronisation and hand-over of the staged results, then y1 and the check that needs it: P5's claim against y1
+    // (src/sumcheck.cpp:3016-3019)
+    int finish() {
+        HB_TRY(sc.finish());
+        if (!sc.top) HB_TRY(ctx->sync());            // (inside another call's scope the drain is that call's: y1 is needed here)
+        if (y1_pin) y1 = *y1_pin;
+        o->scalars[4] = *reinterpret_cast<hobbit_F *>(&y1);
+        CHP q5 = cF(Q5); const F c5 = fadd(fadd(q5[0], q5[1]), fadd(q5[2], q5[2]));
+        o->checks[2] = feq(c5, y1);
         return 0;
     }
     // shockwave_prove(C_f, P5.randomness minus its last entry) (:384-385); P5.randomness = [sumcheck r | r1 = P4.r[logc .. logc+log2 trs)] (src/sumcheck.cpp:3021-3023)
     int prove_cf() {
         std::vector<hobbit_F> x5((size_t)logc + (size_t)(R1 - 1));
         memcpy(x5.data(), Rr5, sizeof(hobbit_F) * (size_t)logc); memcpy(x5.data() + logc, Rr4 + logc, sizeof(hobbit_F) * (size_t)(R1 - 1));
-        HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<hobbit_F *>(d_aggr), reinterpret_cast<hobbit_F *>(encf), lvf, M, 32, x5.data(), (int)x5.size() - 1, o->sp_f));
+        HB_TRY(shockwave_prove_run(ctx, reinterpret_cast<hobbit_F *>(d_aggr), reinterpret_cast<hobbit_F *>(encf), lvf, M, 32, x5.data(), (int)x5.size() - 1, o->sp_f, plan_f));
         tr.mark("shockwave_prove C_f");
         return 0;
     }
@@ -3128,7 +3177,7 @@ static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
     HB_TRY(r.size_scratch_and_lay_out_arena());
     HB_TRY(r.aggregate_and_tensor_code());
     HB_TRY(r.inner_commitments());                   // overlapped: on helper2's stream
-    r.libc_draws();
+    HB_TRY(r.libc_draws());                          // both shockwave plans included; overlapped: the helper thread starts here and parks
     HB_TRY(r.query_answers());                       // overlapped: behind them on helper2's stream, handed over by a short-lived thread
     HB_TRY(r.host_tables());
     HB_TRY(r.p1_evals_p2());
@@ -3136,15 +3185,15 @@ static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
     HB_TRY(r.p4());
     HB_TRY(r.start_prove_cc());                      // overlapped: helper2's work joins the main stream; shockwave_prove(C_c) on the helper context, second thread
     HB_TRY(r.y1_p5());
-    if (!full) return r.sc.finish();
-    if (!r.overlapped) HB_TRY(r.prove_cc());         // serial: the reference runs it before P5; P5 draws nothing from libc, so every draw stays where the reference has it
+    if (!full) return r.finish();
+    if (!r.cc_on_helper) HB_TRY(r.prove_cc());       // serial, or no helper thread: the reference runs it before P5; its draws were taken with the others, in the reference's order
     HB_TRY(r.prove_cf());
-    if (r.overlapped) {
+    if (r.cc_on_helper) {
         r.sp_thread.join();
         if (r.sp_rc) return ctx->fail(r.sp_rc, std::string("shockwave_prove(C_c) on the helper context: ") + ctx->helper->err);
     }
     if (r.tr.on) fprintf(stderr, "[hobbit open] scratch at exit:  ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws_bytes, ctx->ws2_bytes, ctx->ws3_bytes, ctx->ws4_bytes, ctx->pin_bytes);
-    return r.sc.finish();
+    return r.finish();
 }
 static int open_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
                      bool full) {

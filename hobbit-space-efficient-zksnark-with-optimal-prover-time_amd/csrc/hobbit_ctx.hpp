@@ -351,11 +351,17 @@ struct hobbit_ctx {
     // ---- mailbox: the one-workgroup reduction kernel of a sumcheck round writes its few coefficients straight into coherent pinned
     // host memory and then a sequence number; the host spins on that word (HOBBIT_MBOX=sync: sleeps in hipStreamSynchronize)
     // instead of queueing a copy and synchronising.
+    // ---- tail area: behind the mailbox in the same coherent pinned allocation, two tables of TAIL_ELEMS elements.  The launch that
+    // produces the tables a two-product sumcheck hands to the host (hobbit_kernels.hip, sumcheck2_impl) also stores them here, and the
+    // round's post -- behind that launch in stream order -- tells the host they have landed: no copy command, no stream drain.
+    static constexpr size_t TAIL_ELEMS = 2048, MBOX_BYTES = 4096, TAIL_BYTES = 2 * TAIL_ELEMS * sizeof(hobbit::F);
     hobbit::Mailbox *mbox = nullptr; unsigned *d_ticket = nullptr; uint32_t mbox_seq = 0;
+    hobbit::F *tail = nullptr;                   // tables at tail and tail + TAIL_ELEMS
     int mailbox(hobbit::Mailbox **m, unsigned **ticket) {
         if (!mbox) {
-            if (hipHostMalloc((void **)&mbox, 4096, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) { mbox = nullptr; err = "mailbox hipHostMalloc failed"; return HOBBIT_ENOMEM; }
-            memset((void *)mbox, 0, 4096);
+            if (hipHostMalloc((void **)&mbox, MBOX_BYTES + TAIL_BYTES, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) { mbox = nullptr; err = "mailbox hipHostMalloc failed"; return HOBBIT_ENOMEM; }
+            memset((void *)mbox, 0, MBOX_BYTES + TAIL_BYTES);
+            tail = reinterpret_cast<hobbit::F *>(reinterpret_cast<uint8_t *>(mbox) + MBOX_BYTES);
             if (hipMalloc((void **)&d_ticket, 256) != hipSuccess) { err = "mailbox ticket alloc failed"; return HOBBIT_ENOMEM; }
             if (hipMemsetAsync(d_ticket, 0, 256, stream) != hipSuccess) { err = "mailbox ticket memset failed"; return HOBBIT_EHIP; }
         }

@@ -2232,12 +2232,16 @@ int launch_axpy(hobbit_ctx *ctx, F *y, const F *x, F a, size_t n) {
 // 48-64 bytes go to the HOST, which runs the MiMC transcript (3-4 x 161 strictly sequential
 // cubings: ~4 us on a CPU core, ~80 us on a GPU scalar unit -- measured 5.7 of 6.7 ms at n = 2^24
 // with the transcript on the device) and passes the next challenge to the next launch as a kernel
-// argument.  Once the tables are down to SC_TAIL elements they are copied out and the last rounds
-// run on the host.  Coefficient sums are exact field sums, so any reduction tree is bit-identical
+// argument.  Once the tables are down to SC_TAIL elements the last rounds run on the host; the
+// two-product sumcheck's tables reach it through the context's pinned tail area, stored by the
+// launch that produces them and announced by the round's post (no copy command, no stream drain).
+// Coefficient sums are exact field sums, so any reduction tree is bit-identical
 // to the reference's sequential accumulation.
 // ============================================================================================
 static constexpr size_t SC_TAIL = 1024;      // table size at which the remaining rounds go to the host
 static constexpr size_t SC_DOUBLE_MIN = 16 * SC_TAIL;      // tables at least this large take two rounds per round trip
+static constexpr size_t SC_TAIL_AREA = hobbit_ctx::TAIL_ELEMS;      // elements per table of the context's tail area: the largest table handed to the host
+static_assert(SC_TAIL_AREA == 2 * SC_TAIL, "the tail area holds the unfolded tables of the round that ends at SC_TAIL");
 
 template <int NC>
 __device__ __forceinline__ void block_reduce_store(F (&c)[NC], F *partials) {
@@ -2269,7 +2273,7 @@ __global__ void __launch_bounds__(256) k_sc2_poly(const F *__restrict__ v1, cons
 // rounds >= 1: fold the previous tables with the challenge just derived (4 -> 2 elements per
 // thread and table) and accumulate this round's polynomial from the folded pair in registers.
 __global__ void __launch_bounds__(256) k_sc2_fold_poly(const F *__restrict__ s1, const F *__restrict__ s2, F *__restrict__ d1, F *__restrict__ d2,
-                                                       size_t L, F r, F *__restrict__ partials) {
+                                                       size_t L, F r, F *__restrict__ partials, F *__restrict__ tail) {
     F c[3] = {fmake(0), fmake(0), fmake(0)};
     for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < L; j += (size_t)gridDim.x * blockDim.x) {
         F a0 = ldF(s1 + 4 * j), a1 = ldF(s1 + 4 * j + 1), a2 = ldF(s1 + 4 * j + 2), a3 = ldF(s1 + 4 * j + 3);
@@ -2277,9 +2281,26 @@ __global__ void __launch_bounds__(256) k_sc2_fold_poly(const F *__restrict__ s1,
         F x0 = fadd(a0, fmul(r, fsub(a1, a0))), x1 = fadd(a2, fmul(r, fsub(a3, a2)));
         F y0 = fadd(b0, fmul(r, fsub(b1, b0))), y1 = fadd(b2, fmul(r, fsub(b3, b2)));
         stF(d1 + 2 * j, x0); stF(d1 + 2 * j + 1, x1); stF(d2 + 2 * j, y0); stF(d2 + 2 * j + 1, y1);
+        if (tail) {           // the launch whose output the host continues from (2 L <= SC_TAIL_AREA): the same elements into the context's tail area
+            stF(tail + 2 * j, x0); stF(tail + 2 * j + 1, x1); stF(tail + SC_TAIL_AREA + 2 * j, y0); stF(tail + SC_TAIL_AREA + 2 * j + 1, y1);
+        }
         acc_quad(c, x0, x1, y0, y1);
     }
     block_reduce_store<3>(c, partials);
+}
+// The paths that reach the host tail without a fold launch: both tables (len <= SC_TAIL_AREA elements each) into the tail area as they are
+__global__ void __launch_bounds__(256) k_sc2_tail_copy(const F *__restrict__ s1, const F *__restrict__ s2, size_t len, F *__restrict__ tail) {
+    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < len; j += (size_t)gridDim.x * blockDim.x) {
+        stF(tail + j, ldF(s1 + j)); stF(tail + SC_TAIL_AREA + j, ldF(s2 + j));
+    }
+}
+// n <= SC_TAIL, where no round runs on the device and no reduction follows: ONE workgroup copies both tables and posts itself.  Every
+// thread makes its stores visible at system scope before the barrier; thread 0 posts behind the barrier.
+__global__ void __launch_bounds__(256) k_sc2_tail_copy_post(const F *__restrict__ s1, const F *__restrict__ s2, uint32_t len, F *__restrict__ tail, Mailbox *mb, uint32_t seq) {
+    for (uint32_t j = threadIdx.x; j < len; j += blockDim.x) { stF(tail + j, ldF(s1 + j)); stF(tail + SC_TAIL_AREA + j, ldF(s2 + j)); }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(&mb->flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // Two rounds per transcript round trip.  For a quad (a0..a3) of the round-i tables, X(r, t) = x0(r) + t (x1(r) - x0(r)) with
 // x0 = a0 + r (a1 - a0), x1 = a2 + r (a3 - a2) is bilinear in (r, t); G(r, t) = sum over quads of X(r, t) Y(r, t) is biquadratic and
@@ -2373,10 +2394,10 @@ __global__ void __launch_bounds__(256) k_sc_reduce_post(const F *__restrict__ pa
 }
 
 // host tail of the 2-product sumcheck: tables a,b of size sz (not yet folded with `rnd` when
-// pending_fold), continuing at round `round` exactly as src/sumcheck.cpp:2401-2452
-static void sc2_host_tail(std::vector<F> &a, std::vector<F> &b, F &rnd, bool pending_fold, int round, int rounds, MHP h_qpoly, MHP h_r) {
-    size_t sz = a.size();
-    auto fold = [&](std::vector<F> &v) { for (size_t j = 0; j < sz / 2; j++) v[j] = fadd(v[2 * j], fmul(rnd, fsub(v[2 * j + 1], v[2 * j]))); };
+// pending_fold), continuing at round `round` exactly as src/sumcheck.cpp:2401-2452.  Folds in
+// place: the caller hands it the context's tail area, where the device left the tables.
+static void sc2_host_tail(F *a, F *b, size_t sz, F &rnd, bool pending_fold, int round, int rounds, MHP h_qpoly, MHP h_r) {
+    auto fold = [&](F *v) { for (size_t j = 0; j < sz / 2; j++) v[j] = fadd(v[2 * j], fmul(rnd, fsub(v[2 * j + 1], v[2 * j]))); };
     if (pending_fold) { fold(a); fold(b); sz /= 2; }
     for (int i = round; i < rounds; i++) {
         F pa = fmake(0), pb = fmake(0), pc = fmake(0);
@@ -2781,7 +2802,9 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
     if (((size_t)1 << rounds) != n || n < 2) return ctx->fail(HOBBIT_EINVAL, "sumcheck2: n must be a power of two >= 2");
     const int MAXB = 1024, EQ_MAXB = 2048;
     F rnd = prev_r;
-    std::vector<F> ta, tb;
+    // the host's last rounds run in place in the context's tail area, where the device leaves their tables (hobbit_ctx.hpp)
+    Mailbox *mb; unsigned *ticket; HB_TRY(ctx->mailbox(&mb, &ticket));
+    F *const ta = ctx->tail, *const tb = ctx->tail + SC_TAIL_AREA;
     EqPts pts;
     if (eq) for (int j = 0; j < 2; j++) for (int b = 0; b < 40; b++) pts.r[j][b] = (j < eq->T && b < rounds) ? (F)eq->r[j][b] : fmake(0);
     // the eq-sum table itself, level `from` with scalars al: what the dense path reads where the table is short
@@ -2803,11 +2826,11 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
             HB_TRY(launch_scatter(ctx, sp_idx, sp_val, sp_m, dv2));
             v2 = dv2;
         }
-        ta.resize(n); tb.resize(n);
-        HB_CHECK(ctx, hipMemcpyAsync(ta.data(), v1, n * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-        HB_CHECK(ctx, hipMemcpyAsync(tb.data(), v2, n * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-        HB_TRY(ctx->sync());
-        sc2_host_tail(ta, tb, rnd, false, 0, rounds, h_qpoly, h_r);
+        // no round runs on the device: one launch copies the tables into the tail area and posts, no copy command and no stream drain
+        const uint32_t seq = ++ctx->mbox_seq;
+        HB_LAUNCH(ctx, "k_sc2_tail_copy_post", k_sc2_tail_copy_post, dim3(1), dim3(256), 0, v1, v2, (uint32_t)n, ctx->tail, mb, seq);
+        HB_TRY(ctx->mbox_wait(seq));
+        sc2_host_tail(ta, tb, n, rnd, false, 0, rounds, h_qpoly, h_r);
     } else {
         size_t szA = n / 2, szB = n / 4;
         const bool sparse = sp_idx && n >= 16 * SC_DOUBLE_MIN;            // (shorter tables: scatter at once, dense path)
@@ -2833,7 +2856,6 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
         if (eq_double)
             HB_LAUNCH(ctx, "k_eq_factors", k_eq_factors, dim3(grid_for((size_t)1 << std::max(eq_s, rounds - eq_s), 256, 64), eq->T * (eq_nlev + 1)), dim3(256), 0, pts, rounds,
                       eq_s, eq_nlev, eq_fac);
-        Mailbox *mb; unsigned *ticket; HB_TRY(ctx->mailbox(&mb, &ticket));
         const F *s1 = v1, *s2 = v2;
         F *d1 = A1, *d2 = A2;
         int i = 0;
@@ -2926,7 +2948,7 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
             const bool at_A = eq ? S2 == A2 : S1 == A1;
             F *b1 = at_A ? B1 : A1, *b2 = at_A ? B2 : A2;
             const size_t L = S_size / 4;
-            HB_LAUNCH(ctx, "k_sc2_fold_poly", k_sc2_fold_poly, dim3(grid_for(L, 256, MAXB)), dim3(256), 0, S1, S2, b1, b2, L, pr0, part);
+            HB_LAUNCH(ctx, "k_sc2_fold_poly", k_sc2_fold_poly, dim3(grid_for(L, 256, MAXB)), dim3(256), 0, S1, S2, b1, b2, L, pr0, part, (F *)nullptr);   // (2 L >= 8 SC_TAIL: never the tail)
             s1 = b1; s2 = b2; cur = 2 * L;
             if (b1 == A1) { d1 = B1; d2 = B2; } else { d1 = A1; d2 = A2; }
         }
@@ -2934,9 +2956,14 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
             size_t L = n >> (i + 1);          // pairs of the round-i tables
             int nb = grid_for(L, 256, MAXB);
             const uint32_t seq = ++ctx->mbox_seq;
-            if (i == 0) HB_LAUNCH(ctx, "k_sc2_poly", k_sc2_poly, dim3(nb), dim3(256), 0, s1, s2, L, part);
-            else {
-                HB_LAUNCH(ctx, "k_sc2_fold_poly", k_sc2_fold_poly, dim3(nb), dim3(256), 0, s1, s2, d1, d2, L, rnd, part);
+            // The round whose tables the host continues from also lands them in the tail area, in front of the round's post: the fold launch
+            // stores them there itself; round 0 on the caller's tables (SC_TAIL < n <= 2 SC_TAIL) has no fold launch and takes a copy launch.
+            const bool last = 2 * L <= SC_TAIL_AREA || i == rounds - 1;      // the round-i tables (2 L elements each) are the host's: this round writes the tail area and ends the loop
+            if (i == 0) {
+                HB_LAUNCH(ctx, "k_sc2_poly", k_sc2_poly, dim3(nb), dim3(256), 0, s1, s2, L, part);
+                if (last) HB_LAUNCH(ctx, "k_sc2_tail_copy", k_sc2_tail_copy, dim3(grid_for(cur, 256, 64)), dim3(256), 0, s1, s2, cur, ctx->tail);
+            } else {
+                HB_LAUNCH(ctx, "k_sc2_fold_poly", k_sc2_fold_poly, dim3(nb), dim3(256), 0, s1, s2, d1, d2, L, rnd, part, last ? ctx->tail : (F *)nullptr);
                 s1 = d1; s2 = d2; cur = 2 * L;
                 if (d1 == A1) { d1 = B1; d2 = B2; } else { d1 = A1; d2 = A2; }
             }
@@ -2944,13 +2971,9 @@ static int sumcheck2_impl(hobbit_ctx *ctx, const F *v1, const F *v2, const uint6
             HB_TRY(ctx->mbox_wait(seq));                                  // the last workgroup posts the three coefficients to the host
             for (int q = 0; q < 3; q++) { const F cq = mb->vals[q]; rnd = mimc_hash(rnd, cq); h_qpoly[3 * i + q] = cq; }
             h_r[i] = rnd;
-            if (cur <= 2 * SC_TAIL || i == rounds - 1) break;   // hand the (unfolded) round-i tables to the host
+            if (last) break;                                    // the (unfolded) round-i tables are in the tail area: stored in front of the post that mbox_wait has just seen
         }
-        ta.resize(cur); tb.resize(cur);
-        HB_CHECK(ctx, hipMemcpyAsync(ta.data(), s1, cur * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-        HB_CHECK(ctx, hipMemcpyAsync(tb.data(), s2, cur * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-        HB_TRY(ctx->sync());
-        sc2_host_tail(ta, tb, rnd, true, i + 1, rounds, h_qpoly, h_r);
+        sc2_host_tail(ta, tb, cur, rnd, true, i + 1, rounds, h_qpoly, h_r);
     }
     rnd = mimc_hash(rnd, ta[0]); rnd = mimc_hash(rnd, tb[0]);          // src/sumcheck.cpp:2444-2446
     h_vr[0] = ta[0]; h_vr[1] = tb[0]; *h_final = rnd;
