@@ -28,7 +28,7 @@ c_ll = ctypes.c_longlong
 # every symbol include/hobbit_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "hobbit_ctx_create", "hobbit_ctx_create_on_stream", "hobbit_ctx_destroy", "hobbit_last_error", "hobbit_version", "hobbit_sync",
-    "hobbit_malloc", "hobbit_free", "hobbit_memcpy_h2d", "hobbit_memcpy_d2h", "hobbit_memset", "hobbit_timer_begin", "hobbit_timer_end_ms",
+    "hobbit_malloc", "hobbit_free", "hobbit_mem_live", "hobbit_memcpy_h2d", "hobbit_memcpy_d2h", "hobbit_memset", "hobbit_timer_begin", "hobbit_timer_end_ms",
     "hobbit_profile_enable", "hobbit_profile_reset", "hobbit_profile_get", "hobbit_profile_names",
     "hobbit_mimc", "hobbit_f_mul_host", "hobbit_f_inv_host", "hobbit_f_binop",
     "hobbit_graph_reset", "hobbit_graph_upload", "hobbit_graph_finalize", "hobbit_encode_forms", "hobbit_encode_batch", "hobbit_fft_batch", "hobbit_fft_any",
@@ -121,7 +121,7 @@ def load_library(path=LIB_PATH):
     V, S, I, L, U64 = c_vp, c_sz, c_int, c_ll, ctypes.c_uint64
     protos = {
         "hobbit_ctx_create": [I, V], "hobbit_ctx_create_on_stream": [I, V, V], "hobbit_ctx_destroy": [V], "hobbit_last_error": [V],
-        "hobbit_sync": [V], "hobbit_malloc": [V, S, V], "hobbit_free": [V, V], "hobbit_memcpy_h2d": [V, V, V, S],
+        "hobbit_sync": [V], "hobbit_malloc": [V, S, V], "hobbit_free": [V, V], "hobbit_mem_live": [V, V], "hobbit_memcpy_h2d": [V, V, V, S],
         "hobbit_memcpy_d2h": [V, V, V, S], "hobbit_memset": [V, V, I, S], "hobbit_timer_begin": [V], "hobbit_timer_end_ms": [V, V],
         "hobbit_profile_enable": [V, I], "hobbit_profile_reset": [V], "hobbit_profile_get": [V, ctypes.c_char_p, V, V],
         "hobbit_profile_names": [V, V, S], "hobbit_mimc": [V, V, V], "hobbit_f_mul_host": [V, V, V, S], "hobbit_f_inv_host": [V, V, S],

@@ -20,19 +20,11 @@ namespace {
 
 constexpr size_t QUERIES = HOBBIT_BRAKINGBASE_QUERIES;
 
-// device scratch of one opening, released on every way out
-struct Scratch {
-    hobbit_ctx *ctx; std::vector<void *> bufs; hobbit_parity_commitment *pc = nullptr;
-    explicit Scratch(hobbit_ctx *c) : ctx(c) {}
-    ~Scratch() { if (pc) hobbit_parity_commitment_free(pc); for (void *p : bufs) hobbit_free(ctx, p); }
-    int get(size_t bytes, void **p) { HB_TRY(hobbit_malloc(ctx, bytes, p)); bufs.push_back(*p); return 0; }
-};
-
 }  // namespace
 
 struct hobbit_brakingbase {
     hobbit_ctx *ctx; size_t N, K, trs;
-    hobbit_brakedown *bd;                     // the matrix (2 trs x K, rows-innermost) and the levels over its 2 trs column digests
+    Handle<hobbit_brakedown, hobbit_brakedown_free> bd;     // the matrix (2 trs x K, rows-innermost) and the levels over its 2 trs column digests
 };
 
 extern "C" {
@@ -45,11 +37,7 @@ int hobbit_brakingbase_shape(size_t N, size_t K, size_t *trs) {
     return 0;
 }
 
-void hobbit_brakingbase_free(hobbit_brakingbase *c) {
-    if (!c) return;
-    hobbit_brakedown_free(c->bd);
-    delete c;
-}
+void hobbit_brakingbase_free(hobbit_brakingbase *c) { delete c; }
 
 int hobbit_brakingbase_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, size_t K, int left_left_quirk, hobbit_brakingbase **out) {
     if (!out) return ctx->fail(HOBBIT_EINVAL, "brakingbase_commit: null output");
@@ -64,7 +52,7 @@ int hobbit_brakingbase_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N,
     if (ctx->code.n != (long long)trs) return ctx->fail(HOBBIT_ESTATE, "brakingbase_commit: graphs for n = N / K are not finalized (expander_init_store(N / K))");
     hobbit_brakedown *bd = nullptr;
     HB_TRY(brakedown_commit_shape(ctx, reinterpret_cast<const F *>(d_poly), trs, (uint32_t)K, left_left_quirk, &bd));
-    *out = new hobbit_brakingbase{ctx, N, K, trs, bd};
+    *out = new hobbit_brakingbase{ctx, N, K, trs, Handle<hobbit_brakedown, hobbit_brakedown_free>(bd)};
     return 0;
 }
 
@@ -73,21 +61,21 @@ int hobbit_brakingbase_dims(const hobbit_brakingbase *c, size_t *N, size_t *K, s
     if (N) *N = c->N;
     if (K) *K = c->K;
     if (trs) *trs = c->trs;
-    return hobbit_brakedown_dims(c->bd, nullptr, nullptr, len);
+    return hobbit_brakedown_dims(c->bd.get(), nullptr, nullptr, len);
 }
-const hobbit_F *hobbit_brakingbase_matrix_dev(const hobbit_brakingbase *c) { return c ? hobbit_brakedown_matrix_dev(c->bd) : nullptr; }
-const uint8_t *hobbit_brakingbase_levels_dev(const hobbit_brakingbase *c) { return c ? hobbit_brakedown_levels_dev(c->bd) : nullptr; }
+const hobbit_F *hobbit_brakingbase_matrix_dev(const hobbit_brakingbase *c) { return c ? hobbit_brakedown_matrix_dev(c->bd.get()) : nullptr; }
+const uint8_t *hobbit_brakingbase_levels_dev(const hobbit_brakingbase *c) { return c ? hobbit_brakedown_levels_dev(c->bd.get()) : nullptr; }
 int hobbit_brakingbase_levels(hobbit_ctx *ctx, const hobbit_brakingbase *c, uint8_t *h_levels) {
     if (!c || !h_levels) return ctx->fail(HOBBIT_EINVAL, "brakingbase_levels: null argument");
-    return hobbit_brakedown_levels(ctx, c->bd, h_levels);
+    return hobbit_brakedown_levels(ctx, c->bd.get(), h_levels);
 }
 int hobbit_brakingbase_root(hobbit_ctx *ctx, const hobbit_brakingbase *c, uint8_t *h_root) {
     if (!c || !h_root) return ctx->fail(HOBBIT_EINVAL, "brakingbase_root: null argument");
-    return hobbit_brakedown_root(ctx, c->bd, h_root);
+    return hobbit_brakedown_root(ctx, c->bd.get(), h_root);
 }
 int hobbit_brakingbase_tensor(hobbit_ctx *ctx, const hobbit_brakingbase *c, size_t col_lo, size_t ncols, hobbit_F *h_out) {
     if (!c || (ncols && !h_out)) return ctx->fail(HOBBIT_EINVAL, "brakingbase_tensor: null argument");
-    return hobbit_brakedown_tensor(ctx, c->bd, col_lo, ncols, h_out);
+    return hobbit_brakedown_tensor(ctx, c->bd.get(), col_lo, ncols, h_out);
 }
 
 int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const hobbit_F *h_x, hobbit_brakingbase_open_out *o) {
@@ -99,8 +87,8 @@ int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const 
     const size_t trs = c->trs, K = c->K, S = 2 * trs;
     const int lk = ilog2x(K), l = ilog2x(S);
     if (ctx->code.n != (long long)trs) return ctx->fail(HOBBIT_ESTATE, "brakingbase_open: graphs for n = N / K are not finalized (expander_init_store(N / K))");
-    const F *mat = reinterpret_cast<const F *>(hobbit_brakedown_matrix_dev(c->bd));
-    const uint8_t *levels = hobbit_brakedown_levels_dev(c->bd);
+    const F *mat = reinterpret_cast<const F *>(hobbit_brakedown_matrix_dev(c->bd.get()));
+    const uint8_t *levels = hobbit_brakedown_levels_dev(c->bd.get());
 
     // ---- the draws that come before any device work (:374, :382-385; _aggregate_brakingbase and shockwave_commit draw nothing) -----------------
     hobbit_F rv0; hobbit_generate_randomness(1, &rv0); (void)rv0;                       // r_v[0]: its powers feed nothing
@@ -156,8 +144,9 @@ int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const 
     HB_TRY(stage(1));
 
     // ---- recursive_prover_brakingbase (src/PC_utils.cpp:389-394) ----------------------------------------------------------------------------------
-    HB_TRY(hobbit_parity_commit_device(ctx, (long long)trs, &sc.pc));
-    if (o->cp_root) HB_TRY(hobbit_parity_root(ctx, sc.pc, o->cp_root));
+    ParityHandle pc;
+    { hobbit_parity_commitment *p = nullptr; HB_TRY(hobbit_parity_commit_device(ctx, (long long)trs, &p)); pc.reset(p); }
+    if (o->cp_root) HB_TRY(hobbit_parity_root(ctx, pc.get(), o->cp_root));
     HB_TRY(stage(2));
 
     std::vector<F> r1((size_t)l), q((size_t)3 * l), r((size_t)l); F vr[2], fin;
@@ -174,13 +163,13 @@ int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const 
     }
     HB_TRY(stage(3));
 
-    HB_TRY(hobbit_parity_open(ctx, sc.pc, aF(r.data()), aF(r1.data()), l, o->parity));
+    HB_TRY(hobbit_parity_open(ctx, pc.get(), aF(r.data()), aF(r1.data()), l, o->parity));
     HB_TRY(stage(4));
     HB_TRY(hobbit_shockwave_prove(ctx, aF(cw), aF(enc), lvc, S, 32, aF(r.data()), l, o->sp_c));
     HB_TRY(stage(5));
 
     if (o->ps) {
-        size_t P = 0; hobbit_parity_dims(sc.pc, nullptr, nullptr, &P, nullptr);
+        size_t P = 0; hobbit_parity_dims(pc.get(), nullptr, nullptr, &P, nullptr);
         const int L = ilog2x(P);
         double ps = 0.0;
         ps += (double)(K * QUERIES * sizeof(hobbit_F)) / 1024.0;                        // (:393)

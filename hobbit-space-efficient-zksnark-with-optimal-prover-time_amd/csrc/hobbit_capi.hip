@@ -26,8 +26,7 @@ static_assert(sizeof(hobbit_F) == sizeof(F), "ABI field element must be 16 bytes
 struct hobbit_commitment {
     hobbit_ctx *ctx;
     size_t N, M; int K, trs, lin; uint32_t cols, rows2;
-    F *d_tensor; uint8_t *d_levels;
-    size_t tensor_bytes, levels_bytes;
+    mem::Buf<F> d_tensor; mem::Buf<uint8_t> d_levels;
     // Rows [rows_valid, rows2) of every column are zero by construction (an RS x expander codeword ends at `len`; rows_valid = len rounded up to the
     // leaf group) and were NOT written: the leaf chain, the gathers and the row reads answer them as zeros; hobbit_commitment_tensor_dev fills them
     // in before it hands the raw pointer out.  rows_valid == rows2: everything is in memory (RS x RS, shallow codes, HOBBIT_COMMIT_SKIP_TAIL=0).
@@ -78,10 +77,10 @@ static int get_twiddles(hobbit_ctx *ctx, int logn, bool inverse, const F **out) 
         w[1] = w1;
         for (size_t i = 2; i < half; i++) w[i] = fmul(w[i - 1], w1);
     }
-    F *d = nullptr;
-    if (hipMalloc((void **)&d, half * sizeof(F)) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
+    mem::Buf<F> d;
+    if (d.alloc(half)) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
     HB_CHECK(ctx, hipMemcpy(d, w.data(), half * sizeof(F), hipMemcpyHostToDevice));
-    m[logn] = d; *out = d; return 0;
+    *out = d; m[logn] = std::move(d); return 0;
 }
 
 // per-pass twiddle tables of k_fft4096 (true radix-8 DIT): the pass with octet stride h stores, for t = 1..7 and k < h,
@@ -98,10 +97,10 @@ static int get_tw8(hobbit_ctx *ctx, bool inverse) {
     std::vector<F> t;
     for (uint32_t h : {8u, 64u, 512u})
         for (uint32_t b = 1; b < 8; b++) for (uint32_t k = 0; k < h; k++) t.push_back(w[(rev3[b] * k * (len / (8 * h))) % len]);
-    F *dptr = nullptr;
-    if (hipMalloc((void **)&dptr, t.size() * sizeof(F)) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
+    mem::Buf<F> dptr;
+    if (dptr.alloc(t.size())) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
     HB_CHECK(ctx, hipMemcpy(dptr, t.data(), t.size() * sizeof(F), hipMemcpyHostToDevice));
-    ctx->tw8[d] = dptr;
+    ctx->tw8[d] = std::move(dptr);
     ctx->tw8_w8[d] = w[512]; ctx->tw8_w83[d] = w[1536];
     const F w4 = w[1024];
     if (w4.re != 0 || (w4.im != 1 && w4.im != P61 - 1)) return ctx->fail(HOBBIT_EINVAL, "unexpected 4th root of unity");
@@ -126,10 +125,10 @@ static int get_tw_r8(hobbit_ctx *ctx, int logn, bool inverse, const F **out) {
         for (uint32_t b = 1; b < 8; b++) for (uint32_t k = 0; k < h; k++) t.push_back(w[(size_t)R * ((rev3[b] * k * (N2 / (8 * h))) % N2)]);
     for (uint32_t q = 1; q < R; q++) for (uint32_t k = 0; k < N2; k++) t.push_back(w[((size_t)q * k) % N]);
     if (t.empty()) t.push_back(fmake(1));
-    F *d = nullptr;
-    if (hipMalloc((void **)&d, t.size() * sizeof(F)) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
+    mem::Buf<F> d;
+    if (d.alloc(t.size())) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
     HB_CHECK(ctx, hipMemcpy(d, t.data(), t.size() * sizeof(F), hipMemcpyHostToDevice));
-    ctx->tw_r8[key] = d; *out = d;
+    *out = d; ctx->tw_r8[key] = std::move(d);
     return 0;
 }
 // The twiddles of a length 2^25 .. 2^28 as two small tables, w^(a 2^14 + b) = hi[a] lo[b]: [lo: 2^14 | hi: 2^(logn-14)] entries, at most
@@ -146,10 +145,10 @@ static int get_tw_split(hobbit_ctx *ctx, int logn, bool inverse, const F **lo, c
         const F wh = fmul(t[nlo - 1], w1);                            // w^(2^14)
         t[nlo] = fmake(1);
         for (size_t i = 1; i < nhi; i++) t[nlo + i] = fmul(t[nlo + i - 1], wh);
-        F *d = nullptr;
-        if (hipMalloc((void **)&d, t.size() * sizeof(F)) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
+        mem::Buf<F> d;
+        if (d.alloc(t.size())) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
         HB_CHECK(ctx, hipMemcpy(d, t.data(), t.size() * sizeof(F), hipMemcpyHostToDevice));
-        it = ctx->tw_split.emplace(key, d).first;
+        it = ctx->tw_split.emplace(key, std::move(d)).first;
     }
     *lo = it->second; *hi = it->second + ((size_t)1 << 14);
     return 0;
@@ -157,25 +156,6 @@ static int get_tw_split(hobbit_ctx *ctx, int logn, bool inverse, const F **lo, c
 // FFT dispatch: the 4096-point kernel when it applies, the generic LDS kernel otherwise
 static int fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, bool inverse,
                     uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs);
-
-static void free_code(DeviceCode &c) {
-    for (FatStep *f : {&c.fatA, &c.fatC1, &c.fatD}) { if (f->d_wt) hipFree(f->d_wt); if (f->d_ot) hipFree(f->d_ot); if (f->d_oidx) hipFree(f->d_oidx); if (f->d_w) hipFree(f->d_w); }
-    for (uint32_t *q : {c.narrow.d_wt, c.narrow.d_ot, c.narrow.d_q}) if (q) hipFree(q);
-    if (c.d_steps) hipFree(c.d_steps);
-    if (c.d_slice_ptr) hipFree(c.d_slice_ptr);
-    if (c.d_slice_width) hipFree(c.d_slice_width);
-    if (c.d_slice_out) hipFree(c.d_slice_out);
-    if (c.d_edges32) hipFree(c.d_edges32);
-    if (c.d_eidx) hipFree(c.d_eidx);
-    if (c.d_ew) hipFree(c.d_ew);
-    if (c.d_pm_rowptr) hipFree(c.d_pm_rowptr);
-    if (c.d_pm_idx) hipFree(c.d_pm_idx);
-    if (c.d_pm_w) hipFree(c.d_pm_w);
-    for (void *q : {(void *)c.d_tile_ptr, (void *)c.d_tile_width, (void *)c.d_tile_out, (void *)c.d_tile_e32, (void *)c.d_tile_eidx, (void *)c.d_tile_ew}) if (q) hipFree(q);
-    for (void *q : {(void *)c.d_ilv_ptr, (void *)c.d_ilv_e32, (void *)c.d_ilv_eidx, (void *)c.d_ilv_ew}) if (q) hipFree(q);
-    for (void *q : {(void *)c.d_fwd_segs, (void *)c.d_fwd_nbr, (void *)c.d_fwd_w32, (void *)c.d_fwd_w}) if (q) hipFree(q);
-    c = DeviceCode();
-}
 
 // the transform with an explicit factor on the way out (do_scale == 0: none)
 static int fft_rows_scaled(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, bool inverse,
@@ -235,10 +215,10 @@ static int fft_long(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len
         const int key = logn + (inverse ? 64 : 0);
         auto it = ctx->tw2d.find(key);
         if (it == ctx->tw2d.end()) {
-            F *d2 = nullptr;
-            if (hipMalloc((void **)&d2, len * sizeof(F)) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "twiddle table alloc failed");
+            mem::Buf<F> d2;
+            if (d2.alloc(len)) return ctx->fail(HOBBIT_ENOMEM, "twiddle table alloc failed");
             HB_TRY(launch_build_tw2d(ctx, twl, (uint32_t)(len / 2), R, d2));
-            it = ctx->tw2d.emplace(key, d2).first;
+            it = ctx->tw2d.emplace(key, std::move(d2)).first;
         }
         tw2 = it->second;
     }
@@ -324,56 +304,19 @@ int hobbit_ctx_create_on_stream(int device, void *hip_stream, hobbit_ctx **out) 
     c->device = device;
     if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->owns_stream = false; }
     else { if (hipStreamCreate(&c->stream) != hipSuccess) { delete c; return HOBBIT_EHIP; } c->owns_stream = true; }
+    c->pool.stream = c->stream;
     hipEventCreate(&c->t0); hipEventCreate(&c->t1);
     {   // first allocation + first launch + first pinned allocation, still under the guard
-        void *p = nullptr, *hp = nullptr;
-        if (hipMalloc(&p, 4096) == hipSuccess) { hobbit_fill_splitmix(c, reinterpret_cast<hobbit_F *>(p), 256, 1); hipStreamSynchronize(c->stream); hipFree(p); }
-        if (hipHostMalloc(&hp, 4096) == hipSuccess) hipHostFree(hp);
+        mem::Buf<hobbit_F> p; mem::Buf<void, mem::Pinned> hp;
+        if (!p.alloc(256)) { hobbit_fill_splitmix(c, p, 256, 1); hipStreamSynchronize(c->stream); }
+        (void)hp.alloc_bytes(4096);
     }
     *out = c;
     return 0;
 }
 int hobbit_ctx_create(int device, hobbit_ctx **out) { return hobbit_ctx_create_on_stream(device, nullptr, out); }
 
-void hobbit_ctx_destroy(hobbit_ctx *ctx) {
-    if (!ctx) return;
-    if (ctx->helper) { hobbit_ctx_destroy(ctx->helper); ctx->helper = nullptr; }
-    if (ctx->helper2) { hobbit_ctx_destroy(ctx->helper2); ctx->helper2 = nullptr; }
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    ctx->prof_collect();
-    for (auto &kv : ctx->tw_fwd) hipFree(kv.second);
-    for (auto &kv : ctx->tw_inv) hipFree(kv.second);
-    for (auto &kv : ctx->tw2d) hipFree(kv.second);
-    for (auto &kv : ctx->tw_split) hipFree(kv.second);
-    for (auto &kv : ctx->tw_r8) hipFree(kv.second);
-    ctx->pool_drain();
-    for (int d = 0; d < 2; d++) if (ctx->tw8[d]) hipFree(ctx->tw8[d]);
-    free_code(ctx->code);
-    if (ctx->ws) hipFree(ctx->ws);
-    if (ctx->ws2) hipFree(ctx->ws2);
-    if (ctx->pin) hipHostFree(ctx->pin);
-    if (ctx->stage) hipHostFree(ctx->stage);
-    if (ctx->mbox) hipHostFree((void *)ctx->mbox);
-    if (ctx->d_ticket) hipFree(ctx->d_ticket);
-    for (hipEvent_t e : ctx->ev_pool) hipEventDestroy(e);
-    if (ctx->ws3) hipFree(ctx->ws3);
-    if (ctx->ws4) hipFree(ctx->ws4);
-    if (ctx->ws5) hipFree(ctx->ws5);
-    if (ctx->spare_tensor) hipFree(ctx->spare_tensor);
-    if (ctx->spare_levels) hipFree(ctx->spare_levels);
-    ctx->spare_parity_release();
-    hipEventDestroy(ctx->t0); hipEventDestroy(ctx->t1);
-    if (ctx->up_stream) {
-        hipStreamSynchronize(ctx->up_stream);
-        for (int i = 0; i < 2; i++) { if (ctx->up_pin[i]) hipHostFree(ctx->up_pin[i]); if (ctx->up_done[i]) hipEventDestroy(ctx->up_done[i]); }
-        for (auto &e : ctx->up_ready) if (e) hipEventDestroy(e);
-        hipStreamDestroy(ctx->up_stream);
-    }
-    if (ctx->side) { hipStreamSynchronize(ctx->side); for (auto &e : ctx->side_ev) if (e) hipEventDestroy(e); hipStreamDestroy(ctx->side); }
-    if (ctx->owns_stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
+void hobbit_ctx_destroy(hobbit_ctx *ctx) { delete ctx; }     // the order of the teardown: ~hobbit_ctx
 const char *hobbit_last_error(const hobbit_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 int hobbit_sync(hobbit_ctx *ctx) { HB_TRY(ctx->sync()); return 0; }
 // Temporaries of up to 256 MiB come from / go back to the context's size-keyed pool (the host mirror and the Python harness allocate
@@ -383,21 +326,29 @@ int hobbit_malloc(hobbit_ctx *ctx, size_t bytes, void **d_ptr) {
     hipSetDevice(ctx->device);
     if (!bytes) bytes = 16;
     if (bytes <= HB_POOLED_MAX) {
-        if (ctx->pool_get(bytes, d_ptr)) return ctx->fail(HOBBIT_ENOMEM, "hipMalloc failed");
-        ctx->pooled[*d_ptr] = bytes;
+        if (ctx->pool.lend(bytes, d_ptr)) return ctx->fail(HOBBIT_ENOMEM, "hipMalloc failed");
         return 0;
     }
-    if (hipMalloc(d_ptr, bytes) != hipSuccess) {
+    mem::Buf<void> b;
+    if (b.alloc_bytes(bytes)) {
         ctx->pool_drain();
-        if (hipMalloc(d_ptr, bytes) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "hipMalloc failed");
+        if (b.alloc_bytes(bytes)) return ctx->fail(HOBBIT_ENOMEM, "hipMalloc failed");
     }
+    ctx->large[b.get()] = bytes; *d_ptr = b.release();
     return 0;
 }
 int hobbit_free(hobbit_ctx *ctx, void *d_ptr) {
     if (!d_ptr) return 0;
-    auto it = ctx->pooled.find(d_ptr);
-    if (it != ctx->pooled.end()) { const size_t bytes = it->second; ctx->pooled.erase(it); ctx->pool_put(bytes, d_ptr); return 0; }
-    HB_TRY(ctx->sync()); HB_CHECK(ctx, hipFree(d_ptr)); return 0;
+    if (ctx->pool.take_back(d_ptr)) return 0;
+    HB_TRY(ctx->sync());
+    auto it = ctx->large.find(d_ptr);                        // (a pointer this context did not hand out is freed all the same, counted as 0 bytes)
+    mem::Buf<void> b; b.adopt(d_ptr, it != ctx->large.end() ? it->second : 0);
+    if (it != ctx->large.end()) ctx->large.erase(it);
+    return 0;
+}
+void hobbit_mem_live(size_t *allocs, size_t *bytes) {
+    if (allocs) *allocs = mem::live_allocs.load();
+    if (bytes) *bytes = mem::live_bytes.load();
 }
 // Large transfers between the device and PAGEABLE host memory go through the context's two pinned 64 MiB staging pieces, the host side of
 // each piece copied by a few threads while the other piece is on the bus: a plain hipMemcpy of 512 MB of Merkle levels into a std::vector ran at
@@ -492,7 +443,7 @@ int hobbit_f_binop(hobbit_ctx *ctx, int op, const hobbit_F *a, const hobbit_F *b
 int hobbit_fill_splitmix(hobbit_ctx *ctx, hobbit_F *o, size_t n, uint64_t seed) { if (!n) return 0; return launch_fill_splitmix(ctx, mF(o), n, seed); }
 
 // ---- expander graphs --------------------------------------------------------------------------
-int hobbit_graph_reset(hobbit_ctx *ctx) { ctx->graphs.clear(); ctx->graph_gen++; hipStreamSynchronize(ctx->stream); free_code(ctx->code); return 0; }
+int hobbit_graph_reset(hobbit_ctx *ctx) { ctx->graphs.clear(); ctx->graph_gen++; hipStreamSynchronize(ctx->stream); ctx->code = DeviceCode(); return 0; }
 int hobbit_graph_upload(hobbit_ctx *ctx, int dep, int kind, long long L, long long R, int degree, const long long *nbr, const hobbit_F *w) {
     if (dep < 0 || dep >= 100 || (kind != 0 && kind != 1) || L <= 0 || R <= 0 || degree <= 0) return ctx->fail(HOBBIT_EINVAL, "graph_upload: bad dims");
     HostGraph g; g.L = L; g.R = R; g.degree = degree;
@@ -522,10 +473,10 @@ static std::vector<uint32_t> by_in_degree(const InEdges &rows) {
 }
 // a host table into a fresh device allocation (16 bytes for an empty one)
 template <class T>
-static int upload(hobbit_ctx *ctx, T **d, const std::vector<T> &h) {
+static int upload(hobbit_ctx *ctx, mem::Buf<T> *d, const std::vector<T> &h) {
     const size_t bytes = h.size() * sizeof(T);
-    if (hipMalloc((void **)d, bytes ? bytes : 16) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "graph alloc failed");
-    if (bytes) HB_CHECK(ctx, hipMemcpy(*d, h.data(), bytes, hipMemcpyHostToDevice));
+    if (d->alloc_bytes(bytes ? bytes : 16)) return ctx->fail(HOBBIT_ENOMEM, "graph alloc failed");
+    if (bytes) HB_CHECK(ctx, hipMemcpy(d->get(), h.data(), bytes, hipMemcpyHostToDevice));
     return 0;
 }
 // fat form of one step (hobbit_ctx.hpp FatStep): `nout` outputs per lane of `ncons` consumer waves, cap[j] register slots at position j.
@@ -812,7 +763,7 @@ int ensure_fwd(hobbit_ctx *ctx) {
 extern "C" {
 int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
     hipStreamSynchronize(ctx->stream);
-    free_code(ctx->code);
+    ctx->code = DeviceCode();                                     // (the owners in it free their tables: the stream has drained)
     DeviceCode &c = ctx->code;
     const long long thr = 13;   // distance_threshold, src/parameter.h:5
     if (n <= 0 || n > (1 << 20)) return ctx->fail(HOBBIT_EINVAL, "graph_finalize: bad n");
@@ -1010,7 +961,7 @@ struct Uploader {
             // every refill waits for the piece's last transfer, the first two of a call included: an earlier hobbit_commit_standard_host on this
             // context returns with its last pieces still on the bus (an event that was never recorded returns at once)
             if (hipEventSynchronize(ctx->up_done[b]) != hipSuccess) return ctx->fail(HOBBIT_EHIP, "upload: staging buffer wait failed");
-            unsigned char *pin = (unsigned char *)ctx->up_pin[b];
+            unsigned char *pin = (unsigned char *)ctx->up_pin[b].get();
             par_memcpy(pin, src + off, n);
             HB_CHECK(ctx, hipMemcpyAsync(dst + off, pin, n, hipMemcpyHostToDevice, ctx->up_stream));
             HB_CHECK(ctx, hipEventRecord(ctx->up_done[b], ctx->up_stream));
@@ -1122,26 +1073,20 @@ static int commit_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int K,
     if (trs < 4 || trs % 4 || M % (size_t)trs) return ctx->fail(HOBBIT_EINVAL, "commit_standard: trs must be a multiple of 4 dividing N/K");
     if (ilog2_exact(M) < 0) return ctx->fail(HOBBIT_EINVAL, "commit_standard: N/K must be a power of two");
     size_t cols = 2 * M / trs, rows2 = 2 * (size_t)trs;
-    hobbit_commitment *c = new hobbit_commitment();
+    Handle<hobbit_commitment, hobbit_commitment_free> c(new hobbit_commitment());
     c->ctx = ctx; c->N = N; c->M = M; c->K = K; c->trs = trs; c->lin = linear_time; c->cols = (uint32_t)cols; c->rows2 = (uint32_t)rows2;
-    c->d_tensor = nullptr; c->d_levels = nullptr;
-    size_t tbytes = (size_t)K * cols * rows2 * sizeof(F);
-    c->tensor_bytes = tbytes; c->levels_bytes = 64 * M;
-    if (ctx->spare_tensor && ctx->spare_tensor_bytes == tbytes && ctx->spare_levels_bytes == 64 * M) {
-        c->d_tensor = (F *)ctx->spare_tensor; c->d_levels = (uint8_t *)ctx->spare_levels;
-        ctx->spare_tensor = nullptr; ctx->spare_levels = nullptr;
+    const size_t tbytes = (size_t)K * cols * rows2 * sizeof(F);
+    if (ctx->spare_tensor && ctx->spare_tensor.bytes() == tbytes && ctx->spare_levels.bytes() == 64 * M) {
+        c->d_tensor = std::move(ctx->spare_tensor); c->d_levels = std::move(ctx->spare_levels);
     } else {
         if (ctx->spare_tensor) {          // a parked commitment of another shape: release it BEFORE allocating (it can be 16.5 GiB)
             HB_TRY(ctx->sync());
-            hipFree(ctx->spare_tensor); hipFree(ctx->spare_levels);
-            ctx->spare_tensor = nullptr; ctx->spare_levels = nullptr; ctx->spare_tensor_bytes = ctx->spare_levels_bytes = 0;
+            ctx->spare_tensor.reset(); ctx->spare_levels.reset();
         }
-        if (hipMalloc((void **)&c->d_tensor, tbytes) != hipSuccess || hipMalloc((void **)&c->d_levels, 64 * M) != hipSuccess) {
+        if (c->d_tensor.alloc_bytes(tbytes) || c->d_levels.alloc_bytes(64 * M)) {
             ctx->pool_drain();                                    // give back what the pool parks, then once more
-            if (c->d_tensor) { hipFree(c->d_tensor); c->d_tensor = nullptr; }
-            if (hipMalloc((void **)&c->d_tensor, tbytes) != hipSuccess || hipMalloc((void **)&c->d_levels, 64 * M) != hipSuccess) {
-                hobbit_commitment_free(c); return ctx->fail(HOBBIT_ENOMEM, "commit_standard: tensor allocation failed");
-            }
+            c->d_tensor.reset();
+            if (c->d_tensor.alloc_bytes(tbytes) || c->d_levels.alloc_bytes(64 * M)) return ctx->fail(HOBBIT_ENOMEM, "commit_standard: tensor allocation failed");
         }
     }
     const char *st_env = getenv("HOBBIT_COMMIT_SKIP_TAIL");
@@ -1154,8 +1099,8 @@ static int commit_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int K,
     if (!r) r = launch_leaf_chain(ctx, c->d_tensor, cols * rows2, K, (uint32_t)cols, (uint32_t)(trs / 2), c->d_levels,
                                        linear_time && ctx->code.n == trs ? (uint32_t)ctx->code.len : (uint32_t)rows2);
     if (!r) r = launch_merkle_levels(ctx, c->d_levels, M, 1);
-    if (r) { hobbit_commitment_free(c); return r; }
-    *out = c;
+    if (r) return r;
+    *out = c.release();
     return 0;
 }
 void hobbit_commitment_free(hobbit_commitment *c) {
@@ -1163,11 +1108,7 @@ void hobbit_commitment_free(hobbit_commitment *c) {
     hobbit_ctx *ctx = c->ctx;
     hipStreamSynchronize(ctx->stream);
     if (c->d_tensor && c->d_levels && !ctx->spare_tensor) {      // park the buffers for the next commit
-        ctx->spare_tensor = c->d_tensor; ctx->spare_tensor_bytes = c->tensor_bytes;
-        ctx->spare_levels = c->d_levels; ctx->spare_levels_bytes = c->levels_bytes;
-    } else {
-        if (c->d_tensor) hipFree(c->d_tensor);
-        if (c->d_levels) hipFree(c->d_levels);
+        ctx->spare_tensor = std::move(c->d_tensor); ctx->spare_levels = std::move(c->d_levels);
     }
     delete c;
 }
@@ -1179,7 +1120,7 @@ const hobbit_F *hobbit_commitment_tensor_dev(const hobbit_commitment *c) {
         if (launch_zero_rows(m->ctx, m->d_tensor, (size_t)m->K * m->cols, m->rows2, m->rows_valid) != 0 || m->ctx->sync() != 0) return nullptr;
         m->rows_valid = m->rows2;
     }
-    return reinterpret_cast<const hobbit_F *>(c->d_tensor);
+    return reinterpret_cast<const hobbit_F *>(c->d_tensor.get());
 }
 int hobbit_commitment_levels(hobbit_ctx *ctx, const hobbit_commitment *c, uint8_t *h_levels) { return hobbit_memcpy_d2h(ctx, h_levels, c->d_levels, 32 * (2 * c->M - 1)); }
 int hobbit_commitment_root(hobbit_ctx *ctx, const hobbit_commitment *c, uint8_t *h_root) { return hobbit_memcpy_d2h(ctx, h_root, c->d_levels + 32 * (2 * c->M - 2), 32); }
@@ -1236,23 +1177,21 @@ int hobbit_commitment_path(hobbit_ctx *ctx, const hobbit_commitment *c, size_t c
 // ---- Elastic_PC streaming commit (src/Elastic_PC.cpp:174-285) ----------------------------------
 struct hobbit_elastic {
     hobbit_ctx *ctx; size_t B; int trs, lin, shift; uint32_t cols, rows2; size_t count;
-    F *t[4]; uint8_t *state;
+    mem::Pooled<F> t[4]; mem::Pooled<uint8_t> state;
 };
 int hobbit_elastic_begin(hobbit_ctx *ctx, size_t B, int trs, int linear_time, int gcc_arg_order, hobbit_elastic **out) {
     if (!out) return HOBBIT_EINVAL;
     *out = nullptr;
     if (trs <= 0 || B % (size_t)trs || ilog2_exact(B) < 0) return ctx->fail(HOBBIT_EINVAL, "elastic_begin: B must be a power of two and trs divide it");
-    hobbit_elastic *e = new hobbit_elastic();
+    Handle<hobbit_elastic, hobbit_elastic_free> e(new hobbit_elastic());
     e->ctx = ctx; e->B = B; e->trs = trs; e->lin = linear_time; e->shift = gcc_arg_order ? 1 : 0; e->count = 0;
     e->cols = (uint32_t)(2 * B / trs); e->rows2 = (uint32_t)(2 * trs);
-    for (int i = 0; i < 4; i++) e->t[i] = nullptr;
-    e->state = nullptr;
     bool ok = true;
-    for (int i = 0; i < 4 && ok; i++) ok = ctx->pool_get(4 * B * sizeof(F), (void **)&e->t[i]) == 0;
-    ok = ok && ctx->pool_get(4 * B * 32, (void **)&e->state) == 0;
-    if (!ok) { hobbit_elastic_free(e); return ctx->fail(HOBBIT_ENOMEM, "elastic_begin: allocation failed"); }
+    for (int i = 0; i < 4 && ok; i++) ok = ctx->pool_get(4 * B * sizeof(F), e->t[i]) == 0;
+    ok = ok && ctx->pool_get(4 * B * 32, e->state) == 0;
+    if (!ok) return ctx->fail(HOBBIT_ENOMEM, "elastic_begin: allocation failed");
     HB_TRY(launch_zero(ctx, e->state, 4 * B * 32));       // buff_hash starts at zero (:186-193)
-    *out = e;
+    *out = e.release();
     return 0;
 }
 int hobbit_elastic_push(hobbit_ctx *ctx, hobbit_elastic *e, const hobbit_F *d_chunk) {
@@ -1278,12 +1217,7 @@ int hobbit_elastic_finish(hobbit_ctx *ctx, hobbit_elastic *e, uint8_t *d_levels)
     HB_TRY(launch_elastic_finish(ctx, e->state, e->rows2, e->cols, d_levels));
     return launch_merkle_levels(ctx, d_levels, 4 * e->B, 1);                    // :277-283
 }
-void hobbit_elastic_free(hobbit_elastic *e) {
-    if (!e) return;
-    for (int i = 0; i < 4; i++) e->ctx->pool_put(4 * e->B * sizeof(F), e->t[i]);
-    e->ctx->pool_put(4 * e->B * 32, e->state);
-    delete e;
-}
+void hobbit_elastic_free(hobbit_elastic *e) { delete e; }
 
 // ---- inner PCS commitments of the opening (src/Virgo.cpp:104-178) --------------------------------------
 // rows zero-padded to twice their length and transformed: d_enc row i = FFT(row i of d_poly | zeros)
@@ -1744,7 +1678,7 @@ int hobbit_parity_matrix(hobbit_ctx *ctx, const hobbit_F *d_beta, size_t size_a,
     if (size_a < (size_t)c.len) return ctx->fail(HOBBIT_EINVAL, "parity_matrix: A must hold at least the codeword length");
     if (!c.d_pm_rowptr || c.pm_rows != size_a) {
         HB_TRY(ctx->sync());
-        if (c.d_pm_rowptr) { hipFree(c.d_pm_rowptr); hipFree(c.d_pm_idx); hipFree(c.d_pm_w); c.d_pm_rowptr = nullptr; }
+        c.d_pm_rowptr.reset(); c.d_pm_idx.reset(); c.d_pm_w.reset();
         std::vector<std::vector<std::pair<uint32_t, F>>> rows(size_a);
         long long lvl = 0;
         parity_triples(ctx, rows, 0, n, 0, &lvl);
@@ -1753,8 +1687,8 @@ int hobbit_parity_matrix(hobbit_ctx *ctx, const hobbit_F *d_beta, size_t size_a,
             rp[a + 1] = rp[a] + (uint32_t)rows[a].size();
             for (auto &e : rows[a]) { if (e.first >= size_a) return ctx->fail(HOBBIT_EINVAL, "parity_matrix: beta index out of range"); idx.push_back(e.first); w.push_back(e.second); }
         }
-        if (hipMalloc((void **)&c.d_pm_rowptr, rp.size() * 4) != hipSuccess || hipMalloc((void **)&c.d_pm_idx, idx.size() * 4 + 16) != hipSuccess ||
-            hipMalloc((void **)&c.d_pm_w, w.size() * sizeof(F) + 16) != hipSuccess) return ctx->fail(HOBBIT_ENOMEM, "parity_matrix: alloc failed");
+        if (c.d_pm_rowptr.alloc_bytes(rp.size() * 4) || c.d_pm_idx.alloc_bytes(idx.size() * 4 + 16) || c.d_pm_w.alloc_bytes(w.size() * sizeof(F) + 16))
+            return ctx->fail(HOBBIT_ENOMEM, "parity_matrix: alloc failed");
         HB_CHECK(ctx, hipMemcpy(c.d_pm_rowptr, rp.data(), rp.size() * 4, hipMemcpyHostToDevice));
         if (!idx.empty()) { HB_CHECK(ctx, hipMemcpy(c.d_pm_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice)); HB_CHECK(ctx, hipMemcpy(c.d_pm_w, w.data(), w.size() * sizeof(F), hipMemcpyHostToDevice)); }
         c.pm_rows = size_a;
@@ -2027,12 +1961,15 @@ struct hobbit_elastic_open {
     hobbit_ctx *ctx; size_t N, B, K; int trs, queries; uint32_t cols, rows2;
     std::vector<F> beta; std::vector<uint32_t> qc, qr, ucols, qci; F rv0;
     size_t n_aggr, n_reply; bool committed;
-    F *d_aggr, *d_T, *d_G, *d_reply, *d_encf; uint8_t *d_lvf; uint32_t *d_ucols; uint64_t *d_pick; int *d_nz;
-    size_t bytes[9];              // sizes of the nine buffers above (for the context's buffer pool); capacities, not the distinct-column count
+    mem::Pooled<F> d_aggr, d_T, d_G, d_reply, d_encf; mem::Pooled<uint8_t> d_lvf; mem::Pooled<uint32_t> d_ucols; mem::Pooled<uint64_t> d_pick; mem::Pooled<int> d_nz;
     // option 2 (linear_time, RS x expander): the "remaining" columns (a queried parity row), the aggregate's row codes M, aux_commit and C_c
     bool lin; std::vector<uint32_t> rem; size_t np;
-    F *d_M, *d_aux, *d_encc; uint8_t *d_lvc; uint32_t *d_rem;
-    size_t bytes2[5];
+    mem::Pooled<F> d_M, d_aux, d_encc; mem::Pooled<uint8_t> d_lvc; mem::Pooled<uint32_t> d_rem;
+    // the nine buffers both options use, of these sizes (capacities, not the distinct-column count), in this order
+    int get9(const size_t (&sz)[9]) {
+        return ctx->pool_get(sz[0], d_aggr) || ctx->pool_get(sz[1], d_T) || ctx->pool_get(sz[2], d_G) || ctx->pool_get(sz[3], d_reply) || ctx->pool_get(sz[4], d_encf) ||
+               ctx->pool_get(sz[5], d_lvf) || ctx->pool_get(sz[6], d_ucols) || ctx->pool_get(sz[7], d_pick) || ctx->pool_get(sz[8], d_nz);
+    }
 };
 // precompute_beta (src/utils.cpp:251-296) on the host for a handful of variables
 static void host_eq_table(CHP r, int k, std::vector<F> &out) {
@@ -2105,14 +2042,7 @@ static int rs_prover_dev(hobbit_ctx *ctx, const F *d_aggr, size_t B, size_t trs,
     if (o->sp_f) HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<const hobbit_F *>(d_aggr), reinterpret_cast<const hobbit_F *>(d_encf), d_lvf, B, 32, rx.data(), (int)rx.size(), o->sp_f));   // (:507)
     return 0;
 }
-void hobbit_elastic_open_free(hobbit_elastic_open *e) {
-    if (!e) return;
-    void *ptrs[9] = {e->d_aggr, e->d_T, e->d_G, e->d_reply, e->d_encf, e->d_lvf, e->d_ucols, e->d_pick, e->d_nz};
-    for (int i = 0; i < 9; i++) e->ctx->pool_put(e->bytes[i], ptrs[i]);
-    void *ptrs2[5] = {e->d_M, e->d_aux, e->d_encc, e->d_lvc, e->d_rem};
-    if (e->lin) for (int i = 0; i < 5; i++) e->ctx->pool_put(e->bytes2[i], ptrs2[i]);
-    delete e;
-}
+void hobbit_elastic_open_free(hobbit_elastic_open *e) { delete e; }
 
 // ---- Elastic_PC open, RS x expander (test_Elastic_PC option 2, linear_time == true): src/Elastic_PC.cpp:625-726 with aggregate()'s linear_time
 // branch (:348-413), update_reply_spielman (:431-485) and recursive_prover_Spielman_stream (src/PC_utils.cpp:168-270) ------------------------
@@ -2124,11 +2054,9 @@ static int elastic_open_begin_lin(hobbit_ctx *ctx, size_t N, size_t B, int trs, 
     if (trs <= 0 || trs > 4096 || ilog2_exact(B) < 0 || ilog2_exact((size_t)trs) < 0 || B % (size_t)trs || 2 * B / (size_t)trs < 64 || 2 * B / (size_t)trs > ((size_t)1 << 24))
         return ctx->fail(HOBBIT_EINVAL, "elastic_open (linear_time): needs power-of-two B and trs <= 4096 with row codes of 64 .. 2^24 points (the reference: trs = B/2^14)");
     if (N % B || ilog2_exact(N / B) < 0 || queries <= 0 || !h_x) return ctx->fail(HOBBIT_EINVAL, "elastic_open: N/B must be a power of two");
-    hobbit_elastic_open *e = new hobbit_elastic_open();
+    Handle<hobbit_elastic_open, hobbit_elastic_open_free> e(new hobbit_elastic_open());
     e->ctx = ctx; e->N = N; e->B = B; e->K = N / B; e->trs = trs; e->queries = queries; e->cols = (uint32_t)(2 * B / (size_t)trs); e->rows2 = (uint32_t)(2 * trs);
     e->n_aggr = e->n_reply = 0; e->committed = false; e->lin = true;
-    e->d_aggr = e->d_T = e->d_G = e->d_reply = e->d_encf = nullptr; e->d_lvf = nullptr; e->d_ucols = nullptr; e->d_pick = nullptr; e->d_nz = nullptr;
-    e->d_M = e->d_aux = e->d_encc = nullptr; e->d_lvc = nullptr; e->d_rem = nullptr;
     host_eq_table(cF(h_x), ilog2_exact(e->K), e->beta);                                                     // precompute_beta(x1, beta) (:638-643)
     e->rv0 = fadd(fmake((uint64_t)random()), fmake((uint64_t)rand()));                                      // r_v[0] = generate_randomness(1)[0] (:645)
     const size_t nq = (size_t)queries;
@@ -2159,14 +2087,9 @@ static int elastic_open_begin_lin(hobbit_ctx *ctx, size_t N, size_t B, int trs, 
     }
     const size_t sizes[9] = {B * sizeof(F), 2 * B * sizeof(F), (nc + 1) * e->rows2 * sizeof(F), e->K * nq * sizeof(F), 2 * B * sizeof(F),
                              64 * (2 * B / 32), nq * 4, nq * 8, e->K * sizeof(int)};
-    void **slots[9] = {(void **)&e->d_aggr, (void **)&e->d_T, (void **)&e->d_G, (void **)&e->d_reply, (void **)&e->d_encf, (void **)&e->d_lvf, (void **)&e->d_ucols,
-                       (void **)&e->d_pick, (void **)&e->d_nz};
-    const size_t sizes2[5] = {2 * B * sizeof(F), e->np * sizeof(F), 2 * e->np * sizeof(F), 64 * (2 * e->np / 32), (nr ? nr : 1) * 4};
-    void **slots2[5] = {(void **)&e->d_M, (void **)&e->d_aux, (void **)&e->d_encc, (void **)&e->d_lvc, (void **)&e->d_rem};
-    bool ok = true;
-    for (int i = 0; i < 9; i++) { e->bytes[i] = sizes[i]; if (ok) ok = ctx->pool_get(sizes[i], slots[i]) == 0; }
-    for (int i = 0; i < 5; i++) { e->bytes2[i] = sizes2[i]; if (ok) ok = ctx->pool_get(sizes2[i], slots2[i]) == 0; }
-    if (!ok) { hobbit_elastic_open_free(e); return ctx->fail(HOBBIT_ENOMEM, "elastic_open_begin: allocation failed"); }
+    if (e->get9(sizes) || ctx->pool_get(2 * B * sizeof(F), e->d_M) || ctx->pool_get(e->np * sizeof(F), e->d_aux) || ctx->pool_get(2 * e->np * sizeof(F), e->d_encc) ||
+        ctx->pool_get(64 * (2 * e->np / 32), e->d_lvc) || ctx->pool_get((nr ? nr : 1) * 4, e->d_rem))
+        return ctx->fail(HOBBIT_ENOMEM, "elastic_open_begin: allocation failed");
     HB_TRY(launch_zero(ctx, e->d_aggr, B * sizeof(F)));
     HB_TRY(launch_zero(ctx, e->d_nz, e->K * sizeof(int)));
     HB_TRY(launch_zero(ctx, e->d_G, (nc + 1) * e->rows2 * sizeof(F)));                                     // the zero row; the tails past the codeword length stay zero
@@ -2174,7 +2097,7 @@ static int elastic_open_begin_lin(hobbit_ctx *ctx, size_t N, size_t B, int trs, 
     HB_CHECK(ctx, hipMemcpyAsync(e->d_pick, pick.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream));
     if (nr) HB_CHECK(ctx, hipMemcpyAsync(e->d_rem, e->rem.data(), nr * 4, hipMemcpyHostToDevice, ctx->stream));
     HB_TRY(ctx->sync());                                                        // `pick` is a local
-    *out = e;
+    *out = e.release();
     return 0;
 }
 // recursive_prover_Spielman_stream(aggr_vector, aggr_tensor = d_M, aux_commit = d_aux, I) (src/PC_utils.cpp:168-270).  Transcripts P1, P2, P3, P5 back
@@ -2213,23 +2136,23 @@ static int spielman_stream_dev(hobbit_ctx *ctx, hobbit_elastic_open *e, hobbit_e
     for (size_t i = 0; i < nq; i++) { pw[i] = s2; s2 = fmul(s2, s2); }                                      // buff2[i] = s2; s2 = s2*s2 (:243-246): repeated squares at 0 .. nq-1
     HB_TRY(launch_zero(ctx, d_b2, np * sizeof(F)));
     HB_TRY(h2d_staged(ctx, d_b2, pw.data(), nq * sizeof(F)));
-    HB_TRY(hobbit_sumcheck2(ctx, reinterpret_cast<hobbit_F *>(e->d_aux), reinterpret_cast<hobbit_F *>(d_b2), np, &p121, Q3, Rr3, o->vr + 4, o->fin + 2));   // P3 (:248)
-    HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<hobbit_F *>(e->d_aux), reinterpret_cast<hobbit_F *>(e->d_encc), e->d_lvc, np, 32, Rr3, R3, o->sp_c));   // (:252)
+    HB_TRY(hobbit_sumcheck2(ctx, reinterpret_cast<hobbit_F *>(e->d_aux.get()), reinterpret_cast<hobbit_F *>(d_b2), np, &p121, Q3, Rr3, o->vr + 4, o->fin + 2));   // P3 (:248)
+    HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<hobbit_F *>(e->d_aux.get()), reinterpret_cast<hobbit_F *>(e->d_encc.get()), e->d_lvc, np, 32, Rr3, R3, o->sp_c));   // (:252)
     // r = P1.randomness[0] (all of it: the pop_back at :256 follows the copy) | P2.randomness[0]; evaluate_vector and prove_fft_matrix use its first
     // log2(trs * cols) entries, the transcript of P5 is seeded with its last one (:255-266)
     std::vector<hobbit_F> rcat((size_t)R1 + (size_t)logc);
     memcpy(rcat.data(), Rr1, sizeof(hobbit_F) * (size_t)R1); memcpy(rcat.data() + R1, Rr2, sizeof(hobbit_F) * (size_t)logc);
     F y1;
-    HB_TRY(hobbit_eval_vector(ctx, reinterpret_cast<hobbit_F *>(e->d_M), trs * cols, rcat.data(), reinterpret_cast<hobbit_F *>(&y1)));
+    HB_TRY(hobbit_eval_vector(ctx, reinterpret_cast<hobbit_F *>(e->d_M.get()), trs * cols, rcat.data(), reinterpret_cast<hobbit_F *>(&y1)));
     *mF(&o->scal[2]) = y1;
-    HB_TRY(prove_fft_matrix_seeded(ctx, reinterpret_cast<const hobbit_F *>(e->d_aggr), trs, half, rcat.data(), &rcat[rcat.size() - 1], Q5, Rr5, o->vr + 6, o->fin + 3));   // P5 (:266)
+    HB_TRY(prove_fft_matrix_seeded(ctx, reinterpret_cast<const hobbit_F *>(e->d_aggr.get()), trs, half, rcat.data(), &rcat[rcat.size() - 1], Q5, Rr5, o->vr + 6, o->fin + 3));   // P5 (:266)
     { CHP q5 = cF(Q5); o->checks[0] = feq(fadd(fadd(q5[0], q5[1]), fadd(q5[2], q5[2])), y1); }      // src/sumcheck.cpp:3016-3019
     // P5.randomness[0] = its logc challenges | r1 = r[logc .. logc + log2 trs); pop_back (:268); shockwave_prove(C_f, .) (:269)
     std::vector<hobbit_F> rx((size_t)logc + (size_t)logt);
     memcpy(rx.data(), Rr5, sizeof(hobbit_F) * (size_t)logc); memcpy(rx.data() + logc, rcat.data() + logc, sizeof(hobbit_F) * (size_t)logt);
     rx.pop_back();
     if (o->rx) memcpy(o->rx, rx.data(), sizeof(hobbit_F) * rx.size());
-    HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<const hobbit_F *>(e->d_aggr), reinterpret_cast<const hobbit_F *>(e->d_encf), e->d_lvf, B, 32, rx.data(), (int)rx.size(), o->sp_f));
+    HB_TRY(hobbit_shockwave_prove(ctx, reinterpret_cast<const hobbit_F *>(e->d_aggr.get()), reinterpret_cast<const hobbit_F *>(e->d_encf.get()), e->d_lvf, B, 32, rx.data(), (int)rx.size(), o->sp_f));
     return sc.finish();
 }
 static int elastic_open_begin_lin(hobbit_ctx *ctx, size_t N, size_t B, int trs, const hobbit_F *h_x, int queries, hobbit_elastic_open **out);
@@ -2244,10 +2167,9 @@ int hobbit_elastic_open_begin(hobbit_ctx *ctx, size_t N, size_t B, int trs, cons
     if (trs <= 0 || ilog2_exact(B) < 0 || ilog2_exact((size_t)trs) < 0 || B % (size_t)trs || 2 * B / (size_t)trs != 4096 || 2 * trs > 4096)
         return ctx->fail(HOBBIT_EINVAL, "elastic_open: needs trs = B/2^11 (4096-point row codes) and 2*trs <= 4096");
     if (N % B || ilog2_exact(N / B) < 0 || queries <= 0 || !h_x) return ctx->fail(HOBBIT_EINVAL, "elastic_open: N/B must be a power of two");
-    hobbit_elastic_open *e = new hobbit_elastic_open();
+    Handle<hobbit_elastic_open, hobbit_elastic_open_free> e(new hobbit_elastic_open());
     e->ctx = ctx; e->N = N; e->B = B; e->K = N / B; e->trs = trs; e->queries = queries; e->cols = 4096; e->rows2 = (uint32_t)(2 * trs);
     e->n_aggr = e->n_reply = 0; e->committed = false; e->lin = false;
-    e->d_aggr = e->d_T = e->d_G = e->d_reply = e->d_encf = nullptr; e->d_lvf = nullptr; e->d_ucols = nullptr; e->d_pick = nullptr; e->d_nz = nullptr;
     host_eq_table(cF(h_x), ilog2_exact(e->K), e->beta);                                                     // precompute_beta(x1, beta) (:638-643)
     e->rv0 = fadd(fmake((uint64_t)random()), fmake((uint64_t)rand()));                                      // r_v[0] = generate_randomness(1)[0] (:645)
     e->qc.resize(queries); e->qr.resize(queries);
@@ -2261,17 +2183,13 @@ int hobbit_elastic_open_begin(hobbit_ctx *ctx, size_t N, size_t B, int trs, cons
     }
     const size_t sizes[9] = {B * sizeof(F), (size_t)trs * 4096 * sizeof(F), (size_t)queries * e->rows2 * sizeof(F), e->K * (size_t)queries * sizeof(F), 2 * B * sizeof(F),
                              64 * (2 * B / 32), (size_t)queries * 4, (size_t)queries * 8, e->K * sizeof(int)};
-    void **slots[9] = {(void **)&e->d_aggr, (void **)&e->d_T, (void **)&e->d_G, (void **)&e->d_reply, (void **)&e->d_encf, (void **)&e->d_lvf, (void **)&e->d_ucols,
-                       (void **)&e->d_pick, (void **)&e->d_nz};
-    bool ok = true;
-    for (int i = 0; i < 9; i++) { e->bytes[i] = sizes[i]; if (ok) ok = ctx->pool_get(sizes[i], slots[i]) == 0; }
-    if (!ok) { hobbit_elastic_open_free(e); return ctx->fail(HOBBIT_ENOMEM, "elastic_open_begin: allocation failed"); }
+    if (e->get9(sizes)) return ctx->fail(HOBBIT_ENOMEM, "elastic_open_begin: allocation failed");
     HB_TRY(launch_zero(ctx, e->d_aggr, B * sizeof(F)));
     HB_TRY(launch_zero(ctx, e->d_nz, e->K * sizeof(int)));
     HB_CHECK(ctx, hipMemcpyAsync(e->d_ucols, e->ucols.data(), nc * 4, hipMemcpyHostToDevice, ctx->stream));
     HB_CHECK(ctx, hipMemcpyAsync(e->d_pick, pick.data(), (size_t)queries * 8, hipMemcpyHostToDevice, ctx->stream));
     HB_TRY(ctx->sync());                                                        // `pick` is a local
-    *out = e;
+    *out = e.release();
     return 0;
 }
 void hobbit_elastic_open_dims(const hobbit_elastic_open *e, int *ncols, int *nrem, size_t *np) {
@@ -2293,7 +2211,7 @@ static int elastic_row_codes(hobbit_ctx *ctx, const F *d_v, size_t B, size_t trs
 }
 int hobbit_elastic_open_aggregate_finish(hobbit_ctx *ctx, hobbit_elastic_open *e) {
     if (e->n_aggr != e->K) return ctx->fail(HOBBIT_ESTATE, "elastic_open: aggregate pass incomplete");
-    HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(e->d_aggr), e->B, 32, reinterpret_cast<hobbit_F *>(e->d_encf), e->d_lvf));   // C_f (:343-346, :349)
+    HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(e->d_aggr.get()), e->B, 32, reinterpret_cast<hobbit_F *>(e->d_encf.get()), e->d_lvf));   // C_f (:343-346, :349)
     if (e->lin) {
         // aggregate()'s linear_time branch (:350-411): aggregated_tensor = the aggregate's rows RS-encoded; aux_commit = the expander codewords of
         // the queried columns that have a parity-row query; C_c = shockwave_commit(pad(aux_commit), 32)
@@ -2303,7 +2221,7 @@ int hobbit_elastic_open_aggregate_finish(hobbit_ctx *ctx, hobbit_elastic_open *e
         HB_TRY(launch_zero(ctx, e->d_aux, e->np * sizeof(F)));
         HB_TRY(launch_gather_cols(ctx, e->d_M, e->cols, (uint32_t)e->trs, e->d_rem, nr, e->d_aux, e->rows2));
         HB_TRY(launch_encode(ctx, e->d_aux, e->rows2, e->d_aux, e->rows2, e->trs, nr, 0));
-        HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(e->d_aux), e->np, 32, reinterpret_cast<hobbit_F *>(e->d_encc), e->d_lvc));
+        HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(e->d_aux.get()), e->np, 32, reinterpret_cast<hobbit_F *>(e->d_encc.get()), e->d_lvc));
     }
     e->committed = true;
     return 0;
@@ -2369,13 +2287,12 @@ int hobbit_open_standard_rs(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, c
     if (N != c->N || logK < 0) return ctx->fail(HOBBIT_EINVAL, "open_standard_rs: polynomial / commitment mismatch");
     std::vector<F> beta; host_eq_table(cF(h_x), logK, beta);                                                // precompute_beta(x1, beta) (:619-621)
     const F rv0 = fadd(fmake((uint64_t)random()), fmake((uint64_t)rand()));                                 // r_v[0] = generate_randomness(1)[0] (:623)
-    F *d_aggr = nullptr, *d_encf = nullptr; uint8_t *d_lvf = nullptr; uint32_t *d_ucols = nullptr;
-    auto release = [&]() { ctx->pool_put(B * sizeof(F), d_aggr); ctx->pool_put(2 * B * sizeof(F), d_encf); ctx->pool_put(64 * (2 * B / 32), d_lvf); ctx->pool_put(nq * 4, d_ucols); };
-    if (ctx->pool_get(B * sizeof(F), (void **)&d_aggr) || ctx->pool_get(2 * B * sizeof(F), (void **)&d_encf) || ctx->pool_get(64 * (2 * B / 32), (void **)&d_lvf) ||
-        ctx->pool_get(nq * 4, (void **)&d_ucols)) { release(); return ctx->fail(HOBBIT_ENOMEM, "open_standard_rs: allocation failed"); }
-    int rc = [&]() -> int {
+    mem::Pooled<F> d_aggr, d_encf; mem::Pooled<uint8_t> d_lvf; mem::Pooled<uint32_t> d_ucols;
+    if (ctx->pool_get(B * sizeof(F), d_aggr) || ctx->pool_get(2 * B * sizeof(F), d_encf) || ctx->pool_get(64 * (2 * B / 32), d_lvf) || ctx->pool_get(nq * 4, d_ucols))
+        return ctx->fail(HOBBIT_ENOMEM, "open_standard_rs: allocation failed");
+    {
         HB_TRY(launch_aggregate(ctx, cF(d_poly), B, K, beta.data(), d_aggr));                               // _aggregate (:267-272)
-        HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(d_aggr), B, 32, reinterpret_cast<hobbit_F *>(d_encf), d_lvf));   // C_f (:274-275)
+        HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(d_aggr.get()), B, 32, reinterpret_cast<hobbit_F *>(d_encf.get()), d_lvf));   // C_f (:274-275)
         std::vector<uint32_t> qc(nq), qr(nq);
         for (size_t q = 0; q < nq; q++) { qc[q] = (uint32_t)(rand() % (long)cols); qr[q] = (uint32_t)(rand() % (long)rows2); }      // (:634-638)
         std::vector<uint32_t> ucols(qc); std::sort(ucols.begin(), ucols.end()); ucols.erase(std::unique(ucols.begin(), ucols.end()), ucols.end());
@@ -2389,9 +2306,7 @@ int hobbit_open_standard_rs(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, c
         if (o->reply_len) *o->reply_len = K;
         if (o->paths) HB_TRY(hobbit_commitment_paths(ctx, c, qc.data(), qr.data(), nq, o->paths));          // open_tree_blake(Commitment_MT, I[i], 2B/trs) (:643-645)
         return rs_prover_dev(ctx, d_aggr, B, trs, qc, qr, ucols, d_ucols, d_encf, d_lvf, o);                // (:651-653)
-    }();
-    release();
-    return rc;
+    }
 }
 
 // ---- streaming (space-efficient) provers over a caller-supplied chunk source -------------------------------------------------
@@ -2937,7 +2852,7 @@ struct OpenRun {
         if (full) HB_TRY(ctx->workspace4((shockwave_nested_elems(nc_el / 32) + shockwave_own_elems(nc_el / 32, 32)) * sizeof(F), &dummy));
         HB_TRY(ctx->pinned(std::max((size_t)queries * (sizeof(F) + 8) + 4096, (WHIR_DIN * 6 + WHIR_DRES) * sizeof(F)), &dummy));
         tr.mark("scratch sizing");
-        if (tr.on) fprintf(stderr, "[hobbit open] scratch at entry: ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws_bytes, ctx->ws2_bytes, ctx->ws3_bytes, ctx->ws4_bytes, ctx->pin_bytes);
+        if (tr.on) fprintf(stderr, "[hobbit open] scratch at entry: ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws[0].bytes(), ctx->ws[1].bytes(), ctx->ws[2].bytes(), ctx->ws[3].bytes(), ctx->pin.bytes());
         d_aggr = arena; BIG = d_aggr + M; Tcm = BIG + big; d_s = Tcm + big; d_ev = d_s + cols; d_ac = d_ev + cols; d_b1 = d_ac + rows2;
         Mp = BIG; C = BIG + nc_el;
         tmpv = d_b1 + rows2; tmpi = reinterpret_cast<uint64_t *>(tmpv + queries + 1);                 // the sparse buff2: (index, value) lists
@@ -3192,7 +3107,7 @@ static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
         r.sp_thread.join();
         if (r.sp_rc) return ctx->fail(r.sp_rc, std::string("shockwave_prove(C_c) on the helper context: ") + ctx->helper->err);
     }
-    if (r.tr.on) fprintf(stderr, "[hobbit open] scratch at exit:  ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws_bytes, ctx->ws2_bytes, ctx->ws3_bytes, ctx->ws4_bytes, ctx->pin_bytes);
+    if (r.tr.on) fprintf(stderr, "[hobbit open] scratch at exit:  ws %zu ws2 %zu ws3 %zu ws4 %zu pin %zu\n", ctx->ws[0].bytes(), ctx->ws[1].bytes(), ctx->ws[2].bytes(), ctx->ws[3].bytes(), ctx->pin.bytes());
     return r.finish();
 }
 static int open_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
@@ -3255,7 +3170,7 @@ int hobbit_encode_interleaved(hobbit_ctx *ctx, const hobbit_F *d_src, hobbit_F *
 struct hobbit_brakedown {
     hobbit_ctx *ctx;
     size_t N, B; uint32_t rows; long long len; int quirk;
-    F *d_mat; uint8_t *d_levels;           // 2B columns x rows, element (i, c) at c * rows + i | flat levels over the 2B column digests
+    mem::Buf<F> d_mat; mem::Buf<uint8_t> d_levels;     // 2B columns x rows, element (i, c) at c * rows + i | flat levels over the 2B column digests
 };
 int hobbit_brakedown_shape(size_t N, size_t *B, uint32_t *rows) {
     const int n = ilog2_exact(N);
@@ -3268,8 +3183,6 @@ int hobbit_brakedown_shape(size_t N, size_t *B, uint32_t *rows) {
 void hobbit_brakedown_free(hobbit_brakedown *c) {
     if (!c) return;
     hipStreamSynchronize(c->ctx->stream);
-    if (c->d_mat) hipFree(c->d_mat);
-    if (c->d_levels) hipFree(c->d_levels);
     delete c;
 }
 }  // extern "C"
@@ -3279,18 +3192,16 @@ int hobbit::brakedown_commit_shape(hobbit_ctx *ctx, const F *d_poly, size_t B, u
     *out = nullptr;
     HB_TRY(ensure_ilv(ctx));
     const size_t W = 2 * B;
-    hobbit_brakedown *c = new hobbit_brakedown{ctx, B * rows, B, rows, ctx->code.len, left_left_quirk ? 1 : 0, nullptr, nullptr};
-    if (hipMalloc((void **)&c->d_mat, W * rows * sizeof(F)) != hipSuccess || hipMalloc((void **)&c->d_levels, (2 * W - 1) * 32) != hipSuccess) {
-        hobbit_brakedown_free(c); return ctx->fail(HOBBIT_ENOMEM, "brakedown_commit: device allocation failed");
-    }
+    Handle<hobbit_brakedown, hobbit_brakedown_free> c(new hobbit_brakedown{ctx, B * rows, B, rows, ctx->code.len, left_left_quirk ? 1 : 0, {}, {}});
+    if (c->d_mat.alloc(W * rows) || c->d_levels.alloc((2 * W - 1) * 32)) return ctx->fail(HOBBIT_ENOMEM, "brakedown_commit: device allocation failed");
     // row i of the message (poly[i B .. (i + 1) B)) becomes entry i of columns 0 .. B - 1; every row is then encoded in place (tensor[0][i])
     int r = launch_transpose(ctx, d_poly, 0, rows, (uint32_t)B, c->d_mat, 0, rows, 1);
     if (!r) r = launch_encode_ilv(ctx, c->d_mat, c->d_mat, rows);
     // MT_commit_Blake of every column -> level 0 (columns [len, 2B) are zero), then create_tree_blake over the 2B digests
     if (!r) r = launch_brakedown_digests(ctx, c->d_mat, rows, (size_t)c->len, W - (size_t)c->len, c->quirk, c->d_levels);
     if (!r) r = launch_merkle_levels(ctx, c->d_levels, W, c->quirk);
-    if (r) { hobbit_brakedown_free(c); return r; }
-    *out = c;
+    if (r) return r;
+    *out = c.release();
     return 0;
 }
 extern "C" {
@@ -3307,7 +3218,7 @@ int hobbit_brakedown_dims(const hobbit_brakedown *c, size_t *B, uint32_t *rows, 
     if (len) *len = c->len;
     return 0;
 }
-const hobbit_F *hobbit_brakedown_matrix_dev(const hobbit_brakedown *c) { return reinterpret_cast<const hobbit_F *>(c->d_mat); }
+const hobbit_F *hobbit_brakedown_matrix_dev(const hobbit_brakedown *c) { return reinterpret_cast<const hobbit_F *>(c->d_mat.get()); }
 const uint8_t *hobbit_brakedown_levels_dev(const hobbit_brakedown *c) { return c->d_levels; }
 int hobbit_brakedown_levels(hobbit_ctx *ctx, const hobbit_brakedown *c, uint8_t *h_levels) { return hobbit_memcpy_d2h(ctx, h_levels, c->d_levels, 32 * (4 * c->B - 1)); }
 int hobbit_brakedown_root(hobbit_ctx *ctx, const hobbit_brakedown *c, uint8_t *h_root) { return hobbit_memcpy_d2h(ctx, h_root, c->d_levels + 32 * (4 * c->B - 2), 32); }
@@ -3371,32 +3282,23 @@ int hobbit_brakedown_stream_shape(size_t N, size_t *B, uint32_t *chunks) {
     return 0;
 }
 struct hobbit_brakedown_stream {
-    hobbit_ctx *ctx; size_t B; long long len; int shift; size_t count; bool finished; size_t bytes;
-    F *d_mat; uint8_t *state;              // 2B columns x 4 rows | the 2B running leaves
+    hobbit_ctx *ctx; size_t B; long long len; int shift; size_t count; bool finished;
+    mem::Pooled<F> d_mat; mem::Pooled<uint8_t> state;      // 2B columns x 4 rows | the 2B running leaves
 };
-void hobbit_brakedown_stream_free(hobbit_brakedown_stream *s) {
-    if (!s) return;
-    s->ctx->pool_put(8 * s->B * sizeof(F), s->d_mat);
-    s->ctx->pool_put(2 * s->B * 32, s->state);
-    delete s;
-}
+void hobbit_brakedown_stream_free(hobbit_brakedown_stream *s) { delete s; }
 int hobbit_brakedown_stream_begin(hobbit_ctx *ctx, size_t B, int gcc_arg_order, hobbit_brakedown_stream **out) {
     if (!out) return HOBBIT_EINVAL;
     *out = nullptr;
     if (ilog2_exact(B) < 0 || B > ((size_t)1 << 20)) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_begin: B must be a power of two, at most 2^20");
     if (ctx->code.n != (long long)B) return ctx->fail(HOBBIT_ESTATE, "brakedown_stream_begin: graphs for n = B are not finalized (expander_init_store(B))");
     HB_TRY(ensure_ilv(ctx));
-    hobbit_brakedown_stream *s = new hobbit_brakedown_stream{ctx, B, ctx->code.len, gcc_arg_order ? 1 : 0, 0, false, 0, nullptr, nullptr};
-    if (ctx->pool_get(8 * B * sizeof(F), (void **)&s->d_mat) || ctx->pool_get(2 * B * 32, (void **)&s->state)) {
-        hobbit_brakedown_stream_free(s); return ctx->fail(HOBBIT_ENOMEM, "brakedown_stream_begin: allocation failed");
-    }
-    s->bytes = 8 * B * sizeof(F) + 2 * B * 32;
-    int r = launch_zero(ctx, s->state, 2 * B * 32);       // buff_hash starts at zero (:125-130)
-    if (r) { hobbit_brakedown_stream_free(s); return r; }
-    *out = s;
+    Handle<hobbit_brakedown_stream, hobbit_brakedown_stream_free> s(new hobbit_brakedown_stream{ctx, B, ctx->code.len, gcc_arg_order ? 1 : 0, 0, false, {}, {}});
+    if (ctx->pool_get(8 * B * sizeof(F), s->d_mat) || ctx->pool_get(2 * B * 32, s->state)) return ctx->fail(HOBBIT_ENOMEM, "brakedown_stream_begin: allocation failed");
+    HB_TRY(launch_zero(ctx, s->state, 2 * B * 32));       // buff_hash starts at zero (:125-130)
+    *out = s.release();
     return 0;
 }
-size_t hobbit_brakedown_stream_device_bytes(const hobbit_brakedown_stream *s) { return s->bytes; }
+size_t hobbit_brakedown_stream_device_bytes(const hobbit_brakedown_stream *s) { return s->d_mat.bytes() + s->state.bytes(); }
 int hobbit_brakedown_stream_push(hobbit_ctx *ctx, hobbit_brakedown_stream *s, const hobbit_F *d_chunk) {
     if (s->finished) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_push: the commitment is finished");
     if (ctx->code.n != (long long)s->B) return ctx->fail(HOBBIT_ESTATE, "brakedown_stream_push: graphs for n = B are not finalized");
@@ -3419,16 +3321,10 @@ int hobbit_brakedown_stream_finish(hobbit_ctx *ctx, hobbit_brakedown_stream *s, 
 }
 
 struct hobbit_brakedown_stream_open {
-    hobbit_ctx *ctx; size_t B, chunks, nq; long long len; size_t n_aggr, n_reply, bytes;
-    F *d_mat, *d_ab, *d_ar, *d_w, *d_reply; uint32_t *d_I;      // d_w: beta (chunks F) then r_v (chunks F)
-    size_t sz[6];
+    hobbit_ctx *ctx; size_t B, chunks, nq; long long len; size_t n_aggr, n_reply;
+    mem::Pooled<F> d_mat, d_ab, d_ar, d_w, d_reply; mem::Pooled<uint32_t> d_I;      // d_w: beta (chunks F) then r_v (chunks F)
 };
-void hobbit_brakedown_stream_open_free(hobbit_brakedown_stream_open *o) {
-    if (!o) return;
-    void *ptrs[6] = {o->d_mat, o->d_ab, o->d_ar, o->d_w, o->d_reply, o->d_I};
-    for (int i = 0; i < 6; i++) o->ctx->pool_put(o->sz[i], ptrs[i]);
-    delete o;
-}
+void hobbit_brakedown_stream_open_free(hobbit_brakedown_stream_open *o) { delete o; }
 int hobbit_brakedown_stream_open_begin(hobbit_ctx *ctx, size_t B, size_t chunks, const hobbit_F *h_beta, const hobbit_F *h_rv, const uint64_t *h_I, size_t nq,
                                        hobbit_brakedown_stream_open **out) {
     if (!out) return HOBBIT_EINVAL;
@@ -3439,13 +3335,11 @@ int hobbit_brakedown_stream_open_begin(hobbit_ctx *ctx, size_t B, size_t chunks,
     for (size_t q = 0; q < nq; q++) if (h_I[q] >= 2 * B) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_begin: query out of range");
     if (ctx->code.n != (long long)B) return ctx->fail(HOBBIT_ESTATE, "brakedown_stream_open_begin: graphs for n = B are not finalized (expander_init_store(B))");
     HB_TRY(ensure_ilv(ctx));
-    hobbit_brakedown_stream_open *o = new hobbit_brakedown_stream_open();
-    o->ctx = ctx; o->B = B; o->chunks = chunks; o->nq = nq; o->len = ctx->code.len; o->n_aggr = o->n_reply = 0; o->bytes = 0;
-    const size_t sizes[6] = {8 * B * sizeof(F), B * sizeof(F), B * sizeof(F), 2 * chunks * sizeof(F), (nq ? nq : 1) * chunks * sizeof(F), (nq ? nq : 1) * 4};
-    void **slots[6] = {(void **)&o->d_mat, (void **)&o->d_ab, (void **)&o->d_ar, (void **)&o->d_w, (void **)&o->d_reply, (void **)&o->d_I};
-    bool ok = true;
-    for (int i = 0; i < 6; i++) { o->sz[i] = sizes[i]; *slots[i] = nullptr; if (ok) { ok = ctx->pool_get(sizes[i], slots[i]) == 0; if (ok) o->bytes += sizes[i]; } }
-    if (!ok) { hobbit_brakedown_stream_open_free(o); return ctx->fail(HOBBIT_ENOMEM, "brakedown_stream_open_begin: allocation failed"); }
+    Handle<hobbit_brakedown_stream_open, hobbit_brakedown_stream_open_free> o(new hobbit_brakedown_stream_open());
+    o->ctx = ctx; o->B = B; o->chunks = chunks; o->nq = nq; o->len = ctx->code.len; o->n_aggr = o->n_reply = 0;
+    if (ctx->pool_get(8 * B * sizeof(F), o->d_mat) || ctx->pool_get(B * sizeof(F), o->d_ab) || ctx->pool_get(B * sizeof(F), o->d_ar) || ctx->pool_get(2 * chunks * sizeof(F), o->d_w) ||
+        ctx->pool_get((nq ? nq : 1) * chunks * sizeof(F), o->d_reply) || ctx->pool_get((nq ? nq : 1) * 4, o->d_I))
+        return ctx->fail(HOBBIT_ENOMEM, "brakedown_stream_open_begin: allocation failed");
     StageScope sc(ctx);
     int r = h2d_staged(ctx, o->d_w, h_beta, chunks * sizeof(F));
     if (!r) r = h2d_staged(ctx, o->d_w + chunks, h_rv, chunks * sizeof(F));
@@ -3453,11 +3347,13 @@ int hobbit_brakedown_stream_open_begin(hobbit_ctx *ctx, size_t B, size_t chunks,
     if (!r) r = launch_zero(ctx, o->d_ab, B * sizeof(F));
     if (!r) r = launch_zero(ctx, o->d_ar, B * sizeof(F));
     if (!r) r = sc.finish();
-    if (r) { hobbit_brakedown_stream_open_free(o); return r; }
-    *out = o;
+    if (r) return r;
+    *out = o.release();
     return 0;
 }
-size_t hobbit_brakedown_stream_open_device_bytes(const hobbit_brakedown_stream_open *o) { return o->bytes; }
+size_t hobbit_brakedown_stream_open_device_bytes(const hobbit_brakedown_stream_open *o) {
+    return o->d_mat.bytes() + o->d_ab.bytes() + o->d_ar.bytes() + o->d_w.bytes() + o->d_reply.bytes() + o->d_I.bytes();
+}
 int hobbit_brakedown_stream_open_aggregate_push(hobbit_ctx *ctx, hobbit_brakedown_stream_open *o, const hobbit_F *d_chunk) {
     if (o->n_aggr >= o->chunks) return ctx->fail(HOBBIT_EINVAL, "brakedown_stream_open_aggregate_push: more chunks than the opening was begun with");
     const uint32_t slot = (uint32_t)(o->n_aggr % 4);

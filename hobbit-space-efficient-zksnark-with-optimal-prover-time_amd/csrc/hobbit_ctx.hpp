@@ -6,10 +6,13 @@
 #include <chrono>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 #include "hobbit_field.hpp"
+#include "hobbit_mem.hpp"
 #include "../../include/hobbit_hip.h"
+#include "../../include/hobbit_parity.h"
 
 namespace hobbit {
 
@@ -53,7 +56,7 @@ struct HostGraph {          // one uploaded level (src/expanders.h:7-16)
 struct FatStep {
     bool ok = false;
     uint32_t in_off = 0, in_len = 0, out_off = 0, out_len = 0;
-    uint32_t *d_wt = nullptr, *d_ot = nullptr, *d_oidx = nullptr, *d_w = nullptr;
+    mem::Buf<uint32_t> d_wt, d_ot, d_oidx, d_w;
 };
 // outputs per lane, consumer waves, register slots per position, workgroups per launch
 static constexpr uint32_t FAT_A_NOUT = 2, FAT_A_CONS = 7, FAT_A_CAP0 = 72, FAT_A_CAP1 = 48, FAT_A_WGS = 256;          // C_0 of n = 4096: 864 outputs, in-degree 42.7 +- 6.5
@@ -82,7 +85,7 @@ static constexpr uint32_t NARROW_WGS = 2048;                             // one-
 struct NarrowPlan {
     bool ok = false;
     uint32_t x2_off = 0;                                                 // x_2's place in the column
-    uint32_t *d_wt = nullptr, *d_ot = nullptr, *d_q = nullptr;           // slot-major [slot][lane]: weights, packed places, packed output byte offsets
+    mem::Buf<uint32_t> d_wt, d_ot, d_q;                                  // slot-major [slot][lane]: weights, packed places, packed output byte offsets
 };
 
 // Long codes (codeword over 160 KB: n >= ~6000, tensor_row_size 8192 / 16384 of Our_PC): the outer steps C_0 .. C_{d-1} and D_{d-1} .. D_0,
@@ -118,19 +121,19 @@ struct DeviceCode {         // finalized code for one message length n
     long long n = 0, len = 0;
     bool small_weights = true;               // all weights real and < 2^32
     std::vector<EncStep> steps;
-    EncStep *d_steps = nullptr;
-    uint32_t *d_slice_ptr = nullptr, *d_slice_width = nullptr, *d_slice_out = nullptr;   // per slice: offset, records per output, output ids
-    uint2 *d_edges32 = nullptr;              // {idx, w32}          (small_weights)
-    uint32_t *d_eidx = nullptr; F *d_ew = nullptr;   // general weights
+    mem::Buf<EncStep> d_steps;
+    mem::Buf<uint32_t> d_slice_ptr, d_slice_width, d_slice_out;   // per slice: offset, records per output, output ids
+    mem::Buf<uint2> d_edges32;               // {idx, w32}          (small_weights)
+    mem::Buf<uint32_t> d_eidx; mem::Buf<F> d_ew;     // general weights
     size_t n_edges_padded = 0, n_edges = 0;
     FatStep fatA, fatC1, fatD;               // first, second and last step in fat form (deep codes only: n = 4096)
     NarrowPlan narrow;                       // the five steps between them, one wave per column (n = 4096 with the degrees the kernel was compiled for)
     // long codes: steps [0, tiled_depth) and [nsteps - tiled_depth, nsteps) in tiled form (tiled_depth = 0: the codeword fits in LDS)
     uint32_t tiled_depth = 0;
     std::vector<TiledStep> tsteps;           // C_0 .. C_{d-1}, then D_{d-1} .. D_0 (the order of `steps`)
-    uint32_t *d_tile_ptr = nullptr, *d_tile_width = nullptr, *d_tile_out = nullptr;
-    uint2 *d_tile_e32 = nullptr;             // {index in the tile, w32}   (small_weights)
-    uint32_t *d_tile_eidx = nullptr; F *d_tile_ew = nullptr;   // general weights
+    mem::Buf<uint32_t> d_tile_ptr, d_tile_width, d_tile_out;
+    mem::Buf<uint2> d_tile_e32;              // {index in the tile, w32}   (small_weights)
+    mem::Buf<uint32_t> d_tile_eidx; mem::Buf<F> d_tile_ew;     // general weights
     size_t tile_records = 0;
     // Built on first use, not by hobbit_graph_finalize: the tiled steps (a long code through launch_encode: ensure_tiled) and the CSR steps of
     // the rows-innermost encode (ensure_ilv).  `plan` lists the steps in order (C_0 .. C_{D-1}, D_{D-1} .. D_0) over the uploaded graphs of
@@ -138,18 +141,18 @@ struct DeviceCode {         // finalized code for one message length n
     std::vector<PlanStep> plan; std::vector<long long> cwlen; uint64_t graph_gen = 0; bool tiled_built = false;
     bool ilv_built = false;
     std::vector<IlvStep> isteps;
-    uint32_t *d_ilv_ptr = nullptr;
-    uint2 *d_ilv_e32 = nullptr;              // {index relative to in_off, w32}   (small_weights)
-    uint32_t *d_ilv_eidx = nullptr; F *d_ilv_ew = nullptr;   // general weights
+    mem::Buf<uint32_t> d_ilv_ptr;
+    mem::Buf<uint2> d_ilv_e32;               // {index relative to in_off, w32}   (small_weights)
+    mem::Buf<uint32_t> d_ilv_eidx; mem::Buf<F> d_ilv_ew;       // general weights
     // The code's forward form (hobbit_parity_commit_device: ensure_fwd), built on first use: the neighbours and weights of every plan step
     // in list order (C_0 .. C_{D-1}, D_{D-1} .. D_0), and the segment table of the access lists (m entries in all)
     bool fwd_built = false;
     std::vector<ParitySeg> fwd_segs; size_t fwd_m = 0;
-    ParitySeg *d_fwd_segs = nullptr;
-    uint32_t *d_fwd_nbr = nullptr, *d_fwd_w32 = nullptr;   // w32 under small_weights
-    F *d_fwd_w = nullptr;                                    // general weights
+    mem::Buf<ParitySeg> d_fwd_segs;
+    mem::Buf<uint32_t> d_fwd_nbr, d_fwd_w32;               // w32 under small_weights
+    mem::Buf<F> d_fwd_w;                                     // general weights
     // H^T in CSR (evaluate_parity_matrix), built on first use
-    uint32_t *d_pm_rowptr = nullptr, *d_pm_idx = nullptr; F *d_pm_w = nullptr; size_t pm_rows = 0;
+    mem::Buf<uint32_t> d_pm_rowptr, d_pm_idx; mem::Buf<F> d_pm_w; size_t pm_rows = 0;
 };
 
 struct ProfEntry { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; double ms = 0; long long launches = 0; };
@@ -169,13 +172,13 @@ struct hobbit_ctx {
     // commit_impl <-> launch_encode: "do not materialise the zero tail of the codewords" (asked / done); see hobbit_commitment::rows_valid
     bool enc_skip_tail = false, enc_tail_skipped = false;
     // host -> device streaming of a caller's pageable polynomial (hobbit_commit_standard_host): copy stream, two pinned staging pieces, events
-    hipStream_t up_stream = nullptr; void *up_pin[2] = {nullptr, nullptr}; hipEvent_t up_done[2] = {}; hipEvent_t up_ready[64] = {};
+    hipStream_t up_stream = nullptr; hobbit::mem::Buf<void, hobbit::mem::Pinned> up_pin[2]; hipEvent_t up_done[2] = {}; hipEvent_t up_ready[64] = {};
     static constexpr size_t UP_PIECE = (size_t)64 << 20;
     int up_init() {
         if (up_stream) return 0;
         if (hipStreamCreateWithFlags(&up_stream, hipStreamNonBlocking) != hipSuccess) { err = "upload stream create failed"; return HOBBIT_EHIP; }
         for (int i = 0; i < 2; i++) {
-            if (hipHostMalloc(&up_pin[i], UP_PIECE, hipHostMallocDefault) != hipSuccess) { err = "upload staging hipHostMalloc failed"; return HOBBIT_ENOMEM; }
+            if (up_pin[i].alloc_bytes(UP_PIECE)) { err = "upload staging hipHostMalloc failed"; return HOBBIT_ENOMEM; }
             if (hipEventCreateWithFlags(&up_done[i], hipEventDisableTiming) != hipSuccess) { err = "upload event create failed"; return HOBBIT_EHIP; }
         }
         for (auto &e : up_ready) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { err = "upload event create failed"; return HOBBIT_EHIP; }
@@ -196,13 +199,13 @@ struct hobbit_ctx {
     std::map<std::string, hobbit::ProfEntry> prof;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     // twiddles: logn -> device table of 2^(logn-1) forward (and inverse) roots
-    std::map<int, hobbit::F *> tw_fwd, tw_inv;
+    std::map<int, hobbit::mem::Buf<hobbit::F>> tw_fwd, tw_inv;
     // the next three are keyed by log2(N) + 64 * (inverse ? 1 : 0)
-    std::map<int, hobbit::F *> tw2d;              // inter-stage twiddles of the long transforms, [n1][k2] = w^(n1 k2), read coalesced
-    std::map<int, hobbit::F *> tw_r8;             // tables of k_fft_r8 per log2(N): radix-8 passes, then the radix-R tail
-    std::map<int, hobbit::F *> tw_split;          // lengths 2^25 .. 2^28: [lo: w^b, b < 2^14 | hi: w^(a 2^14), a < 2^(logn-14)], w^(a 2^14 + b) = hi[a] lo[b]
+    std::map<int, hobbit::mem::Buf<hobbit::F>> tw2d;      // inter-stage twiddles of the long transforms, [n1][k2] = w^(n1 k2), read coalesced
+    std::map<int, hobbit::mem::Buf<hobbit::F>> tw_r8;     // tables of k_fft_r8 per log2(N): radix-8 passes, then the radix-R tail
+    std::map<int, hobbit::mem::Buf<hobbit::F>> tw_split;  // lengths 2^25 .. 2^28: [lo: w^b, b < 2^14 | hi: w^(a 2^14), a < 2^(logn-14)], w^(a 2^14 + b) = hi[a] lo[b]
     // radix-8 per-pass tables of the FFT-4096 kernel ([7][8] | [7][64] | [7][512]), fwd / inv
-    hobbit::F *tw8[2] = {nullptr, nullptr};
+    hobbit::mem::Buf<hobbit::F> tw8[2];
     hobbit::F tw8_w8[2], tw8_w83[2]; int tw8_w4_plus_i[2] = {0, 0};
     // graphs
     std::map<std::pair<int, int>, hobbit::HostGraph> graphs;   // (dep, kind)
@@ -210,108 +213,70 @@ struct hobbit_ctx {
     hobbit::DeviceCode code;
     // the reference's globals has_lookups / lookup_rand[0..1] (src/main.cpp:67,70), set through hobbit_set_lookups
     bool has_lookups = false; hobbit::F lookup_rand[2];
-    // scratch
-    void *ws = nullptr; size_t ws_bytes = 0;
-    // second scratch: the row-major FFT output of a tensor code before its transpose
-    void *ws2 = nullptr; size_t ws2_bytes = 0;
-    int workspace2(size_t bytes, void **p) {
-        if (bytes > ws2_bytes) {
-            if (ws2) { hipStreamSynchronize(stream); hipFree(ws2); ws2 = nullptr; ws2_bytes = 0; }
-            if (hipMalloc(&ws2, bytes) != hipSuccess) { err = "workspace2 hipMalloc failed"; return HOBBIT_ENOMEM; }
-            ws2_bytes = bytes;
-        }
-        *p = ws2; return 0;
-    }
-    // Size-keyed free list for the device buffers of short-lived objects (a streaming commit or opening allocates five to nine buffers and
-    // releases them at its end: at the MLP config's shape the hipFree calls cost as much as the whole commit, 0.9 ms).  One stream per
-    // context, so a buffer handed back while kernels still read it is safe to hand out again: the next user is ordered behind them.
-    std::multimap<size_t, void *> pool; size_t pool_bytes = 0;
-    std::map<void *, size_t> pooled;             // live hobbit_malloc allocations that came from the pool (pointer -> size)
-    int pool_get(size_t bytes, void **p) {
-        auto it = pool.find(bytes);
-        if (it != pool.end()) { *p = it->second; pool_bytes -= bytes; pool.erase(it); return 0; }
-        if (hipMalloc(p, bytes) != hipSuccess) {             // make room: drop everything parked, try once more
-            pool_drain();
-            if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; err = "device allocation failed"; return HOBBIT_ENOMEM; }
-        }
-        return 0;
-    }
-    void pool_put(size_t bytes, void *p) {
-        if (!p) return;
-        if (pool.size() >= 48 || pool_bytes + bytes > ((size_t)8 << 30)) { hipStreamSynchronize(stream); hipFree(p); return; }
-        pool.emplace(bytes, p); pool_bytes += bytes;
-    }
-    void pool_drain() {
-        if (pool.empty()) return;
-        hipStreamSynchronize(stream);
-        for (auto &kv : pool) hipFree(kv.second);
-        pool.clear(); pool_bytes = 0;
-    }
+    // Grow-only scratch (mem::GrowBuf: a request beyond the capacity waits for the stream, frees, then allocates).
+    // workspace2: the row-major FFT output of a tensor code before its transpose
+    // workspace3: arena of the open phase (tables that live across several sumchecks), kept between calls
+    // workspace4: scratch of the inner-PCS provers (whir / shockwave), separate from the open arena that holds their inputs
+    // workspace5: the caller's buffer of a three-factor transform (2^25 .. 2^28): its nested long transforms own workspace / workspace2
+    hobbit::mem::GrowBuf<hobbit::mem::Device> ws[5];
+    int grow(int k, size_t bytes, void **p, const char *msg) { if (ws[k].ensure(stream, bytes, p)) { err = msg; return HOBBIT_ENOMEM; } return 0; }
+    int workspace2(size_t bytes, void **p) { return grow(1, bytes, p, "workspace2 hipMalloc failed"); }
+    int workspace3(size_t bytes, void **p) { return grow(2, bytes, p, "workspace3 hipMalloc failed"); }
+    int workspace4(size_t bytes, void **p) { return grow(3, bytes, p, "workspace4 hipMalloc failed"); }
+    int workspace5(size_t bytes, void **p) { return grow(4, bytes, p, "workspace5 hipMalloc failed"); }
+    // The buffers of short-lived objects come from and go back to a size-keyed pool (hobbit_mem.hpp); pool.stream is this context's stream.
+    hobbit::mem::Pool pool;
+    template <class T> int pool_get(size_t bytes, hobbit::mem::Pooled<T> &b) { if (b.get(pool, bytes)) { err = "device allocation failed"; return HOBBIT_ENOMEM; } return 0; }
+    void pool_drain() { pool.drain(); }
+    std::map<void *, size_t> large;              // live hobbit_malloc allocations too large for the pool (pointer -> size)
     // small pinned host buffer for the per-round coefficient read-back of the sumchecks
-    void *pin = nullptr; size_t pin_bytes = 0;
-    int pinned(size_t bytes, void **p) {
-        if (bytes > pin_bytes) {
-            if (pin) hipHostFree(pin);
-            if (hipHostMalloc(&pin, bytes < 4096 ? 4096 : bytes) != hipSuccess) { pin = nullptr; pin_bytes = 0; err = "hipHostMalloc failed"; return HOBBIT_ENOMEM; }
-            pin_bytes = bytes < 4096 ? 4096 : bytes;
-        }
-        *p = pin; return 0;
-    }
+    hobbit::mem::GrowBuf<hobbit::mem::Pinned> pin;
+    int pinned(size_t bytes, void **p) { if (pin.ensure(stream, bytes < 4096 ? 4096 : bytes, p)) { err = "hipHostMalloc failed"; return HOBBIT_ENOMEM; } return 0; }
     // Pinned staging arena of the open path.  hipMemcpyAsync to or from PAGEABLE host memory is not asynchronous on this runtime: a
     // device-to-host copy into a caller's buffer first waits for everything queued on the stream (rocprofv3: 100-170 us of GPU idle time
     // after every such copy, 2 ms per open).  So host inputs are copied here and uploaded from here, results land here and reach the
     // caller's buffers (`deferred`) after the closing synchronisation of the outermost library call (`stage_depth`).
-    uint8_t *stage = nullptr; size_t stage_cap = 0, stage_off = 0; int stage_depth = 0;
+    hobbit::mem::Buf<uint8_t, hobbit::mem::Pinned> stage; size_t stage_cap = 0, stage_off = 0; int stage_depth = 0;
     struct Deferred { void *dst; const void *src; size_t bytes; };
     std::vector<Deferred> deferred;
     void *stage_alloc(size_t bytes) {
-        if (!stage) { if (hipHostMalloc((void **)&stage, (size_t)24 << 20) != hipSuccess) { stage = nullptr; return nullptr; } stage_cap = (size_t)24 << 20; }
+        if (!stage) { if (stage.alloc((size_t)24 << 20)) return nullptr; stage_cap = (size_t)24 << 20; }
         const size_t a = (stage_off + 63) & ~(size_t)63;
         if (a + bytes > stage_cap) return nullptr;
         stage_off = a + bytes; return stage + a;
     }
-    // arena of the open phase (tables that live across several sumchecks), kept between calls
-    void *ws3 = nullptr; size_t ws3_bytes = 0;
-    int workspace3(size_t bytes, void **p) {
-        if (bytes > ws3_bytes) {
-            if (ws3) { hipStreamSynchronize(stream); hipFree(ws3); ws3 = nullptr; ws3_bytes = 0; }
-            if (hipMalloc(&ws3, bytes) != hipSuccess) { err = "workspace3 hipMalloc failed"; return HOBBIT_ENOMEM; }
-            ws3_bytes = bytes;
-        }
-        *p = ws3; return 0;
-    }
-    // scratch of the inner-PCS provers (whir / shockwave), separate from the open arena that holds their inputs
-    void *ws4 = nullptr; size_t ws4_bytes = 0;
-    int workspace4(size_t bytes, void **p) {
-        if (bytes > ws4_bytes) {
-            if (ws4) { hipStreamSynchronize(stream); hipFree(ws4); ws4 = nullptr; ws4_bytes = 0; }
-            if (hipMalloc(&ws4, bytes) != hipSuccess) { err = "workspace4 hipMalloc failed"; return HOBBIT_ENOMEM; }
-            ws4_bytes = bytes;
-        }
-        *p = ws4; return 0;
-    }
-    // the caller's buffer of a three-factor transform (2^25 .. 2^28): its nested long transforms own workspace / workspace2
-    void *ws5 = nullptr; size_t ws5_bytes = 0;
-    int workspace5(size_t bytes, void **p) {
-        if (bytes > ws5_bytes) {
-            if (ws5) { hipStreamSynchronize(stream); hipFree(ws5); ws5 = nullptr; ws5_bytes = 0; }
-            if (hipMalloc(&ws5, bytes) != hipSuccess) { err = "workspace5 hipMalloc failed"; return HOBBIT_ENOMEM; }
-            ws5_bytes = bytes;
-        }
-        *p = ws5; return 0;
-    }
     // one retired commitment's buffers, kept for the next commit of the same shape (a 2^28 commit
     // owns 16.5 GiB; re-allocating it per call would dominate a repeated-commit loop)
-    void *spare_tensor = nullptr; size_t spare_tensor_bytes = 0;
-    void *spare_levels = nullptr; size_t spare_levels_bytes = 0;
+    hobbit::mem::Buf<hobbit::F> spare_tensor; hobbit::mem::Buf<uint8_t> spare_levels;
     // likewise one retired parity commitment's five device buffers (12.6 GiB at n = 2^20), for the next hobbit_parity_commit_device of the same
     // (P, n): the runtime releases freed buffers of this size in bursts, seconds long, inside a later allocation
-    void *spare_parity[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t spare_parity_P = 0; long long spare_parity_n = 0;
-    void spare_parity_release() {
-        for (void *&q : spare_parity) { if (q) hipFree(q); q = nullptr; }
-        spare_parity_P = 0; spare_parity_n = 0;
-    }
+    struct ParityBufs {
+        hobbit::mem::Buf<uint32_t> d_u32;      // idx1 | idx2 | cnt1 | cnt2, P each
+        hobbit::mem::Buf<hobbit::F> d_F;       // weight (P) | acc1 (2n) | acc2 (2n)
+        hobbit::mem::Buf<hobbit::F> d_pw, d_enc; hobbit::mem::Buf<uint8_t> d_levels;
+        bool whole() const { return d_u32 && d_F && d_pw && d_enc && d_levels; }
+    };
+    ParityBufs spare_parity; size_t spare_parity_P = 0; long long spare_parity_n = 0;
 
+    // What is about order: drain the streams and the pool while the streams exist; the members' owners free afterwards, without waiting.
+    ~hobbit_ctx() {
+        delete helper; delete helper2;
+        hipSetDevice(device);
+        hipStreamSynchronize(stream);
+        prof_collect();
+        pool_drain();
+        for (hipEvent_t e : ev_pool) hipEventDestroy(e);
+        if (t0) hipEventDestroy(t0);
+        if (t1) hipEventDestroy(t1);
+        if (up_stream) {
+            hipStreamSynchronize(up_stream);
+            for (auto &e : up_done) if (e) hipEventDestroy(e);
+            for (auto &e : up_ready) if (e) hipEventDestroy(e);
+            hipStreamDestroy(up_stream);
+        }
+        if (side) { hipStreamSynchronize(side); for (auto &e : side_ev) if (e) hipEventDestroy(e); hipStreamDestroy(side); }
+        if (owns_stream) hipStreamDestroy(stream);
+    }
     int fail(int code, const std::string &msg) { err = msg; return code; }
     int hip(hipError_t e, const char *what) {
         if (e == hipSuccess) return 0;
@@ -355,14 +320,14 @@ struct hobbit_ctx {
     // produces the tables a two-product sumcheck hands to the host (hobbit_kernels.hip, sumcheck2_impl) also stores them here, and the
     // round's post -- behind that launch in stream order -- tells the host they have landed: no copy command, no stream drain.
     static constexpr size_t TAIL_ELEMS = 2048, MBOX_BYTES = 4096, TAIL_BYTES = 2 * TAIL_ELEMS * sizeof(hobbit::F);
-    hobbit::Mailbox *mbox = nullptr; unsigned *d_ticket = nullptr; uint32_t mbox_seq = 0;
+    hobbit::mem::Buf<hobbit::Mailbox, hobbit::mem::Pinned> mbox; hobbit::mem::Buf<unsigned> d_ticket; uint32_t mbox_seq = 0;
     hobbit::F *tail = nullptr;                   // tables at tail and tail + TAIL_ELEMS
     int mailbox(hobbit::Mailbox **m, unsigned **ticket) {
         if (!mbox) {
-            if (hipHostMalloc((void **)&mbox, MBOX_BYTES + TAIL_BYTES, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) { mbox = nullptr; err = "mailbox hipHostMalloc failed"; return HOBBIT_ENOMEM; }
-            memset((void *)mbox, 0, MBOX_BYTES + TAIL_BYTES);
-            tail = reinterpret_cast<hobbit::F *>(reinterpret_cast<uint8_t *>(mbox) + MBOX_BYTES);
-            if (hipMalloc((void **)&d_ticket, 256) != hipSuccess) { err = "mailbox ticket alloc failed"; return HOBBIT_ENOMEM; }
+            if (mbox.alloc_bytes(MBOX_BYTES + TAIL_BYTES, hipHostMallocCoherent | hipHostMallocMapped)) { err = "mailbox hipHostMalloc failed"; return HOBBIT_ENOMEM; }
+            memset((void *)mbox.get(), 0, MBOX_BYTES + TAIL_BYTES);
+            tail = reinterpret_cast<hobbit::F *>(reinterpret_cast<uint8_t *>(mbox.get()) + MBOX_BYTES);
+            if (d_ticket.alloc_bytes(256)) { err = "mailbox ticket alloc failed"; return HOBBIT_ENOMEM; }
             if (hipMemsetAsync(d_ticket, 0, 256, stream) != hipSuccess) { err = "mailbox ticket memset failed"; return HOBBIT_EHIP; }
         }
         *m = mbox; *ticket = d_ticket; return 0;
@@ -426,15 +391,13 @@ struct hobbit_ctx {
             if (bytes > ws_lent_bytes) { err = "lent workspace too small"; return HOBBIT_ESTATE; }
             *p = ws_lent; return 0;
         }
-        if (bytes > ws_bytes) {
-            if (ws) { hipStreamSynchronize(stream); hipFree(ws); ws = nullptr; ws_bytes = 0; }
-            hipError_t e = hipMalloc(&ws, bytes);
-            if (e != hipSuccess) { err = "workspace hipMalloc failed"; return HOBBIT_ENOMEM; }
-            ws_bytes = bytes;
-        }
-        *p = ws; return 0;
+        return grow(0, bytes, p, "workspace hipMalloc failed");
     }
 };
+
+// A handle of the ABI while its constructor builds it: every early return frees it the way its *_free does; release() into *out at the end.
+template <class H, void (*Free)(H *)> struct HandleFree { void operator()(H *h) const { Free(h); } };
+template <class H, void (*Free)(H *)> using Handle = std::unique_ptr<H, HandleFree<H, Free>>;
 
 // launch + optional per-kernel event bracket; checks the launch error
 #define HB_LAUNCH(ctx, name, kern, grid, block, lds, ...)                                   \
@@ -447,3 +410,17 @@ struct hobbit_ctx {
     } while (0)
 #define HB_CHECK(ctx, call) do { int r__ = (ctx)->hip((call), #call); if (r__) return r__; } while (0)
 #define HB_TRY(expr) do { int r__ = (expr); if (r__) return r__; } while (0)
+
+namespace hobbit {
+// Device buffers of one call (or one handle) taken through hobbit_malloc -- pooled up to its limit, from the runtime beyond -- and given back
+// through hobbit_free on every way out
+struct Scratch {
+    hobbit_ctx *ctx; std::vector<void *> bufs;
+    explicit Scratch(hobbit_ctx *c) : ctx(c) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() { for (void *p : bufs) hobbit_free(ctx, p); }
+    int get(size_t bytes, void **p) { HB_TRY(hobbit_malloc(ctx, bytes, p)); bufs.push_back(*p); return 0; }
+};
+using ParityHandle = Handle<hobbit_parity_commitment, hobbit_parity_commitment_free>;
+}  // namespace hobbit

@@ -26,14 +26,6 @@ struct LibcRngGuard {
     ~LibcRngGuard() { if (prev) setstate(prev); }
 };
 
-// device scratch of one call, released on every way out
-struct Scratch {
-    hobbit_ctx *ctx; std::vector<void *> bufs; hobbit_parity_commitment *pc = nullptr;
-    explicit Scratch(hobbit_ctx *c) : ctx(c) {}
-    ~Scratch() { if (pc) hobbit_parity_commitment_free(pc); for (void *p : bufs) hobbit_free(ctx, p); }
-    int get(size_t bytes, void **p) { HB_TRY(hobbit_malloc(ctx, bytes, p)); bufs.push_back(*p); return 0; }
-};
-
 // arr[q][c] = T[c][I[q]]: a workgroup moves a tile of GT columns c x GT queries q.  It reads with q fastest -- the 16-byte entries of one row
 // of T at the queried positions, a gather by nature: the positions are random -- and writes with c fastest, 512 contiguous bytes per half
 // wave, the transposition going through LDS (rows padded by one F against bank conflicts).
@@ -96,7 +88,7 @@ bool grid_in_range(const uint32_t *I, const uint32_t *J, size_t nq, size_t cols,
 
 struct hobbit_orion {
     hobbit_ctx *ctx; size_t N, B, Q; long long len;
-    F *d_T; uint8_t *d_levels;             // 2B x 2B row-major | flat levels over the N leaves, (2N - 1) x 32 B
+    Scratch mem; F *d_T = nullptr; uint8_t *d_levels = nullptr;      // `mem` owns: 2B x 2B row-major | flat levels over the N leaves, (2N - 1) x 32 B
 };
 
 extern "C" {
@@ -150,12 +142,7 @@ int hobbit_orion_shape(size_t N, size_t *B, size_t *Q) {
     return 0;
 }
 
-void hobbit_orion_free(hobbit_orion *c) {
-    if (!c) return;
-    if (c->d_T) hobbit_free(c->ctx, c->d_T);
-    if (c->d_levels) hobbit_free(c->ctx, c->d_levels);
-    delete c;
-}
+void hobbit_orion_free(hobbit_orion *c) { delete c; }
 
 int hobbit_orion_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, hobbit_orion **out) {
     if (!out) return ctx->fail(HOBBIT_EINVAL, "orion_commit: null output");
@@ -165,9 +152,9 @@ int hobbit_orion_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, hobbi
     if (!d_poly) return ctx->fail(HOBBIT_EINVAL, "orion_commit: null polynomial");
     if (ctx->code.n != (long long)B) return ctx->fail(HOBBIT_ESTATE, "orion_commit: graphs for n = sqrt(N) are not finalized (expander_init_store(sqrt(N)))");
     const size_t S = 2 * B; const size_t len = (size_t)ctx->code.len;
-    hobbit_orion *c = new hobbit_orion{ctx, N, B, Q, ctx->code.len, nullptr, nullptr};
-    int r = hobbit_malloc(ctx, S * S * sizeof(F), (void **)&c->d_T);
-    if (!r) r = hobbit_malloc(ctx, (2 * N - 1) * 32, (void **)&c->d_levels);
+    Handle<hobbit_orion, hobbit_orion_free> c(new hobbit_orion{ctx, N, B, Q, ctx->code.len, Scratch(ctx)});
+    int r = c->mem.get(S * S * sizeof(F), (void **)&c->d_T);
+    if (!r) r = c->mem.get((2 * N - 1) * 32, (void **)&c->d_levels);
     // rows: message row i to row i of T, all 2B entries written (codeword, then zeros)
     if (!r) r = hobbit_encode_batch(ctx, d_poly, aF(c->d_T), (long long)B, B, B, S);
     // columns: the first B entries of every column encoded in place.  Columns from len on are zero in every message row, so their codewords
@@ -175,8 +162,8 @@ int hobbit_orion_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, hobbi
     if (!r) r = launch_zero_rect(ctx, c->d_T, S, B, B, len, S - len);
     if (!r) r = hobbit_encode_interleaved_ld(ctx, aF(c->d_T), (long long)B, len, S);
     if (!r) r = hobbit_mt_commit_blake(ctx, aF(c->d_T), 4 * N, c->d_levels);
-    if (r) { hobbit_orion_free(c); return r; }
-    *out = c;
+    if (r) return r;
+    *out = c.release();
     return 0;
 }
 
@@ -235,8 +222,9 @@ int hobbit_orion_open(hobbit_ctx *ctx, const hobbit_orion *c, const hobbit_F *h_
     HB_TRY(stage(0));
 
     // ---- 1: commit_parity_matrix(B) (:160) ------------------------------------------------------------------------------------------------------
-    HB_TRY(hobbit_parity_commit_device(ctx, (long long)B, &sc.pc));
-    if (o->cp_root) HB_TRY(hobbit_parity_root(ctx, sc.pc, o->cp_root));
+    ParityHandle pc;
+    { hobbit_parity_commitment *p = nullptr; HB_TRY(hobbit_parity_commit_device(ctx, (long long)B, &p)); pc.reset(p); }
+    if (o->cp_root) HB_TRY(hobbit_parity_root(ctx, pc.get(), o->cp_root));
     HB_TRY(stage(1));
 
     // ---- 2: P1 = prove_linear_code_batch (:161; src/sumcheck.cpp:3201-3221: r1, then r2) ----------------------------------------------------------
@@ -257,7 +245,7 @@ int hobbit_orion_open(hobbit_ctx *ctx, const hobbit_orion *c, const hobbit_F *h_
     HB_TRY(stage(2));
 
     // ---- 3: open_parity_matrix(P1.randomness[0], P1.randomness[1], B) (:163) ----------------------------------------------------------------------
-    HB_TRY(hobbit_parity_open(ctx, sc.pc, aF(r.data()), aF(r1.data()), l, o->parity));
+    HB_TRY(hobbit_parity_open(ctx, pc.get(), aF(r.data()), aF(r1.data()), l, o->parity));
     HB_TRY(stage(3));
 
     // ---- 4: shockwave_prove(C, P1.randomness[0] | r2) (:164-165) -----------------------------------------------------------------------------------

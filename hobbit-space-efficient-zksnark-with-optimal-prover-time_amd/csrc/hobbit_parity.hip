@@ -223,13 +223,14 @@ long long access_lists(hobbit_ctx *ctx, std::vector<uint32_t> &i1, std::vector<u
 
 }  // namespace
 
-struct hobbit_parity_commitment {
+struct hobbit_parity_commitment : hobbit_ctx::ParityBufs {       // the five device buffers: d_u32, d_F, d_pw, d_enc, d_levels
     hobbit_ctx *ctx; long long n; size_t m, P; double list_seconds;
     // pinned host copies of what was uploaded: the uploads are queued (asynchronous from pinned memory), so their sources live as long as the object
-    uint32_t *h_u32 = nullptr; F *h_F = nullptr;
-    uint32_t *d_u32 = nullptr;                 // idx1 | idx2 | cnt1 | cnt2, P each
-    F *d_F = nullptr;                          // weight (P) | acc1 (2n) | acc2 (2n)
-    F *d_pw = nullptr, *d_enc = nullptr; uint8_t *d_levels = nullptr;
+    mem::Buf<uint32_t, mem::Pinned> h_u32; mem::Buf<F, mem::Pinned> h_F;
+    int alloc_device() {
+        const size_t S = 2 * (size_t)n, W = P;                 // W: encoded row length 2 * 8P / 16
+        return d_u32.alloc(4 * P) || d_F.alloc(P + 2 * S) || d_pw.alloc(8 * P) || d_enc.alloc(16 * W) || d_levels.alloc(64 * W);
+    }
     const uint32_t *idx1() const { return d_u32; }
     const uint32_t *idx2() const { return d_u32 + P; }
     const uint32_t *cnt1() const { return d_u32 + 2 * P; }
@@ -245,14 +246,10 @@ void hobbit_parity_commitment_free(hobbit_parity_commitment *c) {
     if (!c) return;
     hipSetDevice(c->ctx->device);
     hipStreamSynchronize(c->ctx->stream);
-    void *bufs[5] = {c->d_u32, c->d_F, c->d_pw, c->d_enc, c->d_levels};
-    if (bufs[0] && bufs[1] && bufs[2] && bufs[3] && bufs[4] && !c->ctx->spare_parity[0]) {       // park a whole set for the next device-built commit
-        for (int k = 0; k < 5; k++) c->ctx->spare_parity[k] = bufs[k];
+    if (c->whole() && !c->ctx->spare_parity.d_u32) {             // park a whole set for the next device-built commit
+        c->ctx->spare_parity = std::move(static_cast<hobbit_ctx::ParityBufs &>(*c));
         c->ctx->spare_parity_P = c->P; c->ctx->spare_parity_n = c->n;
-    } else
-        for (void *q : bufs) if (q) hipFree(q);
-    if (c->h_u32) hipHostFree(c->h_u32);
-    if (c->h_F) hipHostFree(c->h_F);
+    }
     delete c;
 }
 
@@ -272,18 +269,14 @@ int hobbit_parity_commit(hobbit_ctx *ctx, long long n, hobbit_parity_commitment 
     if (m == 0 || 5 * P + 2 * S > 8 * P || 5 * P + 2 * S <= 4 * P) return ctx->fail(HOBBIT_EINVAL, "parity_commit: list length outside the public witness' 8P layout");
     LibcRngGuard guard;
     hipSetDevice(ctx->device);
-    hobbit_parity_commitment *c = new hobbit_parity_commitment();
+    Handle<hobbit_parity_commitment, hobbit_parity_commitment_free> c(new hobbit_parity_commitment());
     c->ctx = ctx; c->n = n; c->m = m; c->P = P;
-    if (hipHostMalloc((void **)&c->h_u32, 4 * P * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_F, (P + 2 * S) * sizeof(F), hipHostMallocDefault) != hipSuccess) {
-        hobbit_parity_commitment_free(c);
-        return ctx->fail(HOBBIT_ENOMEM, "parity_commit: pinned host allocation failed");
-    }
-    memset(c->h_u32, 0, 4 * P * sizeof(uint32_t)); memset((void *)c->h_F, 0, (P + 2 * S) * sizeof(F));
+    if (c->h_u32.alloc(4 * P) || c->h_F.alloc(P + 2 * S)) return ctx->fail(HOBBIT_ENOMEM, "parity_commit: pinned host allocation failed");
+    memset(c->h_u32, 0, 4 * P * sizeof(uint32_t)); memset((void *)c->h_F.get(), 0, (P + 2 * S) * sizeof(F));
     {
         std::vector<uint32_t> a1(S, 0), a2(S, 0);
         for (size_t i = 0; i < m; i++) {
-            if (i1[i] >= S || i2[i] >= S) { hobbit_parity_commitment_free(c); return ctx->fail(HOBBIT_EINVAL, "parity_commit: list index beyond the 2n cells"); }
+            if (i1[i] >= S || i2[i] >= S) { return ctx->fail(HOBBIT_EINVAL, "parity_commit: list index beyond the 2n cells"); }
             c->h_u32[i] = i1[i]; c->h_u32[P + i] = i2[i];
             c->h_u32[2 * P + i] = ++a1[i1[i]]; c->h_u32[3 * P + i] = ++a2[i2[i]];
             c->h_F[i] = w[i];
@@ -291,13 +284,7 @@ int hobbit_parity_commit(hobbit_ctx *ctx, long long n, hobbit_parity_commitment 
         for (size_t i = 0; i < S; i++) { c->h_F[P + i] = fmake(a1[i]); c->h_F[P + S + i] = fmake(a2[i]); }
     }
     c->list_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const size_t W = P;                                        // encoded row length 2 * 8P / 16
-    if (hipMalloc((void **)&c->d_u32, 4 * P * sizeof(uint32_t)) != hipSuccess || hipMalloc((void **)&c->d_F, (P + 2 * S) * sizeof(F)) != hipSuccess ||
-        hipMalloc((void **)&c->d_pw, 8 * P * sizeof(F)) != hipSuccess || hipMalloc((void **)&c->d_enc, 16 * W * sizeof(F)) != hipSuccess ||
-        hipMalloc((void **)&c->d_levels, 64 * W) != hipSuccess) {
-        hobbit_parity_commitment_free(c);
-        return ctx->fail(HOBBIT_ENOMEM, "parity_commit: device allocation failed");
-    }
+    if (c->alloc_device()) return ctx->fail(HOBBIT_ENOMEM, "parity_commit: device allocation failed");
     int rc = ctx->hip(hipMemcpyAsync(c->d_u32, c->h_u32, 4 * P * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "parity_commit: upload");
     if (!rc) rc = ctx->hip(hipMemcpyAsync(c->d_F, c->h_F, (P + 2 * S) * sizeof(F), hipMemcpyHostToDevice, ctx->stream), "parity_commit: upload");
     if (!rc) {
@@ -308,8 +295,8 @@ int hobbit_parity_commit(hobbit_ctx *ctx, long long n, hobbit_parity_commitment 
         rc = ctx->hip(hipGetLastError(), "k_parity_witness");
     }
     if (!rc) rc = hobbit_shockwave_commit(ctx, aF(c->d_pw), 8 * P, 16, aF(c->d_enc), c->d_levels);
-    if (rc) { hobbit_parity_commitment_free(c); return rc; }
-    *out = c;
+    if (rc) return rc;
+    *out = c.release();
     return 0;
 }
 
@@ -349,14 +336,7 @@ int hobbit_parity_lists(hobbit_ctx *ctx, const hobbit_parity_commitment *c, uint
     return 0;
 }
 
-// device scratch of one opening, released on every way out
 namespace {
-struct Scratch {
-    hobbit_ctx *ctx; std::vector<void *> bufs;
-    explicit Scratch(hobbit_ctx *c) : ctx(c) {}
-    ~Scratch() { for (void *p : bufs) hobbit_free(ctx, p); }
-    int get(size_t bytes, void **p) { HB_TRY(hobbit_malloc(ctx, bytes, p)); bufs.push_back(*p); return 0; }
-};
 inline F q2_claim(CHP q) { return fadd(fadd(q[0], q[1]), fadd(q[2], q[2])); }     // q(0) + q(1) of a x^2 + b x + c
 }  // namespace
 
@@ -505,51 +485,46 @@ int hobbit_parity_commit_device(hobbit_ctx *ctx, long long n, hobbit_parity_comm
     hipSetDevice(ctx->device);
     HB_TRY(ensure_fwd(ctx));
     const DeviceCode &code = ctx->code;
-    const size_t S = 2 * (size_t)n, W = P;
+    const size_t S = 2 * (size_t)n;
     const uint32_t nseg = (uint32_t)code.fwd_segs.size();
     Scratch sc(ctx);
     uint32_t *skeys, *spos, *start; void *tmp = nullptr; size_t tmp_bytes = 0;
-    hobbit_parity_commitment *c = new hobbit_parity_commitment();
+    Handle<hobbit_parity_commitment, hobbit_parity_commitment_free> c(new hobbit_parity_commitment());
     c->ctx = ctx; c->n = n; c->m = m; c->P = P;
-    auto bail = [&](int rc) { hobbit_parity_commitment_free(c); return rc; };
-    if (ctx->spare_parity[0] && ctx->spare_parity_P == P && ctx->spare_parity_n == n) {             // the buffers of a retired commitment of this shape
-        c->d_u32 = (uint32_t *)ctx->spare_parity[0]; c->d_F = (F *)ctx->spare_parity[1]; c->d_pw = (F *)ctx->spare_parity[2]; c->d_enc = (F *)ctx->spare_parity[3];
-        c->d_levels = (uint8_t *)ctx->spare_parity[4];
-        for (void *&q : ctx->spare_parity) q = nullptr;
+    hobbit_ctx::ParityBufs &own = *c;
+    if (ctx->spare_parity.d_u32 && ctx->spare_parity_P == P && ctx->spare_parity_n == n) {          // the buffers of a retired commitment of this shape
+        own = std::move(ctx->spare_parity);
     } else {
-        if (ctx->spare_parity[0]) { hipStreamSynchronize(ctx->stream); ctx->spare_parity_release(); }  // another shape: release it before allocating
-        if (hipMalloc((void **)&c->d_u32, 4 * P * sizeof(uint32_t)) != hipSuccess || hipMalloc((void **)&c->d_F, (P + 2 * S) * sizeof(F)) != hipSuccess ||
-            hipMalloc((void **)&c->d_pw, 8 * P * sizeof(F)) != hipSuccess || hipMalloc((void **)&c->d_enc, 16 * W * sizeof(F)) != hipSuccess ||
-            hipMalloc((void **)&c->d_levels, 64 * W) != hipSuccess)
-            return bail(ctx->fail(HOBBIT_ENOMEM, "parity_commit: device allocation failed"));
+        if (ctx->spare_parity.d_u32) { hipStreamSynchronize(ctx->stream); ctx->spare_parity = {}; }   // another shape: release it before allocating
+        if (c->alloc_device()) return ctx->fail(HOBBIT_ENOMEM, "parity_commit: device allocation failed");
     }
     uint32_t *idx1 = c->d_u32, *idx2 = idx1 + P, *cnt1 = idx2 + P, *cnt2 = cnt1 + P;
     int rc = sc.get((2 * m + S) * sizeof(uint32_t), (void **)&skeys);
-    if (rc) return bail(rc);
+    if (rc) return rc;
     spos = skeys + m; start = spos + m;
     const rocprim::counting_iterator<uint32_t> places(0);
     const unsigned key_bits = (unsigned)ilog2x(S);                  // every idx1 is below 2n (ensure_fwd)
     rc = ctx->hip(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const uint32_t *)idx1, skeys, places, spos, m, 0u, key_bits, ctx->stream), "parity_commit: sort scratch");
     if (!rc) rc = sc.get(tmp_bytes, &tmp);
-    if (rc) return bail(rc);
+    if (rc) return rc;
     rc = ctx->hip(hipMemsetAsync(cnt1 + m, 0, (P - m) * sizeof(uint32_t), ctx->stream), "parity_commit: cnt1 padding");
-    if (rc) return bail(rc);
+    if (rc) return rc;
     ctx->prof_begin("k_parity_fill");
     hipLaunchKernelGGL(k_parity_fill, dim3(pgrid(P / 4)), dim3(PB), 0, ctx->stream, code.d_fwd_segs, nseg, code.d_fwd_nbr, code.d_fwd_w32, code.d_fwd_w, m, P, idx1, idx2, cnt2,
                        c->d_F);
     ctx->prof_end("k_parity_fill");
     rc = ctx->hip(hipGetLastError(), "k_parity_fill");
-    if (rc) return bail(rc);
+    if (rc) return rc;
     ctx->prof_begin("k_parity_sort");
     rc = ctx->hip(rocprim::radix_sort_pairs(tmp, tmp_bytes, (const uint32_t *)idx1, skeys, places, spos, m, 0u, key_bits, ctx->stream), "parity_commit: sort");
     ctx->prof_end("k_parity_sort");
-    if (rc) return bail(rc);
+    if (rc) return rc;
     ctx->prof_begin("k_parity_cnt1");
     hipLaunchKernelGGL(k_parity_cells, dim3(pgrid(S)), dim3(PB), 0, ctx->stream, code.d_fwd_segs, nseg, skeys, m, S, start, c->d_F + P, c->d_F + P + S);
     hipLaunchKernelGGL(k_parity_cnt1, dim3(pgrid(m)), dim3(PB), 0, ctx->stream, skeys, spos, start, m, cnt1);
     ctx->prof_end("k_parity_cnt1");
     rc = ctx->hip(hipGetLastError(), "k_parity_cnt1");
-    if (rc) return bail(rc);
+    if (rc) return rc;
     c->list_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     ctx->prof_begin("k_parity_witness");
     hipLaunchKernelGGL(k_parity_witness, dim3(pgrid(8 * P)), dim3(PB), 0, ctx->stream, c->idx1(), c->idx2(), c->cnt1(), c->cnt2(), c->weight(), c->acc1(), c->acc2(), m, P, m, S,
@@ -557,8 +532,8 @@ int hobbit_parity_commit_device(hobbit_ctx *ctx, long long n, hobbit_parity_comm
     ctx->prof_end("k_parity_witness");
     rc = ctx->hip(hipGetLastError(), "k_parity_witness");
     if (!rc) rc = hobbit_shockwave_commit(ctx, aF(c->d_pw), 8 * P, 16, aF(c->d_enc), c->d_levels);
-    if (rc) return bail(rc);
-    *out = c;
+    if (rc) return rc;
+    *out = c.release();
     return 0;
 }
 

@@ -56,6 +56,8 @@ const char *hobbit_version(void);
 int hobbit_sync(hobbit_ctx *ctx);
 int hobbit_malloc(hobbit_ctx *ctx, size_t bytes, void **d_ptr);
 int hobbit_free(hobbit_ctx *ctx, void *d_ptr);
+/* device and pinned allocations the library holds at this moment, over all contexts of the process (host only, any thread) */
+void hobbit_mem_live(size_t *allocs, size_t *bytes);
 int hobbit_memcpy_h2d(hobbit_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int hobbit_memcpy_d2h(hobbit_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
 int hobbit_memset(hobbit_ctx *ctx, void *d_dst, int value, size_t bytes);

@@ -65,6 +65,7 @@ EXEMPT = {
     "hobbit_last_error": "accessor, host only",
     "hobbit_version": "accessor, host only",
     "hobbit_malloc": "allocation; queues nothing",
+    "hobbit_mem_live": "accessor, host only",
     "hobbit_free": "returns a buffer to the pool or waits for the stream before it frees",
     "hobbit_memset": "one hipMemsetAsync with by-value arguments; used by the pair rows' setup",
     "hobbit_timer_begin": "records an event; measured with in this file, nothing shared",
