@@ -78,6 +78,9 @@ BRAKINGBASE_SYMBOLS = [
 ]
 BRAKINGBASE_QUERIES = 2935
 
+# every symbol include/hobbit_longcodes.h declares (checked by tests/test_longcodes.py)
+LONGCODES_SYMBOLS = ["hobbit_brakingbase_shape_any", "hobbit_brakingbase_commit_any", "hobbit_brakingbase_open_any"]
+
 # every symbol include/hobbit_orion.h declares (checked by tests/test_orion.py)
 ORION_SYMBOLS = [
     "hobbit_encode_interleaved_ld", "hobbit_encode_interleaved_ld_order", "hobbit_orion_gather", "hobbit_orion_grid_paths", "hobbit_orion_shape",
@@ -184,6 +187,8 @@ def load_library(path=LIB_PATH):
         "hobbit_brakingbase_dims": [V, V, V, V, V], "hobbit_brakingbase_matrix_dev": [V], "hobbit_brakingbase_levels_dev": [V],
         "hobbit_brakingbase_levels": [V, V, V], "hobbit_brakingbase_root": [V, V, V], "hobbit_brakingbase_tensor": [V, V, S, S, V],
         "hobbit_brakingbase_open": [V, V, V, V],
+        # include/hobbit_longcodes.h
+        "hobbit_brakingbase_shape_any": [S, S, V], "hobbit_brakingbase_commit_any": [V, V, S, S, I, V], "hobbit_brakingbase_open_any": [V, V, V, V],
         # include/hobbit_orion.h
         "hobbit_encode_interleaved_ld": [V, V, L, S, S], "hobbit_encode_interleaved_ld_order": [V, V, L, S, S, ctypes.c_uint32],
         "hobbit_orion_gather": [V, V, S, S, V, S, V], "hobbit_orion_grid_paths": [V, V, S, S, V, V, S, V], "hobbit_orion_shape": [S, V, V],
@@ -1174,6 +1179,33 @@ class Hobbit:
     def brakingbase_commit(self, poly, K, quirk=1, sync=True):
         """commit_brakingbase: poly is a host array (N, 2) or (DeviceBuffer/ptr, N); the graphs for n = N / K must be finalized.  Returns a
         BrakingbaseCommitment; sync=False leaves the work queued on the context's stream."""
+        return self._brakingbase_commit(self.lib.hobbit_brakingbase_commit, poly, K, quirk, sync)
+
+    def brakingbase_open(self, c, x):
+        """open_brakingbase's prover side: x holds at least log2 K F.  libc draws on the host in the reference's order.  Returns dict(I, reply
+        (2935, K, 2), paths (2935, log2 2 trs, 32), aggr, cc_root, cp_root, p1 (poly, r, vr, fin, r1), parity (as open_parity_matrix), sp_c (as
+        shockwave_prove), checks, ps, stage_ms)"""
+        return self._brakingbase_open(self.lib.hobbit_brakingbase_open, c, x)
+
+    # the long forms (include/hobbit_longcodes.h): the same calls with 128 <= N / K <= 2^21
+    @staticmethod
+    def brakingbase_shape_any(N, K):
+        """trs = N / K as brakingbase_shape, with 128 <= trs <= 2^21"""
+        lib = load_library()
+        trs = c_sz()
+        if lib.hobbit_brakingbase_shape_any(c_sz(N), c_sz(K), ctypes.byref(trs)) != 0:
+            raise HobbitError("brakingbase: (N, K) = (%d, %d) is not served: powers of two, 4 <= K <= 512, 128 <= N / K <= 2^21" % (N, K))
+        return trs.value
+
+    def brakingbase_commit_any(self, poly, K, quirk=1, sync=True):
+        """brakingbase_commit at the shapes of brakingbase_shape_any; the commitment is opened by brakingbase_open_any"""
+        return self._brakingbase_commit(self.lib.hobbit_brakingbase_commit_any, poly, K, quirk, sync)
+
+    def brakingbase_open_any(self, c, x):
+        """brakingbase_open for a commitment of either commit"""
+        return self._brakingbase_open(self.lib.hobbit_brakingbase_open_any, c, x)
+
+    def _brakingbase_commit(self, fn, poly, K, quirk, sync):
         if isinstance(poly, tuple):
             ptr, N = poly
             ptr = ptr.ptr if isinstance(ptr, DeviceBuffer) else int(ptr)
@@ -1182,17 +1214,14 @@ class Hobbit:
             N = p.shape[0]
             keep = self.to_device(p); ptr = keep.ptr
         h = c_vp()
-        self._chk(self.lib.hobbit_brakingbase_commit(self.ctx, c_vp(ptr), c_sz(N), c_sz(K), c_int(quirk), ctypes.byref(h)))
+        self._chk(fn(self.ctx, c_vp(ptr), c_sz(N), c_sz(K), c_int(quirk), ctypes.byref(h)))
         if not h.value:
             raise HobbitError("hobbit_brakingbase_commit returned no handle")
         if sync or not isinstance(poly, tuple):
             self.sync()                         # (a host polynomial's device copy is released when this returns)
         return BrakingbaseCommitment(self, h)
 
-    def brakingbase_open(self, c, x):
-        """open_brakingbase's prover side: x holds at least log2 K F.  libc draws on the host in the reference's order.  Returns dict(I, reply
-        (2935, K, 2), paths (2935, log2 2 trs, 32), aggr, cc_root, cp_root, p1 (poly, r, vr, fin, r1), parity (as open_parity_matrix), sp_c (as
-        shockwave_prove), checks, ps, stage_ms)"""
+    def _brakingbase_open(self, fn, c, x):
         lk = c.K.bit_length() - 1; l = c.W.bit_length() - 1; Q = BRAKINGBASE_QUERIES
         x = Fh(x).reshape(-1, 2)[:lk].copy()
         assert x.shape[0] == lk
@@ -1209,7 +1238,7 @@ class Hobbit:
         ptrs = [out[k].ctypes.data for k in ("I", "reply", "paths", "aggr", "cc_root", "cp_root")] + [a.ctypes.data for a in (q, r, vr, fin, r1)]
         ptrs += [ctypes.addressof(po), ctypes.addressof(o_c), out["ps"].ctypes.data, out["stage_ms"].ctypes.data]
         o = (c_vp * len(ptrs))(*ptrs)
-        self._chk(self.lib.hobbit_brakingbase_open(self.ctx, c.h, _hp(x), o))
+        self._chk(fn(self.ctx, c.h, _hp(x), o))
         out["p1"] = dict(poly=q, r=r, vr=vr, fin=fin, r1=r1)
         out["parity"] = self._parity_result(keep)
         out["sp_c"] = self._sp_trim(sp_c, 2 * c.trs, 32)

@@ -8,6 +8,7 @@
 #include "hobbit_kernels.hpp"
 #include "../../include/hobbit_brakingbase.h"
 #include "../../include/hobbit_parity_lists.h"
+#include "../../include/hobbit_longcodes.h"
 #include "hobbit_ps.hpp"
 
 using namespace hobbit;
@@ -19,6 +20,17 @@ static inline hobbit_F *aF(F *p) { return reinterpret_cast<hobbit_F *>(p); }
 namespace {
 
 constexpr size_t QUERIES = HOBBIT_BRAKINGBASE_QUERIES;
+constexpr int CAP_LOG = 20;                                     // hobbit_brakingbase.h: trs <= 2^20; hobbit_longcodes.h: trs <= 2^CODE_MAX_LOG
+
+// the shape rule of both headers: N, K powers of two, 4 <= K <= 512, 128 <= N / K <= 2^cap_log
+bool shape_k_ok(size_t N, size_t K) { return ilog2x(N) >= 0 && ilog2x(K) >= 0 && K >= 4 && K <= 512 && N >= K; }
+int shape_capped(size_t N, size_t K, int cap_log, size_t *trs) {
+    if (!shape_k_ok(N, K)) return HOBBIT_EINVAL;
+    const size_t t = N / K;
+    if (t < 128 || t > ((size_t)1 << cap_log)) return HOBBIT_EINVAL;
+    if (trs) *trs = t;
+    return 0;
+}
 
 }  // namespace
 
@@ -29,31 +41,44 @@ struct hobbit_brakingbase {
 
 extern "C" {
 
-int hobbit_brakingbase_shape(size_t N, size_t K, size_t *trs) {
-    if (ilog2x(N) < 0 || ilog2x(K) < 0 || K < 4 || K > 512 || N < K) return HOBBIT_EINVAL;
-    const size_t t = N / K;
-    if (t < 128 || t > ((size_t)1 << 20)) return HOBBIT_EINVAL;
-    if (trs) *trs = t;
-    return 0;
-}
+int hobbit_brakingbase_shape(size_t N, size_t K, size_t *trs) { return shape_capped(N, K, CAP_LOG, trs); }
+int hobbit_brakingbase_shape_any(size_t N, size_t K, size_t *trs) { return shape_capped(N, K, CODE_MAX_LOG, trs); }
 
 void hobbit_brakingbase_free(hobbit_brakingbase *c) { delete c; }
 
-int hobbit_brakingbase_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, size_t K, int left_left_quirk, hobbit_brakingbase **out) {
+}  // extern "C"
+
+// the body of both commits; cap_log and the two refusal messages are the export's own
+static int commit_capped(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, size_t K, int left_left_quirk, hobbit_brakingbase **out, int cap_log, const char *too_long,
+                         const char *bad_shape) {
     if (!out) return ctx->fail(HOBBIT_EINVAL, "brakingbase_commit: null output");
     *out = nullptr;
     size_t trs;
-    if (hobbit_brakingbase_shape(N, K, &trs)) {
-        if (ilog2x(N) >= 0 && ilog2x(K) >= 0 && K >= 4 && K <= 512 && N / K > ((size_t)1 << 20))
-            return ctx->fail(HOBBIT_EINVAL, "brakingbase_commit: N / K above 2^20: the code proof and the parity opening stop at codes of length 2^20");
-        return ctx->fail(HOBBIT_EINVAL, "brakingbase_commit: N, K powers of two, 4 <= K <= 512, 128 <= N / K <= 2^20");
+    if (shape_capped(N, K, cap_log, &trs)) {
+        if (shape_k_ok(N, K) && N / K > ((size_t)1 << cap_log)) return ctx->fail(HOBBIT_EINVAL, too_long);
+        return ctx->fail(HOBBIT_EINVAL, bad_shape);
     }
     if (!d_poly) return ctx->fail(HOBBIT_EINVAL, "brakingbase_commit: null polynomial");
     if (ctx->code.n != (long long)trs) return ctx->fail(HOBBIT_ESTATE, "brakingbase_commit: graphs for n = N / K are not finalized (expander_init_store(N / K))");
+    // the matrix (2 trs x K) and its levels; past 2^20 the device is asked first (the machines are shared)
+    if (trs > ((size_t)1 << CAP_LOG)) HB_TRY(need_device_bytes(ctx, 2 * trs * K * sizeof(F) + 4 * trs * 32, "brakingbase_commit_any"));
     hobbit_brakedown *bd = nullptr;
     HB_TRY(brakedown_commit_shape(ctx, reinterpret_cast<const F *>(d_poly), trs, (uint32_t)K, left_left_quirk, &bd));
     *out = new hobbit_brakingbase{ctx, N, K, trs, Handle<hobbit_brakedown, hobbit_brakedown_free>(bd)};
     return 0;
+}
+
+extern "C" {
+
+int hobbit_brakingbase_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, size_t K, int left_left_quirk, hobbit_brakingbase **out) {
+    return commit_capped(ctx, d_poly, N, K, left_left_quirk, out, CAP_LOG,
+                         "brakingbase_commit: N / K above 2^20: the code proof and the parity opening stop at codes of length 2^20",
+                         "brakingbase_commit: N, K powers of two, 4 <= K <= 512, 128 <= N / K <= 2^20");
+}
+int hobbit_brakingbase_commit_any(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, size_t K, int left_left_quirk, hobbit_brakingbase **out) {
+    return commit_capped(ctx, d_poly, N, K, left_left_quirk, out, CODE_MAX_LOG,
+                         "brakingbase_commit_any: N / K above 2^21: at 2^22 the parity matrix' encoded rows hold 2^31 elements, a size this library has not been verified at",
+                         "brakingbase_commit_any: N, K powers of two, 4 <= K <= 512, 128 <= N / K <= 2^21");
 }
 
 int hobbit_brakingbase_dims(const hobbit_brakingbase *c, size_t *N, size_t *K, size_t *trs, long long *len) {
@@ -78,8 +103,12 @@ int hobbit_brakingbase_tensor(hobbit_ctx *ctx, const hobbit_brakingbase *c, size
     return hobbit_brakedown_tensor(ctx, c->bd.get(), col_lo, ncols, h_out);
 }
 
-int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const hobbit_F *h_x, hobbit_brakingbase_open_out *o) {
+}  // extern "C"
+
+// the body of both openings: cap_log is the export's own limit on the commitment it takes
+static int open_capped(hobbit_ctx *ctx, const hobbit_brakingbase *c, const hobbit_F *h_x, hobbit_brakingbase_open_out *o, int cap_log) {
     if (!c || !h_x || !o || !o->parity || !o->sp_c) return ctx->fail(HOBBIT_EINVAL, "brakingbase_open: null argument (parity and sp_c are required)");
+    if (c->trs > ((size_t)1 << cap_log)) return ctx->fail(HOBBIT_EINVAL, "brakingbase_open: a commitment of hobbit_brakingbase_commit_any with N / K above 2^20 is opened by hobbit_brakingbase_open_any");
     if (c->ctx != ctx) return ctx->fail(HOBBIT_EINVAL, "brakingbase_open: the commitment belongs to another context");
     if (!o->parity->sp_p || !o->parity->sp_w) return ctx->fail(HOBBIT_EINVAL, "brakingbase_open: parity needs sp_p and sp_w");
     if (o->ps && !(sp_has_queries(o->sp_c) && sp_has_queries(o->parity->sp_p) && sp_has_queries(o->parity->sp_w) && o->parity->t1_layers && o->parity->t2_layers))
@@ -89,6 +118,12 @@ int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const 
     if (ctx->code.n != (long long)trs) return ctx->fail(HOBBIT_ESTATE, "brakingbase_open: graphs for n = N / K are not finalized (expander_init_store(N / K))");
     const F *mat = reinterpret_cast<const F *>(hobbit_brakedown_matrix_dev(c->bd.get()));
     const uint8_t *levels = hobbit_brakedown_levels_dev(c->bd.get());
+    if (trs > ((size_t)1 << CAP_LOG)) {
+        // the parity matrix committed and opened inside this call: asked of the device before the first draw
+        size_t P = 0;
+        HB_TRY(hobbit_parity_shape(ctx, (long long)trs, nullptr, &P));
+        if (parity_is_long(P)) HB_TRY(need_device_bytes(ctx, parity_commit_bytes(P, S) + parity_open_bytes(P), "brakingbase_open_any"));
+    }
 
     // ---- the draws that come before any device work (:374, :382-385; _aggregate_brakingbase and shockwave_commit draw nothing) -----------------
     hobbit_F rv0; hobbit_generate_randomness(1, &rv0); (void)rv0;                       // r_v[0]: its powers feed nothing
@@ -183,6 +218,15 @@ int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const 
         *o->ps = ps;
     }
     return 0;
+}
+
+extern "C" {
+
+int hobbit_brakingbase_open(hobbit_ctx *ctx, const hobbit_brakingbase *c, const hobbit_F *h_x, hobbit_brakingbase_open_out *o) {
+    return open_capped(ctx, c, h_x, o, CAP_LOG);
+}
+int hobbit_brakingbase_open_any(hobbit_ctx *ctx, const hobbit_brakingbase *c, const hobbit_F *h_x, hobbit_brakingbase_open_out *o) {
+    return open_capped(ctx, c, h_x, o, CODE_MAX_LOG);
 }
 
 }  // extern "C"

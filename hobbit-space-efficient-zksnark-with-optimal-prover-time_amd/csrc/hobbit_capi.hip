@@ -606,12 +606,60 @@ static int build_narrow(hobbit_ctx *ctx, const std::vector<PlanStep> &plan, Narr
     np.ok = true;
     return 0;
 }
+// The slice tables of k_encode (hobbit_ctx.hpp EncStep) from the plan hobbit_graph_finalize kept: built by the finalize for codes whose codeword
+// fits LDS, by the first launch_encode (through ensure_tiled) for longer ones.
+static int build_slices(hobbit_ctx *ctx) {
+    DeviceCode &c = ctx->code;
+    if (c.slices_built) return 0;
+    const std::vector<PlanStep> &plan = c.plan;
+    std::vector<uint32_t> slice_ptr, slice_width, slice_out, eidx; std::vector<uint2> e32; std::vector<F> ew;
+    size_t pos = 0;
+    for (auto &p : plan) {
+        const HostGraph &g = *p.g;
+        const InEdges rows = in_edges(g);
+        EncStep s; s.in_off = (uint32_t)p.in_off; s.out_off = (uint32_t)p.out_off; s.out_len = (uint32_t)g.R;
+        const uint32_t sw = (uint32_t)g.R >= ENC_WIDE_MIN ? 64u : ENC_SW, split = 64 / sw;
+        // records per output are padded to the lane-group count, and for the wide steps to whole unrolled groups (no remainder loop)
+        const uint32_t pad = sw == 64 ? ENC_UNROLL : split;
+        s.sw = sw; s.out_base = (uint32_t)slice_out.size();
+        s.n_slices = (uint32_t)((g.R + sw - 1) / sw); s.slice_base = (uint32_t)slice_ptr.size();
+        const std::vector<uint32_t> order = by_in_degree(rows);
+        for (uint32_t sl = 0; sl < s.n_slices; sl++) {
+            size_t width = 0;
+            for (uint32_t l = 0; l < sw; l++) { size_t q = (size_t)sl * sw + l; if (q < (size_t)g.R) width = std::max(width, rows[order[q]].size()); }
+            width = (width + pad - 1) / pad * pad;
+            slice_ptr.push_back((uint32_t)pos); slice_width.push_back((uint32_t)width);
+            for (uint32_t l = 0; l < sw; l++) { size_t q = (size_t)sl * sw + l; slice_out.push_back(q < (size_t)g.R ? order[q] : 0xFFFFFFFFu); }
+            for (size_t k = 0; k < width; k++)
+                for (uint32_t l = 0; l < sw; l++) {
+                    size_t q = (size_t)sl * sw + l;
+                    uint32_t id = 0; F w = fmake(0);
+                    if (q < (size_t)g.R && k < rows[order[q]].size()) { id = rows[order[q]][k].first; w = rows[order[q]][k].second; c.n_edges++; }
+                    if (c.small_weights) e32.push_back(make_uint2(id, (uint32_t)w.re)); else { eidx.push_back(id); ew.push_back(w); }
+                }
+            pos += width * sw;
+        }
+        c.steps.push_back(s);
+    }
+    c.n_edges_padded = pos;
+    // slice_ptr holds record offsets as 32 bits, and the plan's offsets (at most 2n) and the CSR pointers of ensure_ilv are 32-bit too
+    if (pos >> 32) return ctx->fail(HOBBIT_EINVAL, "graph_finalize: more than 2^32 padded edge records");
+    HB_TRY(upload(ctx, &c.d_steps, c.steps));
+    HB_TRY(upload(ctx, &c.d_slice_ptr, slice_ptr));
+    HB_TRY(upload(ctx, &c.d_slice_width, slice_width));
+    HB_TRY(upload(ctx, &c.d_slice_out, slice_out));
+    if (c.small_weights) HB_TRY(upload(ctx, &c.d_edges32, e32));
+    else { HB_TRY(upload(ctx, &c.d_eidx, eidx)); HB_TRY(upload(ctx, &c.d_ew, ew)); }
+    c.slices_built = true;
+    return 0;
+}
 // Long codes (codeword over 160 KB): the outer steps whose windows do not fit in LDS, in tiled form (hobbit_ctx.hpp TiledStep).  Built by the
 // first launch_encode of the finalized code, from the plan hobbit_graph_finalize kept.
 int ensure_tiled(hobbit_ctx *ctx) {
     DeviceCode &c = ctx->code;
     if (c.tiled_built) return 0;
     if (c.graph_gen != ctx->graph_gen) return ctx->fail(HOBBIT_ESTATE, "encode: the graphs changed after hobbit_graph_finalize");
+    HB_TRY(build_slices(ctx));
     const std::vector<PlanStep> &plan = c.plan;
     const std::vector<long long> &cwlen = c.cwlen;
     const uint32_t D = (uint32_t)cwlen.size() - 1;
@@ -759,6 +807,17 @@ int ensure_fwd(hobbit_ctx *ctx) {
     c.fwd_segs = segs; c.fwd_m = m; c.fwd_built = true;
     return 0;
 }
+int need_device_bytes(hobbit_ctx *ctx, size_t bytes, const char *what) {
+    size_t free_b = 0, total_b = 0;
+    hipSetDevice(ctx->device);
+    HB_CHECK(ctx, hipMemGetInfo(&free_b, &total_b));
+    if (free_b < bytes) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "%s: needs about %.1f GiB of device memory, %.1f GiB are free", what, (double)bytes / 1073741824.0, (double)free_b / 1073741824.0);
+        return ctx->fail(HOBBIT_ENOMEM, msg);
+    }
+    return 0;
+}
 }  // namespace hobbit
 extern "C" {
 int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
@@ -766,7 +825,7 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
     ctx->code = DeviceCode();                                     // (the owners in it free their tables: the stream has drained)
     DeviceCode &c = ctx->code;
     const long long thr = 13;   // distance_threshold, src/parameter.h:5
-    if (n <= 0 || n > (1 << 20)) return ctx->fail(HOBBIT_EINVAL, "graph_finalize: bad n");
+    if (n <= 0 || n > (1LL << CODE_MAX_LOG)) return ctx->fail(HOBBIT_EINVAL, "graph_finalize: bad n");
     // level sizes and offsets
     std::vector<long long> nd{n}, off{0};
     int D = 0;
@@ -788,42 +847,10 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
     for (int d = D - 1; d >= 0; d--) plan.push_back({&ctx->graphs[{d, 1}], off[d + 1], off[d + 1] + cwlen[d + 1]});
     c.small_weights = true;
     for (auto &p : plan) for (auto &w : p.g->w) if (w.im != 0 || w.re >> 32) { c.small_weights = false; break; }
-    std::vector<uint32_t> slice_ptr, slice_width, slice_out, eidx; std::vector<uint2> e32; std::vector<F> ew;
-    size_t pos = 0;
-    for (auto &p : plan) {
-        const HostGraph &g = *p.g;
-        const InEdges rows = in_edges(g);
-        EncStep s; s.in_off = (uint32_t)p.in_off; s.out_off = (uint32_t)p.out_off; s.out_len = (uint32_t)g.R;
-        const uint32_t sw = (uint32_t)g.R >= ENC_WIDE_MIN ? 64u : ENC_SW, split = 64 / sw;
-        // records per output are padded to the lane-group count, and for the wide steps to whole unrolled groups (no remainder loop)
-        const uint32_t pad = sw == 64 ? ENC_UNROLL : split;
-        s.sw = sw; s.out_base = (uint32_t)slice_out.size();
-        s.n_slices = (uint32_t)((g.R + sw - 1) / sw); s.slice_base = (uint32_t)slice_ptr.size();
-        const std::vector<uint32_t> order = by_in_degree(rows);
-        for (uint32_t sl = 0; sl < s.n_slices; sl++) {
-            size_t width = 0;
-            for (uint32_t l = 0; l < sw; l++) { size_t q = (size_t)sl * sw + l; if (q < (size_t)g.R) width = std::max(width, rows[order[q]].size()); }
-            width = (width + pad - 1) / pad * pad;
-            slice_ptr.push_back((uint32_t)pos); slice_width.push_back((uint32_t)width);
-            for (uint32_t l = 0; l < sw; l++) { size_t q = (size_t)sl * sw + l; slice_out.push_back(q < (size_t)g.R ? order[q] : 0xFFFFFFFFu); }
-            for (size_t k = 0; k < width; k++)
-                for (uint32_t l = 0; l < sw; l++) {
-                    size_t q = (size_t)sl * sw + l;
-                    uint32_t id = 0; F w = fmake(0);
-                    if (q < (size_t)g.R && k < rows[order[q]].size()) { id = rows[order[q]][k].first; w = rows[order[q]][k].second; c.n_edges++; }
-                    if (c.small_weights) e32.push_back(make_uint2(id, (uint32_t)w.re)); else { eidx.push_back(id); ew.push_back(w); }
-                }
-            pos += width * sw;
-        }
-        c.steps.push_back(s);
-    }
-    c.n_edges_padded = pos;
-    HB_TRY(upload(ctx, &c.d_steps, c.steps));
-    HB_TRY(upload(ctx, &c.d_slice_ptr, slice_ptr));
-    HB_TRY(upload(ctx, &c.d_slice_width, slice_width));
-    HB_TRY(upload(ctx, &c.d_slice_out, slice_out));
-    if (c.small_weights) HB_TRY(upload(ctx, &c.d_edges32, e32));
-    else { HB_TRY(upload(ctx, &c.d_eidx, eidx)); HB_TRY(upload(ctx, &c.d_ew, ew)); }
+    // The slice tables of k_encode.  A code whose codeword fits LDS (up to 160 KB) gets them now; a longer one when its first launch_encode asks
+    // for its tiled steps (ensure_tiled): the rows-innermost encode, the code proof and the parity matrix never read them, and at n = 2^21 they
+    // were 3.2 s of a 3.2 s finalize
+    if ((size_t)c.len * 16 <= 160 * 1024) HB_TRY(build_slices(ctx));
     // deep codes (n = 4096: the codeword does not leave room for two workgroups per CU): first, second and last step also in fat form
     if (c.small_weights && c.steps.size() >= 4 && (size_t)c.len * 16 > 80 * 1024 && (size_t)c.len * 16 <= 160 * 1024) {
         const uint32_t capA[3] = {FAT_A_CAP0, FAT_A_CAP1, 0}, capC1[3] = {FAT_C1_CAP0, 0, 0}, capD[3] = {FAT_D_CAP0, FAT_D_CAP1, FAT_D_CAP2};
@@ -1481,7 +1508,10 @@ int hobbit_whir_prove_any(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
 }
 // shockwave_prove (src/Virgo.cpp:435-517), prover side
 // workspace4 elements of one shockwave_prove: [0, nested) belongs to the nested whir_commit / whir_prove calls, its own vectors follow
-static size_t shockwave_nested_elems(size_t w) { return 4 * w + whir_scratch_elems(w) + 64; }
+// The nested proof's form by the aggregate's width: up to 2^24 the materialised out-of-domain tables (today's plan, scratch and code path,
+// bit for bit), in (2^24, 2^26] the table-free step of hobbit_whir_prove_any (the parity opening of a code of 2^21: w = 2^25)
+static const WhirCfg &shockwave_whir_cfg(size_t w) { return w > ((size_t)1 << WHIR_TABLES.max_log) ? WHIR_ANY : WHIR_TABLES; }
+static size_t shockwave_nested_elems(size_t w) { return 4 * w + whir_scratch_elems(w, shockwave_whir_cfg(w)) + 64; }
 static size_t shockwave_own_elems(size_t w, int k) {
     return w + 2 * w + 2 * w + 64 + 256 + 256 /* idx */ + 2 * w + 2 * w /* whir_commit outputs: com, levels */ + 240 * (size_t)k /* replies */ + 240 * 64 /* paths */ + 64;
 }
@@ -1493,7 +1523,7 @@ static int shockwave_plan(size_t N, int k, ShockPlan &P) {
     P.I.resize(240);
     for (int i = 0; i < 240; i++) P.I[i] = (uint64_t)(rand() % (long)W);
     P.committed = w > 256;
-    return P.committed ? whir_plan(w, P.whir) : 0;
+    return P.committed ? whir_plan(w, P.whir, shockwave_whir_cfg(w)) : 0;
 }
 struct OpenTrace {
     // HOBBIT_TRACE=1: stage times with the stream drained at every mark (everything on one thread and stream); HOBBIT_TRACE=host: the host
@@ -1564,7 +1594,7 @@ static int shockwave_prove_run(hobbit_ctx *ctx, const hobbit_F *d_matrix, const 
     if (committed) {
         // _whir_prove works on a copy of aggr inside its own scratch (from the start of workspace4): aggr and the commitment live beyond it
         hobbit_whir_out wo = {o->wq, o->wa, o->wroots, o->wscal, o->wchecks, &iters, o->wqidx, o->wqreply, o->wqpaths, o->wfinal, o->wqn};
-        HB_TRY(whir_prove_run(ctx, reinterpret_cast<hobbit_F *>(aggr), w, reinterpret_cast<hobbit_F *>(wcom), wlv, o->r2, &wo, plan.whir));                    // (:480-481)
+        HB_TRY(whir_prove_run(ctx, reinterpret_cast<hobbit_F *>(aggr), w, reinterpret_cast<hobbit_F *>(wcom), wlv, o->r2, &wo, plan.whir, shockwave_whir_cfg(w)));   // (:480-481)
     }
     if (o->iters) *o->iters = iters;
     tr.mark("  sp: whir_prove");

@@ -139,6 +139,7 @@ struct DeviceCode {         // finalized code for one message length n
     // the rows-innermost encode (ensure_ilv).  `plan` lists the steps in order (C_0 .. C_{D-1}, D_{D-1} .. D_0) over the uploaded graphs of
     // generation `graph_gen` (hobbit_ctx::graph_gen); `cwlen[d]`: length of the sub-codeword of depth d.
     std::vector<PlanStep> plan; std::vector<long long> cwlen; uint64_t graph_gen = 0; bool tiled_built = false;
+    bool slices_built = false;               // the slice tables above: at the finalize for codewords up to 160 KB, with the tiled steps for longer ones
     bool ilv_built = false;
     std::vector<IlvStep> isteps;
     mem::Buf<uint32_t> d_ilv_ptr;

@@ -3432,8 +3432,9 @@ template <bool SMALLW>
 __global__ void __launch_bounds__(256)
 k_enc_ilv(F *__restrict__ mat, uint32_t rows, uint32_t lg_rows, IlvStep st, const uint32_t *__restrict__ ptr, const uint2 *__restrict__ e32,
           const uint32_t *__restrict__ eidx, const F *__restrict__ ew) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;              // out_len * rows < 2^31 (hobbit_encode_interleaved)
-    const uint32_t t = g >> lg_rows, i = g & (rows - 1);
+    // 64-bit: a step of a code of 2^21 has up to 2^21 outputs, and hobbit_brakingbase_commit_any encodes up to 512 rows of them
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const uint32_t t = (uint32_t)(g >> lg_rows), i = (uint32_t)g & (rows - 1);
     if (t >= st.out_len) return;
     const F *in = mat + (size_t)st.in_off * rows + i;
     uint32_t beg = ptr[st.ptr_base + t], end = ptr[st.ptr_base + t + 1];
@@ -3468,6 +3469,7 @@ int launch_encode_ilv(hobbit_ctx *ctx, const F *src, F *dst, uint32_t rows) {
     if (src != dst) HB_TRY(launch_copy(ctx, dst, src, (size_t)c.n * rows * sizeof(F)));
     for (const IlvStep &st : c.isteps) {
         const size_t threads = (size_t)st.out_len * rows;
+        if ((threads + 255) / 256 >> 31) return ctx->fail(HOBBIT_EINVAL, "encode_interleaved: a step of more than 2^39 outputs x rows");
         if (c.small_weights)
             HB_LAUNCH(ctx, "k_enc_ilv", k_enc_ilv<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, dst, rows, lg, st, c.d_ilv_ptr, c.d_ilv_e32,
                       c.d_ilv_eidx, c.d_ilv_ew);

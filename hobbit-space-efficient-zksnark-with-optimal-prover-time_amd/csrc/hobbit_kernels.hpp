@@ -3,6 +3,20 @@
 #include "hobbit_ctx.hpp"
 
 namespace hobbit {
+// The longest code: hobbit_graph_finalize, the rows-innermost encode, hobbit_parity_commit[_device] / hobbit_parity_open and the long forms of
+// include/hobbit_longcodes.h stop at n = 2^CODE_MAX_LOG.  At 2^21 the parity matrix' padded list has P = 2^26 entries and its encoded rows
+// 2^30 elements; 2^22 would put an element index past 2^31 and is not served (DESIGN.md section 4 "Codes of 2^21").
+constexpr int CODE_MAX_LOG = 21;
+// HOBBIT_ENOMEM unless the device has `bytes` free right now (hipMemGetInfo): asked before the large allocations of the long codes, on
+// machines whose memory other processes share, and before any libc draw of the call.  `what` names the caller in the message.
+int need_device_bytes(hobbit_ctx *ctx, size_t bytes, const char *what);
+// The parity matrix past P = 2^25 (n = 2^21), in device bytes.  A commitment: its five buffers (480 P + 32 S), the sort's keys, places and
+// scratch and the three transform workspaces of hobbit_shockwave_commit's 16 rows of P points (80 P).  An opening: its own scratch (320 P),
+// the multiplication tree's arena over 4 P (256 P), P4's ping-pong tables over 8 P (192 P), shockwave_prove(C_p) at width P / 2 with its
+// nested WHIR proof (152 P) and prove_fft's tables (32 P) -- workspaces the context keeps.  Sums of the allocations' sizes, not measurements.
+inline bool parity_is_long(size_t P) { return P > ((size_t)1 << 25); }
+inline size_t parity_commit_bytes(size_t P, size_t S) { return 560 * P + 32 * S; }
+inline size_t parity_open_bytes(size_t P) { return 952 * P; }
 // plans built on first use (hobbit_capi.hip): the tiled steps of a long code, the CSR steps of the rows-innermost encode
 int ensure_tiled(hobbit_ctx *ctx);
 int ensure_ilv(hobbit_ctx *ctx);

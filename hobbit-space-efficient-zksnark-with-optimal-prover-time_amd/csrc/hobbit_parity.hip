@@ -256,7 +256,7 @@ void hobbit_parity_commitment_free(hobbit_parity_commitment *c) {
 int hobbit_parity_commit(hobbit_ctx *ctx, long long n, hobbit_parity_commitment **out) {
     if (!out) return ctx->fail(HOBBIT_EINVAL, "parity_commit: null output");
     *out = nullptr;
-    if (n < 16 || n > (1LL << 20) || (n & (n - 1))) return ctx->fail(HOBBIT_EINVAL, "parity_commit: n must be a power of two in [16, 2^20]");
+    if (n < 16 || n > (1LL << CODE_MAX_LOG) || (n & (n - 1))) return ctx->fail(HOBBIT_EINVAL, "parity_commit: n must be a power of two in [16, 2^21]");
     if (ctx->code.n != n) return ctx->fail(HOBBIT_ESTATE, "parity_commit: graphs for this n are not finalized (hobbit_graph_finalize)");
     const size_t S = 2 * (size_t)n;
     const auto t0 = std::chrono::steady_clock::now();
@@ -269,6 +269,7 @@ int hobbit_parity_commit(hobbit_ctx *ctx, long long n, hobbit_parity_commitment 
     if (m == 0 || 5 * P + 2 * S > 8 * P || 5 * P + 2 * S <= 4 * P) return ctx->fail(HOBBIT_EINVAL, "parity_commit: list length outside the public witness' 8P layout");
     LibcRngGuard guard;
     hipSetDevice(ctx->device);
+    if (parity_is_long(P)) HB_TRY(need_device_bytes(ctx, parity_commit_bytes(P, S), "parity_commit"));
     Handle<hobbit_parity_commitment, hobbit_parity_commitment_free> c(new hobbit_parity_commitment());
     c->ctx = ctx; c->n = n; c->m = m; c->P = P;
     if (c->h_u32.alloc(4 * P) || c->h_F.alloc(P + 2 * S)) return ctx->fail(HOBBIT_ENOMEM, "parity_commit: pinned host allocation failed");
@@ -346,7 +347,8 @@ int hobbit_parity_open(hobbit_ctx *ctx, const hobbit_parity_commitment *c, const
     const size_t P = c->P, m = c->m, S = 2 * (size_t)c->n;
     const int L = ilog2x(P), l = ilog2x(S);
     if (rlen != l) return ctx->fail(HOBBIT_EINVAL, "parity_open: rlen must be log2(2n)");
-    if (L < 12 || L > 25 || L <= l) return ctx->fail(HOBBIT_EINVAL, "parity_open: needs 2^12 <= P <= 2^25 (n = 128 .. 2^20): the nested WHIR proofs take widths 2^9 .. 2^24");
+    if (L < 12 || L > 26 || L <= l) return ctx->fail(HOBBIT_EINVAL, "parity_open: needs 2^12 <= P <= 2^26 (n = 128 .. 2^21): the nested WHIR proofs take widths 2^9 .. 2^25");
+    if (parity_is_long(P)) HB_TRY(need_device_bytes(ctx, parity_open_bytes(P), "parity_open"));      // (before the first draw)
     Scratch sc(ctx);
     F *beta1, *beta2, *betas12, *rows, *encw, *eq, *part, *pw2; uint8_t *lvw;
     const uint32_t nb = pgrid(m, 1024);
@@ -463,7 +465,7 @@ int hobbit_prove_linear_code_batch(hobbit_ctx *ctx, const hobbit_F *d_codewords,
 
 // ---- include/hobbit_parity_lists.h ----------------------------------------------------------------------------------------------------------------
 int hobbit_parity_shape(hobbit_ctx *ctx, long long n, size_t *m_out, size_t *P_out) {
-    if (n < 16 || n > (1LL << 20) || (n & (n - 1))) return ctx->fail(HOBBIT_EINVAL, "parity_commit: n must be a power of two in [16, 2^20]");
+    if (n < 16 || n > (1LL << CODE_MAX_LOG) || (n & (n - 1))) return ctx->fail(HOBBIT_EINVAL, "parity_commit: n must be a power of two in [16, 2^21]");
     if (ctx->code.n != n) return ctx->fail(HOBBIT_ESTATE, "parity_commit: graphs for this n are not finalized (hobbit_graph_finalize)");
     std::vector<ParitySeg> segs; size_t m = 0;
     HB_TRY(parity_segments(ctx, segs, &m));
@@ -496,6 +498,7 @@ int hobbit_parity_commit_device(hobbit_ctx *ctx, long long n, hobbit_parity_comm
         own = std::move(ctx->spare_parity);
     } else {
         if (ctx->spare_parity.d_u32) { hipStreamSynchronize(ctx->stream); ctx->spare_parity = {}; }   // another shape: release it before allocating
+        if (parity_is_long(P)) HB_TRY(need_device_bytes(ctx, parity_commit_bytes(P, S), "parity_commit"));
         if (c->alloc_device()) return ctx->fail(HOBBIT_ENOMEM, "parity_commit: device allocation failed");
     }
     uint32_t *idx1 = c->d_u32, *idx2 = idx1 + P, *cnt1 = idx2 + P, *cnt2 = cnt1 + P;

@@ -1395,13 +1395,16 @@ static hobbit_parity_open_out parity_open_buffers(hobbit_host_parity_transcript 
 }
 static hobbit_host_brakingbase_transcript g_bb_open;
 hobbit_host_brakingbase_transcript &hobbit_host_last_brakingbase() { return g_bb_open; }
-void commit_brakingbase(vector<F> &poly, vector<vector<_hash>> &MT_hashes) {                                     // (:114-144)
+// the two forms of the baseline: the calls of hobbit_brakingbase.h (N / K <= 2^20) and the long ones of hobbit_longcodes.h (N / K <= 2^21)
+typedef int (*bb_commit_fn)(hobbit_ctx *, const hobbit_F *, size_t, size_t, int, hobbit_brakingbase **);
+typedef int (*bb_open_fn)(hobbit_ctx *, const hobbit_brakingbase *, const hobbit_F *, hobbit_brakingbase_open_out *);
+static void commit_brakingbase_with(bb_commit_fn commit, vector<F> &poly, vector<vector<_hash>> &MT_hashes) {     // (:114-144)
     BUFFER_SPACE = tensor_row_size;
     const size_t N = poly.size(), trs = (size_t)tensor_row_size, K = N / trs;
     printf("%d,%d\n", (int)BUFFER_SPACE, (int)K);
     if (g_bb) { hobbit_brakingbase_free(g_bb); g_bb = nullptr; }
     DevBuf d(poly.data(), N * sizeof(F));
-    HCHK(hobbit_brakingbase_commit(hobbit_host_ctx(), (const hobbit_F *)d.p, N, K, 1, &g_bb));
+    HCHK(commit(hobbit_host_ctx(), (const hobbit_F *)d.p, N, K, 1, &g_bb));
     // MT_hashes: level 0 = the 2 trs column digests (MT_commit_Blake of every column), then create_tree_blake (:127-143)
     const size_t W = 2 * trs, levels = (size_t)log2((double)W) + 1;
     vector<_hash> flat(2 * W - 1);
@@ -1409,6 +1412,8 @@ void commit_brakingbase(vector<F> &poly, vector<vector<_hash>> &MT_hashes) {    
     MT_hashes.assign(levels, vector<_hash>());
     for (size_t l = 0, off = 0, sz = W; l < levels; l++, off += sz, sz /= 2) MT_hashes[l].assign(flat.begin() + off, flat.begin() + off + sz);
 }
+void commit_brakingbase(vector<F> &poly, vector<vector<_hash>> &MT_hashes) { commit_brakingbase_with(hobbit_brakingbase_commit, poly, MT_hashes); }
+void commit_brakingbase_any(vector<F> &poly, vector<vector<_hash>> &MT_hashes) { commit_brakingbase_with(hobbit_brakingbase_commit_any, poly, MT_hashes); }
 void _aggregate_brakingbase(vector<F> &poly, vector<F> beta1, vector<F> random_points, vector<F> &codeword) {    // (:238-256)
     (void)random_points;                                             // the reference never reads it either
     const size_t trs = (size_t)tensor_row_size;
@@ -1427,7 +1432,7 @@ void recursive_prover_brakingbase(vector<F> &codeword, vector<size_t> I, double 
     shockwave_prove(C_c, P1.randomness[0], vt, ps);
     C_c = nullptr;                                                   // shockwave_prove deleted it (src/Virgo.cpp:515)
 }
-void open_brakingbase(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_hashes) {                          // (:355-429)
+static void open_brakingbase_with(bb_open_fn open, vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_hashes) {     // (:355-429)
     (void)MT_hashes;
     if (!g_bb) { printf("Error: open_brakingbase without commit_brakingbase\n"); exit(-1); }
     size_t N = 0, K = 0, trs = 0;
@@ -1448,7 +1453,7 @@ void open_brakingbase(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_ha
     hobbit_brakingbase_open_out o = {t.I.data(), hF(t.reply.data()), t.paths.data(), hF(t.aggr.data()), t.cc_root, t.cp_root, hF(t.p1_q.data()), hF(t.p1_r.data()), hF(t.p1_vr),
                                      hF(&t.p1_fin), hF(t.p1_r1.data()), &po, &bc.o, &t.ps, t.stage_ms};
     vector<F> xs(x.begin(), x.begin() + lk);
-    HCHK(hobbit_brakingbase_open(g_ctx, g_bb, hF(xs.data()), &o));
+    HCHK(open(g_ctx, g_bb, hF(xs.data()), &o));
     if (t.p1_q[0] + t.p1_q[1] + t.p1_q[2] + t.p1_q[2] != F(0)) printf("Error in codeword\n");                   // q(0) + q(1) of P1's first round (src/sumcheck.cpp:3231)
     if (!pt.checks[0]) { printf("Error 1\n"); exit(-1); }
     if (!pt.checks[1]) { printf("Error 2\n"); exit(-1); }
@@ -1458,12 +1463,16 @@ void open_brakingbase(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_ha
     t.vt = 0.0;
     printf("Ps : %lf, Vt : %lf \n", t.ps, t.vt);
 }
-void test_brakingbase(size_t N, int K) {                                                                         // (:757-761, 827-842)
+void open_brakingbase(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_hashes) { open_brakingbase_with(hobbit_brakingbase_open, poly, x, MT_hashes); }
+void open_brakingbase_any(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_hashes) { open_brakingbase_with(hobbit_brakingbase_open_any, poly, x, MT_hashes); }
+static void test_brakingbase_with(bool any, size_t N, int K) {                                                   // (:757-761, 827-842)
     size_t trs = 0;
-    if (K <= 0 || hobbit_brakingbase_shape(N, (size_t)K, &trs) != 0) {
-        if (K >= 4 && K <= 512 && (K & (K - 1)) == 0 && N / (size_t)K > ((size_t)1 << 20))
-            printf("Error: Braking base at N / K = %zu needs a code longer than 2^20, which the code proof and the parity opening do not build\n", N / (size_t)K);
-        else printf("Error: Braking base takes N, K powers of two with 4 <= K <= 512 and 128 <= N / K <= 2^20\n");
+    const int cap = any ? 21 : 20;
+    if (K <= 0 || (any ? hobbit_brakingbase_shape_any : hobbit_brakingbase_shape)(N, (size_t)K, &trs) != 0) {
+        if (K >= 4 && K <= 512 && (K & (K - 1)) == 0 && N / (size_t)K > ((size_t)1 << cap)) {
+            if (any) printf("Error: Braking base at N / K = %zu needs a code longer than 2^21: its parity matrix' encoded rows would hold 2^31 elements, a size that has not been verified\n", N / (size_t)K);
+            else printf("Error: Braking base at N / K = %zu needs a code longer than 2^20, which the code proof and the parity opening do not build\n", N / (size_t)K);
+        } else printf("Error: Braking base takes N, K powers of two with 4 <= K <= 512 and 128 <= N / K <= 2^%d\n", cap);
         exit(-1);
     }
     vector<F> poly = generate_randomness((int)N);
@@ -1471,7 +1480,7 @@ void test_brakingbase(size_t N, int K) {                                        
     tensor_row_size = (int)trs;
     expander_init_store(tensor_row_size);
     auto start = std::chrono::steady_clock::now();
-    commit_brakingbase(poly, MT_hashes);
+    if (any) commit_brakingbase_any(poly, MT_hashes); else commit_brakingbase(poly, MT_hashes);
     auto end = std::chrono::steady_clock::now();
     double elapsed_seconds = std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
     std::cout << "Commit time: " << elapsed_seconds << " seconds" << std::endl;
@@ -1479,11 +1488,18 @@ void test_brakingbase(size_t N, int K) {                                        
     for (int i = 0; i < 32; i++) printf("%02x", MT_hashes.back()[0].arr[i]);
     printf("\n");
     start = std::chrono::steady_clock::now();
-    open_brakingbase(poly, generate_randomness((int)log2((double)poly.size())), MT_hashes);
+    if (any) open_brakingbase_any(poly, generate_randomness((int)log2((double)poly.size())), MT_hashes);
+    else open_brakingbase(poly, generate_randomness((int)log2((double)poly.size())), MT_hashes);
     end = std::chrono::steady_clock::now();
     elapsed_seconds += std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
     std::cout << "Total time: " << elapsed_seconds << " seconds" << std::endl;
+    if (any) {                                                       // the long driver also prints what a measurement of these shapes records
+        const hobbit_host_brakingbase_transcript &t = hobbit_host_last_brakingbase();
+        printf("stage_ms %.3f %.3f %.3f %.3f %.3f %.3f\n", t.stage_ms[0], t.stage_ms[1], t.stage_ms[2], t.stage_ms[3], t.stage_ms[4], t.stage_ms[5]);
+    }
 }
+void test_brakingbase(size_t N, int K) { test_brakingbase_with(false, N, K); }
+void test_brakingbase_any(size_t N, int K) { test_brakingbase_with(true, N, K); }
 
 // ---- Orion baseline (src/Our_PC.cpp:28-65, 173-195, 523-602, 780-793; src/PC_utils.cpp:150-166; include/hobbit_orion.h) ----------------------
 static hobbit_host_orion_transcript g_or_open;

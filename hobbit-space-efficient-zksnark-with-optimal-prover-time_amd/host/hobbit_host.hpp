@@ -17,6 +17,7 @@
 #include "hobbit_parity_lists.h"
 #include "hobbit_whir.h"
 #include "hobbit_brakingbase.h"
+#include "hobbit_longcodes.h"
 #include "hobbit_orion.h"
 
 using std::vector;
@@ -275,6 +276,11 @@ struct hobbit_host_brakingbase_transcript {
 };
 hobbit_host_brakingbase_transcript &hobbit_host_last_brakingbase();       /* the parity part: hobbit_host_last_parity_open() */
 void test_brakingbase(size_t N, int K);
+/* the long forms (include/hobbit_longcodes.h): the same three with 128 <= N / K <= 2^21, reached as `host/test_pc brakingbase_any <logN> <K>`;
+ * test_brakingbase_any also prints the opening's six stage times ("stage_ms ...") */
+void commit_brakingbase_any(vector<F> &poly, vector<vector<_hash>> &MT_hashes);
+void open_brakingbase_any(vector<F> &poly, vector<F> x, vector<vector<_hash>> &MT_hashes);
+void test_brakingbase_any(size_t N, int K);
 #endif
 /* src/Our_PC.cpp:28-65, 173-195, 523-602, 780-793 ; src/PC_utils.cpp:150-166: the Orion comparison baseline (test_PC option 2), on the device
  * through include/hobbit_orion.h.  commit_standard_orion draws the graphs of n = sqrt(N) as the reference does, prints its "OK" line and keeps

@@ -3,6 +3,7 @@
 // Brakedown baseline, which sets its own buffer size, so <logB> is ignored there as in the reference) and `whir <logN>` (the standalone WHIR
 // baseline: test_PC's last branch, which test_PC itself keeps refusing) and `brakingbase <logN> <K>` (the Braking base baseline: test_PC's
 // option 5, which test_PC itself keeps refusing; shapes outside 4 <= K <= 512, 128 <= N / K <= 2^20 print an error and return 255) and
+// `brakingbase_any <logN> <K>` (the same baseline through include/hobbit_longcodes.h: N / K up to 2^21, which `28 5 128` of PC_tests.sh needs) and
 // `orion <logN>` (the Orion baseline: test_PC's option 2, which test_PC itself keeps refusing; logN even in [14, 28], else an error and 255)
 // (src/main.cpp:1176: test_PC(1ULL<<atoi(argv[1]), atoi(argv[2]), atoi(argv[3]))) over the
 // device-backed host mirror.  Build: see __graft_entry__.build_host().
@@ -13,10 +14,11 @@
 int main(int argc, char **argv) {
     const bool whir = argc == 3 && std::string(argv[1]) == "whir";
     const bool bbase = argc == 4 && std::string(argv[1]) == "brakingbase";
+    const bool bbase_any = argc == 4 && std::string(argv[1]) == "brakingbase_any";
     const bool orion = argc == 3 && std::string(argv[1]) == "orion";
     if (argc < 4 && !whir && !orion) {
-        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>   |   %s orion <logN>\n", argv[0], argv[0], argv[0],
-               argv[0], argv[0]);
+        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>   |   %s brakingbase_any <logN> <K>   |   %s orion <logN>\n",
+               argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 1;
     }
     init_hash();
@@ -24,6 +26,11 @@ int main(int argc, char **argv) {
         const int logn = atoi(argv[2]);
         if (logn < 14 || logn > 28 || (logn & 1)) { printf("Error: Orion takes N = 2^n with n even and 14 <= n <= 28\n"); return 255; }
         test_orion(1ULL << logn);
+    } else
+    if (bbase_any) {                                  // src/Our_PC.cpp:827-842, rows to 2^21
+        const int logn = atoi(argv[2]);
+        if (logn < 1 || logn > 40) { printf("Error: Braking base takes N, K powers of two with 4 <= K <= 512 and 128 <= N / K <= 2^21\n"); return 255; }
+        test_brakingbase_any(1ULL << logn, atoi(argv[3]));
     } else
     if (bbase) {                                      // src/Our_PC.cpp:827-842
         const int logn = atoi(argv[2]);

@@ -21,9 +21,9 @@ typedef struct hobbit_brakingbase hobbit_brakingbase;
 #define HOBBIT_BRAKINGBASE_QUERIES 2935      /* src/Our_PC.cpp:360 */
 
 /* Shapes served: N and K powers of two, 4 <= K <= 512 (MT_commit_Blake of a column needs one 64-byte leaf; the general column digest keeps
- * a stack for at most 512 rows), trs = N / K with 128 <= trs <= 2^20 (below: the parity opening's smallest n; above: the longest code
- * hobbit_graph_finalize builds and hobbit_parity_commit takes -- `28 5 64` and `28 5 128` of PC_tests.sh need codes of 2^22 and 2^21 and are
- * refused).  Anything else is HOBBIT_EINVAL.  Host only; trs may be NULL. */
+ * a stack for at most 512 rows), trs = N / K with 128 <= trs <= 2^20 (below: the parity opening's smallest n; above: these three calls keep
+ * the cap they were built with -- `28 5 128` of PC_tests.sh needs a code of 2^21 and is served by the long forms of hobbit_longcodes.h,
+ * `28 5 64` needs 2^22 and is refused there too).  Anything else is HOBBIT_EINVAL.  Host only; trs may be NULL. */
 int hobbit_brakingbase_shape(size_t N, size_t K, size_t *trs);
 
 /* commit_brakingbase: d_poly (N F, device) cut into K rows of trs, row i transposed into entry i of columns 0 .. trs - 1 of a 2 trs x K

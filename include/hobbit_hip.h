@@ -97,7 +97,7 @@ int hobbit_f_binop(hobbit_ctx *ctx, int op, const hobbit_F *d_a, const hobbit_F 
 int hobbit_graph_reset(hobbit_ctx *ctx);
 int hobbit_graph_upload(hobbit_ctx *ctx, int dep, int kind, long long L, long long R, int degree,
                         const long long *h_nbr, const hobbit_F *h_w);
-/* call after all levels for code length n are uploaded; returns codeword length via *len */
+/* call after all levels for code length n are uploaded; returns codeword length via *len.  n <= 2^21 (else HOBBIT_EINVAL) */
 int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len);
 /* which kernel forms the finalized code runs in (chosen at finalize from the graphs' shape and in-degrees).  *flags: the bits below; a fat or
  * narrow bit says that the step's register-resident tables were built, so an in-place encode runs k_enc_fat / k_enc_narrow there.
@@ -298,7 +298,9 @@ int hobbit_whir_prove(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const h
  * their replies (column I[i] of the encoded matrix, k F) and paths (open_tree_blake(MT, {I[i],0}, 0), log2(2N/k) x 32 B),
  * P1 = 2-product sumcheck against the query indicator, P2 = prove_fft, then _whir_prove.  d_matrix: k x N/k, d_enc: k x 2N/k,
  * d_levels: the column tree (all as produced by hobbit_shockwave_commit; d_levels NULL: no paths).  All outputs are host
- * buffers (sizes as hobbit_sumcheck2 / hobbit_whir_out; reply, paths and the wq* query fields may be NULL). */
+ * buffers (sizes as hobbit_sumcheck2 / hobbit_whir_out; reply, paths and the wq* query fields may be NULL).
+ * The aggregate's width N/k is at most 2^26: up to 2^24 the nested proof is hobbit_whir_prove's (plan, scratch and bits unchanged), in
+ * (2^24, 2^26] it is hobbit_whir_prove_any's table-free out-of-domain step (hobbit_whir.h) with that form's scratch; wider is HOBBIT_EINVAL. */
 typedef struct {
     uint32_t *I; hobbit_F *q1, *r1, *vr1, *fin1, *q2, *r2, *vr2, *fin2, *wq, *wa; uint8_t *wroots; hobbit_F *wscal; int *wchecks; uint8_t *whir_root; int *iters;
     hobbit_F *reply; uint8_t *paths;

@@ -16,7 +16,8 @@ extern "C" {
 typedef struct hobbit_parity_commitment hobbit_parity_commitment;
 
 /* commit_parity_matrix(n) for the graphs finalized for code length n (hobbit_graph_finalize(ctx, n, .), else HOBBIT_ESTATE).
- * n a power of two, 16 <= n <= 2^20 (else HOBBIT_EINVAL).  The lists of generate_access_idx (:2622-2669) are public data of the graphs: they
+ * n a power of two, 16 <= n <= 2^21 (else HOBBIT_EINVAL; at 2^21 P = 2^26, the object holds about 30 GiB, and the device is asked for the
+ * memory first: HOBBIT_ENOMEM before any allocation when it is not free).  The lists of generate_access_idx (:2622-2669) are public data of the graphs: they
  * are built once per object on the host, from the levels the context holds, and uploaded.  The object owns
  *   idx1, idx2, cnt1, cnt2 : P x u32 (m entries, then zeros): A index, beta index, and the two occurrence counters (1-based: how often the
  *                            index has appeared up to and including this entry);
@@ -43,8 +44,9 @@ int hobbit_parity_lists(hobbit_ctx *ctx, const hobbit_parity_commitment *c, uint
  * the second; r, _a = F(random()); generate_randomness(3); the draws of shockwave_prove(C_p, .); those of shockwave_prove(C_w, .).
  * The reference reads access_idx1[i] / access_idx2[i] for m <= i < P past the vectors' size (:2756-2763); this library defines those
  * entries as 0 (the reference under a zero-filling allocator).
- * The nested hobbit_whir_prove takes widths 2^9 .. 2^24: 2^12 <= P <= 2^25, i.e. n = 128 .. 2^20.  A commitment outside that range, a wrong
- * rlen or a NULL argument is HOBBIT_EINVAL before any draw, allocation or launch.
+ * The nested WHIR proofs take widths 2^9 .. 2^25 (hobbit_shockwave_prove: the table-free form above 2^24): 2^12 <= P <= 2^26, i.e.
+ * n = 128 .. 2^21.  A commitment outside that range, a wrong rlen or a NULL argument is HOBBIT_EINVAL before any draw, allocation or launch.
+ * At P = 2^26 the opening takes about 60 GiB of scratch and workspaces; the device is asked first (HOBBIT_ENOMEM before any draw).
  * All output pointers are host buffers (L = log2 P, l = log2 2n):
  *   t1_* / t2_*   : the two multiplication trees (4 x P and 4 x 2n) as hobbit_mul_tree lays them out; *_evals = {out_eval, final_eval};
  *   p2_*          : _generate_3product_sumcheck_proof(weight, betas1, betas2) as hobbit_sumcheck3 (L rounds);

@@ -10,7 +10,7 @@
 extern "C" {
 #endif
 
-/* hobbit_parity_commit with the lists built by kernels: same range of n (a power of two, 16 <= n <= 2^20), same refusals with the same codes,
+/* hobbit_parity_commit with the lists built by kernels: same range of n (a power of two, 16 <= n <= 2^21), same refusals with the same codes,
  * and every byte the object owns -- idx1, idx2, cnt1, cnt2, weight, acc1, acc2, the 8P public witness, the encoded rows, the tree -- equal to
  * what hobbit_parity_commit produces for the same graphs.  The lists are a function of the finalized code alone: its forward form (every
  * level's neighbours and weights in list order, and a table of the list's segments) is uploaded by the first such commit after
