@@ -20,6 +20,7 @@ import pytest
 
 import brakingbase_model as bm
 import commit_refs
+from open_verifier import ONE, ZERO, check_rounds, claim, ev, fadd, fi, fmul, fsub
 from oracle import pyoracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,42 +40,7 @@ def _mod():
     return load_package()
 
 
-# ---- F_{p^2} (p = 2^61 - 1, i^2 = -1) in Python integers, and the verifier's round test -----------------------------------------------------------
-def fi(a):
-    return (int(a[0]), int(a[1]))
-
-
-def fadd(a, b): return ((a[0] + b[0]) % P, (a[1] + b[1]) % P)
-def fsub(a, b): return ((a[0] - b[0]) % P, (a[1] - b[1]) % P)
-def fmul(a, b): return ((a[0] * b[0] - a[1] * b[1]) % P, (a[0] * b[1] + a[1] * b[0]) % P)
-
-
-ONE, ZERO = (1, 0), (0, 0)
-
-
-def ev(q, x):
-    """a polynomial's value, coefficients highest degree first (quadratics a, b, c; cubics a, b, c, d)"""
-    v = ZERO
-    for c in q:
-        v = fadd(fmul(v, x), fi(c))
-    return v
-
-
-def claim(q):
-    return fadd(ev(q, ZERO), ev(q, ONE))
-
-
-def check_rounds(poly, r, vr, what):
-    """the verifier's round test of one sumcheck: q_i(0) + q_i(1) = q_{i-1}(r_{i-1}), and q_last(r_last) = the product of the final values"""
-    poly = np.asarray(poly); r = np.asarray(r)
-    assert len(poly) == len(r) and len(poly) >= 1, what
-    for i in range(1, len(poly)):
-        assert claim(poly[i]) == ev(poly[i - 1], fi(r[i - 1])), "%s: round %d" % (what, i)
-    prod = ONE
-    for v in np.asarray(vr).reshape(-1, 2):
-        prod = fmul(prod, fi(v))
-    assert ev(poly[-1], fi(r[-1])) == prod, what + ": final values"
-    return claim(poly[0])
+# ---- F_{p^2} in Python integers and the verifier's round test: tests/open_verifier.py ------------------------------------------------------------------
 
 
 def check_tree(t, vectors, what):
