@@ -31,6 +31,10 @@ struct hobbit_commitment {
     // leaf group) and were NOT written: the leaf chain, the gathers and the row reads answer them as zeros; hobbit_commitment_tensor_dev fills them
     // in before it hands the raw pointer out.  rows_valid == rows2: everything is in memory (RS x RS, shallow codes, HOBBIT_COMMIT_SKIP_TAIL=0).
     uint32_t rows_valid;
+    // The message half (rows [0, trs)) of every column is rotated inside its own ring (hobbit_rot.hpp): msg_rot = trs - 1, else 0.  Written so by
+    // the commit's row FFT where the shape has the rotated form (tensorcode_chunks); read through msg_rot_row by the encode's loader, the leaf
+    // chain, the gathers and the row reads.  d_tensor never escapes except through hobbit_commitment_tensor_dev, which un-rotates it first, once.
+    uint32_t msg_rot = 0;
 };
 
 // Scope of one library call for the staging arena (hobbit_ctx.hpp): the outermost scope resets the arena on entry and, in finish(),
@@ -999,7 +1003,11 @@ struct Uploader {
     int wait(int g, hipStream_t s) { HB_TRY(start(g)); HB_CHECK(ctx, hipStreamWaitEvent(s, ctx->up_ready[g], 0)); return 0; }
     int all(hipStream_t s) { for (int g = 0; g < groups; g++) HB_TRY(wait(g, s)); return 0; }
 };
-static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, int trs, int lin, F *d_out, Uploader *up = nullptr) {
+// msg_rot (commit_impl only; default off): where every piece of the rotated form exists -- linear-time code, trs = 4096, rows of 4096, a tensor of
+// 64 MiB or more, the fat in-place encode -- the tensor's message half is written rotated (hobbit_rot.hpp) and *msg_rot becomes the ring's mask;
+// every other shape and every other caller gets today's linear tensor and *msg_rot = 0.
+static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, int trs, int lin, F *d_out, Uploader *up = nullptr, uint32_t *msg_rot = nullptr) {
+    if (msg_rot) *msg_rot = 0;
     if (trs <= 0 || M % (size_t)trs) return ctx->fail(HOBBIT_EINVAL, "tensorcode: trs must divide M");
     size_t half = M / trs, cols = 2 * half, rows2 = 2 * (size_t)trs;
     int logc = ilog2_exact(cols), logr = ilog2_exact(rows2);
@@ -1007,6 +1015,7 @@ static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, i
     if (logr < 1) return ctx->fail(HOBBIT_EINVAL, "tensorcode: trs must be a power of two");
     // rows: RS encode = zero-padded FFT (src/PC_utils.cpp:75-84,105-107)
     const bool piped_shape = logc <= 12 && (size_t)K * trs * cols * sizeof(F) >= ((size_t)64 << 20);
+    const bool rotated = msg_rot && lin && piped_shape && logc == 12 && trs == 4096 && encode_reads_rotated(ctx, trs);
     if (up && !piped_shape) { up->groups = 1; up->group_bytes = (size_t)K * M * sizeof(F); HB_TRY(up->all(ctx->stream)); up = nullptr; }
     if (logc > 15) {
         // very long rows (test_PC option 1 at 2^27 and beyond: tensor_row_size stays 128): one chunk at a time through the long transform
@@ -1032,13 +1041,31 @@ static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, i
     // Large tensors: FFT to a row-major scratch (coalesced stores) + tiled transpose; small ones write the
     // transposed layout directly (one launch less, the scattered stores stay in L2).
     if ((size_t)K * trs * cols * sizeof(F) >= ((size_t)64 << 20)) {
+        const char *pp_env = getenv("HOBBIT_COMMIT_PIPE");
+        int pipe = pp_env ? atoi(pp_env) : (K % 8 == 0 ? 8 : K % 4 == 0 ? 4 : K % 2 == 0 ? 2 : 0);
+        if (pipe > 56) pipe = 56;                                    // side_ev[0 .. pipe) are this loop's; 60, 62, 63 belong to the opening (OpenRun), 61 is free, 64/65 to the brackets below
+        if (rotated) {
+            // A commitment's tensor (hobbit_rot.hpp): the row FFT stores the codeword-major layout itself, each column's message half rotated, so
+            // that the 4096 stores of a row spread over the memory channels instead of meeting on one.  No row-major scratch, no transpose and no
+            // side stream; the chunk groups remain because the upload of hobbit_commit_standard_host is waited for group by group.
+            const int groups = pipe > 1 && K % pipe == 0 ? pipe : 1, per = K / groups;
+            HB_TRY(get_tw8(ctx, false));
+            const F *t8 = ctx->tw8[0];
+            if (up) { up->groups = groups; up->group_bytes = (size_t)per * M * sizeof(F); }
+            for (int g = 0; g < groups; g++) {
+                const size_t c0 = (size_t)g * per;
+                if (up) HB_TRY(up->wait(g, ctx->stream));
+                HB_TRY(launch_fft4096(ctx, d_msg + c0 * M, half, 1, 2048, d_out + c0 * cols * rows2, 1, rows2, t8, t8 + 7 * 8, t8 + 7 * 8 + 7 * 64, ctx->tw8_w8[0],
+                                      ctx->tw8_w83[0], ctx->tw8_w4_plus_i[0], fmake(1), 0, (uint32_t)per, (uint32_t)trs, M, cols * rows2, (uint32_t)trs - 1));
+                if (up) HB_TRY(up->start(g + 1));                 // (host copy + PCIe of the next group, beside this group's kernel)
+            }
+            *msg_rot = (uint32_t)trs - 1;
+            return launch_encode(ctx, d_out, rows2, d_out, rows2, trs, (size_t)K * cols, 0, *msg_rot);
+        }
         F *rm; HB_TRY(ctx->workspace2((size_t)K * trs * cols * sizeof(F), (void **)&rm));
         // Two-stream pipeline over chunk groups (default on; HOBBIT_COMMIT_PIPE=0 turns it off, =G asks for G groups): group g's layout
         // change (HBM-bound, next to no VALU work) runs on the side stream while group g+1's row FFT (VALU-bound, one pass over the
         // data) runs on the main one.  Same kernels, same bytes, bit-identical tensor; DESIGN.md section 4 has the A/B.
-        const char *pp_env = getenv("HOBBIT_COMMIT_PIPE");
-        int pipe = pp_env ? atoi(pp_env) : (K % 8 == 0 ? 8 : K % 4 == 0 ? 4 : K % 2 == 0 ? 2 : 0);
-        if (pipe > 56) pipe = 56;                                    // side_ev[0 .. pipe) are this loop's; 60, 62, 63 belong to the opening (OpenRun), 61 is free, 64/65 to the brackets below
         if (pipe > 1 && K % pipe == 0) {
             HB_TRY(ctx->side_init());
             const int per = K / pipe; hipStream_t mainS = ctx->stream;
@@ -1118,13 +1145,13 @@ static int commit_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int K,
     }
     const char *st_env = getenv("HOBBIT_COMMIT_SKIP_TAIL");
     ctx->enc_skip_tail = linear_time && !(st_env && st_env[0] == '0'); ctx->enc_tail_skipped = false;
-    int r = tensorcode_chunks(ctx, cF(d_poly), M, K, trs, linear_time, c->d_tensor, up);
+    int r = tensorcode_chunks(ctx, cF(d_poly), M, K, trs, linear_time, c->d_tensor, up, &c->msg_rot);
     c->rows_valid = (!r && ctx->enc_tail_skipped) ? std::min<uint32_t>((uint32_t)rows2, ((uint32_t)ctx->code.len + 3) & ~3u) : (uint32_t)rows2;
     ctx->enc_skip_tail = false; ctx->enc_tail_skipped = false;
     // leaf chain over the K chunks (src/Our_PC.cpp:155-167), then the tree (src/Our_PC.cpp:169);
     // rows >= the codeword length are zero in every chunk of an RS x expander tensor (RS x RS fills all 2*trs rows)
     if (!r) r = launch_leaf_chain(ctx, c->d_tensor, cols * rows2, K, (uint32_t)cols, (uint32_t)(trs / 2), c->d_levels,
-                                       linear_time && ctx->code.n == trs ? (uint32_t)ctx->code.len : (uint32_t)rows2);
+                                       linear_time && ctx->code.n == trs ? (uint32_t)ctx->code.len : (uint32_t)rows2, c->msg_rot);
     if (!r) r = launch_merkle_levels(ctx, c->d_levels, M, 1);
     if (r) return r;
     *out = c.release();
@@ -1142,10 +1169,11 @@ void hobbit_commitment_free(hobbit_commitment *c) {
 size_t hobbit_commitment_num_leaves(const hobbit_commitment *c) { return c->M; }
 const uint8_t *hobbit_commitment_levels_dev(const hobbit_commitment *c) { return c->d_levels; }
 const hobbit_F *hobbit_commitment_tensor_dev(const hobbit_commitment *c) {
-    if (c->rows_valid < c->rows2) {                       // a raw pointer leaves the library: the implicit zeros become real ones, once
-        hobbit_commitment *m = const_cast<hobbit_commitment *>(c);
-        if (launch_zero_rows(m->ctx, m->d_tensor, (size_t)m->K * m->cols, m->rows2, m->rows_valid) != 0 || m->ctx->sync() != 0) return nullptr;
-        m->rows_valid = m->rows2;
+    if (c->rows_valid < c->rows2 || c->msg_rot) {         // a raw pointer leaves the library: the implicit zeros become real ones and a rotated
+        hobbit_commitment *m = const_cast<hobbit_commitment *>(c);      // message half a linear one, once, in place (one drain for both)
+        if (launch_zero_rows(m->ctx, m->d_tensor, (size_t)m->K * m->cols, m->rows2, m->rows_valid) != 0 ||
+            launch_unrotate_msg(m->ctx, m->d_tensor, (size_t)m->K * m->cols, m->rows2, m->msg_rot) != 0 || m->ctx->sync() != 0) return nullptr;
+        m->rows_valid = m->rows2; m->msg_rot = 0;
     }
     return reinterpret_cast<const hobbit_F *>(c->d_tensor.get());
 }
@@ -1154,7 +1182,7 @@ int hobbit_commitment_root(hobbit_ctx *ctx, const hobbit_commitment *c, uint8_t 
 int hobbit_commitment_tensor_row(hobbit_ctx *ctx, const hobbit_commitment *c, int chunk, int row, hobbit_F *h_out) {
     if (chunk < 0 || chunk >= c->K || row < 0 || (uint32_t)row >= c->rows2) return ctx->fail(HOBBIT_EINVAL, "tensor_row: index out of range");
     F *tmp; HB_TRY(ctx->workspace((size_t)c->cols * sizeof(F), (void **)&tmp));
-    HB_TRY(launch_tensor_row(ctx, c->d_tensor + (size_t)chunk * c->cols * c->rows2, c->rows2, c->cols, (uint32_t)row, tmp, c->rows_valid));
+    HB_TRY(launch_tensor_row(ctx, c->d_tensor + (size_t)chunk * c->cols * c->rows2, c->rows2, c->cols, (uint32_t)row, tmp, c->rows_valid, c->msg_rot));
     return hobbit_memcpy_d2h(ctx, h_out, tmp, (size_t)c->cols * sizeof(F));
 }
 int hobbit_commitment_gather(hobbit_ctx *ctx, const hobbit_commitment *c, const uint32_t *h_rows, const uint32_t *h_cols, size_t nq, hobbit_F *h_reply) {
@@ -1166,7 +1194,7 @@ int hobbit_commitment_gather(hobbit_ctx *ctx, const hobbit_commitment *c, const 
     F *d_reply = reinterpret_cast<F *>(buf); uint32_t *d_rows = reinterpret_cast<uint32_t *>(buf + rb), *d_cols = d_rows + nq;
     HB_TRY(h2d_staged(ctx, d_rows, h_rows, 4 * nq));
     HB_TRY(h2d_staged(ctx, d_cols, h_cols, 4 * nq));
-    HB_TRY(launch_gather(ctx, c->d_tensor, (size_t)c->cols * c->rows2, c->rows2, c->K, d_rows, d_cols, nq, d_reply, c->rows_valid));
+    HB_TRY(launch_gather(ctx, c->d_tensor, (size_t)c->cols * c->rows2, c->rows2, c->K, d_rows, d_cols, nq, d_reply, c->rows_valid, c->msg_rot));
     HB_TRY(d2h_staged(ctx, h_reply, d_reply, nq * c->K * sizeof(F)));
     return sc.finish();
 }

@@ -166,7 +166,8 @@ struct hobbit_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = false;
-    // second stream + events: the commit's layout change (HBM-bound) of one chunk group runs beside the next group's row FFT (VALU-bound).
+    // second stream + events: the layout change (HBM-bound) of one chunk group of a large linear tensor runs beside the next group's row FFT
+    // (VALU-bound); a commitment with the rotated message half (hobbit_rot.hpp) has no layout change and does not use them.
     // Event slots: [0, 56) the commit pipeline's chunk groups (tensorcode_chunks clamps its group count to 56), 60-63 open_impl's cross-stream
     // fences, 64/65 the pipeline's opening / closing brackets.
     hipStream_t side = nullptr; hipEvent_t side_ev[66] = {};
@@ -215,7 +216,7 @@ struct hobbit_ctx {
     // the reference's globals has_lookups / lookup_rand[0..1] (src/main.cpp:67,70), set through hobbit_set_lookups
     bool has_lookups = false; hobbit::F lookup_rand[2];
     // Grow-only scratch (mem::GrowBuf: a request beyond the capacity waits for the stream, frees, then allocates).
-    // workspace2: the row-major FFT output of a tensor code before its transpose
+    // workspace2: the row-major FFT output of a tensor code before its transpose (not asked for where the row FFT stores the tensor itself)
     // workspace3: arena of the open phase (tables that live across several sumchecks), kept between calls
     // workspace4: scratch of the inner-PCS provers (whir / shockwave), separate from the open arena that holds their inputs
     // workspace5: the caller's buffer of a three-factor transform (2^25 .. 2^28): its nested long transforms own workspace / workspace2

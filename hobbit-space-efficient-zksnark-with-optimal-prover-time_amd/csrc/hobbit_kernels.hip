@@ -305,7 +305,7 @@ template <bool PADDED>
 __global__ void __launch_bounds__(512)
 k_fft4096(const F *__restrict__ src, size_t src_ld, size_t src_es, F *__restrict__ dst, size_t dst_ld, size_t dst_es, const F *__restrict__ tw1,
           const F *__restrict__ tw2, const F *__restrict__ tw3, Fft4kConst cst, F scale, int do_scale, uint32_t rows_per_group, size_t src_gs,
-          size_t dst_gs, int line_remap) {
+          size_t dst_gs, int line_remap, uint32_t rot_mask) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     F *s = reinterpret_cast<F *>(lds_raw);
     // Transposed stores (dst_ld == 1): row r's element lands 16 B into the 128-byte line it shares with rows 8g .. 8g+7.  Workgroups b, b+8,
@@ -368,7 +368,11 @@ k_fft4096(const F *__restrict__ src, size_t src_ld, size_t src_es, F *__restrict
 #pragma unroll
             for (int t8 = 0; t8 < 8; t8++) {
                 F v = do_scale ? fmul_lz(ffold(a[t8]), scale) : fcanon(a[t8]);    // canonical out (a product already is)
-                stF(out + (size_t)(i0 + t8 * h) * dst_es, v);
+                const uint32_t c = i0 + t8 * h;
+                if (rot_mask)         // a commitment's rotated message half (hobbit_rot.hpp): dst_ld == 1, row r of column c at its rotated place
+                    stF(out - r + msg_rot_row(r, c, rot_mask) + (size_t)c * dst_es, v);
+                else
+                    stF(out + (size_t)c * dst_es, v);
             }
         }
     }
@@ -376,20 +380,22 @@ k_fft4096(const F *__restrict__ src, size_t src_ld, size_t src_es, F *__restrict
 
 int launch_fft4096(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_es, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, const F *tw1,
                    const F *tw2, const F *tw3, F w8, F w8_3, int w4_plus_i, F scale, int do_scale, uint32_t groups, uint32_t rows_per_group,
-                   size_t src_gs, size_t dst_gs) {
+                   size_t src_gs, size_t dst_gs, uint32_t rot_mask) {
     size_t blocks = (size_t)groups * rows_per_group;
     if (blocks == 0) return 0;
+    if (rot_mask && !(src_len == 2048 && dst_ld == 1 && rot_mask == rows_per_group - 1 && (rows_per_group & rot_mask) == 0 && dst_es >= rows_per_group))
+        return ctx->fail(HOBBIT_EINVAL, "fft4096: rotated stores need transposed output and a power-of-two row count");
     const size_t lds = (size_t)(4096 + 512) * 16;
     Fft4kConst cst; cst.w8 = w8; cst.w8_3 = w8_3; cst.w4_plus_i = w4_plus_i;
     if (src_len == 2048) {
         hipFuncSetAttribute((const void *)k_fft4096<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         const int remap = (dst_ld == 1 && dst_es > 1 && rows_per_group % 64 == 0) ? 1 : 0;
         HB_LAUNCH(ctx, "k_fft4096", k_fft4096<true>, dim3((unsigned)blocks), dim3(512), lds, src, src_ld, src_es, dst, dst_ld, dst_es, tw1, tw2, tw3, cst,
-                  scale, do_scale, rows_per_group, src_gs, dst_gs, remap);
+                  scale, do_scale, rows_per_group, src_gs, dst_gs, remap, rot_mask);
     } else {
         hipFuncSetAttribute((const void *)k_fft4096<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         HB_LAUNCH(ctx, "k_fft4096_full", k_fft4096<false>, dim3((unsigned)blocks), dim3(512), lds, src, src_ld, src_es, dst, dst_ld, dst_es, tw1, tw2, tw3,
-                  cst, scale, do_scale, rows_per_group, src_gs, dst_gs, 0);
+                  cst, scale, do_scale, rows_per_group, src_gs, dst_gs, 0, 0u);
     }
     return 0;
 }
@@ -1021,7 +1027,7 @@ static uint32_t block_for(const DeviceCode &c, uint32_t s_lo, uint32_t s_hi, uin
 template <int NOUT, int CAP0, int CAP1, int CAP2, int NW>
 __global__ void __launch_bounds__((NW + 1) * 64)
 k_enc_fat(F *__restrict__ tensor, size_t ld, uint32_t ncols, uint32_t in_off, uint32_t in_len, uint32_t out_off, uint32_t z_lo, uint32_t z_hi,
-          const uint32_t *__restrict__ wt, const uint32_t *__restrict__ ot, const uint32_t *__restrict__ oidx, const uint32_t *__restrict__ wid) {
+          const uint32_t *__restrict__ wt, const uint32_t *__restrict__ ot, const uint32_t *__restrict__ oidx, const uint32_t *__restrict__ wid, uint32_t rot_mask) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     constexpr int LANES = NW * 64, TOT = CAP0 + CAP1 + CAP2;
     constexpr int CAP[3] = {CAP0, CAP1, CAP2}, BASE[3] = {0, CAP0, CAP0 + CAP1};
@@ -1033,6 +1039,17 @@ k_enc_fat(F *__restrict__ tensor, size_t ld, uint32_t ncols, uint32_t in_off, ui
     if (loader) {
         auto issue = [&](uint32_t c, uint32_t buf) {                                     // column c's window -> buffer buf
             const F *colp = tensor + (size_t)c * ld + in_off;
+            if (rot_mask) {
+                // A rotated message half (pass A of a commitment, hobbit_rot.hpp: in_off == 0, in_len == rot_mask + 1, whole pieces) is read through
+                // its index; the LDS image is linear either way.  The column's rotation is wave-uniform and stays out of the piece loop: three vector
+                // instructions per piece against the linear loop's four.  Every instruction of this wave waits for an issue slot among the fat
+                // waves: five more per piece cost pass A 0.6 ms.
+                const uint32_t rot = msg_rot_elems(c, rot_mask);
+                for (uint32_t p = first_piece; p < pieces && p < end_piece; p++)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(colp + msg_rot_at((p << 6) + lane, rot, rot_mask)),
+                                                     (__attribute__((address_space(3))) void *)(lds_raw + buf * win_bytes + (p << 10)), 16, 0, 0);
+                return;
+            }
             for (uint32_t p = first_piece; p < pieces && p < end_piece; p++) {
                 uint32_t i = (p << 6) + lane; i = i < in_len ? i : in_len - 1;         // (the pad lanes of the last piece re-read the last element)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(colp + i),
@@ -1097,13 +1114,14 @@ k_enc_fat(F *__restrict__ tensor, size_t ld, uint32_t ncols, uint32_t in_off, ui
     }
 }
 template <int NOUT, int CAP0, int CAP1, int CAP2, int NW>
-static int launch_enc_fat(hobbit_ctx *ctx, const char *name, const FatStep &f, F *tensor, size_t ld, size_t ncols, uint32_t z_lo, uint32_t z_hi, uint32_t wgs) {
+static int launch_enc_fat(hobbit_ctx *ctx, const char *name, const FatStep &f, F *tensor, size_t ld, size_t ncols, uint32_t z_lo, uint32_t z_hi, uint32_t wgs,
+                          uint32_t rot_mask = 0) {
     const size_t lds = (size_t)2 * ((f.in_len + 63) / 64) * 1024;
     auto kern = k_enc_fat<NOUT, CAP0, CAP1, CAP2, NW>;
     hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     const size_t grid = std::min(ncols, (size_t)wgs);
     HB_LAUNCH(ctx, name, kern, dim3((unsigned)grid), dim3((NW + 1) * 64), lds, tensor, ld, (uint32_t)ncols, f.in_off, f.in_len, f.out_off, z_lo, z_hi,
-              f.d_wt, f.d_ot, f.d_oidx, f.d_w);
+              f.d_wt, f.d_ot, f.d_oidx, f.d_w, rot_mask);
     return 0;
 }
 
@@ -1329,10 +1347,21 @@ static int launch_encode_long(hobbit_ctx *ctx, const F *src, size_t ld_src, F *d
     return 0;
 }
 
-int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t ld_dst, long long n, size_t batch, int write_msg) {
+// The in-place encode of a deep code reads its message in exactly one place, the loader wave of k_enc_fat's pass A (window [0, n)); C_1, the
+// narrow steps, pass B and D_0 read and write the parity half [n, 2n) only.  That pass is the one form that follows a rotated message half.
+bool encode_reads_rotated(const hobbit_ctx *ctx, long long n) {
+    const DeviceCode &c = ctx->code;
+    if (c.n != n || (size_t)c.len * 16 > 160 * 1024 || c.steps.size() < 2 || (size_t)c.len * 16 <= 80 * 1024) return false;
+    if (!c.small_weights || !c.fatA.ok || c.fatA.in_off != 0 || c.fatA.in_len != (uint32_t)n) return false;
+    if (c.fatD.ok && c.steps.size() >= 5 && (c.fatD.in_off < (uint32_t)n || (c.fatC1.ok && c.fatC1.in_off < (uint32_t)n))) return false;
+    return true;
+}
+int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t ld_dst, long long n, size_t batch, int write_msg, uint32_t rot_mask) {
     DeviceCode &c = ctx->code;
     if (c.n != n) return ctx->fail(HOBBIT_ESTATE, "encode: graphs for this n are not finalized (hobbit_graph_finalize)");
     if (batch == 0) return 0;
+    if (rot_mask && !(rot_mask == (uint32_t)n - 1 && src == dst && ld_src == ld_dst && !write_msg && encode_reads_rotated(ctx, n)))
+        return ctx->fail(HOBBIT_ESTATE, "encode: a rotated message half needs the fat in-place form of this code");
     if ((size_t)c.len * 16 > 160 * 1024) {
         HB_TRY(ensure_tiled(ctx));
         if (!c.tiled_depth) return ctx->fail(HOBBIT_ESTATE, "encode: long code without its tiled steps (hobbit_graph_finalize)");
@@ -1354,7 +1383,7 @@ int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t l
     // deep codes in place (the message is where the codeword goes): C_0 by the persistent register-resident kernel, then the rest as one
     // pass B unless D_0 fits that kernel too
     if (c.small_weights && c.fatA.ok && src == dst && ld_src == ld_dst && !write_msg) {
-        HB_TRY((launch_enc_fat<FAT_A_NOUT, FAT_A_CAP0, FAT_A_CAP1, 0, FAT_A_CONS>(ctx, "k_enc_fat_A", c.fatA, dst, ld_dst, batch, 0, 0, FAT_A_WGS)));
+        HB_TRY((launch_enc_fat<FAT_A_NOUT, FAT_A_CAP0, FAT_A_CAP1, 0, FAT_A_CONS>(ctx, "k_enc_fat_A", c.fatA, dst, ld_dst, batch, 0, 0, FAT_A_WGS, rot_mask)));
         if (!c.fatD.ok || nsteps < 5)
             return launch_encode_pass<true>(ctx, "k_encode_B", dst, ld_dst, dst, ld_dst, batch, pb, (uint32_t)c.len - nn, block_for(c, 1, nsteps, 8));
         // C_1 alone -- 21 % of the edges on a 14 KB window: fat form, three workgroups per CU -- then the five short steps C_2 .. D_1 on the
@@ -1520,7 +1549,8 @@ __global__ void __launch_bounds__(1024) k_merkle_sub(const uint8_t *__restrict__
 struct ZeroDig { uint32_t w[8]; };
 template <int NL>
 __global__ void __launch_bounds__(256)
-k_leaf_chain(const F *__restrict__ tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *__restrict__ leaves, uint32_t zf, ZeroDig zk) {
+k_leaf_chain(const F *__restrict__ tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *__restrict__ leaves, uint32_t zf, ZeroDig zk,
+             uint32_t rot_mask) {
     const uint32_t stride = gridDim.x * blockDim.x;
     // the leaves of the zero groups: 2 (half_trs - zf) cols stores of 16 bytes, ending exactly at the end of the leaf array
     {
@@ -1545,7 +1575,8 @@ k_leaf_chain(const F *__restrict__ tensor, size_t chunk_stride, int K, uint32_t 
 #pragma unroll
             for (int q = 0; q < 8; q++) st[l][q] = 0;
             c[l] = gg / zf; j[l] = gg - c[l] * zf;
-            p[l] = tensor + ((size_t)c[l] * half_trs + j[l]) * 4;     // (c * 2trs + 4j)
+            // (c * 2trs + 4j; in a commitment's rotated message half the group sits at its rotated place, whole and aligned: hobbit_rot.hpp)
+            p[l] = tensor + (size_t)c[l] * half_trs * 4 + msg_rot_row(4 * j[l], c[l], rot_mask);
         }
         for (int i = 0; i < K; i++) {
             uint32_t m[NL][16], h[NL][8];
@@ -1871,7 +1902,8 @@ int launch_merkle_levels(hobbit_ctx *ctx, uint8_t *levels, size_t n, int quirk) 
 }
 // zero_rows_from: first row index that is zero in EVERY chunk (the expander codeword length; 2*half_trs = none).  The chain starts from the
 // zero state -- the commit, its one caller, always does -- and only that makes the leaves of the all-zero groups the constant Z_K.
-int launch_leaf_chain(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from) {
+int launch_leaf_chain(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from,
+                      uint32_t rot_mask) {
     constexpr int NL = 1;   // 2 interleaved chains measured no faster: the kernel sits at the VALU issue limit (profiles/r01_microbench.txt)
     if (((size_t)cols * half_trs) >> 32) return ctx->fail(HOBBIT_EINVAL, "leaf chain: more than 2^32 leaves");
     const uint32_t zf = std::min((zero_rows_from + 3) / 4, half_trs);
@@ -1882,7 +1914,7 @@ int launch_leaf_chain(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int
     // spread of the other -- and 4028 (7 equal passes) 8.84; in an earlier job 2048 9.04 and 3524 (8 equal passes) 9.00 against 4096 8.89.
     // Equal passes buy nothing: the hardware hands the next workgroup to whichever CU is free, so the cap stays where it was.
     HB_LAUNCH(ctx, "k_leaf_chain", k_leaf_chain<NL>, dim3(grid_for(((size_t)cols * zf + NL - 1) / NL, 256, 4096)), dim3(256), 0, tensor, chunk_stride, K, cols,
-              half_trs, leaves, zf, zk);
+              half_trs, leaves, zf, zk, rot_mask);
     return 0;
 }
 int launch_merkle_paths(hobbit_ctx *ctx, const uint8_t *levels, size_t n, const uint64_t *d_pos, size_t nq, int depth, uint8_t *d_paths) {
@@ -1996,18 +2028,18 @@ int launch_aggregate(hobbit_ctx *ctx, const F *poly, size_t M, int K, CHP h_beta
 // rows >= rows_valid of a column are zero BY CONSTRUCTION and may never have been written (a commitment's RS x expander tensor past its codeword
 // length: commit_impl): they are answered as zero, not read
 __global__ void k_gather(const F *__restrict__ tensor, size_t chunk_stride, uint32_t rows2, int K, const uint32_t *__restrict__ rows,
-                         const uint32_t *__restrict__ cols, size_t nq, F *__restrict__ reply, uint32_t rows_valid) {
+                         const uint32_t *__restrict__ cols, size_t nq, F *__restrict__ reply, uint32_t rows_valid, uint32_t rot_mask) {
     size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (g >= nq * K) return;
     size_t q = g / K; int i = (int)(g % K);
-    stF(reply + g, rows[q] < rows_valid ? ldF(tensor + (size_t)i * chunk_stride + (size_t)cols[q] * rows2 + rows[q]) : fmake(0));
+    stF(reply + g, rows[q] < rows_valid ? ldF(tensor + (size_t)i * chunk_stride + (size_t)cols[q] * rows2 + msg_rot_row(rows[q], cols[q], rot_mask)) : fmake(0));
 }
 int launch_gather(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, uint32_t rows2, int K, const uint32_t *d_rows, const uint32_t *d_cols,
-                  size_t nq, F *d_reply, uint32_t rows_valid) {
+                  size_t nq, F *d_reply, uint32_t rows_valid, uint32_t rot_mask) {
     size_t total = nq * K;
     if (!total) return 0;
     HB_LAUNCH(ctx, "k_gather", k_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tensor, chunk_stride, rows2, K, d_rows, d_cols, nq, d_reply,
-              rows_valid);
+              rows_valid, rot_mask);
     return 0;
 }
 // the unwritten tails made real: rows [rows_valid, rows2) of every column := 0 (before a raw pointer to the tensor leaves the library)
@@ -2022,12 +2054,34 @@ int launch_zero_rows(hobbit_ctx *ctx, F *tensor, size_t ncols, uint32_t rows2, u
     return 0;
 }
 // row `row` of one chunk in the reference's row-major order: out[c] = tensor[c*rows2 + row]
-__global__ void k_tensor_row(const F *__restrict__ chunk, uint32_t rows2, uint32_t cols, uint32_t row, F *__restrict__ out, uint32_t rows_valid) {
+__global__ void k_tensor_row(const F *__restrict__ chunk, uint32_t rows2, uint32_t cols, uint32_t row, F *__restrict__ out, uint32_t rows_valid, uint32_t rot_mask) {
     uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < cols) stF(out + c, row < rows_valid ? ldF(chunk + (size_t)c * rows2 + row) : fmake(0));
+    if (c < cols) stF(out + c, row < rows_valid ? ldF(chunk + (size_t)c * rows2 + msg_rot_row(row, c, rot_mask)) : fmake(0));
 }
-int launch_tensor_row(hobbit_ctx *ctx, const F *chunk, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid) {
-    HB_LAUNCH(ctx, "k_tensor_row", k_tensor_row, dim3((cols + 255) / 256), dim3(256), 0, chunk, rows2, cols, row, d_out, rows_valid);
+int launch_tensor_row(hobbit_ctx *ctx, const F *chunk, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid, uint32_t rot_mask) {
+    HB_LAUNCH(ctx, "k_tensor_row", k_tensor_row, dim3((cols + 255) / 256), dim3(256), 0, chunk, rows2, cols, row, d_out, rows_valid, rot_mask);
+    return 0;
+}
+// A rotated message half made linear, in place (before a raw pointer to the tensor leaves the library).  One workgroup per column and pass:
+// the rot_mask + 1 message rows (64 KiB at trs = 4096) come into LDS through the rotated index and go back in row order.
+__global__ void __launch_bounds__(1024)
+k_unrotate_msg(F *__restrict__ tensor, size_t ncols, uint32_t rows2, uint32_t rot_mask) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    F *s = reinterpret_cast<F *>(lds_raw);
+    for (size_t c = blockIdx.x; c < ncols; c += gridDim.x) {
+        F *col = tensor + c * rows2;
+        for (uint32_t r = threadIdx.x; r <= rot_mask; r += blockDim.x) stF(&s[r], ldF(col + msg_rot_row(r, (uint32_t)c, rot_mask)));
+        __syncthreads();                                            // the whole ring is in LDS before any of it is overwritten
+        for (uint32_t r = threadIdx.x; r <= rot_mask; r += blockDim.x) stF(col + r, ldF(&s[r]));
+        __syncthreads();
+    }
+}
+int launch_unrotate_msg(hobbit_ctx *ctx, F *tensor, size_t ncols, uint32_t rows2, uint32_t rot_mask) {
+    if (!rot_mask || !ncols) return 0;
+    const size_t lds = ((size_t)rot_mask + 1) * sizeof(F);
+    if ((rot_mask & (rot_mask + 1)) || rot_mask >= rows2 || lds > 64 * 1024) return ctx->fail(HOBBIT_EINVAL, "unrotate: the message ring must be a power of two of at most 4096 rows");
+    hipFuncSetAttribute((const void *)k_unrotate_msg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    HB_LAUNCH(ctx, "k_unrotate_msg", k_unrotate_msg, dim3(grid_for(ncols, 1, 65536)), dim3(1024), lds, tensor, ncols, rows2, rot_mask);
     return 0;
 }
 // multilinear evaluation fold step of evaluate_vector (src/utils.cpp:789-802): v'[j] = (1-r) v[2j] + r v[2j+1]

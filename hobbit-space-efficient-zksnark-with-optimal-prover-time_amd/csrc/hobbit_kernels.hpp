@@ -1,6 +1,7 @@
 // hobbit_kernels.hpp -- launcher prototypes (definitions in hobbit_kernels.hip)
 #pragma once
 #include "hobbit_ctx.hpp"
+#include "hobbit_rot.hpp"
 
 namespace hobbit {
 // The longest code: hobbit_graph_finalize, the rows-innermost encode, hobbit_parity_commit[_device] / hobbit_parity_open and the long forms of
@@ -43,13 +44,16 @@ int launch_fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_l
                     const F *tw, F scale, int do_scale, uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs);
 int launch_fft4096(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_es, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, const F *tw1,
                    const F *tw2, const F *tw3, F w8, F w8_3, int w4_plus_i, F scale, int do_scale, uint32_t groups, uint32_t rows_per_group,
-                   size_t src_gs, size_t dst_gs);
+                   size_t src_gs, size_t dst_gs, uint32_t rot_mask = 0);
 int launch_fft_combine(hobbit_ctx *ctx, int logr, const F *Y, F *dst, size_t dst_ld, const F *tw, uint32_t rows);
 int launch_elastic_leaf(hobbit_ctx *ctx, const F *t0, const F *t1, const F *t2, const F *t3, uint32_t rows2, uint32_t cols, int shift, uint8_t *state);
 int launch_elastic_inner(hobbit_ctx *ctx, const F *t0, const F *t1, const F *t2, const F *t3, uint32_t rows2, uint32_t cols, int shift, uint8_t *out);
 int launch_elastic_finish(hobbit_ctx *ctx, const uint8_t *state, uint32_t rows2, uint32_t cols, uint8_t *leaves);
 int launch_transpose(hobbit_ctx *ctx, const F *in, size_t in_gs, uint32_t rows, uint32_t cols, F *out, size_t out_gs, size_t ld_out, uint32_t groups);
-int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t ld_dst, long long n, size_t batch, int write_msg);
+// rot_mask (hobbit_rot.hpp): the message half of every column is rotated; served by the fat in-place form only (encode_reads_rotated)
+int launch_encode(hobbit_ctx *ctx, const F *src, size_t ld_src, F *dst, size_t ld_dst, long long n, size_t batch, int write_msg, uint32_t rot_mask = 0);
+// whether the in-place encode of the finalized code for n reads its message through k_enc_fat's loader, the one form that knows the rotation
+bool encode_reads_rotated(const hobbit_ctx *ctx, long long n);
 int launch_blake3_64(hobbit_ctx *ctx, const uint8_t *in, uint8_t *out, size_t n);
 int launch_hash_md(hobbit_ctx *ctx, const F *xyzw, const uint8_t *prev, uint8_t *out, size_t n);
 int launch_merkle_levels(hobbit_ctx *ctx, uint8_t *levels, size_t n, int quirk);
@@ -58,16 +62,19 @@ int launch_fft_r8(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len
 int launch_leaf_chain_relay(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, size_t g_begin, size_t g_count,
                             const uint8_t *state_in, uint8_t *state_out, uint8_t *leaves, uint32_t zero_rows_from, int leaves_inout = 0);
 // the commit's chain: starts from the zero state, so the leaves of the groups at or past zero_rows_from are written as one host-computed constant
-int launch_leaf_chain(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from);
+int launch_leaf_chain(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from,
+                      uint32_t rot_mask = 0);
 int launch_inner_digests(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, int nchunks, uint32_t cols, uint32_t half_trs, uint8_t *out);
 int launch_chain_digests(hobbit_ctx *ctx, const uint8_t *digests, size_t stride_bytes, int K, size_t m, uint8_t *leaves);
 int launch_merkle_paths(hobbit_ctx *ctx, const uint8_t *levels, size_t n, const uint64_t *d_pos, size_t nq, int depth, uint8_t *d_paths);
 int launch_eq_table(hobbit_ctx *ctx, CHP h_r, int k, F *d_out);
 int launch_aggregate(hobbit_ctx *ctx, const F *poly, size_t M, int K, CHP h_beta, F *aggr);
 int launch_gather(hobbit_ctx *ctx, const F *tensor, size_t chunk_stride, uint32_t rows2, int K, const uint32_t *d_rows, const uint32_t *d_cols,
-                  size_t nq, F *d_reply, uint32_t rows_valid);
+                  size_t nq, F *d_reply, uint32_t rows_valid, uint32_t rot_mask = 0);
 int launch_zero_rows(hobbit_ctx *ctx, F *tensor, size_t ncols, uint32_t rows2, uint32_t rows_valid);
-int launch_tensor_row(hobbit_ctx *ctx, const F *chunk, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid);
+int launch_tensor_row(hobbit_ctx *ctx, const F *chunk, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid, uint32_t rot_mask = 0);
+// a rotated message half made linear, in place: rows [0, rot_mask] of each of the ncols columns (hobbit_commitment_tensor_dev)
+int launch_unrotate_msg(hobbit_ctx *ctx, F *tensor, size_t ncols, uint32_t rows2, uint32_t rot_mask);
 int launch_eval_fold(hobbit_ctx *ctx, const F *v, F *o, size_t L, F r);
 int launch_eval_fold2(hobbit_ctx *ctx, const F *v, F *o, size_t L, F r0, F r1);
 int launch_eval_tail(hobbit_ctx *ctx, const F *v, F *o, size_t n, int levels, const F *r);
