@@ -11,6 +11,7 @@
 #include <thread>
 #include <functional>
 #include "hobbit_kernels.hpp"
+#include "hobbit_fft.hpp"
 #include "hobbit_blake3.hpp"
 #include "../../include/hobbit_whir.h"
 
@@ -68,218 +69,6 @@ static int d2h_staged(hobbit_ctx *ctx, void *h, const void *d, size_t bytes) {
     return 0;
 }
 static int ilog2_exact(size_t n) { int l = 0; while (((size_t)1 << l) < n) l++; return ((size_t)1 << l) == n ? l : -1; }
-
-static int get_twiddles(hobbit_ctx *ctx, int logn, bool inverse, const F **out) {
-    auto &m = inverse ? ctx->tw_inv : ctx->tw_fwd;
-    auto it = m.find(logn);
-    if (it != m.end()) { *out = it->second; return 0; }
-    size_t half = logn >= 1 ? ((size_t)1 << (logn - 1)) : 1;
-    std::vector<F> w(half);
-    w[0] = fmake(1);
-    if (half > 1) {   // src/utils.cpp:646-653: w[1] = rou (or its inverse), w[i] = w[i-1]*w[1]
-        F w1 = root_of_unity(logn); if (inverse) w1 = finv(w1);
-        w[1] = w1;
-        for (size_t i = 2; i < half; i++) w[i] = fmul(w[i - 1], w1);
-    }
-    mem::Buf<F> d;
-    if (d.alloc(half)) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
-    HB_CHECK(ctx, hipMemcpy(d, w.data(), half * sizeof(F), hipMemcpyHostToDevice));
-    *out = d; m[logn] = std::move(d); return 0;
-}
-
-// per-pass twiddle tables of k_fft4096 (true radix-8 DIT): the pass with octet stride h stores, for t = 1..7 and k < h,
-//   T[t-1][k] = w^(rev3(t) * k * len / (8h))     (block t of an octet holds the sub-transform of the samples = rev3(t) mod 8)
-static int get_tw8(hobbit_ctx *ctx, bool inverse) {
-    const int d = inverse ? 1 : 0;
-    if (ctx->tw8[d]) return 0;
-    const uint32_t len = 4096;
-    std::vector<F> w(len);
-    w[0] = fmake(1);
-    F w1 = root_of_unity(12); if (inverse) w1 = finv(w1);
-    for (uint32_t i = 1; i < len; i++) w[i] = fmul(w[i - 1], w1);
-    static const uint32_t rev3[8] = {0, 4, 2, 6, 1, 5, 3, 7};
-    std::vector<F> t;
-    for (uint32_t h : {8u, 64u, 512u})
-        for (uint32_t b = 1; b < 8; b++) for (uint32_t k = 0; k < h; k++) t.push_back(w[(rev3[b] * k * (len / (8 * h))) % len]);
-    mem::Buf<F> dptr;
-    if (dptr.alloc(t.size())) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
-    HB_CHECK(ctx, hipMemcpy(dptr, t.data(), t.size() * sizeof(F), hipMemcpyHostToDevice));
-    ctx->tw8[d] = std::move(dptr);
-    ctx->tw8_w8[d] = w[512]; ctx->tw8_w83[d] = w[1536];
-    const F w4 = w[1024];
-    if (w4.re != 0 || (w4.im != 1 && w4.im != P61 - 1)) return ctx->fail(HOBBIT_EINVAL, "unexpected 4th root of unity");
-    ctx->tw8_w4_plus_i[d] = w4.im == 1;
-    return 0;
-}
-// tables of k_fft_r8 for N = 2^logn = 8^P * R: per pass p = 1 .. P-1 (h = 8^p): [7][h] = w_N2^(rev3(t) k N2 / (8h)), w_N2 = w_N^R; then the tail
-// [R-1][N2] = w_N^(q k)
-static int get_tw_r8(hobbit_ctx *ctx, int logn, bool inverse, const F **out) {
-    const int key = logn + (inverse ? 64 : 0);
-    auto it = ctx->tw_r8.find(key);
-    if (it != ctx->tw_r8.end()) { *out = it->second; return 0; }
-    const uint32_t N = 1u << logn, P = (uint32_t)logn / 3, R = 1u << (logn % 3), N2 = N / R;
-    std::vector<F> w(N);
-    w[0] = fmake(1);
-    F w1 = root_of_unity(logn); if (inverse) w1 = finv(w1);
-    for (uint32_t i = 1; i < N; i++) w[i] = fmul(w[i - 1], w1);
-    static const uint32_t rev3[8] = {0, 4, 2, 6, 1, 5, 3, 7};
-    std::vector<F> t;
-    uint32_t h = 8;
-    for (uint32_t p = 1; p < P; p++, h *= 8)
-        for (uint32_t b = 1; b < 8; b++) for (uint32_t k = 0; k < h; k++) t.push_back(w[(size_t)R * ((rev3[b] * k * (N2 / (8 * h))) % N2)]);
-    for (uint32_t q = 1; q < R; q++) for (uint32_t k = 0; k < N2; k++) t.push_back(w[((size_t)q * k) % N]);
-    if (t.empty()) t.push_back(fmake(1));
-    mem::Buf<F> d;
-    if (d.alloc(t.size())) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
-    HB_CHECK(ctx, hipMemcpy(d, t.data(), t.size() * sizeof(F), hipMemcpyHostToDevice));
-    *out = d; ctx->tw_r8[key] = std::move(d);
-    return 0;
-}
-// The twiddles of a length 2^25 .. 2^28 as two small tables, w^(a 2^14 + b) = hi[a] lo[b]: [lo: 2^14 | hi: 2^(logn-14)] entries, at most
-// 512 KB together, each built by its own short chain of products (the full table would be 2^27 dependent products and a 2 GiB upload).
-static int get_tw_split(hobbit_ctx *ctx, int logn, bool inverse, const F **lo, const F **hi) {
-    const int key = logn + (inverse ? 64 : 0);
-    auto it = ctx->tw_split.find(key);
-    if (it == ctx->tw_split.end()) {
-        const size_t nlo = (size_t)1 << 14, nhi = (size_t)1 << (logn - 14);
-        std::vector<F> t(nlo + nhi);
-        F w1 = root_of_unity(logn); if (inverse) w1 = finv(w1);
-        t[0] = fmake(1);
-        for (size_t i = 1; i < nlo; i++) t[i] = fmul(t[i - 1], w1);
-        const F wh = fmul(t[nlo - 1], w1);                            // w^(2^14)
-        t[nlo] = fmake(1);
-        for (size_t i = 1; i < nhi; i++) t[nlo + i] = fmul(t[nlo + i - 1], wh);
-        mem::Buf<F> d;
-        if (d.alloc(t.size())) return ctx->fail(HOBBIT_ENOMEM, "twiddle alloc failed");
-        HB_CHECK(ctx, hipMemcpy(d, t.data(), t.size() * sizeof(F), hipMemcpyHostToDevice));
-        it = ctx->tw_split.emplace(key, std::move(d)).first;
-    }
-    *lo = it->second; *hi = it->second + ((size_t)1 << 14);
-    return 0;
-}
-// FFT dispatch: the 4096-point kernel when it applies, the generic LDS kernel otherwise
-static int fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, bool inverse,
-                    uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs);
-
-// the transform with an explicit factor on the way out (do_scale == 0: none)
-static int fft_rows_scaled(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, bool inverse,
-                           F scale, int do_scale, uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs) {
-    if (logn == 12 && (src_len == 2048 || src_len == 4096)) {
-        HB_TRY(get_tw8(ctx, inverse));
-        const int d = inverse ? 1 : 0;
-        const F *t = ctx->tw8[d];
-        return launch_fft4096(ctx, src, src_ld, 1, src_len, dst, dst_ld, dst_es, t, t + 7 * 8, t + 7 * 8 + 7 * 64, ctx->tw8_w8[d], ctx->tw8_w83[d],
-                              ctx->tw8_w4_plus_i[d], scale, do_scale, groups, rows_per_group, src_gs, dst_gs);
-    }
-    static const int r8_mode = [] { const char *e = getenv("HOBBIT_FFT_R8"); return e ? atoi(e) : 1; }();
-    if (r8_mode && !inverse && logn >= 6 && logn <= 11 && (src_len == (1u << logn) || src_len == (1u << (logn - 1)))) {
-        HB_TRY(get_tw8(ctx, false));                                  // (the direction of w_4: the same element for every length)
-        const F *tabs; HB_TRY(get_tw_r8(ctx, logn, false, &tabs));
-        return launch_fft_r8(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, logn, tabs, ctx->tw8_w4_plus_i[0], groups, rows_per_group, src_gs, dst_gs);
-    }
-    const F *tw; HB_TRY(get_twiddles(ctx, logn, inverse, &tw));
-    return launch_fft_rows(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, logn, tw, scale, do_scale, groups, rows_per_group, src_gs, dst_gs);
-}
-static int fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, bool inverse,
-                    uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs) {
-    F scale = fmake(1);
-    if (inverse) scale = finv(fmake((uint64_t)1 << logn));          // src/utils.cpp:663-671
-    return fft_rows_scaled(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, logn, inverse, scale, inverse ? 1 : 0, groups, rows_per_group, src_gs, dst_gs);
-}
-
-// Long forward/inverse transform of `batch` rows: row b of src (src_len nonzero elements, the rest of the 2^logn
-// transform length zero) -> row b of dst (2^logn elements, contiguous).  13 <= logn <= 24.  src may equal dst.
-// do_scale: every result is multiplied by `scale`, fused into the last arithmetic pass (the inverse's 1/len; a nested call of a longer
-// transform passes none).  An inverse transform takes full-length sources only.
-static int fft_long(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *dst, int logn, bool inverse, uint32_t batch, F scale, int do_scale) {
-    const size_t len = (size_t)1 << logn; const int lr = logn - 12; const uint32_t R = 1u << lr;
-    if (lr < 1 || lr > 12) return ctx->fail(HOBBIT_EINVAL, "fft_long: the two-factor form serves logn in [13,24]");
-    if (src_len != len && (inverse || src_len != len / 2)) return ctx->fail(HOBBIT_EINVAL, "fft_long: source must be the full length or, forward, its zero-padded half");
-    if ((size_t)batch * 4096 >> 32) return ctx->fail(HOBBIT_EINVAL, "fft_long: too many rows");
-    F *t1, *t2;
-    HB_TRY(ctx->workspace((size_t)batch * len * sizeof(F), (void **)&t1));
-    HB_TRY(ctx->workspace2((size_t)batch * len * sizeof(F), (void **)&t2));
-    const F *twl; HB_TRY(get_twiddles(ctx, logn, inverse, &twl));
-    HB_TRY(get_tw8(ctx, inverse));
-    const int d = inverse ? 1 : 0; const F *t8 = ctx->tw8[d];
-    if (R <= 64) {
-        // short strides: the R sub-transforms read x[R n2 + n1] in place (element stride R) -- adjacent n1 share cache lines, and the
-        // separate transpose pass costs more than it saves (measured: -0.15 ms per shockwave_prove; for R >= 128 the transpose wins)
-        HB_TRY(launch_fft4096(ctx, src, 1, R, src_len == len ? 4096u : 2048u, t1, 4096, 1, t8, t8 + 7 * 8, t8 + 7 * 8 + 7 * 64, ctx->tw8_w8[d], ctx->tw8_w83[d],
-                              ctx->tw8_w4_plus_i[d], fmake(1), 0, batch, R, src_ld, len));
-    } else {
-    // (n2, n1) -> (n1, n2); only the nonzero n2 rows are moved (x[R n2 + n1] != 0 needs n2 < src_len / R)
-    HB_TRY(launch_transpose_ld(ctx, src, src_ld, R, (uint32_t)(src_len / R), R, t1, len, 4096, batch));
-    HB_TRY(launch_fft4096(ctx, t1, 4096, 1, src_len == len ? 4096u : 2048u, t1, 4096, 1, t8, t8 + 7 * 8, t8 + 7 * 8 + 7 * 64, ctx->tw8_w8[d], ctx->tw8_w83[d],
-                          ctx->tw8_w4_plus_i[d], fmake(1), 0, batch, R, len, len));
-    }
-    // inter-stage twiddles as a 2-D table (len entries, built once per length and direction, <= 32 MB)
-    const F *tw2 = nullptr;
-    if (logn <= 21) {
-        const int key = logn + (inverse ? 64 : 0);
-        auto it = ctx->tw2d.find(key);
-        if (it == ctx->tw2d.end()) {
-            mem::Buf<F> d2;
-            if (d2.alloc(len)) return ctx->fail(HOBBIT_ENOMEM, "twiddle table alloc failed");
-            HB_TRY(launch_build_tw2d(ctx, twl, (uint32_t)(len / 2), R, d2));
-            it = ctx->tw2d.emplace(key, std::move(d2)).first;
-        }
-        tw2 = it->second;
-    }
-    if (tw2 && lr >= 2 && lr <= 8 && batch <= 65535) {
-        // one pass: twiddle on load, 16 columns x R rows per workgroup, final order on store (t1 -> dst; src was consumed above)
-        static const int r8_cols = [] { const char *e = getenv("HOBBIT_FFT_COLS_R8"); return e ? atoi(e) : 1; }();
-        if (r8_cols && lr >= 5) {
-            const F *tabs; HB_TRY(get_tw_r8(ctx, lr, inverse, &tabs));
-            return launch_fft_cols_r8(ctx, t1, len, lr, dst, tw2, tabs, ctx->tw8_w4_plus_i[d], scale, do_scale, batch);
-        }
-        const F *twr; HB_TRY(get_twiddles(ctx, lr, inverse, &twr));
-        return launch_fft_cols(ctx, t1, len, lr, dst, tw2, twr, scale, do_scale, batch);
-    }
-    HB_TRY(launch_transpose_tw(ctx, t1, len, R, t2, twl, (uint32_t)(len / 2), tw2, batch));
-    // (forward, the R-point rows run as before: radix-8 where it is built; the inverse's 1/len rides on this pass, the last with arithmetic)
-    HB_TRY(fft_rows_scaled(ctx, t2, R, R, t2, R, 1, lr, inverse, scale, do_scale, 1, (uint32_t)((size_t)batch * 4096), 0, 0));
-    HB_TRY(launch_transpose_ld(ctx, t2, len, R, 4096, R, dst, len, 4096, batch));
-    return 0;
-}
-static int fft_long(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *dst, int logn, bool inverse, uint32_t batch) {
-    return fft_long(ctx, src, src_ld, src_len, dst, logn, inverse, batch, inverse ? finv(fmake((uint64_t)1 << logn)) : fmake(1), inverse ? 1 : 0);
-}
-
-// 2^25 <= len <= 2^28 as three factors, len = 256 * S = 256 * (4096 * R'), in place on `batch` contiguous rows (one row at a time: a row alone
-// fills the chip).  x[256 m + n1] is moved to y[n1][m] (workspace5), the 256 rows of S = 2^17 .. 2^20 points are transformed by the two-factor
-// form above (one batched call, workspace / workspace2), and the 256-point last factor takes its twiddle W_len^(n1 k2) from the split tables and
-// writes X[k1 S + k2] back over the input.  Sweeps over the data: transpose, (transpose for S >= 2^19,) FFT-4096, S-columns, 256-columns = 4 or 5.
-static int fft_wide(hobbit_ctx *ctx, F *data, int logn, bool inverse, size_t batch) {
-    if (logn < 25 || logn > 28) return ctx->fail(HOBBIT_EINVAL, "fft_wide: the three-factor form serves logn in [25,28]");
-    const size_t len = (size_t)1 << logn, S = len >> 8;
-    F *y; HB_TRY(ctx->workspace5(len * sizeof(F), (void **)&y));
-    const F *lo, *hi; HB_TRY(get_tw_split(ctx, logn, inverse, &lo, &hi));
-    const F *tabs; HB_TRY(get_tw_r8(ctx, 8, inverse, &tabs));
-    HB_TRY(get_tw8(ctx, inverse));
-    const F scale = inverse ? finv(fmake((uint64_t)1 << logn)) : fmake(1);
-    for (size_t b = 0; b < batch; b++) {
-        F *x = data + b * len;
-        HB_TRY(launch_transpose_ld(ctx, x, 0, 256, (uint32_t)S, 256, y, 0, S, 1));
-        HB_TRY(fft_long(ctx, y, S, S, y, logn - 8, inverse, 256, fmake(1), 0));
-        HB_TRY(launch_fft_cols_wide(ctx, y, S, x, lo, hi, tabs, ctx->tw8_w4_plus_i[inverse ? 1 : 0], scale, inverse ? 1 : 0));
-    }
-    return 0;
-}
-// every length: rows of src_len (the full length, or forward its zero-padded half) elements, src_ld apart -> contiguous rows of dst
-static int fft_any_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *dst, int logn, bool inverse, size_t batch) {
-    const size_t len = (size_t)1 << logn;
-    if (logn <= 12) return fft_rows(ctx, src, src_ld, (uint32_t)src_len, dst, len, 1, logn, inverse, 1, (uint32_t)batch, 0, 0);
-    if (logn <= 24) return fft_long(ctx, src, src_ld, src_len, dst, logn, inverse, (uint32_t)batch);
-    if (src == dst && (src_len != len || src_ld != len)) return ctx->fail(HOBBIT_EINVAL, "fft: in place, rows of 2^25 and more must be full and contiguous");
-    if (src != dst) {
-        for (size_t b = 0; b < batch; b++) {
-            HB_TRY(launch_copy(ctx, dst + b * len, src + b * src_ld, src_len * sizeof(F)));
-            if (src_len < len) HB_TRY(launch_zero(ctx, dst + b * len + src_len, (len - src_len) * sizeof(F)));
-        }
-    }
-    return fft_wide(ctx, dst, logn, inverse, batch);
-}
 
 namespace hobbit { TranscriptRec &transcript_rec() { static thread_local TranscriptRec t; return t; } }
 
@@ -886,30 +675,6 @@ int hobbit_encode_batch(hobbit_ctx *ctx, const hobbit_F *d_src, hobbit_F *d_dst,
     return launch_encode(ctx, cF(d_src), ld_src, mF(d_dst), ld_dst, n, batch, in_place ? 0 : 1);
 }
 
-// ---- FFT --------------------------------------------------------------------------------------
-int hobbit_fft_batch(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, size_t ld, int inverse) {
-    if (logn < 0 || logn > 24) return ctx->fail(HOBBIT_EINVAL, "fft_batch: logn must be in [0,24]");
-    if (logn == 0 || batch == 0) return 0;
-    if (ld < ((size_t)1 << logn)) return ctx->fail(HOBBIT_EINVAL, "fft_batch: ld < 2^logn");
-    if (logn > 12) {
-        if (inverse) return ctx->fail(HOBBIT_EINVAL, "fft_batch: inverse transforms longer than 4096 are not built (the hot path only needs forward)");
-        if (ld != ((size_t)1 << logn)) return ctx->fail(HOBBIT_EINVAL, "fft_batch: long rows must be contiguous");
-        return fft_long(ctx, cF(d_data), ld, (size_t)1 << logn, mF(d_data), logn, false, (uint32_t)batch);
-    }
-    return fft_rows(ctx, cF(d_data), ld, 1u << logn, mF(d_data), ld, 1, logn, inverse != 0, 1, (uint32_t)batch, 0, 0);
-}
-int hobbit_fft_any(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, size_t ld, int inverse) {
-    if (logn < 1 || logn > 28) return ctx->fail(HOBBIT_EINVAL, "fft_any: logn must be in [1,28]");
-    const size_t len = (size_t)1 << logn;
-    if (!d_data) return ctx->fail(HOBBIT_EINVAL, "fft_any: null data");
-    if (batch > (((size_t)1 << 30) >> logn)) return ctx->fail(HOBBIT_EINVAL, "fft_any: batch * 2^logn must not exceed 2^30");
-    if (ld < len) return ctx->fail(HOBBIT_EINVAL, "fft_any: ld < 2^logn");
-    if (logn > 12 && ld != len) return ctx->fail(HOBBIT_EINVAL, "fft_any: rows longer than 4096 must be contiguous");
-    if (batch == 0) return 0;
-    if (logn <= 12) return fft_rows(ctx, cF(d_data), ld, (uint32_t)len, mF(d_data), ld, 1, logn, inverse != 0, 1, (uint32_t)batch, 0, 0);
-    return fft_any_rows(ctx, cF(d_data), len, len, mF(d_data), logn, inverse != 0, batch);
-}
-
 // ---- BLAKE3 / Merkle --------------------------------------------------------------------------
 int hobbit_blake3_64(hobbit_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, size_t n) { return launch_blake3_64(ctx, d_in, d_out, n); }
 int hobbit_hash_md(hobbit_ctx *ctx, const hobbit_F *d_xyzw, const uint8_t *d_prev, uint8_t *d_out, size_t n) { return launch_hash_md(ctx, cF(d_xyzw), d_prev, d_out, n); }
@@ -1021,21 +786,16 @@ static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, i
         // very long rows (test_PC option 1 at 2^27 and beyond: tensor_row_size stays 128): one chunk at a time through the long transform
         F *rm; HB_TRY(ctx->workspace3((size_t)trs * cols * sizeof(F), (void **)&rm));
         for (int i = 0; i < K; i++) {
-            HB_TRY(fft_long(ctx, d_msg + (size_t)i * M, half, half, rm, logc, false, (uint32_t)trs));
+            HB_TRY(fft::any_rows(ctx, d_msg + (size_t)i * M, half, half, rm, logc, false, (size_t)trs));
             HB_TRY(launch_transpose(ctx, rm, (size_t)trs * cols, (uint32_t)trs, (uint32_t)cols, d_out + (size_t)i * cols * rows2, cols * rows2, rows2, 1));
         }
     } else if (logc > 12) {
         // long rows (Elastic_PC opt 2: 32768): R strided FFT-4096 per row + twiddle/R-point combine, then transpose
-        const int lr = logc - 12; const uint32_t R = 1u << lr; const size_t nrows = (size_t)K * trs;
+        const size_t nrows = (size_t)K * trs;
         F *Y, *rm;
         HB_TRY(ctx->workspace(nrows * cols * sizeof(F), (void **)&Y));
         HB_TRY(ctx->workspace2(nrows * cols * sizeof(F), (void **)&rm));
-        HB_TRY(get_tw8(ctx, false));
-        const F *t8 = ctx->tw8[0];
-        HB_TRY(launch_fft4096(ctx, d_msg, 1, R, 2048, Y, 4096, 1, t8, t8 + 7 * 8, t8 + 7 * 8 + 7 * 64, ctx->tw8_w8[0], ctx->tw8_w83[0], ctx->tw8_w4_plus_i[0],
-                              fmake(1), 0, (uint32_t)nrows, R, half, cols));
-        const F *twl; HB_TRY(get_twiddles(ctx, logc, false, &twl));
-        HB_TRY(launch_fft_combine(ctx, lr, Y, rm, cols, twl, (uint32_t)nrows));
+        HB_TRY(fft::rowcode_combine(ctx, d_msg, logc, (uint32_t)nrows, Y, rm));
         HB_TRY(launch_transpose(ctx, rm, (size_t)trs * cols, (uint32_t)trs, (uint32_t)cols, d_out, cols * rows2, rows2, (uint32_t)K));
     } else
     // Large tensors: FFT to a row-major scratch (coalesced stores) + tiled transpose; small ones write the
@@ -1049,14 +809,11 @@ static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, i
             // that the 4096 stores of a row spread over the memory channels instead of meeting on one.  No row-major scratch, no transpose and no
             // side stream; the chunk groups remain because the upload of hobbit_commit_standard_host is waited for group by group.
             const int groups = pipe > 1 && K % pipe == 0 ? pipe : 1, per = K / groups;
-            HB_TRY(get_tw8(ctx, false));
-            const F *t8 = ctx->tw8[0];
             if (up) { up->groups = groups; up->group_bytes = (size_t)per * M * sizeof(F); }
             for (int g = 0; g < groups; g++) {
                 const size_t c0 = (size_t)g * per;
                 if (up) HB_TRY(up->wait(g, ctx->stream));
-                HB_TRY(launch_fft4096(ctx, d_msg + c0 * M, half, 1, 2048, d_out + c0 * cols * rows2, 1, rows2, t8, t8 + 7 * 8, t8 + 7 * 8 + 7 * 64, ctx->tw8_w8[0],
-                                      ctx->tw8_w83[0], ctx->tw8_w4_plus_i[0], fmake(1), 0, (uint32_t)per, (uint32_t)trs, M, cols * rows2, (uint32_t)trs - 1));
+                HB_TRY(fft::rowcode_4096(ctx, d_msg + c0 * M, half, d_out + c0 * cols * rows2, 1, rows2, (uint32_t)per, (uint32_t)trs, M, cols * rows2, (uint32_t)trs - 1));
                 if (up) HB_TRY(up->start(g + 1));                 // (host copy + PCIe of the next group, beside this group's kernel)
             }
             *msg_rot = (uint32_t)trs - 1;
@@ -1077,7 +834,7 @@ static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, i
             for (int g = 0; g < pipe; g++) {
                 const size_t c0 = (size_t)g * per;
                 if (up) HB_TRY(up->wait(g, mainS));
-                HB_TRY(fft_rows(ctx, d_msg + c0 * M, half, (uint32_t)half, rm + c0 * trs * cols, cols, 1, logc, false, (uint32_t)per, (uint32_t)trs, M, (size_t)trs * cols));
+                HB_TRY(fft::rows(ctx, d_msg + c0 * M, half, (uint32_t)half, rm + c0 * trs * cols, cols, 1, logc, false, (uint32_t)per, (uint32_t)trs, M, (size_t)trs * cols));
                 HB_CHECK(ctx, hipEventRecord(ctx->side_ev[g], mainS)); HB_CHECK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_ev[g], 0));
                 ctx->stream = ctx->side;
                 const int rc = launch_transpose(ctx, rm + c0 * trs * cols, (size_t)trs * cols, (uint32_t)trs, (uint32_t)cols, d_out + c0 * cols * rows2, cols * rows2, rows2, (uint32_t)per);
@@ -1089,11 +846,11 @@ static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, i
             join.done = true;
         } else {
             if (up) { up->groups = 1; up->group_bytes = (size_t)K * M * sizeof(F); HB_TRY(up->all(ctx->stream)); }
-            HB_TRY(fft_rows(ctx, d_msg, half, (uint32_t)half, rm, cols, 1, logc, false, (uint32_t)K, (uint32_t)trs, M, (size_t)trs * cols));
+            HB_TRY(fft::rows(ctx, d_msg, half, (uint32_t)half, rm, cols, 1, logc, false, (uint32_t)K, (uint32_t)trs, M, (size_t)trs * cols));
             HB_TRY(launch_transpose(ctx, rm, (size_t)trs * cols, (uint32_t)trs, (uint32_t)cols, d_out, cols * rows2, rows2, (uint32_t)K));
         }
     } else
-        HB_TRY(fft_rows(ctx, d_msg, half, (uint32_t)half, d_out, 1, rows2, logc, false, (uint32_t)K, (uint32_t)trs, M, cols * rows2));
+        HB_TRY(fft::rows(ctx, d_msg, half, (uint32_t)half, d_out, 1, rows2, logc, false, (uint32_t)K, (uint32_t)trs, M, cols * rows2));
     if (lin) {     // columns: expander code, in place on contiguous codewords (src/PC_utils.cpp:110-121)
         if (trs > 13 && ctx->code.n != trs) return ctx->fail(HOBBIT_ESTATE, "tensorcode: expander graphs for n = trs not finalized");
         if (trs <= 13 && ctx->code.n != trs) { long long l; HB_TRY(hobbit_graph_finalize(ctx, trs, &l)); }
@@ -1101,7 +858,7 @@ static int tensorcode_chunks(hobbit_ctx *ctx, const F *d_msg, size_t M, int K, i
     }
     if (logr > 12) return ctx->fail(HOBBIT_EINVAL, "tensorcode: RSxRS needs 2*trs <= 4096");
     // columns: RS (src/PC_utils.cpp:92-101)
-    return fft_rows(ctx, d_out, rows2, (uint32_t)trs, d_out, rows2, 1, logr, false, 1, (uint32_t)((size_t)K * cols), 0, 0);
+    return fft::rows(ctx, d_out, rows2, (uint32_t)trs, d_out, rows2, 1, logr, false, 1, (uint32_t)((size_t)K * cols), 0, 0);
 }
 int hobbit_tensorcode(hobbit_ctx *ctx, const hobbit_F *d_msg, size_t M, int trs, int linear_time, hobbit_F *d_out) {
     return tensorcode_chunks(ctx, cF(d_msg), M, 1, trs, linear_time, mF(d_out));
@@ -1280,7 +1037,7 @@ static int rs_rows(hobbit_ctx *ctx, const F *d_poly, size_t w, int k, F *d_enc) 
     const size_t W = 2 * w; const int lg = ilog2_exact(W);
     if (lg < 1) return ctx->fail(HOBBIT_EINVAL, "row length must be a power of two");
     if (lg > 27) return ctx->fail(HOBBIT_EINVAL, "rs_rows: encoded rows of at most 2^27 points");
-    return fft_any_rows(ctx, d_poly, w, w, d_enc, lg, false, (size_t)k);
+    return fft::any_rows(ctx, d_poly, w, w, d_enc, lg, false, (size_t)k);
 }
 int hobbit_shockwave_commit(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int k, hobbit_F *d_enc, uint8_t *d_levels) {
     if (k < 4 || k > 64 || ilog2_exact((size_t)k) < 0 || N % (size_t)k) return ctx->fail(HOBBIT_EINVAL, "shockwave_commit: k must be a power of two in [4,64] dividing N");
@@ -1322,7 +1079,7 @@ static int whir_fri_layer(hobbit_ctx *ctx, const F *d_poly, size_t cur, size_t f
     HB_TRY(launch_zero(ctx, fp, fsz * sizeof(F)));
     HB_TRY(launch_copy(ctx, fp, d_poly, cur * sizeof(F)));
     HB_TRY(hobbit_change_form(ctx, reinterpret_cast<hobbit_F *>(fp), ilog2_exact(cur)));
-    HB_TRY(fft_any_rows(ctx, fp, fsz, fsz, fp, ilog2_exact(fsz), false, 1));         // (2^25, 2^26: the first layer of hobbit_whir_prove_any)
+    HB_TRY(fft::any_rows(ctx, fp, fsz, fsz, fp, ilog2_exact(fsz), false, 1));         // (2^25, 2^26: the first layer of hobbit_whir_prove_any)
     HB_TRY(launch_transpose_ld(ctx, fp, 0, fsz / 16, 16, (uint32_t)(fsz / 16), buf, 0, 16, 1));
     HB_TRY(hobbit_mt_commit_blake(ctx, reinterpret_cast<hobbit_F *>(buf), fsz, lv));
     HB_TRY(launch_copy(ctx, d_root, lv + 32 * (2 * (fsz / 4) - 2), 32));
@@ -1756,7 +1513,7 @@ int hobbit_parity_matrix(hobbit_ctx *ctx, const hobbit_F *d_beta, size_t size_a,
 int hobbit_phi_g(hobbit_ctx *ctx, const hobbit_F *h_rx, int n, const hobbit_F *h_scale, int is_ifft, hobbit_F *d_out) {
     if (n < 1 || n > 30) return ctx->fail(HOBBIT_EINVAL, "phi_g: n must be in [1,30]");
     const size_t N = (size_t)1 << n;
-    const F *pm; HB_TRY(get_twiddles(ctx, n, is_ifft != 0, &pm));      // phi_mul[k] = rou^k, k < N/2 (all that is indexed)
+    const F *pm; HB_TRY(fft::roots(ctx, n, is_ifft != 0, &pm));      // phi_mul[k] = rou^k, k < N/2 (all that is indexed)
     F *g = mF(d_out);
     HB_TRY(launch_zero(ctx, g, N * sizeof(F)));
     const int last = is_ifft ? n : n - 1;
@@ -2045,11 +1802,10 @@ static int rs_prover_dev(hobbit_ctx *ctx, const F *d_aggr, size_t B, size_t trs,
     const int R0 = ilog2_exact(np2 * rows2);
     F *arena; HB_TRY(ctx->workspace3((2 * B + np2 * trs + 2 * np2 * rows2 + 2 * B + 4096 + 64) * sizeof(F), (void **)&arena));
     F *out1 = arena, *sel = out1 + 2 * B, *out3 = sel + np2 * trs, *bt = out3 + np2 * rows2, *b2 = bt + np2 * rows2, *stage = b2 + 2 * B;
-    if (logc <= 12) { HB_TRY(fft_rows(ctx, d_aggr, half, (uint32_t)half, out1, cols, 1, logc, false, 1, (uint32_t)trs, 0, 0)); }   // out_1 (:406-420)
-    else { HB_TRY(fft_long(ctx, d_aggr, half, half, out1, logc, false, (uint32_t)trs)); }
+    HB_TRY(fft::any_rows(ctx, d_aggr, half, half, out1, logc, false, trs));                                                   // out_1 (:406-420)
     HB_TRY(launch_zero(ctx, sel, (np2 * trs + 2 * np2 * rows2 + 2 * B) * sizeof(F)));                         // sel | out3 | bt | b2
     HB_TRY(launch_gather_cols(ctx, out1, cols, (uint32_t)trs, d_ucols, (uint32_t)nc, sel, trs));                                // selected_collumns (:422-431)
-    HB_TRY(fft_rows(ctx, sel, trs, (uint32_t)trs, out3, rows2, 1, logr, false, 1, (uint32_t)nc, 0, 0));                            // out_3 (:436-452)
+    HB_TRY(fft::rows(ctx, sel, trs, (uint32_t)trs, out3, rows2, 1, logr, false, 1, (uint32_t)nc, 0, 0));                            // out_3 (:436-452)
     std::vector<F> rq(nq);
     { F cst = fmake(0); for (size_t i = 0; i < nq; i++) { if (i % 100 == 0) cst = fmake((uint64_t)random()); rq[i] = fadd(cst, fmake((uint64_t)rand())); } }   // r = generate_randomness(I.size()) (:459)
     {   // beta (:461-470): the sorted column walk is paired with the UNSORTED query rows, duplicates accumulate
@@ -2264,8 +2020,7 @@ int hobbit_elastic_open_aggregate_push(hobbit_ctx *ctx, hobbit_elastic_open *e, 
 // rows of a B-element vector (trs rows of B/trs) RS-encoded to twice their length
 static int elastic_row_codes(hobbit_ctx *ctx, const F *d_v, size_t B, size_t trs, F *d_out) {
     const size_t half = B / trs; const int logc = ilog2_exact(2 * half);
-    if (logc <= 12) return fft_rows(ctx, d_v, half, (uint32_t)half, d_out, 2 * half, 1, logc, false, 1, (uint32_t)trs, 0, 0);
-    return fft_long(ctx, d_v, half, half, d_out, logc, false, (uint32_t)trs);
+    return fft::any_rows(ctx, d_v, half, half, d_out, logc, false, trs);
 }
 int hobbit_elastic_open_aggregate_finish(hobbit_ctx *ctx, hobbit_elastic_open *e) {
     if (e->n_aggr != e->K) return ctx->fail(HOBBIT_ESTATE, "elastic_open: aggregate pass incomplete");
@@ -2300,9 +2055,9 @@ int hobbit_elastic_open_reply_push(hobbit_ctx *ctx, hobbit_elastic_open *e, cons
         return 0;
     }
     // update_reply (:59-111): rows to twice their length, then each queried column (trs entries, zero-padded) to 2*trs, its queried row kept
-    HB_TRY(fft_rows(ctx, cF(d_chunk), half, (uint32_t)half, e->d_T, e->cols, 1, 12, false, 1, (uint32_t)e->trs, 0, 0));
+    HB_TRY(fft::rows(ctx, cF(d_chunk), half, (uint32_t)half, e->d_T, e->cols, 1, 12, false, 1, (uint32_t)e->trs, 0, 0));
     HB_TRY(launch_gather_cols(ctx, e->d_T, e->cols, (uint32_t)e->trs, e->d_ucols, nc, e->d_G, e->rows2));
-    HB_TRY(fft_rows(ctx, e->d_G, e->rows2, (uint32_t)e->trs, e->d_G, e->rows2, 1, ilog2_exact(e->rows2), false, 1, nc, 0, 0));
+    HB_TRY(fft::rows(ctx, e->d_G, e->rows2, (uint32_t)e->trs, e->d_G, e->rows2, 1, ilog2_exact(e->rows2), false, 1, nc, 0, 0));
     HB_TRY(launch_gather_strided(ctx, e->d_G, e->d_pick, (size_t)e->queries, 1, 1, 0, e->d_reply + i * (size_t)e->queries));
     e->n_reply++;
     return 0;
@@ -2926,7 +2681,7 @@ struct OpenRun {
         else HB_TRY(launch_copy(ctx, d_aggr, d_poly, M * sizeof(F)));
         // compute_tensorcode(aggr) (:277): M' = row FFTs (row-major), codeword-major copy, expander encode, parity half back to row-major C
         tr.mark("beta, arena, aggregate");
-        HB_TRY(fft_rows(ctx, d_aggr, cols / 2, (uint32_t)(cols / 2), Mp, cols, 1, logc, false, 1, (uint32_t)trs, 0, 0));
+        HB_TRY(fft::rows(ctx, d_aggr, cols / 2, (uint32_t)(cols / 2), Mp, cols, 1, logc, false, 1, (uint32_t)trs, 0, 0));
         tr.mark("row FFTs");
         HB_TRY(launch_transpose(ctx, Mp, 0, (uint32_t)trs, (uint32_t)cols, Tcm, 0, rows2, 1));
         tr.mark("transpose");

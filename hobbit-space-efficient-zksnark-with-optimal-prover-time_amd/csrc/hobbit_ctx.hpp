@@ -8,6 +8,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 #include "hobbit_field.hpp"
 #include "hobbit_mem.hpp"
@@ -162,6 +163,12 @@ struct ProfEntry { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; double ms 
 
 namespace hobbit { struct Mailbox { F vals[16]; uint32_t flag; uint32_t pad[3]; }; }
 
+namespace hobbit { namespace fft {
+struct R8Set { const F *t1 = nullptr, *t2, *t3; F w8, w8_3; int w4_plus_i; };    // k_fft4096's pass tables [7][8], [7][64], [7][512]; the direction's 8th roots
+// dev: device tables by (kind of hobbit_fft_tables.hpp, logn, inverse); r8: per direction, filled with its pass tables
+struct Tables { std::map<std::tuple<int, int, bool>, mem::Buf<F>> dev; R8Set r8[2]; };
+}}
+
 struct hobbit_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -200,15 +207,8 @@ struct hobbit_ctx {
     int prof_on = 0;
     std::map<std::string, hobbit::ProfEntry> prof;
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    // twiddles: logn -> device table of 2^(logn-1) forward (and inverse) roots
-    std::map<int, hobbit::mem::Buf<hobbit::F>> tw_fwd, tw_inv;
-    // the next three are keyed by log2(N) + 64 * (inverse ? 1 : 0)
-    std::map<int, hobbit::mem::Buf<hobbit::F>> tw2d;      // inter-stage twiddles of the long transforms, [n1][k2] = w^(n1 k2), read coalesced
-    std::map<int, hobbit::mem::Buf<hobbit::F>> tw_r8;     // tables of k_fft_r8 per log2(N): radix-8 passes, then the radix-R tail
-    std::map<int, hobbit::mem::Buf<hobbit::F>> tw_split;  // lengths 2^25 .. 2^28: [lo: w^b, b < 2^14 | hi: w^(a 2^14), a < 2^(logn-14)], w^(a 2^14 + b) = hi[a] lo[b]
-    // radix-8 per-pass tables of the FFT-4096 kernel ([7][8] | [7][64] | [7][512]), fwd / inv
-    hobbit::mem::Buf<hobbit::F> tw8[2];
-    hobbit::F tw8_w8[2], tw8_w83[2]; int tw8_w4_plus_i[2] = {0, 0};
+    // every twiddle table of the FFT module (hobbit_fft.hip), built on first use and kept until the context goes
+    hobbit::fft::Tables fft;
     // graphs
     std::map<std::pair<int, int>, hobbit::HostGraph> graphs;   // (dep, kind)
     uint64_t graph_gen = 0;                                     // bumped by every hobbit_graph_upload / hobbit_graph_reset

@@ -6,42 +6,14 @@
 // of the CU's 160 KB; longer codewords stream their outer steps through 64 KB tiles, k_enc_tiled)
 // and are bound by the v_mad_u64_u32 rate.
 #include "hobbit_kernels.hpp"
-#include <atomic>
+#include "hobbit_dev.hpp"
 #include "hobbit_blake3.hpp"
 #include <vector>
 
 namespace hobbit {
-// The dynamic-LDS limit is an attribute of the function ON ONE DEVICE: latched per device (bit = device ordinal), not per process -- a host that
-// creates contexts on several devices from one process must set it on each (torchrun's one device per process never noticed).
-static inline void set_lds_limit_once(hobbit_ctx *ctx, const void *kernel, int bytes, std::atomic<uint64_t> &done) {
-    const uint64_t bit = 1ull << (ctx->device & 63);
-    if (!(done.load(std::memory_order_relaxed) & bit)) { hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); done.fetch_or(bit); }
-}
-
 // ============================================================================================
 // small utilities
 // ============================================================================================
-__device__ __forceinline__ F ldF(const F *p) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(p);     // one global_load_dwordx4 / ds_read_b128
-    F r; r.re = (uint64_t)v.x | ((uint64_t)v.y << 32); r.im = (uint64_t)v.z | ((uint64_t)v.w << 32); return r;
-}
-__device__ __forceinline__ void stF(F *p, const F &a) {
-    uint4 v; v.x = (uint32_t)a.re; v.y = (uint32_t)(a.re >> 32); v.z = (uint32_t)a.im; v.w = (uint32_t)(a.im >> 32);
-    *reinterpret_cast<uint4 *>(p) = v;
-}
-__device__ __forceinline__ F shfl_down_F(const F &a, int d) {
-    F r;
-    r.re = __shfl_down((unsigned long long)a.re, d, 64);
-    r.im = __shfl_down((unsigned long long)a.im, d, 64);
-    return r;
-}
-// sum over the 64 lanes of a wavefront; result valid in lane 0
-__device__ __forceinline__ F wave_sum(F a) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) a = fadd(a, shfl_down_F(a, d));
-    return a;
-}
-
 __global__ void k_f_binop(int op, const F *a, const F *b, F *o, size_t n) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         F x = ldF(a + i), y = ldF(b + i);
@@ -57,13 +29,6 @@ __device__ __forceinline__ uint64_t splitmix(uint64_t seed, uint64_t idx) {
 __global__ void k_fill_splitmix(F *o, size_t n, uint64_t seed) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         stF(o + i, fmake(splitmix(seed, 2 * i + 1) % P61, splitmix(seed, 2 * i + 2) % P61));
-}
-
-static inline int grid_for(size_t n, int block, int cap = 4096) {
-    size_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > (size_t)cap) g = cap;
-    return (int)g;
 }
 
 int launch_f_binop(hobbit_ctx *ctx, int op, const F *a, const F *b, F *o, size_t n) {
@@ -86,744 +51,6 @@ int launch_u64_bias_fold(hobbit_ctx *ctx, uint64_t *w, size_t n, uint64_t bias, 
 }
 int launch_fill_splitmix(hobbit_ctx *ctx, F *o, size_t n, uint64_t seed) {
     HB_LAUNCH(ctx, "k_fill_splitmix", k_fill_splitmix, dim3(grid_for(n, 256)), dim3(256), 0, o, n, seed);
-    return 0;
-}
-
-// ============================================================================================
-// FFT: one workgroup per row, the whole row (<= 4096 x 16 B = 64 KB) in LDS.
-// Radix-2 DIT on bit-reversed input == the reference's _fft (src/utils.cpp:605-673): same DFT,
-// natural order in and out.  Two radix-2 stages are fused per barrier (radix-4 in registers).
-// The source row may be shorter than the transform (zero padding, src/PC_utils.cpp:75-84) and the
-// destination may be strided (dst_es = element stride), which is how the row FFT of the tensor
-// code writes straight into the codeword-major tensor.
-// ============================================================================================
-// Short transforms (len < 1024) are packed: a workgroup owns tpw = 1024 / len consecutive rows, so that every radix-4 stage still
-// has one butterfly per thread (a single 256-point row would keep one wave of four busy).
-// The stages themselves, on `span / len` bit-reversed rows held in LDS.  Element i of a row sits at slot i + i/8 (one pad per eight):
-// the stride-4 and stride-16 butterflies of the first two radix-4 stages then spread over all banks (a plain layout is 4-way
-// conflicted there); the row stride ldr must be >= fft_row_slots(len).
-__device__ __host__ __forceinline__ uint32_t fft_slot(uint32_t i) { return i + (i >> 3); }
-__device__ __host__ __forceinline__ uint32_t fft_row_slots(uint32_t len) { return len + (len >> 3); }
-__device__ __forceinline__ void fft_lds_stages(F *s, int logn, const F *__restrict__ tw, uint32_t span, uint32_t ldr) {
-    const uint32_t len = 1u << logn;
-    uint32_t h = 1;
-    int st = 0;
-    if (logn & 1) {   // single radix-2 stage first when the stage count is odd
-        for (uint32_t g = threadIdx.x; g < span / 2; g += blockDim.x) {
-            const uint32_t base = (g >> (logn - 1)) * ldr, i = 2 * (g & (len / 2 - 1));
-            F u = ldF(&s[base + fft_slot(i)]), v = ldF(&s[base + fft_slot(i + 1)]);   // twiddle w^0 = 1
-            stF(&s[base + fft_slot(i)], fadd(u, v)); stF(&s[base + fft_slot(i + 1)], fsub(u, v));
-        }
-        __syncthreads();
-        h = 2; st = 1;
-    }
-    for (; st < logn; st += 2, h <<= 2) {
-        const uint32_t sA = len / (2 * h), sB = len / (4 * h);   // twiddle strides of the two stages
-        for (uint32_t g = threadIdx.x; g < span / 4; g += blockDim.x) {
-            const uint32_t t = g >> (logn - 2), b = g & (len / 4 - 1);
-            const uint32_t k = b & (h - 1), j = b / h;
-            const uint32_t base = t * ldr, i0 = j * 4 * h + k;
-            const uint32_t p0 = base + fft_slot(i0), p1 = base + fft_slot(i0 + h), p2 = base + fft_slot(i0 + 2 * h), p3 = base + fft_slot(i0 + 3 * h);
-            F a0 = ldF(&s[p0]), a1 = ldF(&s[p1]), a2 = ldF(&s[p2]), a3 = ldF(&s[p3]);
-            const F wA = ldF(tw + (size_t)k * sA);
-            F t1 = fmul(a1, wA), t3 = fmul(a3, wA);
-            F b0 = fadd(a0, t1), b1 = fsub(a0, t1), b2 = fadd(a2, t3), b3 = fsub(a2, t3);
-            const F wB0 = ldF(tw + (size_t)k * sB), wB1 = ldF(tw + (size_t)(k + h) * sB);
-            F u2 = fmul(b2, wB0), u3 = fmul(b3, wB1);
-            stF(&s[p0], fadd(b0, u2)); stF(&s[p2], fsub(b0, u2));
-            stF(&s[p1], fadd(b1, u3)); stF(&s[p3], fsub(b1, u3));
-        }
-        __syncthreads();
-    }
-}
-__global__ void __launch_bounds__(256)
-k_fft_rows(const F *__restrict__ src, size_t src_ld, uint32_t src_len, F *__restrict__ dst, size_t dst_ld, size_t dst_es,
-           int logn, const F *__restrict__ tw, F scale, int do_scale, uint32_t rows_per_group, size_t src_gs, size_t dst_gs, uint32_t total_rows,
-           uint32_t tpw) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    F *s = reinterpret_cast<F *>(lds_raw);
-    const uint32_t len = 1u << logn;
-    const uint32_t row0 = blockIdx.x * tpw, nrows = min(tpw, total_rows - row0), span = nrows * len, ldr = fft_row_slots(len);
-    // row = (group, r): lets one launch cover K chunks x trs rows with per-chunk base strides
-    for (uint32_t e = threadIdx.x; e < span; e += blockDim.x) {
-        const uint32_t t = e >> logn, i = e & (len - 1), row = row0 + t;
-        const F *in = src + (size_t)(row / rows_per_group) * src_gs + (size_t)(row % rows_per_group) * src_ld;
-        F v = i < src_len ? ldF(in + i) : fmake(0);
-        stF(&s[t * ldr + fft_slot(__brev(i) >> (32 - logn))], v);
-    }
-    __syncthreads();
-    fft_lds_stages(s, logn, tw, span, ldr);
-    for (uint32_t e = threadIdx.x; e < span; e += blockDim.x) {
-        const uint32_t t = e >> logn, i = e & (len - 1), row = row0 + t;
-        F *out = dst + (size_t)(row / rows_per_group) * dst_gs + (size_t)(row % rows_per_group) * dst_ld;
-        F v = ldF(&s[t * ldr + fft_slot(i)]);
-        if (do_scale) v = fmul(v, scale);
-        stF(out + (size_t)i * dst_es, v);
-    }
-}
-// The second half of a long transform len = 4096 R in ONE pass (was: twiddle + transpose, 4096 x FFT-R, transpose).  Input
-// y[n1][k2] (R rows of 4096: the R sub-transforms), output X[k1 * 4096 + k2] = sum_n1 W_R^(n1 k1) W_len^(n1 k2) y[n1][k2].
-// A workgroup owns C = 16 adjacent k2 for all n1: loads and stores are 256-byte segments, the twiddles come from the 2-D table
-// tw2[n1][k2] with the same pattern, each of the C columns is one length-R transform in LDS (row stride odd: the column-major
-// fill and drain are bank-conflict-free).
-// SCALE: every result leaves multiplied by `scale` (the inverse transform's 1/len); the forward instantiation is the kernel as it was.
-template <bool SCALE>
-__global__ void __launch_bounds__(512)
-k_fft_cols(const F *__restrict__ y, size_t gs, int logr, F *__restrict__ out, const F *__restrict__ tw2, const F *__restrict__ twr, F scale) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    F *s = reinterpret_cast<F *>(lds_raw);
-    constexpr uint32_t C = 16;
-    const uint32_t R = 1u << logr, ldr = fft_row_slots(R) + 1, k20 = blockIdx.x * C;
-    const F *src = y + (size_t)blockIdx.y * gs;
-    F *dst = out + (size_t)blockIdx.y * gs;
-    for (uint32_t e = threadIdx.x; e < C * R; e += blockDim.x) {
-        const uint32_t n1 = e / C, t = e % C;
-        const size_t at = (size_t)n1 * 4096 + k20 + t;
-        F v = ldF(src + at);
-        if (n1) v = fmul(v, ldF(tw2 + at));                               // W_len^(n1 k2); row 0 of the table is all ones
-        stF(&s[t * ldr + fft_slot(__brev(n1) >> (32 - logr))], v);
-    }
-    __syncthreads();
-    fft_lds_stages(s, logr, twr, C * R, ldr);
-    for (uint32_t e = threadIdx.x; e < C * R; e += blockDim.x) {
-        const uint32_t k1 = e / C, t = e % C;
-        F v = ldF(&s[t * ldr + fft_slot(k1)]);
-        if (SCALE) v = fmul(v, scale);
-        stF(dst + (size_t)k1 * 4096 + k20 + t, v);
-    }
-}
-int launch_fft_cols(hobbit_ctx *ctx, const F *y, size_t gs, int logr, F *out, const F *tw2, const F *twr, F scale, int do_scale, uint32_t batch) {
-    if (logr < 2 || logr > 8) return ctx->fail(HOBBIT_EINVAL, "fft_cols: R must be in [4, 256]");
-    const size_t lds = (size_t)16 * (fft_row_slots(1u << logr) + 1) * 16;
-    static std::atomic<uint64_t> attr_set{0};
-    static std::atomic<uint64_t> attr_set_scaled{0};
-    if (do_scale) {
-        set_lds_limit_once(ctx, (const void *)k_fft_cols<true>, 16 * 289 * 16, attr_set_scaled);
-        HB_LAUNCH(ctx, "k_fft_cols", k_fft_cols<true>, dim3(4096 / 16, batch), dim3(512), lds, y, gs, logr, out, tw2, twr, scale);
-        return 0;
-    }
-    set_lds_limit_once(ctx, (const void *)k_fft_cols<false>, 16 * 289 * 16, attr_set);
-    HB_LAUNCH(ctx, "k_fft_cols", k_fft_cols<false>, dim3(4096 / 16, batch), dim3(512), lds, y, gs, logr, out, tw2, twr, scale);
-    return 0;
-}
-
-int launch_fft_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es,
-                    int logn, const F *tw, F scale, int do_scale, uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs) {
-    if (logn < 1 || logn > 12) return ctx->fail(HOBBIT_EINVAL, "fft: logn must be in [1,12] for the LDS-resident kernel");
-    static std::atomic<uint64_t> attr_set{0};
-    set_lds_limit_once(ctx, (const void *)k_fft_rows, 81920, attr_set);
-    const size_t total = (size_t)groups * rows_per_group;
-    if (total == 0) return 0;
-    if (total >> 32) return ctx->fail(HOBBIT_EINVAL, "fft: too many rows");
-    const uint32_t tpw = logn < 10 ? (1024u >> logn) : 1u;
-    const size_t lds = (size_t)16 * fft_row_slots(1u << logn) * tpw;
-    const size_t blocks = (total + tpw - 1) / tpw;
-    HB_LAUNCH(ctx, "k_fft_rows", k_fft_rows, dim3((unsigned)blocks), dim3(256), lds, src, src_ld, src_len, dst, dst_ld, dst_es, logn, tw,
-              scale, do_scale, rows_per_group, src_gs, dst_gs, (uint32_t)total, tpw);
-    return 0;
-}
-
-// --------------------------------------------------------------------------------------------
-// FFT-4096, the hot size (row RS-encode of every tensor code): 512 threads, radix-8 DIT in
-// registers, four passes, LDS padded by one slot per eight (phys(i) = i + i/8) so that the
-// stride-8 / stride-64 / stride-512 butterflies and the bit-reversed first-pass gather are all
-// bank-conflict-free; 73.7 KB of LDS -> two workgroups per CU.
-//   load     global -> LDS in natural order (coalesced, contiguous LDS writes)
-//   pass 0   butterfly b reads x[rev9(b) + 512 u]  (= DIT positions 8b+t), writes positions 8b+t.
-//            Its twiddles are the 8th roots of unity: 1, w4 = +-i (free), w8, w8^3; with the
-//            zero-padded message rows (upper half 0) the first stage has no arithmetic at all.
-//   pass 1,2 in place, twiddle tables stored per pass as [7][h] (contiguous in k)
-//   pass 3   results go straight to global memory (row-major or codeword-major/transposed)
-// Same DFT as the reference's _fft (src/utils.cpp:605-673): bit-exact by exactness of F_{p^2}.
-// --------------------------------------------------------------------------------------------
-struct Fft4kConst { F w8, w8_3; int w4_plus_i; };
-
-// Inside the transform the sums are lazy.  p = 2^61 - 1 leaves three spare bits in a 64-bit word (8p + 7 = 2^64 - 1), exactly the
-// growth of the three add/sub levels of an 8-point DFT: a + b is a plain 64-bit add, a - b is a + (B p - b) with B p the static bound of
-// b, and every output is folded once (mask / shift / add) into [0, p + 7] -- 16 folds per octet instead of 48.  Bounds: the octet's
-// first element comes from LDS in [0, p + 7], the other seven are products (canonical, < p); the first element is always the left
-// operand of its butterflies, so the +7 only rides along: level 1 <= 2p + 7, level 2 <= 4p + 7, level 3 <= 8p + 7.
-// (Same-box A/B at 2^28: 5.56 vs 6.04 ms for the zero-padded rows, 6.26 vs 6.74 ms for full rows.)
-__device__ __forceinline__ uint64_t fold61(uint64_t s) { return (s & P61) + (s >> 61); }            // any u64 -> [0, p + 7], same residue
-__device__ __forceinline__ F ffold(const F &a) { return fmake(fold61(a.re), fold61(a.im)); }
-__device__ __forceinline__ F fcanon(const F &a) {                                                    // any u64 pair -> canonical
-    const uint64_t r = fold61(a.re), i = fold61(a.im);
-    return fmake(r >= P61 ? r - P61 : r, i >= P61 ? i - P61 : i);
-}
-__device__ __forceinline__ F faddl(const F &a, const F &b) { return fmake(a.re + b.re, a.im + b.im); }
-template <int B> __device__ __forceinline__ F fsubl(const F &a, const F &b) {                       // b's components <= B p
-    return fmake(a.re + ((uint64_t)B * P61 - b.re), a.im + ((uint64_t)B * P61 - b.im));
-}
-// a * b for a lazy a (components < 2^62 - 2^10) and a canonical twiddle b.  Same Karatsuba form as fmul, with the offset that keeps
-// ac - bd non-negative doubled: C = p 2^62 >= bd, ac + C < 2^124, ad + bc < 2^124.
-#if !defined(HOBBIT_FMUL_U128)
-// (the carry-free limb product of hobbit_field.hpp takes components up to p + 7 -- what ffold leaves -- and its canonical form is what the octet's
-// bounds need for the seven right-hand operands)
-__device__ __forceinline__ F fmul_lz(const F &a, const F &b) { return fmul(a, b); }
-#else
-__device__ __forceinline__ F fmul_lz(const F &a, const F &b) {
-    const u128 ac = (u128)a.re * b.re, bd = (u128)a.im * b.im;
-    const u128 all = (u128)(a.re + a.im) * (b.re + b.im);
-    const u128 C = ((u128)P61) << 62;
-    return fmake(red124(ac + C - bd), red124(all - ac - bd));
-}
-#endif
-template <int B> __device__ __forceinline__ F fmul_w4(const F &a, int plus_i) {   // a * (+i) or a * (-i); components <= B p in and out
-    return plus_i ? fmake((uint64_t)B * P61 - a.im, a.re) : fmake(a.im, (uint64_t)B * P61 - a.re);
-}
-// a * w8, w8 = the primitive 8th root of unity of the transform direction.  sqrt(2) = 2^31 in F_p (2^62 = 2), so
-// w8 = 2^30 (1 - i) forward (w4 = -i) and 2^30 (1 + i) inverse: a rotation by 30 bits of (a.re +- a.im), no product at all.
-__device__ __forceinline__ uint64_t rot30(uint64_t x) {      // x * 2^30 mod p for any u64 x; result < 2^61 + 2^31 <= 2p
-    x = fold61(x);                                           // < 2^62: x = lo31 + hi 2^31, x 2^30 = lo31 2^30 + hi (2^61 = 1)
-    return ((x << 30) & P61) + (x >> 31);
-}
-template <int B> __device__ __forceinline__ F fmul_w8(const F &a, int plus_i) {   // components <= B p (B <= 4) in, <= 2p out
-    const uint64_t s = a.re + a.im;
-    return plus_i ? fmake(rot30(a.re + ((uint64_t)B * P61 - a.im)), rot30(s)) : fmake(rot30(s), rot30(a.im + ((uint64_t)B * P61 - a.re)));
-}
-__device__ __forceinline__ uint32_t fft_phys(uint32_t i) { return i + (i >> 3); }
-#define HB_BFLY(x, y, w) do { F v__ = fmul(y, w); y = fsub(x, v__); x = fadd(x, v__); } while (0)
-#define HB_BFLYL(B, x, y) do { F v__ = y; y = fsubl<B>(x, v__); x = faddl(x, v__); } while (0)      /* y <= B p */
-// first stage of the 8-point DIT DFT: right operands canonical
-#define HB_DFT8_HEAD(a) do { HB_BFLYL(1, a[0], a[1]); HB_BFLYL(1, a[2], a[3]); HB_BFLYL(1, a[4], a[5]); HB_BFLYL(1, a[6], a[7]); } while (0)
-// the last two stages of an 8-point DIT DFT on a[0..7] (inputs in bit-reversed order, first stage done): twiddles 1, w4, w8, w8^3.
-// In: a[0], a[1] <= 2p + 7, the rest <= 2p.  Out: <= 8p + 7 = 2^64 - 1, unfolded.
-__device__ __forceinline__ void dft8_tail(F (&a)[8], int plus_i) {
-    F t;
-    HB_BFLYL(2, a[0], a[2]);
-    t = fmul_w4<2>(a[3], plus_i); a[3] = fsubl<2>(a[1], t); a[1] = faddl(a[1], t);
-    HB_BFLYL(2, a[4], a[6]);
-    t = fmul_w4<2>(a[7], plus_i); a[7] = fsubl<2>(a[5], t); a[5] = faddl(a[5], t);
-    // left operands a[0..3] <= 4p + 7, right operands a[4..7] <= 4p
-    HB_BFLYL(4, a[0], a[4]);
-    t = fmul_w8<4>(a[5], plus_i); a[5] = fsubl<2>(a[1], t); a[1] = faddl(a[1], t);
-    t = fmul_w4<4>(a[6], plus_i); a[6] = fsubl<4>(a[2], t); a[2] = faddl(a[2], t);
-    t = fmul_w4<2>(fmul_w8<4>(a[7], plus_i), plus_i); a[7] = fsubl<2>(a[3], t); a[3] = faddl(a[3], t);
-}
-
-template <bool PADDED>
-__global__ void __launch_bounds__(512)
-k_fft4096(const F *__restrict__ src, size_t src_ld, size_t src_es, F *__restrict__ dst, size_t dst_ld, size_t dst_es, const F *__restrict__ tw1,
-          const F *__restrict__ tw2, const F *__restrict__ tw3, Fft4kConst cst, F scale, int do_scale, uint32_t rows_per_group, size_t src_gs,
-          size_t dst_gs, int line_remap, uint32_t rot_mask) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    F *s = reinterpret_cast<F *>(lds_raw);
-    // Transposed stores (dst_ld == 1): row r's element lands 16 B into the 128-byte line it shares with rows 8g .. 8g+7.  Workgroups b, b+8,
-    // b+16, ... share an XCD and its L2, so with line_remap the eight rows of a line group go to eight consecutive slots of ONE XCD, whose
-    // L2 can merge the pieces into whole lines (within every run of 64 blocks: block (xcd, j) -> row 8 xcd + j).  Placement only.
-    uint32_t bid = blockIdx.x;
-    if (line_remap) bid = (bid & ~63u) + 8 * (bid & 7u) + ((bid >> 3) & 7u);
-    const uint32_t grp = bid / rows_per_group, r = bid % rows_per_group;
-    const F *in = src + (size_t)grp * src_gs + (size_t)r * src_ld;
-    F *out = dst + (size_t)grp * dst_gs + (size_t)r * dst_ld;
-    const uint32_t tid = threadIdx.x;
-    const int plus_i = cst.w4_plus_i;
-    constexpr uint32_t NLOAD = PADDED ? 2048 : 4096;
-    F w[7];                                                         // the next pass's seven twiddles, requested one pass early (-2 %, same-box A/B)
-#pragma unroll
-    for (int t8 = 0; t8 < 7; t8++) w[t8] = ldF(tw1 + t8 * 8 + (tid & 7));          // pass 1's, in flight over the load and pass 0
-#pragma unroll
-    for (uint32_t i = 0; i < NLOAD; i += 512) stF(&s[fft_phys(i + tid)], ldF(in + (size_t)(i + tid) * src_es));
-    __syncthreads();
-    F a[8];
-    {   // ---- pass 0 (h = 1): a plain 8-point DFT
-        const uint32_t m = __brev(tid) >> 23;                       // rev9(b), b = tid
-        a[0] = ldF(&s[fft_phys(m)]); a[2] = ldF(&s[fft_phys(m + 1024)]); a[4] = ldF(&s[fft_phys(m + 512)]); a[6] = ldF(&s[fft_phys(m + 1536)]);
-        if (PADDED) { a[1] = a[0]; a[3] = a[2]; a[5] = a[4]; a[7] = a[6]; }       // (u, 0) -> (u, u)
-        else {
-            a[1] = ldF(&s[fft_phys(m + 2048)]); a[3] = ldF(&s[fft_phys(m + 3072)]); a[5] = ldF(&s[fft_phys(m + 2560)]); a[7] = ldF(&s[fft_phys(m + 3584)]);
-            HB_DFT8_HEAD(a);
-        }
-        dft8_tail(a, plus_i);
-        __syncthreads();                                            // every input has been read
-        const uint32_t o = fft_phys(8 * tid);                       // 9*tid: positions 8b..8b+7 are contiguous
-#pragma unroll
-        for (int t8 = 0; t8 < 8; t8++) stF(&s[o + t8], ffold(a[t8]));
-        __syncthreads();
-    }
-    // ---- passes 1..3: true radix-8 DIT.  Block t of the stride-h octet holds the sub-transform of the samples = rev3(t) mod 8, so
-    // X[k + m h] = sum_t W_8^{rev3(t) m} (W_{8h}^{rev3(t) k} a[t]): seven general products (tables [7][h], t = 1..7), then the same
-    // product-free 8-point DFT as pass 0 -- 7 instead of 12 products per octet.
-#pragma unroll
-    for (int pass = 1; pass <= 3; pass++) {
-        const uint32_t h = pass == 1 ? 8u : pass == 2 ? 64u : 512u;
-        const uint32_t k = tid & (h - 1), j = tid / h, i0 = j * 8 * h + k;
-#pragma unroll
-        for (int t8 = 0; t8 < 8; t8++) a[t8] = ldF(&s[fft_phys(i0 + t8 * h)]);
-#pragma unroll
-        for (int t8 = 1; t8 < 8; t8++) a[t8] = fmul_lz(a[t8], w[t8 - 1]);
-        if (pass < 3) {                                    // next pass's twiddles: in flight over this pass's sums, stores and barrier
-            const uint32_t hn = pass == 1 ? 64u : 512u;
-            const F *twn = pass == 1 ? tw2 : tw3;
-#pragma unroll
-            for (int t8 = 0; t8 < 7; t8++) w[t8] = ldF(twn + t8 * hn + (tid & (hn - 1)));
-        }
-        HB_DFT8_HEAD(a);
-        dft8_tail(a, plus_i);
-        if (pass < 3) {
-#pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) stF(&s[fft_phys(i0 + t8 * h)], ffold(a[t8]));
-            __syncthreads();
-        } else {
-#pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) {
-                F v = do_scale ? fmul_lz(ffold(a[t8]), scale) : fcanon(a[t8]);    // canonical out (a product already is)
-                const uint32_t c = i0 + t8 * h;
-                if (rot_mask)         // a commitment's rotated message half (hobbit_rot.hpp): dst_ld == 1, row r of column c at its rotated place
-                    stF(out - r + msg_rot_row(r, c, rot_mask) + (size_t)c * dst_es, v);
-                else
-                    stF(out + (size_t)c * dst_es, v);
-            }
-        }
-    }
-}
-
-int launch_fft4096(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_es, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, const F *tw1,
-                   const F *tw2, const F *tw3, F w8, F w8_3, int w4_plus_i, F scale, int do_scale, uint32_t groups, uint32_t rows_per_group,
-                   size_t src_gs, size_t dst_gs, uint32_t rot_mask) {
-    size_t blocks = (size_t)groups * rows_per_group;
-    if (blocks == 0) return 0;
-    if (rot_mask && !(src_len == 2048 && dst_ld == 1 && rot_mask == rows_per_group - 1 && (rows_per_group & rot_mask) == 0 && dst_es >= rows_per_group))
-        return ctx->fail(HOBBIT_EINVAL, "fft4096: rotated stores need transposed output and a power-of-two row count");
-    const size_t lds = (size_t)(4096 + 512) * 16;
-    Fft4kConst cst; cst.w8 = w8; cst.w8_3 = w8_3; cst.w4_plus_i = w4_plus_i;
-    if (src_len == 2048) {
-        hipFuncSetAttribute((const void *)k_fft4096<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        const int remap = (dst_ld == 1 && dst_es > 1 && rows_per_group % 64 == 0) ? 1 : 0;
-        HB_LAUNCH(ctx, "k_fft4096", k_fft4096<true>, dim3((unsigned)blocks), dim3(512), lds, src, src_ld, src_es, dst, dst_ld, dst_es, tw1, tw2, tw3, cst,
-                  scale, do_scale, rows_per_group, src_gs, dst_gs, remap, rot_mask);
-    } else {
-        hipFuncSetAttribute((const void *)k_fft4096<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        HB_LAUNCH(ctx, "k_fft4096_full", k_fft4096<false>, dim3((unsigned)blocks), dim3(512), lds, src, src_ld, src_es, dst, dst_ld, dst_es, tw1, tw2, tw3,
-                  cst, scale, do_scale, rows_per_group, src_gs, dst_gs, 0, 0u);
-    }
-    return 0;
-}
-
-// Long rows (len = R * 4096, R = 2, 4, 8; Elastic_PC opt 2 uses 32768-point row codes,
-// src/Elastic_PC.cpp:737-771) by one Cooley-Tukey split:
-//   X[4096 k1 + k2] = sum_{n1 < R} W_R^{n1 k1} * W_len^{n1 k2} * Y_{n1}[k2],   Y_{n1} = FFT_4096(x[R n2 + n1])
-// --------------------------------------------------------------------------------------------
-// The same radix-8 machinery for the shorter transforms (64 ... 2048 points): the column codes of the RS x RS tensors
-// (Elastic_PC option 1: 1024 points; Our_PC option 1 and the MLP witness: 256) ran in the generic radix-2/4 kernel at log2(N)/2 products
-// per element.  N = 8^P * R (R = 1, 2, 4): the R sub-sequences x[R i' + q] are transformed by P radix-8 passes (7/8 product per element
-// and pass, none in the first), then ONE radix-R stage combines them (1/2 resp. 3/4 product per element): 1024 points = 2.25 N products
-// instead of 5 N.  512 threads, 4096 / N rows per workgroup, the LDS layout and the lazy sums of k_fft4096.
-// tabs: [pass 1 | pass 2 | ...] each [7][h] = w_N2^(rev3(t) k N2 / (8h)), then the tail [R-1][N2] = w_N^(q k).  Forward transform only.
-// --------------------------------------------------------------------------------------------
-template <int LOGN, bool PADDED>
-__global__ void __launch_bounds__(512)
-k_fft_r8(const F *__restrict__ src, size_t src_ld, F *__restrict__ dst, size_t dst_ld, size_t dst_es, const F *__restrict__ tabs, int plus_i,
-         uint32_t rows_per_group, size_t src_gs, size_t dst_gs, uint32_t total_rows) {
-    constexpr uint32_t N = 1u << LOGN, P = LOGN / 3, R = 1u << (LOGN % 3), N2 = N / R, TPR = N / 8, ROWS = 512 / TPR, LDR = N + N / 8, OCT = N2 / 8;
-    constexpr uint32_t SRCLEN = PADDED ? N / 2 : N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    F *s = reinterpret_cast<F *>(lds_raw);
-    const uint32_t tid = threadIdx.x, row0 = blockIdx.x * ROWS;
-    // load: natural order, coalesced
-    for (uint32_t e = tid; e < ROWS * SRCLEN; e += 512) {
-        const uint32_t t = e / SRCLEN, i = e % SRCLEN, row = row0 + t;
-        if (row < total_rows) {
-            const F *in = src + (size_t)(row / rows_per_group) * src_gs + (size_t)(row % rows_per_group) * src_ld;
-            stF(&s[t * LDR + fft_phys(i)], ldF(in + i));
-        }
-    }
-    __syncthreads();
-    const uint32_t t = tid / TPR, u = tid % TPR, q = u / OCT, b = u % OCT;
-    F *sr = s + t * LDR;
-    const bool live = row0 + t < total_rows;
-    F a[8];
-    {   // ---- pass 0 (h = 1): plain 8-point DFTs; octet b of sub-sequence q gathers x[R (rev(b) + OCT rev3(j)) + q]
-        const uint32_t m = P > 1 ? (__brev(b) >> (32 - 3 * (P - 1))) : 0u;
-        if (live) {
-            a[0] = ldF(&sr[fft_phys(R * m + q)]); a[2] = ldF(&sr[fft_phys(R * (m + 2 * OCT) + q)]);
-            a[4] = ldF(&sr[fft_phys(R * (m + OCT) + q)]); a[6] = ldF(&sr[fft_phys(R * (m + 3 * OCT) + q)]);
-            if (PADDED) { a[1] = a[0]; a[3] = a[2]; a[5] = a[4]; a[7] = a[6]; }      // the upper half of the input is zero: (u, 0) -> (u, u)
-            else {
-                a[1] = ldF(&sr[fft_phys(R * (m + 4 * OCT) + q)]); a[3] = ldF(&sr[fft_phys(R * (m + 6 * OCT) + q)]);
-                a[5] = ldF(&sr[fft_phys(R * (m + 5 * OCT) + q)]); a[7] = ldF(&sr[fft_phys(R * (m + 7 * OCT) + q)]);
-                HB_DFT8_HEAD(a);
-            }
-            dft8_tail(a, plus_i);
-        }
-        __syncthreads();                                            // every input has been read
-        if (live) {
-            const uint32_t o = fft_phys(q * N2 + 8 * b);
-#pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) stF(&sr[o + t8], ffold(a[t8]));
-        }
-        __syncthreads();
-    }
-    const F *tw = tabs;
-#pragma unroll
-    for (uint32_t pass = 1; pass < P; pass++) {
-        const uint32_t h = pass == 1 ? 8u : pass == 2 ? 64u : 512u;
-        const uint32_t k = b & (h - 1), j = b / h, i0 = q * N2 + j * 8 * h + k;
-        if (live) {
-#pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) a[t8] = ldF(&sr[fft_phys(i0 + t8 * h)]);
-#pragma unroll
-            for (int t8 = 1; t8 < 8; t8++) a[t8] = fmul_lz(a[t8], ldF(tw + (t8 - 1) * h + k));
-            HB_DFT8_HEAD(a);
-            dft8_tail(a, plus_i);
-        }
-        // (an octet reads and writes the same eight slots: no barrier between its loads and stores)
-        if (live) {
-            if (R == 1 && pass == P - 1) {
-                F *out = dst + (size_t)((row0 + t) / rows_per_group) * dst_gs + (size_t)((row0 + t) % rows_per_group) * dst_ld;
-#pragma unroll
-                for (int t8 = 0; t8 < 8; t8++) stF(out + (size_t)(i0 + t8 * h) * dst_es, fcanon(a[t8]));
-            } else {
-#pragma unroll
-                for (int t8 = 0; t8 < 8; t8++) stF(&sr[fft_phys(i0 + t8 * h)], ffold(a[t8]));
-            }
-        }
-        tw += 7 * h;
-        __syncthreads();
-    }
-    if (R == 1 || !live) return;
-    F *out = dst + (size_t)((row0 + t) / rows_per_group) * dst_gs + (size_t)((row0 + t) % rows_per_group) * dst_ld;
-    if (R == 2) {               // X[k] = E[k] + w^k O[k], X[k + N/2] = E[k] - w^k O[k]
-#pragma unroll
-        for (uint32_t c = 0; c < N2 / TPR; c++) {
-            const uint32_t k = u + TPR * c;
-            const F x = ldF(&sr[fft_phys(k)]), y = fmul_lz(ldF(&sr[fft_phys(N2 + k)]), ldF(tw + k));
-            stF(out + (size_t)k * dst_es, fcanon(faddl(x, y)));
-            stF(out + (size_t)(k + N2) * dst_es, fcanon(fsubl<1>(x, y)));
-        }
-    } else {                    // X[k + m N/4] = sum_q W_4^(q m) w^(q k) S_q[k]
-#pragma unroll
-        for (uint32_t c = 0; c < N2 / TPR; c++) {
-            const uint32_t k = u + TPR * c;
-            const F y0 = ldF(&sr[fft_phys(k)]);
-            const F y1 = fmul_lz(ldF(&sr[fft_phys(N2 + k)]), ldF(tw + k));
-            const F y2 = fmul_lz(ldF(&sr[fft_phys(2 * N2 + k)]), ldF(tw + N2 + k));
-            const F y3 = fmul_lz(ldF(&sr[fft_phys(3 * N2 + k)]), ldF(tw + 2 * N2 + k));
-            const F t0 = faddl(y0, y2), t1 = fsubl<1>(y0, y2), t2 = faddl(y1, y3), t3 = fmul_w4<2>(fsubl<1>(y1, y3), plus_i);     // <= 2p + 7, 2p + 7, 2p, 2p
-            stF(out + (size_t)k * dst_es, fcanon(faddl(t0, t2)));
-            stF(out + (size_t)(k + N2) * dst_es, fcanon(faddl(t1, t3)));
-            stF(out + (size_t)(k + 2 * N2) * dst_es, fcanon(fsubl<2>(t0, t2)));
-            stF(out + (size_t)(k + 3 * N2) * dst_es, fcanon(fsubl<2>(t1, t3)));
-        }
-    }
-}
-template <int LOGN>
-static int launch_fft_r8_n(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, const F *tabs, int plus_i,
-                           uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs) {
-    constexpr uint32_t N = 1u << LOGN, ROWS = 512 / (N / 8);
-    const size_t total = (size_t)groups * rows_per_group, lds = (size_t)(4096 + 512) * 16;
-    const unsigned blocks = (unsigned)((total + ROWS - 1) / ROWS);
-    if (src_len == N / 2) {
-        hipFuncSetAttribute((const void *)k_fft_r8<LOGN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        HB_LAUNCH(ctx, "k_fft_r8", (k_fft_r8<LOGN, true>), dim3(blocks), dim3(512), lds, src, src_ld, dst, dst_ld, dst_es, tabs, plus_i, rows_per_group, src_gs, dst_gs, (uint32_t)total);
-    } else {
-        hipFuncSetAttribute((const void *)k_fft_r8<LOGN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        HB_LAUNCH(ctx, "k_fft_r8", (k_fft_r8<LOGN, false>), dim3(blocks), dim3(512), lds, src, src_ld, dst, dst_ld, dst_es, tabs, plus_i, rows_per_group, src_gs, dst_gs, (uint32_t)total);
-    }
-    return 0;
-}
-// src_len must be N or N/2 (zero-padded upper half); 6 <= logn <= 11
-int launch_fft_r8(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t src_len, F *dst, size_t dst_ld, size_t dst_es, int logn, const F *tabs, int plus_i,
-                  uint32_t groups, uint32_t rows_per_group, size_t src_gs, size_t dst_gs) {
-    if ((size_t)groups * rows_per_group == 0) return 0;
-    switch (logn) {
-        case 6: return launch_fft_r8_n<6>(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, tabs, plus_i, groups, rows_per_group, src_gs, dst_gs);
-        case 7: return launch_fft_r8_n<7>(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, tabs, plus_i, groups, rows_per_group, src_gs, dst_gs);
-        case 8: return launch_fft_r8_n<8>(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, tabs, plus_i, groups, rows_per_group, src_gs, dst_gs);
-        case 9: return launch_fft_r8_n<9>(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, tabs, plus_i, groups, rows_per_group, src_gs, dst_gs);
-        case 10: return launch_fft_r8_n<10>(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, tabs, plus_i, groups, rows_per_group, src_gs, dst_gs);
-        case 11: return launch_fft_r8_n<11>(ctx, src, src_ld, src_len, dst, dst_ld, dst_es, tabs, plus_i, groups, rows_per_group, src_gs, dst_gs);
-    }
-    return ctx->fail(HOBBIT_EINVAL, "fft_r8: logn must be in [6, 11]");
-}
-
-// The same passes for the SECOND half of a long transform (k_fft_cols's job: N-point transforms down the columns of y[n1][k2], N = len / 4096
-// = 32 ... 256, inter-stage twiddle on load, result X[k1 * 4096 + k2]).  A workgroup owns C = 4096 / N adjacent columns; the column index is
-// the fastest thread index, so global loads and stores are C * 16-byte runs and -- with an odd LDS row stride -- the butterflies of the 64 lanes
-// of a wave fall on different banks.  Products per element: 1 (twiddle) + 7/8 per radix-8 pass after the first + 1/2 or 3/4 for the tail,
-// against 1 + log2(N)/2 in the radix-2/4 stages of k_fft_cols.
-// SCALE: the result leaves multiplied by `scale` (the inverse transform's 1/len; a product is canonical, so it replaces the final fold).
-// WIDE: the last factor of a three-factor transform of 2^25 .. 2^28 points: the N rows are `rs` = len / N apart instead of 4096,
-// a workgroup still owns C adjacent columns, and the twiddle W_len^(n1 k2), n1 k2 < 2^28, is composed from two cache-resident tables:
-// tw2 = lo[b] = W^b (b < 2^14), twhi[a] = W^(a 2^14).
-template <bool SCALE> __device__ __forceinline__ F fft_cols_out(const F &a, const F &scale) { return SCALE ? fmul_lz(ffold(a), scale) : fcanon(a); }
-template <int LOGN, bool SCALE, bool WIDE>
-__global__ void __launch_bounds__(512)
-k_fft_cols_r8(const F *__restrict__ y, size_t gs, F *__restrict__ out, const F *__restrict__ tw2, const F *__restrict__ tabs, int plus_i, F scale,
-              size_t rs_wide, const F *__restrict__ twhi) {
-    const size_t rs = WIDE ? rs_wide : (size_t)4096;
-    constexpr uint32_t N = 1u << LOGN, P = LOGN / 3, T = 1u << (LOGN % 3), N2 = N / T, TPR = N / 8, C = 4096 / N, LDR = N + N / 8 + 1, OCT = N2 / 8;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    F *s = reinterpret_cast<F *>(lds_raw);
-    const uint32_t tid = threadIdx.x, k20 = blockIdx.x * C;
-    const F *src = y + (size_t)blockIdx.y * gs;
-    F *dst = out + (size_t)blockIdx.y * gs;
-    for (uint32_t e = tid; e < C * N; e += 512) {
-        const uint32_t n1 = e / C, t = e % C;
-        const size_t at = (size_t)n1 * rs + k20 + t;
-        F v = ldF(src + at);
-        if (WIDE) {
-            const uint32_t m = n1 * (k20 + t);                            // < len <= 2^28
-            if (n1) v = fmul(v, fmul(ldF(twhi + (m >> 14)), ldF(tw2 + (m & 16383u))));
-        } else if (n1) v = fmul(v, ldF(tw2 + at));                        // W_len^(n1 k2); row 0 of the table is all ones
-        stF(&s[t * LDR + fft_phys(n1)], v);
-    }
-    __syncthreads();
-    const uint32_t t = tid % C, u = tid / C, q = u / OCT, b = u % OCT;
-    F *sr = s + t * LDR;
-    F a[8];
-    {   // pass 0: plain 8-point DFTs on the T interleaved sub-sequences
-        const uint32_t m = P > 1 ? (__brev(b) >> (32 - 3 * (P - 1))) : 0u;
-        a[0] = ldF(&sr[fft_phys(T * m + q)]); a[2] = ldF(&sr[fft_phys(T * (m + 2 * OCT) + q)]);
-        a[4] = ldF(&sr[fft_phys(T * (m + OCT) + q)]); a[6] = ldF(&sr[fft_phys(T * (m + 3 * OCT) + q)]);
-        a[1] = ldF(&sr[fft_phys(T * (m + 4 * OCT) + q)]); a[3] = ldF(&sr[fft_phys(T * (m + 6 * OCT) + q)]);
-        a[5] = ldF(&sr[fft_phys(T * (m + 5 * OCT) + q)]); a[7] = ldF(&sr[fft_phys(T * (m + 7 * OCT) + q)]);
-        HB_DFT8_HEAD(a);
-        dft8_tail(a, plus_i);
-        __syncthreads();
-        if (P == 1 && T == 1) {
-#pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) stF(dst + (size_t)t8 * rs + k20 + t, fft_cols_out<SCALE>(a[t8], scale));
-            return;
-        }
-        const uint32_t o = fft_phys(q * N2 + 8 * b);
-#pragma unroll
-        for (int t8 = 0; t8 < 8; t8++) stF(&sr[o + t8], ffold(a[t8]));
-        __syncthreads();
-    }
-    const F *tw = tabs;
-#pragma unroll
-    for (uint32_t pass = 1; pass < P; pass++) {
-        const uint32_t h = pass == 1 ? 8u : 64u;
-        const uint32_t k = b & (h - 1), j = b / h, i0 = q * N2 + j * 8 * h + k;
-#pragma unroll
-        for (int t8 = 0; t8 < 8; t8++) a[t8] = ldF(&sr[fft_phys(i0 + t8 * h)]);
-#pragma unroll
-        for (int t8 = 1; t8 < 8; t8++) a[t8] = fmul_lz(a[t8], ldF(tw + (t8 - 1) * h + k));
-        HB_DFT8_HEAD(a);
-        dft8_tail(a, plus_i);
-        if (T == 1 && pass == P - 1) {
-#pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) stF(dst + (size_t)(i0 + t8 * h) * rs + k20 + t, fft_cols_out<SCALE>(a[t8], scale));
-        } else {
-#pragma unroll
-            for (int t8 = 0; t8 < 8; t8++) stF(&sr[fft_phys(i0 + t8 * h)], ffold(a[t8]));
-        }
-        tw += 7 * h;
-        __syncthreads();
-    }
-    if (T == 1) return;
-    if (T == 2) {
-#pragma unroll
-        for (uint32_t c = 0; c < N2 / TPR; c++) {
-            const uint32_t k = u + TPR * c;
-            const F x = ldF(&sr[fft_phys(k)]), yv = fmul_lz(ldF(&sr[fft_phys(N2 + k)]), ldF(tw + k));
-            stF(dst + (size_t)k * rs + k20 + t, fft_cols_out<SCALE>(faddl(x, yv), scale));
-            stF(dst + (size_t)(k + N2) * rs + k20 + t, fft_cols_out<SCALE>(fsubl<1>(x, yv), scale));
-        }
-    } else {
-#pragma unroll
-        for (uint32_t c = 0; c < N2 / TPR; c++) {
-            const uint32_t k = u + TPR * c;
-            const F y0 = ldF(&sr[fft_phys(k)]);
-            const F y1 = fmul_lz(ldF(&sr[fft_phys(N2 + k)]), ldF(tw + k));
-            const F y2 = fmul_lz(ldF(&sr[fft_phys(2 * N2 + k)]), ldF(tw + N2 + k));
-            const F y3 = fmul_lz(ldF(&sr[fft_phys(3 * N2 + k)]), ldF(tw + 2 * N2 + k));
-            const F t0 = faddl(y0, y2), t1 = fsubl<1>(y0, y2), t2 = faddl(y1, y3), t3 = fmul_w4<2>(fsubl<1>(y1, y3), plus_i);
-            stF(dst + (size_t)k * rs + k20 + t, fft_cols_out<SCALE>(faddl(t0, t2), scale));
-            stF(dst + (size_t)(k + N2) * rs + k20 + t, fft_cols_out<SCALE>(faddl(t1, t3), scale));
-            stF(dst + (size_t)(k + 2 * N2) * rs + k20 + t, fft_cols_out<SCALE>(fsubl<2>(t0, t2), scale));
-            stF(dst + (size_t)(k + 3 * N2) * rs + k20 + t, fft_cols_out<SCALE>(fsubl<2>(t1, t3), scale));
-        }
-    }
-}
-template <int LOGN, bool SCALE, bool WIDE>
-static int launch_fft_cols_r8_n(hobbit_ctx *ctx, const F *y, size_t gs, F *out, const F *tw2, const F *tabs, int plus_i, F scale, size_t rs, const F *twhi,
-                                uint32_t batch) {
-    constexpr uint32_t N = 1u << LOGN, C = 4096 / N, LDR = N + N / 8 + 1;
-    const size_t lds = (size_t)C * LDR * 16;
-    hipFuncSetAttribute((const void *)k_fft_cols_r8<LOGN, SCALE, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    HB_LAUNCH(ctx, WIDE ? "k_fft_cols_wide" : "k_fft_cols", (k_fft_cols_r8<LOGN, SCALE, WIDE>), dim3((unsigned)(rs / C), batch), dim3(512), lds, y, gs, out, tw2,
-              tabs, plus_i, scale, rs, twhi);
-    return 0;
-}
-template <bool SCALE>
-static int launch_fft_cols_r8_s(hobbit_ctx *ctx, const F *y, size_t gs, int logr, F *out, const F *tw2, const F *tabs, int plus_i, F scale, uint32_t batch) {
-    switch (logr) {
-        case 5: return launch_fft_cols_r8_n<5, SCALE, false>(ctx, y, gs, out, tw2, tabs, plus_i, scale, 4096, nullptr, batch);
-        case 6: return launch_fft_cols_r8_n<6, SCALE, false>(ctx, y, gs, out, tw2, tabs, plus_i, scale, 4096, nullptr, batch);
-        case 7: return launch_fft_cols_r8_n<7, SCALE, false>(ctx, y, gs, out, tw2, tabs, plus_i, scale, 4096, nullptr, batch);
-        case 8: return launch_fft_cols_r8_n<8, SCALE, false>(ctx, y, gs, out, tw2, tabs, plus_i, scale, 4096, nullptr, batch);
-    }
-    return ctx->fail(HOBBIT_EINVAL, "fft_cols_r8: R must be in [32, 256]");
-}
-int launch_fft_cols_r8(hobbit_ctx *ctx, const F *y, size_t gs, int logr, F *out, const F *tw2, const F *tabs, int plus_i, F scale, int do_scale,
-                       uint32_t batch) {
-    return do_scale ? launch_fft_cols_r8_s<true>(ctx, y, gs, logr, out, tw2, tabs, plus_i, scale, batch)
-                    : launch_fft_cols_r8_s<false>(ctx, y, gs, logr, out, tw2, tabs, plus_i, scale, batch);
-}
-// The 256-point last factor of a len = 256 * rs transform (2^25 <= len <= 2^28): y[n1][k2], rows rs apart -> X[k1 * rs + k2].  (A workgroup
-// reads its 16 columns whole before it writes them and shares no address with another workgroup, so out may be y.)
-int launch_fft_cols_wide(hobbit_ctx *ctx, const F *y, size_t rs, F *out, const F *twlo, const F *twhi, const F *tabs, int plus_i, F scale, int do_scale) {
-    if (rs < ((size_t)1 << 17) || rs > ((size_t)1 << 20) || (rs & (rs - 1))) return ctx->fail(HOBBIT_EINVAL, "fft_cols_wide: row stride must be 2^17 .. 2^20");
-    if (do_scale) return launch_fft_cols_r8_n<8, true, true>(ctx, y, 0, out, twlo, tabs, plus_i, scale, rs, twhi, 1);
-    return launch_fft_cols_r8_n<8, false, true>(ctx, y, 0, out, twlo, tabs, plus_i, scale, rs, twhi, 1);
-}
-
-// The R sub-transforms run in k_fft4096 (strided source); this kernel applies the twiddles and
-// the R-point DFT across n1, one lane per k2 (coalesced on both sides).  tw[m] = W_len^m, m < len/2.
-template <int LOGR>
-__global__ void __launch_bounds__(256)
-k_fft_combine(const F *__restrict__ Y, F *__restrict__ dst, size_t dst_ld, const F *__restrict__ tw, uint32_t rows) {
-    constexpr uint32_t R = 1u << LOGR, len = R * 4096, half = len / 2;
-    const size_t total = (size_t)rows * 4096;
-    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t row = (uint32_t)(g >> 12), k2 = (uint32_t)(g & 4095);
-        const F *y = Y + (size_t)row * len + k2;
-        F a[R];
-#pragma unroll
-        for (uint32_t n1 = 0; n1 < R; n1++) {
-            F v = ldF(y + (size_t)n1 * 4096);
-            if (n1) {
-                const uint32_t m = n1 * k2;                 // < len
-                F w = ldF(tw + (m & (half - 1)));
-                v = fmul(v, w);
-                if (m >= half) v = fneg(v);                  // W^(m) = -W^(m - len/2)
-            }
-            a[__brev(n1) >> (32 - LOGR)] = v;               // bit-reversed order for the in-register DIT
-        }
-#pragma unroll
-        for (uint32_t h = 1; h < R; h <<= 1)
-#pragma unroll
-            for (uint32_t b = 0; b < R / 2; b++) {
-                const uint32_t k = b & (h - 1), i0 = (b / h) * 2 * h + k;
-                F v = a[i0 + h];
-                if (k) v = fmul(v, ldF(tw + (size_t)k * (len / (2 * h))));   // W_{2h}^k = W_len^(k len/2h)
-                a[i0 + h] = fsub(a[i0], v); a[i0] = fadd(a[i0], v);
-            }
-        F *o = dst + (size_t)row * dst_ld + k2;
-#pragma unroll
-        for (uint32_t k1 = 0; k1 < R; k1++) stF(o + (size_t)k1 * 4096, a[k1]);
-    }
-}
-int launch_fft_combine(hobbit_ctx *ctx, int logr, const F *Y, F *dst, size_t dst_ld, const F *tw, uint32_t rows) {
-    size_t total = (size_t)rows * 4096;
-    if (!total) return 0;
-    dim3 g(grid_for(total, 256, 1 << 16)), b(256);
-    if (logr == 1) HB_LAUNCH(ctx, "k_fft_combine", k_fft_combine<1>, g, b, 0, Y, dst, dst_ld, tw, rows);
-    else if (logr == 2) HB_LAUNCH(ctx, "k_fft_combine", k_fft_combine<2>, g, b, 0, Y, dst, dst_ld, tw, rows);
-    else if (logr == 3) HB_LAUNCH(ctx, "k_fft_combine", k_fft_combine<3>, g, b, 0, Y, dst, dst_ld, tw, rows);
-    else return ctx->fail(HOBBIT_EINVAL, "fft_combine: row length must be 8192, 16384 or 32768");
-    return 0;
-}
-
-// Row-major (rows x cols) -> codeword-major (cols x ld_out) tiled transpose through LDS: both the
-// global reads and the global writes are 512-byte contiguous runs.  (Writing the FFT output
-// transposed directly costs a 16-byte scattered store per element: measured 22 ms vs 8 ms for the
-// 2^28 commit's row pass, hence this separate, HBM-bound pass.)
-__global__ void __launch_bounds__(256)
-k_transpose(const F *__restrict__ in, size_t in_gs, size_t in_ld, uint32_t rows, uint32_t cols, F *__restrict__ out, size_t out_gs, size_t ld_out) {
-    __shared__ F tile[32][33];
-    const F *src = in + (size_t)blockIdx.z * in_gs;
-    F *dst = out + (size_t)blockIdx.z * out_gs;
-    const uint32_t tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
-    const uint32_t c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t r = r0 + ty + 8 * i;
-        if (r < rows && c0 + tx < cols) stF(&tile[ty + 8 * i][tx], ldF(src + (size_t)r * in_ld + c0 + tx));
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t c = c0 + ty + 8 * i;
-        if (c < cols && r0 + tx < rows) stF(dst + (size_t)c * ld_out + r0 + tx, ldF(&tile[tx][ty + 8 * i]));
-    }
-}
-// Large exact multiples: 64 x 64 tiles, 1 KB contiguous on both sides instead of 512 B (measured at 2^28 on one box: 3.08 vs 3.42 ms;
-// 128 x 32 and 128 x 16 tiles, longer on the write side only, gave 3.42 and 3.47).
-template <int TR, int TC>
-__global__ void __launch_bounds__(256)
-k_transpose_big(const F *__restrict__ in, size_t in_gs, size_t in_ld, F *__restrict__ out, size_t out_gs, size_t ld_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    F *tile = reinterpret_cast<F *>(lds_raw);                              // [TR][TC + 1]
-    const F *src = in + (size_t)blockIdx.z * in_gs;
-    F *dst = out + (size_t)blockIdx.z * out_gs;
-    const uint32_t c0 = blockIdx.x * TC, r0 = blockIdx.y * TR;
-    {
-        const uint32_t tx = threadIdx.x % TC, ty = threadIdx.x / TC;
-#pragma unroll
-        for (int i = 0; i < TR; i += 256 / TC) stF(&tile[(ty + i) * (TC + 1) + tx], ldF(src + (size_t)(r0 + ty + i) * in_ld + c0 + tx));
-    }
-    __syncthreads();
-    {
-        const uint32_t tx = threadIdx.x % TR, ty = threadIdx.x / TR;
-#pragma unroll
-        for (int i = 0; i < TC; i += 256 / TR) stF(dst + (size_t)(c0 + ty + i) * ld_out + r0 + tx, ldF(&tile[tx * (TC + 1) + ty + i]));
-    }
-}
-int launch_transpose_ld(hobbit_ctx *ctx, const F *in, size_t in_gs, size_t in_ld, uint32_t rows, uint32_t cols, F *out, size_t out_gs, size_t ld_out,
-                        uint32_t groups) {
-    if (!rows || !cols || !groups) return 0;
-    if (rows % 64 == 0 && cols % 64 == 0 && (size_t)rows * cols * groups >= ((size_t)1 << 24)) {
-        const size_t lds = (size_t)64 * 65 * 16;
-        hipFuncSetAttribute((const void *)k_transpose_big<64, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        HB_LAUNCH(ctx, "k_transpose", (k_transpose_big<64, 64>), dim3(cols / 64, rows / 64, groups), dim3(256), lds, in, in_gs, in_ld, out, out_gs, ld_out);
-        return 0;
-    }
-    HB_LAUNCH(ctx, "k_transpose", k_transpose, dim3((cols + 31) / 32, (rows + 31) / 32, groups), dim3(256), 0, in, in_gs, in_ld, rows, cols, out, out_gs,
-              ld_out);
-    return 0;
-}
-int launch_transpose(hobbit_ctx *ctx, const F *in, size_t in_gs, uint32_t rows, uint32_t cols, F *out, size_t out_gs, size_t ld_out, uint32_t groups) {
-    return launch_transpose_ld(ctx, in, in_gs, cols, rows, cols, out, out_gs, ld_out, groups);
-}
-
-// Long transforms (len = 4096 * R, R up to 4096) by one Cooley-Tukey split, every pass coalesced:
-//   transpose (n2,n1)->(n1,n2) | R x FFT-4096 | twiddle W_len^(n1 k2) fused into the transpose (n1,k2)->(k2,n1)
-//   | 4096 x FFT-R | transpose (k2,k1)->(k1,k2).  This kernel is the middle one.  tw[m] = W_len^m, m < len/2.
-// tw2 != NULL: the twiddles come from a 2-D table tw2[n1 * 4096 + k2] = W_len^(n1 k2), read with the same coalesced pattern as the data
-// (the 1-D lookup tw[n1 k2 mod half] is a 16-byte load per lane from 64 different cache lines: 0.71 -> see DESIGN.md 4).
-__global__ void __launch_bounds__(256)
-k_transpose_tw(const F *__restrict__ in, size_t gs, uint32_t R, F *__restrict__ out, const F *__restrict__ tw, uint32_t half, const F *__restrict__ tw2) {
-    __shared__ F tile[32][33];
-    const F *src = in + (size_t)blockIdx.z * gs;
-    F *dst = out + (size_t)blockIdx.z * gs;
-    const uint32_t tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const uint32_t k20 = blockIdx.x * 32, n10 = blockIdx.y * 32;          // input: R rows (n1) x 4096 cols (k2)
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t n1 = n10 + ty + 8 * i, k2 = k20 + tx;
-        if (n1 < R) {
-            F v = ldF(src + (size_t)n1 * 4096 + k2);
-            const uint32_t m = n1 * k2;                                   // < len = 2*half
-            if (tw2) { if (m) v = fmul(v, ldF(tw2 + (size_t)n1 * 4096 + k2)); }
-            else if (m) { v = fmul(v, ldF(tw + (m & (half - 1)))); if (m >= half) v = fneg(v); }
-            stF(&tile[ty + 8 * i][tx], v);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint32_t k2 = k20 + ty + 8 * i, n1 = n10 + tx;
-        if (n1 < R) stF(dst + (size_t)k2 * R + n1, ldF(&tile[tx][ty + 8 * i]));
-    }
-}
-__global__ void __launch_bounds__(256)
-k_build_tw2d(const F *__restrict__ tw, uint32_t half, uint32_t R, F *__restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)R * 4096) return;
-    const uint32_t n1 = (uint32_t)(i >> 12), k2 = (uint32_t)(i & 4095), m = n1 * k2;
-    F v = ldF(tw + (m & (half - 1)));
-    if (m >= half) v = fneg(v);
-    stF(out + i, v);
-}
-int launch_build_tw2d(hobbit_ctx *ctx, const F *tw, uint32_t half, uint32_t R, F *out) {
-    HB_LAUNCH(ctx, "k_build_tw2d", k_build_tw2d, dim3((unsigned)(((size_t)R * 4096 + 255) / 256)), dim3(256), 0, tw, half, R, out);
-    return 0;
-}
-int launch_transpose_tw(hobbit_ctx *ctx, const F *in, size_t gs, uint32_t R, F *out, const F *tw, uint32_t half, const F *tw2, uint32_t groups) {
-    HB_LAUNCH(ctx, "k_transpose_tw", k_transpose_tw, dim3(4096 / 32, (R + 31) / 32, groups), dim3(256), 0, in, gs, R, out, tw, half, tw2);
     return 0;
 }
 

@@ -18,29 +18,13 @@
 #include <algorithm>
 #include <vector>
 #include "hobbit_kernels.hpp"
+#include "hobbit_dev.hpp"
 #include "hobbit_whir_acc.hpp"
 #include "../../include/hobbit_whir.h"
 
 using namespace hobbit;
 
 namespace {
-
-__device__ __forceinline__ F ldF(const F *p) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(p);
-    F r; r.re = (uint64_t)v.x | ((uint64_t)v.y << 32); r.im = (uint64_t)v.z | ((uint64_t)v.w << 32); return r;
-}
-__device__ __forceinline__ void stF(F *p, const F &a) {
-    uint4 v; v.x = (uint32_t)a.re; v.y = (uint32_t)(a.re >> 32); v.z = (uint32_t)a.im; v.w = (uint32_t)(a.im >> 32);
-    *reinterpret_cast<uint4 *>(p) = v;
-}
-__device__ __forceinline__ F wave_sum(F a) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        F o; o.re = __shfl_down((unsigned long long)a.re, d, 64); o.im = __shfl_down((unsigned long long)a.im, d, 64);
-        a = fadd(a, o);
-    }
-    return a;
-}
 
 constexpr int OOD_WG = 256, OOD_Y_GRID = 1024, OOD_BETA_GRID = 2048;
 

@@ -4,9 +4,6 @@ The row FFT keeps its butterfly sums unreduced (up to 8p + 7 = 2^64 - 1) and fol
 components up to p + 7; the expander encode keeps 96-bit sums and folds each output once.  Uniform inputs practically never reach the
 edges of those bounds: the families here do (zeros and constants give exact multiples of p, bits / small integers / ramps give sums
 B p + j, all-(p-1) under weights 2^32 - 1 gives the largest 96-bit sums).  Every assert names the family."""
-import os
-import subprocess
-import sys
 import numpy as np
 import pytest
 import adversarial as A
@@ -14,7 +11,6 @@ from adversarial import FAT_CHAIN_4096, P, encode_with_kernels, families, graphs
 from oracle.pyoracle import splitmix_field
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -91,32 +87,26 @@ def test_tensorcode_zero_padded_rows_families(hb, oracle, logc, trs):
         assert np.array_equal(hb.compute_tensorcode(msg, trs, 0), oracle.compute_tensorcode(msg, trs, 0)), (name, logc, trs)
 
 
-_KNOB_CHILD = r"""
-import sys, numpy as np
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-from __graft_entry__ import load_package
-from oracle import pyoracle
-import adversarial as A
-hb = load_package().Hobbit(0); orc = pyoracle.Oracle()
-for logn in [int(v) for v in sys.argv[2].split(",")]:
-    fams = A.families(1 << logn, seed=logn)
-    names = list(fams); x = np.stack([fams[k] for k in names])
-    y = hb.fft(x)
+# (kernel's profile name, logn, inverse): every place the two older kernels are still reached.  k_fft_rows, the generic radix-2/4 kernel: forward
+# below the radix-8 lengths, and every inverse of 6 .. 11.  k_fft_cols, the radix-2/4 column pass of the two-factor form: R = 4, 8, 16 (the
+# radix-8 column kernel shares the profile name but is built for R >= 32 only, so at these lengths the name is k_fft_cols's own).
+OLDER_KERNELS = [("k_fft_rows", logn, False) for logn in range(1, 6)] + [("k_fft_rows", logn, True) for logn in range(6, 12)] + \
+                [("k_fft_cols", logn, inv) for logn in (14, 15, 16) for inv in (False, True)]
+
+
+@pytest.mark.parametrize("kernel,logn,inv", OLDER_KERNELS)
+def test_fft_older_kernels_families(hb, oracle, kernel, logn, inv):
+    """the generic radix-2/4 rows and the radix-2/4 column pass where they still run, every family in one batch, every row against the oracle;
+    the profiler names the kernel that was launched"""
+    names, x = _stack(families(1 << logn, seed=logn))
+    hb.profile(True); hb.profile_reset()
+    y = hb.fft_any(x, inverse=inv)
+    rep = hb.profile_report()
+    hb.profile(False)
+    assert rep.get(kernel, (0, 0))[1] == 1, rep
+    assert not any(k in rep for k in ("k_fft_r8", "k_transpose_tw", "k_fft_cols_wide") + (("k_fft4096", "k_fft4096_full", "k_fft_cols") if kernel == "k_fft_rows" else ())), rep
     for r, name in enumerate(names):
-        if not np.array_equal(y[r], orc.fft(x[r])):
-            print("MISMATCH", name, logn); sys.exit(3)
-hb.close()
-print("OK")
-"""
-
-
-@pytest.mark.parametrize("knob,logns", [("HOBBIT_FFT_R8", "6,7,8,9,10,11"), ("HOBBIT_FFT_COLS_R8", "17,18,19,20")])
-def test_fft_non_default_kernels_families(knob, logns):
-    """the knobs that pick the FFT kernels are read once per process: their non-default mode (the generic radix-2/4 rows, the radix-2/4
-    column pass) runs in a fresh child process under a time limit"""
-    env = dict(os.environ); env[knob] = "0"
-    r = subprocess.run([sys.executable, "-c", _KNOB_CHILD, ROOT, logns], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), (knob, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+        assert np.array_equal(y[r], oracle.fft(x[r], inverse=inv)), (name, logn, "inverse" if inv else "forward")
 
 
 # ---- expander encode -----------------------------------------------------------------------------
