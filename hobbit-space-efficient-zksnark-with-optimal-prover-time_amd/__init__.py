@@ -81,6 +81,13 @@ BRAKINGBASE_QUERIES = 2935
 # every symbol include/hobbit_longcodes.h declares (checked by tests/test_longcodes.py)
 LONGCODES_SYMBOLS = ["hobbit_brakingbase_shape_any", "hobbit_brakingbase_commit_any", "hobbit_brakingbase_open_any"]
 
+# every symbol include/hobbit_libcgen.h declares (checked by tests/test_libc_stream_cpu.py)
+LIBCGEN_SYMBOLS = [
+    "hobbit_libc_window", "hobbit_libc_set_window", "hobbit_libc_advance", "hobbit_libc_jump", "hobbit_libc_draws_shape", "hobbit_libc_draws_dev",
+    "hobbit_libc_graph_level_dev", "hobbit_generate_randomness_dev", "hobbit_graph_draw", "hobbit_graph_level_host",
+]
+HOBBIT_ESTATE = -5
+
 # every symbol include/hobbit_orion.h declares (checked by tests/test_orion.py)
 ORION_SYMBOLS = [
     "hobbit_encode_interleaved_ld", "hobbit_encode_interleaved_ld_order", "hobbit_orion_gather", "hobbit_orion_grid_paths", "hobbit_orion_shape",
@@ -194,7 +201,13 @@ def load_library(path=LIB_PATH):
         "hobbit_orion_gather": [V, V, S, S, V, S, V], "hobbit_orion_grid_paths": [V, V, S, S, V, V, S, V], "hobbit_orion_shape": [S, V, V],
         "hobbit_orion_commit": [V, V, S, V], "hobbit_orion_free": [V], "hobbit_orion_dims": [V, V, V, V, V], "hobbit_orion_tensor_dev": [V],
         "hobbit_orion_levels_dev": [V], "hobbit_orion_root": [V, V, V], "hobbit_orion_open": [V, V, V, I, V], "hobbit_orion_proof_size": [V, V, S, V],
+        # include/hobbit_libcgen.h
+        "hobbit_libc_window": [V], "hobbit_libc_set_window": [V], "hobbit_libc_advance": [U64], "hobbit_libc_jump": [V, U64, V], "hobbit_libc_draws_shape": [V, V],
+        "hobbit_libc_draws_dev": [V, V, U64, S, V], "hobbit_libc_graph_level_dev": [V, V, U64, L, L, I, V, V], "hobbit_generate_randomness_dev": [V, S, V],
+        "hobbit_graph_draw": [V, L, V], "hobbit_graph_level_host": [V, I, I, V, V, V, V, V],
     }
+    lib.hobbit_libc_jump.restype = None
+    lib.hobbit_libc_draws_shape.restype = None
     lib.hobbit_orion_free.restype = None
     lib.hobbit_orion_tensor_dev.restype = c_vp
     lib.hobbit_orion_levels_dev.restype = c_vp
@@ -560,6 +573,57 @@ class Hobbit:
         out = np.zeros((n, 2), np.uint64)
         self.lib.hobbit_generate_randomness(c_sz(n), _hp(out))
         return out
+
+    # ---- the libc stream on the device (include/hobbit_libcgen.h)
+    def _chk_libc(self, rc, what):
+        if rc != 0:
+            raise HobbitError("rc=%d: %s: the process generator is not glibc's TYPE_3" % (rc, what))
+
+    def libc_window(self):
+        """the process generator as 31 words in sequence order, undisturbed"""
+        w = np.zeros(31, np.uint32)
+        self._chk_libc(self.lib.hobbit_libc_window(_hp(w)), "libc_window")
+        return w
+
+    def libc_set_window(self, w):
+        w = np.ascontiguousarray(w, np.uint32); assert w.shape == (31,)
+        self._chk_libc(self.lib.hobbit_libc_set_window(_hp(w)), "libc_set_window")
+
+    def libc_advance(self, k):
+        """move the process generator k draws ahead without drawing"""
+        self._chk_libc(self.lib.hobbit_libc_advance(ctypes.c_uint64(k)), "libc_advance")
+
+    def libc_draws_shape(self):
+        """(run length of one lane, span of one workgroup) of the raw-draw kernel"""
+        run, span = c_sz(), c_sz()
+        self.lib.hobbit_libc_draws_shape(ctypes.byref(run), ctypes.byref(span))
+        return run.value, span.value
+
+    def libc_draws_dev(self, w, first, n):
+        """draws first .. first + n - 1 of window w as a device buffer of n uint32"""
+        w = np.ascontiguousarray(w, np.uint32); assert w.shape == (31,)
+        b = self.alloc(4 * n)
+        self._chk(self.lib.hobbit_libc_draws_dev(self.ctx, _hp(w), ctypes.c_uint64(first), c_sz(n), c_vp(b.ptr)))
+        return b
+
+    def libc_graph_level_dev(self, w, first, L, R, degree):
+        """one expander level drawn from draw `first` of window w: device buffers (neighbours int64[L * degree], weights F[L * degree])"""
+        w = np.ascontiguousarray(w, np.uint32); assert w.shape == (31,)
+        dn, dw = self.alloc(8 * L * degree), self.alloc(16 * L * degree)
+        self._chk(self.lib.hobbit_libc_graph_level_dev(self.ctx, _hp(w), ctypes.c_uint64(first), c_ll(L), c_ll(R), c_int(degree), c_vp(dn.ptr), c_vp(dw.ptr)))
+        return dn, dw
+
+    def generate_randomness_dev(self, n):
+        """generate_randomness(n) drawn on the device, as a device buffer of n F; the process generator moves as the host loop moves it"""
+        b = self.alloc(16 * n)
+        self._chk(self.lib.hobbit_generate_randomness_dev(self.ctx, c_sz(n), c_vp(b.ptr)))
+        return b
+
+    def graph_draw(self, n):
+        """expander_init_store(n) with the levels drawn on the device; returns the codeword length"""
+        ln = c_ll()
+        self._chk(self.lib.hobbit_graph_draw(self.ctx, c_ll(n), ctypes.byref(ln)))
+        return ln.value
 
     def _draw(self, L, R, d):
         nbr = np.zeros(L * d, np.int64); w = np.zeros((L * d, 2), np.uint64)

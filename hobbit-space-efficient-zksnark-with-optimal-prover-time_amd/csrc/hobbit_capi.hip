@@ -13,6 +13,7 @@
 #include "hobbit_kernels.hpp"
 #include "hobbit_fft.hpp"
 #include "hobbit_blake3.hpp"
+#include "hobbit_libcgen.hpp"
 #include "../../include/hobbit_whir.h"
 
 using namespace hobbit;
@@ -76,19 +77,11 @@ extern "C" {
 
 const char *hobbit_version(void) { return "hobbit-hip 0.1 (gfx950)"; }
 
-// The reference's transcript is a function of the process-wide libc generator (rand()/random(), never seeded: SURVEY.md 0.8).
-// Initialising the HIP runtime draws from that same generator (measured: srandom(1); <first HIP call>; rand() no longer returns
-// 1804289383), so everything that can trigger runtime initialisation -- device query, stream creation, the first allocation, the
-// first kernel launch (code-object load) -- runs here on a private generator state and the caller's stream is put back untouched.
-struct LibcRngGuard {
-    char tmp[256]; char *prev;
-    LibcRngGuard() { prev = initstate(0x9e3779b9u, tmp, sizeof tmp); }
-    ~LibcRngGuard() { if (prev) setstate(prev); }
-};
+// context creation runs under a parked libc generator: libcgen::Guard (hobbit_libcgen.hpp) says why
 int hobbit_ctx_create_on_stream(int device, void *hip_stream, hobbit_ctx **out) {
     if (!out) return HOBBIT_EINVAL;
     *out = nullptr;
-    LibcRngGuard rng_guard;
+    libcgen::Guard rng_guard;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return HOBBIT_ENODEV;   // no CPU fallback, by design
     if (device < 0 || device >= ndev) return HOBBIT_ENODEV;

@@ -209,6 +209,8 @@ struct hobbit_ctx {
     hipEvent_t t0 = nullptr, t1 = nullptr;
     // every twiddle table of the FFT module (hobbit_fft.hip), built on first use and kept until the context goes
     hobbit::fft::Tables fft;
+    // the jump tables of the libc-stream kernels (hobbit_libcgen.hip), built on first use
+    hobbit::mem::Buf<uint32_t> libcgen_tab;
     // graphs
     std::map<std::pair<int, int>, hobbit::HostGraph> graphs;   // (dep, kind)
     uint64_t graph_gen = 0;                                     // bumped by every hobbit_graph_upload / hobbit_graph_reset

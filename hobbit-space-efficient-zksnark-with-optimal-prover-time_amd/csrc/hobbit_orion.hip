@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <vector>
 #include "hobbit_kernels.hpp"
+#include "hobbit_libcgen.hpp"
 #include "../../include/hobbit_orion.h"
 #include "../../include/hobbit_parity_lists.h"
 #include "hobbit_ps.hpp"
@@ -19,12 +20,8 @@ static inline hobbit_F *aF(F *p) { return reinterpret_cast<hobbit_F *>(p); }
 
 namespace {
 
-// the libc generator is part of the transcript; loading this file's code object (its first launch) must not draw from it (see hobbit_ctx_create)
-struct LibcRngGuard {
-    char tmp[256]; char *prev;
-    LibcRngGuard() { prev = initstate(0x9e3779b9u, tmp, sizeof tmp); }
-    ~LibcRngGuard() { if (prev) setstate(prev); }
-};
+// the libc generator is part of the transcript; loading this file's code object (its first launch) must not draw from it (libcgen::Guard)
+using LibcRngGuard = libcgen::Guard;
 
 // arr[q][c] = T[c][I[q]]: a workgroup moves a tile of GT columns c x GT queries q.  It reads with q fastest -- the 16-byte entries of one row
 // of T at the queried positions, a gather by nature: the positions are random -- and writes with c fastest, 512 contiguous bytes per half

@@ -10,6 +10,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include "hobbit_kernels.hpp"
+#include "hobbit_libcgen.hpp"
 #include "../../include/hobbit_parity.h"
 #include "../../include/hobbit_parity_lists.h"
 
@@ -190,12 +191,8 @@ __global__ void __launch_bounds__(PB) k_parity_cnt1(const uint32_t *__restrict__
     for (size_t j = blockIdx.x * (size_t)PB + threadIdx.x; j < m; j += (size_t)gridDim.x * PB) cnt1[spos[j]] = (uint32_t)j - start[skeys[j]] + 1;
 }
 
-// the libc generator is part of the transcript; loading this file's code object (its first launch) must not draw from it (see hobbit_ctx_create)
-struct LibcRngGuard {
-    char tmp[256]; char *prev;
-    LibcRngGuard() { prev = initstate(0x9e3779b9u, tmp, sizeof tmp); }
-    ~LibcRngGuard() { if (prev) setstate(prev); }
-};
+// the libc generator is part of the transcript; loading this file's code object (its first launch) must not draw from it (libcgen::Guard)
+using LibcRngGuard = libcgen::Guard;
 
 int ilog2x(size_t n) { int l = 0; while (((size_t)1 << l) < n) l++; return ((size_t)1 << l) == n ? l : -1; }
 

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <iostream>
 #include <set>
+#include <thread>
 
 int tensor_row_size = 128;        /* src/main.cpp:31 */
 size_t BUFFER_SPACE = 0;          /* src/main.cpp:38 */
@@ -113,7 +114,30 @@ void init_hash() {}                                                 // constants
 F mimc_hash(F input, F k) { F r; hobbit_mimc(hF(&input), hF(&k), hF(&r)); return r; }
 
 // ---- utils ----------------------------------------------------------------------------------------
+// The libc stream on the device (include/hobbit_libcgen.h): generate_randomness and expander_init_store draw there from these sizes on, with the
+// values and the generator position of the loops below.  HOBBIT_HOST_LIBC_DEVICE=0 keeps the loops at every size (A/B); so does a process
+// generator that is not glibc's TYPE_3.  The sizes: DESIGN.md section 4 "The libc stream on the device".
+static const int k_randomness_dev_min = 1 << 12;
+static const long long k_graphs_dev_min = 1 << 10;
+static int g_libc_force = -1;                                       // hobbit_host_time_libc_stream: 0 / 1 = the loops / the device at any size
+struct LibcForce { explicit LibcForce(int v) { g_libc_force = v; } ~LibcForce() { g_libc_force = -1; } };    // (scoped: no way out leaves it set)
+// calls served by the device path so far: [0] generate_randomness, [1] expander_init_store (hobbit_host_libc_stream_counts; tests)
+static long long g_libc_dev_calls[2] = {0, 0};
+static bool libc_device(bool from_size_on) {
+    if (g_libc_force >= 0 ? !g_libc_force : !from_size_on) return false;
+    const char *e = getenv("HOBBIT_HOST_LIBC_DEVICE");                // (read at every call: a test switches it inside one process)
+    uint32_t w[31];
+    return (g_libc_force > 0 || !(e && !strcmp(e, "0"))) && hobbit_libc_window(w) == 0;
+}
 vector<F> generate_randomness(int size) {                           // src/utils.cpp:873-883 (host, libc)
+    if (libc_device(size >= k_randomness_dev_min)) {
+        vector<F> x((size_t)size);
+        DevBuf d((size_t)size * sizeof(F));
+        HCHK(hobbit_generate_randomness_dev(g_ctx, (size_t)size, (hobbit_F *)d.p));
+        g_libc_dev_calls[0]++;
+        d.to_host(x.data(), (size_t)size * sizeof(F));
+        return x;
+    }
     vector<F> x; x.reserve(size);
     F c;
     for (int i = 0; i < size; i++) { if (i % 100 == 0) c = F(random()); x.push_back(c + F(rand())); }
@@ -190,7 +214,38 @@ void hobbit_host_upload_graphs(long long n) {
     HCHK(hobbit_graph_finalize(g_ctx, n, &len));
     if (len != total) { printf("Error in hobbit_host_upload_graphs\n"); exit(-1); }
 }
+// _C[dep] / D[dep] from one level of the context's graph store, as generate_random_expander_store leaves them: neighbor / weight by left node,
+// r_neighbor / r_weight by target in edge order.  Threads split the left nodes, then the targets (each scans every edge for its own range).
+static void graph_from_store(int dep, int kind, graph &ret) {
+    long long L = 0, R = 0; int d = 0; const long long *nbr = nullptr; const hobbit_F *w = nullptr;
+    HCHK(hobbit_graph_level_host(g_ctx, dep, kind, &L, &R, &d, &nbr, &w));
+    ret = graph(); ret.degree = d; ret.L = L; ret.R = R;
+    ret.neighbor.resize(L); ret.weight.resize(L); ret.r_neighbor.resize(R); ret.r_weight.resize(R);
+    const F *wf = reinterpret_cast<const F *>(w);
+    const int T = L * d >= (1 << 16) ? 8 : 1;
+    auto part = [&](int t) {
+        for (long long i = L * t / T; i < L * (t + 1) / T; i++) { ret.neighbor[i].assign(nbr + i * d, nbr + (i + 1) * d); ret.weight[i].assign(wf + i * d, wf + (i + 1) * d); }
+        const long long lo = R * t / T, hi = R * (t + 1) / T;
+        vector<uint32_t> cnt((size_t)(hi - lo), 0);
+        for (long long e = 0; e < L * d; e++) if (nbr[e] >= lo && nbr[e] < hi) cnt[nbr[e] - lo]++;
+        for (long long r = lo; r < hi; r++) { ret.r_neighbor[r].reserve(cnt[r - lo]); ret.r_weight[r].reserve(cnt[r - lo]); }
+        for (long long e = 0; e < L * d; e++) if (nbr[e] >= lo && nbr[e] < hi) { ret.r_neighbor[nbr[e]].push_back(e / d); ret.r_weight[nbr[e]].push_back(wf[e]); }
+    };
+    if (T == 1) { part(0); return; }
+    std::thread th[8];
+    for (int t = 0; t < T; t++) th[t] = std::thread(part, t);
+    for (int t = 0; t < T; t++) th[t].join();
+}
+static long long expander_device(long long n) {
+    long long len = 0;
+    HCHK(hobbit_graph_draw(hobbit_host_ctx(), n, &len));
+    g_libc_dev_calls[1]++;
+    int dep = 0;
+    for (long long m = n; m > k_distance_threshold; m = (long long)(k_alpha * m), dep++) { graph_from_store(dep, 0, _C[dep]); graph_from_store(dep, 1, D[dep]); }
+    return len;
+}
 long long expander_init_store(long long n, int dep) {
+    if (dep == 0 && libc_device(n >= k_graphs_dev_min)) return expander_device(n);
     if (dep == 0) HCHK(hobbit_graph_reset(hobbit_host_ctx()));
     long long total = expander_rec(n, dep);
     if (dep == 0) { long long len = 0; HCHK(hobbit_graph_finalize(g_ctx, n, &len)); if (len != total) { printf("Error in expander_init_store\n"); exit(-1); } }
@@ -1783,6 +1838,43 @@ int hobbit_host_test_pc_root(size_t N, int K, uint8_t *root_out) {
     commit_standard(poly, comm, MT, T, K);
     memcpy(root_out, MT.back()[0].arr, 32);
     return (int)MT.size();
+}
+// generate_randomness(N), expander_init_store(trs) and commit_standard from srandom(seed): the polynomial, the root, the libc draw that follows and a
+// digest of everything _C / D hold for the code -- the same with the device draws of the libc stream on and off (HOBBIT_HOST_LIBC_DEVICE)
+void hobbit_host_libc_stream_sizes(int *randomness_min, long long *graphs_min) { *randomness_min = k_randomness_dev_min; *graphs_min = k_graphs_dev_min; }
+void hobbit_host_libc_stream_counts(long long *randomness_dev_calls, long long *graphs_dev_calls) { *randomness_dev_calls = g_libc_dev_calls[0]; *graphs_dev_calls = g_libc_dev_calls[1]; }
+int hobbit_host_libc_stream(size_t N, int K, int trs, unsigned seed, uint64_t *poly_out, uint8_t *root_out, long *next_draw, uint64_t *graphs_digest) {
+    srandom(seed);
+    vector<F> poly = generate_randomness((int)N);
+    linear_time = true; tensor_row_size = trs;
+    expander_init_store(tensor_row_size);
+    *next_draw = random();
+    uint64_t h = 1469598103934665603ULL;
+    auto mix = [&](uint64_t v) { h = (h ^ v) * 1099511628211ULL; };
+    int dep = 0;
+    for (long long m = trs; m > k_distance_threshold; m = (long long)(k_alpha * m), dep++)
+        for (const graph *g : {&_C[dep], &D[dep]}) {
+            mix(g->L); mix(g->R); mix(g->degree); mix(g->neighbor.size()); mix(g->r_neighbor.size());
+            for (size_t i = 0; i < g->neighbor.size(); i++) { mix(g->neighbor[i].size()); for (size_t j = 0; j < g->neighbor[i].size(); j++) { mix(g->neighbor[i][j]); mix(g->weight[i][j].real); mix(g->weight[i][j].img); } }
+            for (size_t i = 0; i < g->r_neighbor.size(); i++) { mix(g->r_neighbor[i].size()); for (size_t j = 0; j < g->r_neighbor[i].size(); j++) { mix(g->r_neighbor[i][j]); mix(g->r_weight[i][j].real); mix(g->r_weight[i][j].img); } }
+        }
+    *graphs_digest = h;
+    memcpy(poly_out, poly.data(), N * sizeof(F));
+    _hash comm; vector<vector<_hash>> MT; vector<vector<vector<F>>> T;
+    commit_standard(poly, comm, MT, T, K);
+    memcpy(root_out, MT.back()[0].arr, 32);
+    return (int)MT.size();
+}
+// wall seconds of generate_randomness(n) (what = 0) or expander_init_store(n) (what = 1) from srandom(1), by the loops (device = 0) or the device
+// (device = 1) whatever the size: the measurement behind the two switch-over sizes (scripts/bench_libc_stream.py)
+double hobbit_host_time_libc_stream(int what, long long n, int device) {
+    hobbit_host_ctx();
+    srandom(1);
+    LibcForce force(device ? 1 : 0);
+    const double t0 = now_s();
+    if (what == 0) { vector<F> x = generate_randomness((int)n); if (x.size() != (size_t)n) exit(-1); }
+    else expander_init_store(n);
+    return now_s() - t0;
 }
 // hobbit_host_upload_graphs: wipe the device's graphs, re-upload them from _C / D, commit again -- the root must not change
 int hobbit_host_graph_reupload_check(size_t N, int K) {

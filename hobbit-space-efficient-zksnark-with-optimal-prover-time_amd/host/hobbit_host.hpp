@@ -19,6 +19,7 @@
 #include "hobbit_brakingbase.h"
 #include "hobbit_longcodes.h"
 #include "hobbit_orion.h"
+#include "hobbit_libcgen.h"
 
 using std::vector;
 
