@@ -88,6 +88,13 @@ LIBCGEN_SYMBOLS = [
 ]
 HOBBIT_ESTATE = -5
 
+# every symbol include/hobbit_real.h declares (checked by tests/test_real_symmetry_cpu.py)
+REAL_SYMBOLS = [
+    "hobbit_widen_real", "hobbit_fft_real_rows", "hobbit_commit_standard_real", "hobbit_commit_standard_real_host", "hobbit_commitment_is_half",
+    "hobbit_aggregate_real", "hobbit_open_standard_real", "hobbit_generate_randomness_real_dev",
+]
+HOBBIT_EINVAL = -2
+
 # every symbol include/hobbit_orion.h declares (checked by tests/test_orion.py)
 ORION_SYMBOLS = [
     "hobbit_encode_interleaved_ld", "hobbit_encode_interleaved_ld_order", "hobbit_orion_gather", "hobbit_orion_grid_paths", "hobbit_orion_shape",
@@ -205,6 +212,10 @@ def load_library(path=LIB_PATH):
         "hobbit_libc_window": [V], "hobbit_libc_set_window": [V], "hobbit_libc_advance": [U64], "hobbit_libc_jump": [V, U64, V], "hobbit_libc_draws_shape": [V, V],
         "hobbit_libc_draws_dev": [V, V, U64, S, V], "hobbit_libc_graph_level_dev": [V, V, U64, L, L, I, V, V], "hobbit_generate_randomness_dev": [V, S, V],
         "hobbit_graph_draw": [V, L, V], "hobbit_graph_level_host": [V, I, I, V, V, V, V, V],
+        # include/hobbit_real.h
+        "hobbit_widen_real": [V, V, V, S], "hobbit_fft_real_rows": [V, V, S, V], "hobbit_commit_standard_real": [V, V, S, I, I, I, V],
+        "hobbit_commit_standard_real_host": [V, V, V, S, I, I, I, V], "hobbit_commitment_is_half": [V], "hobbit_aggregate_real": [V, V, S, V, I, V],
+        "hobbit_open_standard_real": [V, V, S, V, V, I, V], "hobbit_generate_randomness_real_dev": [V, S, V],
     }
     lib.hobbit_libc_jump.restype = None
     lib.hobbit_libc_draws_shape.restype = None
@@ -287,6 +298,17 @@ class Commitment:
         out = np.zeros((len(rows), self.K, 2), np.uint64)
         self.hb._chk(self.hb.lib.hobbit_commitment_gather(self.hb.ctx, self.h, _hp(rows), _hp(cols), c_sz(len(rows)), _hp(out)))
         return out
+
+    def is_half(self):
+        """made by commit_standard_real: columns 0 .. cols/2 of every chunk in memory (include/hobbit_real.h)"""
+        return bool(self.hb.lib.hobbit_commitment_is_half(self.h))
+
+    def tensor_dev(self):
+        """the raw device pointer to the full linear tensor [K][cols][2 trs] (a half commitment materialises it once)"""
+        p = self.hb.lib.hobbit_commitment_tensor_dev(self.h)
+        if not p:
+            raise HobbitError("commitment_tensor_dev: %s" % self.hb.lib.hobbit_last_error(self.hb.ctx).decode())
+        return p
 
     def open_tree_blake(self, col, row):
         depth = self.M.bit_length() - 1
@@ -948,11 +970,13 @@ class Hobbit:
         c = _C(); c.K = K; c.trs = trs; c.M = M; c.cols = 2 * M // trs; c.h = None
         return self.open_core((ptr, M), c, None, queries, want_paths=False, full=True, _from_aggregate=True)
 
-    def open_core(self, poly, commitment, x, queries, want_paths=True, full=False, _from_aggregate=False):
+    def open_core(self, poly, commitment, x, queries, want_paths=True, full=False, _from_aggregate=False, _real=False):
         """open_standard + recursive_prover_Spielman (host: libc draws in the reference's order); full=False stops before the
         two shockwave_prove calls.  poly: host array or (DeviceBuffer, N)."""
         if isinstance(poly, tuple):
             ptr, N = poly; ptr = ptr.ptr if isinstance(ptr, DeviceBuffer) else int(ptr); keep = None
+        elif _real:
+            p = self._reals(poly); N = p.shape[0]; keep = self.to_device(p); ptr = keep.ptr
         else:
             p = Fh(poly).reshape(-1, 2); N = p.shape[0]; keep = self.to_device(p); ptr = keep.ptr
         c = commitment; x = Fh(x).reshape(-1, 2) if x is not None else None
@@ -975,7 +999,7 @@ class Hobbit:
         if _from_aggregate:
             self._chk(self.lib.hobbit_open_from_aggregate(self.ctx, ptr, N, c.K, c.trs, queries, ctypes.byref(o)))
         else:
-            fn = self.lib.hobbit_open_standard if full else self.lib.hobbit_open_core
+            fn = self.lib.hobbit_open_standard_real if _real else self.lib.hobbit_open_standard if full else self.lib.hobbit_open_core
             self._chk(fn(self.ctx, ptr, N, c.h, _hp(x), queries, ctypes.byref(o)))
         res["I"] = np.stack([res["cols"], res["rows"]], axis=1)
         if full:
@@ -985,6 +1009,70 @@ class Hobbit:
     def open_standard(self, poly, commitment, x, queries=5900, want_paths=True):
         """open_standard (src/Our_PC.cpp:604-661), prover side, including both shockwave_prove calls"""
         return self.open_core(poly, commitment, x, queries, want_paths, full=True)
+
+    # ---- base-field polynomials (include/hobbit_real.h): N canonical values < p, 8 bytes each
+    @staticmethod
+    def _reals(a):
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        return a.reshape(-1)
+
+    def _real_ptr(self, poly):
+        """host array of reals or (DeviceBuffer/ptr, N) -> (pointer, N, buffer to keep alive)"""
+        if isinstance(poly, tuple):
+            ptr, N = poly
+            return (ptr.ptr if isinstance(ptr, DeviceBuffer) else int(ptr)), N, None
+        p = self._reals(poly); keep = self.to_device(p)
+        return keep.ptr, p.shape[0], keep
+
+    def widen_real(self, reals):
+        """(x, 0) per coefficient, on the device; host array in and out"""
+        ptr, n, keep = self._real_ptr(reals)
+        o = self.alloc(16 * n)
+        self._chk(self.lib.hobbit_widen_real(self.ctx, c_vp(ptr), c_vp(o.ptr), c_sz(n)))
+        return self.to_host(o, (n, 2), np.uint64)
+
+    def fft_real_rows(self, rows):
+        """rows: (R, 2048) reals -> (R, 2049, 2): columns 0 .. 2048 of the 4096-point row code of each zero-padded row"""
+        a = np.ascontiguousarray(rows, dtype=np.uint64)
+        assert a.ndim == 2 and a.shape[1] == 2048
+        d = self.to_device(a); o = self.alloc(16 * 2049 * a.shape[0])
+        self._chk(self.lib.hobbit_fft_real_rows(self.ctx, c_vp(d.ptr), c_sz(a.shape[0]), c_vp(o.ptr)))
+        return self.to_host(o, (a.shape[0], 2049, 2), np.uint64)
+
+    def commit_standard_real(self, poly, K, trs, lin=1, sync=True):
+        """commit_standard of a base-field polynomial as a half commitment; poly: host array of N uint64 or (DeviceBuffer/ptr, N)"""
+        ptr, N, keep = self._real_ptr(poly)
+        h = c_vp()
+        self._chk(self.lib.hobbit_commit_standard_real(self.ctx, c_vp(ptr), c_sz(N), c_int(K), c_int(trs), c_int(lin), ctypes.byref(h)))
+        if sync or keep is not None:
+            self.sync()
+        return Commitment(self, h, N, K, trs)
+
+    def commit_standard_real_host(self, poly, K, trs, lin=1):
+        """the same from (pageable) host memory at 8 bytes per coefficient.  Returns (Commitment, DeviceBuffer holding the uploaded reals)."""
+        p = self._reals(poly); N = p.shape[0]
+        d = self.alloc(8 * N)
+        h = c_vp()
+        self._chk(self.lib.hobbit_commit_standard_real_host(self.ctx, _hp(p), c_vp(d.ptr), c_sz(N), c_int(K), c_int(trs), c_int(lin), ctypes.byref(h)))
+        self.sync()
+        return Commitment(self, h, N, K, trs), d
+
+    def aggregate_real(self, poly, beta):
+        b = Fh(beta).reshape(-1, 2); K = b.shape[0]
+        ptr, N, keep = self._real_ptr(poly)
+        o = self.alloc(16 * (N // K))
+        self._chk(self.lib.hobbit_aggregate_real(self.ctx, c_vp(ptr), c_sz(N), _hp(b), c_int(K), c_vp(o.ptr)))
+        return self.to_host(o, (N // K, 2), np.uint64)
+
+    def open_standard_real(self, poly, commitment, x, queries=5900, want_paths=True):
+        """open_standard for a base-field polynomial (host array of N uint64 or (DeviceBuffer/ptr, N)) and its commitment"""
+        return self.open_core(poly, commitment, x, queries, want_paths, full=True, _real=True)
+
+    def generate_randomness_real_dev(self, n):
+        """generate_randomness(n) drawn on the device as n reals of 8 bytes"""
+        b = self.alloc(8 * n)
+        self._chk(self.lib.hobbit_generate_randomness_real_dev(self.ctx, c_sz(n), c_vp(b.ptr)))
+        return b
 
     _SP_NAMES = ("I", "q1", "r1", "vr1", "fin1", "q2", "r2", "vr2", "fin2", "wq", "wa", "wroots", "wscal", "wchecks", "whir_root", "iters",
                  "reply", "paths", "qidx", "qreply", "qpaths", "final_pb", "qn")

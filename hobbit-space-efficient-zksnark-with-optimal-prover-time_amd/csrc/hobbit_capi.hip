@@ -15,6 +15,7 @@
 #include "hobbit_blake3.hpp"
 #include "hobbit_libcgen.hpp"
 #include "../../include/hobbit_whir.h"
+#include "../../include/hobbit_real.h"
 
 using namespace hobbit;
 
@@ -37,6 +38,13 @@ struct hobbit_commitment {
     // the commit's row FFT where the shape has the rotated form (tensorcode_chunks); read through msg_rot_row by the encode's loader, the leaf
     // chain, the gathers and the row reads.  d_tensor never escapes except through hobbit_commitment_tensor_dev, which un-rotates it first, once.
     uint32_t msg_rot = 0;
+    // A half commitment (hobbit_commit_standard_real; hobbit_half.hpp): d_tensor holds columns 0 .. cols / 2 of every chunk, K cols / 2 + K
+    // codeword-major columns, and column c > cols / 2 is answered as the conjugate of column cols - c.  rows_valid and msg_rot hold for it as for
+    // a full tensor.  Invariant: d_tensor of a half commitment never escapes; hobbit_commitment_tensor_dev materialises the full linear tensor
+    // [K][cols][rows2] once into d_full, which the commitment owns, and hands that out from then on -- d_tensor, rows_valid and msg_rot stay as
+    // they are, and every other reader keeps reading the half form.
+    bool half = false;
+    mem::Buf<F> d_full;
 };
 
 // Scope of one library call for the staging arena (hobbit_ctx.hpp): the outermost scope resets the arena on entry and, in finish(),
@@ -633,6 +641,9 @@ int hobbit_graph_finalize(hobbit_ctx *ctx, long long n, long long *len_out) {
     for (int d = D - 1; d >= 0; d--) plan.push_back({&ctx->graphs[{d, 1}], off[d + 1], off[d + 1] + cwlen[d + 1]});
     c.small_weights = true;
     for (auto &p : plan) for (auto &w : p.g->w) if (w.im != 0 || w.re >> 32) { c.small_weights = false; break; }
+    // base-field weights: Enc(conj x) = conj(Enc x), what a half commitment rests on (hobbit_commit_standard_real asks)
+    c.real_weights = true;
+    for (auto &p : plan) for (auto &w : p.g->w) if (w.im != 0) { c.real_weights = false; break; }
     // The slice tables of k_encode.  A code whose codeword fits LDS (up to 160 KB) gets them now; a longer one when its first launch_encode asks
     // for its tiled steps (ensure_tiled): the rows-innermost encode, the code proof and the parity matrix never read them, and at n = 2^21 they
     // were 3.2 s of a 3.2 s finalize
@@ -869,6 +880,24 @@ int hobbit_commit_standard_host(hobbit_ctx *ctx, const hobbit_F *h_poly, hobbit_
     if (rc) hipStreamSynchronize(ctx->up_stream);                 // nothing of the caller's buffer is still being read on an error return
     return rc;
 }
+// A commitment's tensor (tbytes: its real size, full or half form) and levels: the parked pair of the last freed commitment where both sizes are the
+// same to the byte, fresh allocations otherwise.
+static int commit_buffers(hobbit_ctx *ctx, size_t tbytes, size_t M, mem::Buf<F> &tensor, mem::Buf<uint8_t> &levels) {
+    if (ctx->spare_tensor && ctx->spare_tensor.bytes() == tbytes && ctx->spare_levels.bytes() == 64 * M) {
+        tensor = std::move(ctx->spare_tensor); levels = std::move(ctx->spare_levels);
+        return 0;
+    }
+    if (ctx->spare_tensor) {          // a parked commitment of another shape: release it BEFORE allocating (it can be 16.5 GiB)
+        HB_TRY(ctx->sync());
+        ctx->spare_tensor.reset(); ctx->spare_levels.reset();
+    }
+    if (tensor.alloc_bytes(tbytes) || levels.alloc_bytes(64 * M)) {
+        ctx->pool_drain();                                    // give back what the pool parks, then once more
+        tensor.reset();
+        if (tensor.alloc_bytes(tbytes) || levels.alloc_bytes(64 * M)) return ctx->fail(HOBBIT_ENOMEM, "commit_standard: tensor allocation failed");
+    }
+    return 0;
+}
 static int commit_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int K, int trs, int linear_time, hobbit_commitment **out, Uploader *up) {
     if (!out) return HOBBIT_EINVAL;
     *out = nullptr;
@@ -879,20 +908,7 @@ static int commit_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int K,
     size_t cols = 2 * M / trs, rows2 = 2 * (size_t)trs;
     Handle<hobbit_commitment, hobbit_commitment_free> c(new hobbit_commitment());
     c->ctx = ctx; c->N = N; c->M = M; c->K = K; c->trs = trs; c->lin = linear_time; c->cols = (uint32_t)cols; c->rows2 = (uint32_t)rows2;
-    const size_t tbytes = (size_t)K * cols * rows2 * sizeof(F);
-    if (ctx->spare_tensor && ctx->spare_tensor.bytes() == tbytes && ctx->spare_levels.bytes() == 64 * M) {
-        c->d_tensor = std::move(ctx->spare_tensor); c->d_levels = std::move(ctx->spare_levels);
-    } else {
-        if (ctx->spare_tensor) {          // a parked commitment of another shape: release it BEFORE allocating (it can be 16.5 GiB)
-            HB_TRY(ctx->sync());
-            ctx->spare_tensor.reset(); ctx->spare_levels.reset();
-        }
-        if (c->d_tensor.alloc_bytes(tbytes) || c->d_levels.alloc_bytes(64 * M)) {
-            ctx->pool_drain();                                    // give back what the pool parks, then once more
-            c->d_tensor.reset();
-            if (c->d_tensor.alloc_bytes(tbytes) || c->d_levels.alloc_bytes(64 * M)) return ctx->fail(HOBBIT_ENOMEM, "commit_standard: tensor allocation failed");
-        }
-    }
+    HB_TRY(commit_buffers(ctx, (size_t)K * cols * rows2 * sizeof(F), M, c->d_tensor, c->d_levels));
     const char *st_env = getenv("HOBBIT_COMMIT_SKIP_TAIL");
     ctx->enc_skip_tail = linear_time && !(st_env && st_env[0] == '0'); ctx->enc_tail_skipped = false;
     int r = tensorcode_chunks(ctx, cF(d_poly), M, K, trs, linear_time, c->d_tensor, up, &c->msg_rot);
@@ -907,6 +923,80 @@ static int commit_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, int K,
     *out = c.release();
     return 0;
 }
+// ---- base-field polynomials (include/hobbit_real.h) ---------------------------------------------
+// commit_impl for a real polynomial: the same stages over columns 0 .. cols / 2 of every chunk (hobbit_half.hpp).  The row code stores the half
+// tensor's layout itself -- rotated where the full commit's would be, plainly transposed for the small tensors that fit the cache -- and goes through
+// a row-major scratch of 2049 columns and the tiled transpose for the large tensors that are not rotated; the encode sees K cols / 2 + K columns.
+static int commit_real_impl(hobbit_ctx *ctx, const uint64_t *d_poly, size_t N, int K, int trs, int linear_time, hobbit_commitment **out, Uploader *up) {
+    if (!out) return HOBBIT_EINVAL;
+    *out = nullptr;
+    if (!d_poly) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real: null polynomial");
+    if (K <= 0 || N % (size_t)K) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real: K must divide N");
+    const size_t M = N / K;
+    if (trs < 4 || trs % 4 || M % (size_t)trs) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real: trs must be a multiple of 4 dividing N/K");
+    if (ilog2_exact(M) < 0) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real: N/K must be a power of two");
+    if (!linear_time) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real: only the RS x expander code (linear_time = 1) has the half form; RS x RS is not built");
+    const size_t cols = 2 * M / trs, rows2 = 2 * (size_t)trs;
+    if (cols != 4096) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real: the row code must have 4096 points, 2 (N/K) / trs == 4096");
+    if (trs > 13 && ctx->code.n != trs) return ctx->fail(HOBBIT_ESTATE, "commit_standard_real: expander graphs for n = trs not finalized");
+    if (trs <= 13 && ctx->code.n != trs) { long long l; HB_TRY(hobbit_graph_finalize(ctx, trs, &l)); }
+    if (!ctx->code.real_weights)
+        return ctx->fail(HOBBIT_EINVAL, "commit_standard_real: a weight of the finalized graphs has img != 0, so column cols - c is not the conjugate of column c");
+    Handle<hobbit_commitment, hobbit_commitment_free> c(new hobbit_commitment());
+    c->ctx = ctx; c->N = N; c->M = M; c->K = K; c->trs = trs; c->lin = 1; c->cols = (uint32_t)cols; c->rows2 = (uint32_t)rows2; c->half = true;
+    const size_t hcols = half_ncols((uint32_t)cols, (uint32_t)K);
+    HB_TRY(commit_buffers(ctx, hcols * rows2 * sizeof(F), M, c->d_tensor, c->d_levels));
+    const bool piped_shape = (size_t)K * trs * cols * sizeof(F) >= ((size_t)64 << 20);            // the full commit's threshold: the same shapes rotate
+    const bool rotated = piped_shape && trs == 4096 && encode_reads_rotated(ctx, trs);
+    c->msg_rot = rotated ? (uint32_t)trs - 1 : 0;
+    const int pipe = K % 8 == 0 ? 8 : K % 4 == 0 ? 4 : K % 2 == 0 ? 2 : 1, groups = up && piped_shape ? pipe : 1, per = K / groups;
+    if (up) { up->groups = groups; up->group_bytes = (size_t)per * M * sizeof(uint64_t); }
+    F *rm = nullptr;
+    if (piped_shape && !rotated) HB_TRY(ctx->workspace2((size_t)K * trs * 2049 * sizeof(F), (void **)&rm));
+    for (int g = 0; g < groups; g++) {
+        const size_t c0 = (size_t)g * per;
+        if (up) HB_TRY(up->wait(g, ctx->stream));
+        if (rm) HB_TRY(fft::rowcode_real4096(ctx, d_poly + c0 * M, (size_t)per * trs, rm + c0 * trs * 2049, false, 0, 0, 0, 0));
+        else HB_TRY(fft::rowcode_real4096(ctx, d_poly + c0 * M, (size_t)per * trs, c->d_tensor, true, (uint32_t)trs, (uint32_t)K, c->msg_rot, (uint32_t)c0));
+        if (up) HB_TRY(up->start(g + 1));                 // (host copy + PCIe of the next group, beside this group's kernel)
+    }
+    if (rm) {       // columns 0 .. 2047 of every chunk into the main block, column 2048 into the strip
+        HB_TRY(launch_transpose_ld(ctx, rm, (size_t)trs * 2049, 2049, (uint32_t)trs, 2048, c->d_tensor, 2048 * rows2, rows2, (uint32_t)K));
+        HB_TRY(launch_transpose_ld(ctx, rm + 2048, (size_t)trs * 2049, 2049, (uint32_t)trs, 1, c->d_tensor + (size_t)K * 2048 * rows2, rows2, rows2, (uint32_t)K));
+    }
+    const char *st_env = getenv("HOBBIT_COMMIT_SKIP_TAIL");
+    ctx->enc_skip_tail = !(st_env && st_env[0] == '0'); ctx->enc_tail_skipped = false;
+    int r = launch_encode(ctx, c->d_tensor, rows2, c->d_tensor, rows2, trs, hcols, 0, c->msg_rot);
+    c->rows_valid = (!r && ctx->enc_tail_skipped) ? std::min<uint32_t>((uint32_t)rows2, ((uint32_t)ctx->code.len + 3) & ~3u) : (uint32_t)rows2;
+    ctx->enc_skip_tail = false; ctx->enc_tail_skipped = false;
+    if (!r) r = launch_leaf_chain_half(ctx, c->d_tensor, K, (uint32_t)cols, (uint32_t)(trs / 2), c->d_levels, (uint32_t)ctx->code.len, c->msg_rot);
+    if (!r) r = launch_merkle_levels(ctx, c->d_levels, M, 1);
+    if (r) return r;
+    *out = c.release();
+    return 0;
+}
+int hobbit_commit_standard_real(hobbit_ctx *ctx, const uint64_t *d_poly, size_t N, int K, int trs, int linear_time, hobbit_commitment **out) {
+    return commit_real_impl(ctx, d_poly, N, K, trs, linear_time, out, nullptr);
+}
+int hobbit_commit_standard_real_host(hobbit_ctx *ctx, const uint64_t *h_poly, uint64_t *d_poly, size_t N, int K, int trs, int linear_time, hobbit_commitment **out) {
+    if (!h_poly || !d_poly) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_host: null polynomial");
+    HB_TRY(ctx->up_init());
+    Uploader up{ctx, reinterpret_cast<const unsigned char *>(h_poly), reinterpret_cast<unsigned char *>(d_poly), 0, 0};
+    const int rc = commit_real_impl(ctx, d_poly, N, K, trs, linear_time, out, &up);
+    if (rc) hipStreamSynchronize(ctx->up_stream);                 // nothing of the caller's buffer is still being read on an error return
+    return rc;
+}
+int hobbit_commitment_is_half(const hobbit_commitment *c) { return c && c->half ? 1 : 0; }
+int hobbit_widen_real(hobbit_ctx *ctx, const uint64_t *d_reals, hobbit_F *d_out, size_t n) {
+    if (n && (!d_reals || !d_out)) return ctx->fail(HOBBIT_EINVAL, "widen_real: null argument");
+    return launch_widen_real(ctx, d_reals, mF(d_out), n);
+}
+int hobbit_aggregate_real(hobbit_ctx *ctx, const uint64_t *d_poly, size_t N, const hobbit_F *h_beta, int K, hobbit_F *d_aggr) {
+    if (K <= 0 || N % (size_t)K) return ctx->fail(HOBBIT_EINVAL, "aggregate_real: K must divide N");
+    if (!d_poly || !h_beta || !d_aggr) return ctx->fail(HOBBIT_EINVAL, "aggregate_real: null argument");
+    return launch_aggregate_real(ctx, d_poly, N / K, K, cF(h_beta), mF(d_aggr));
+}
+
 void hobbit_commitment_free(hobbit_commitment *c) {
     if (!c) return;
     hobbit_ctx *ctx = c->ctx;
@@ -919,6 +1009,16 @@ void hobbit_commitment_free(hobbit_commitment *c) {
 size_t hobbit_commitment_num_leaves(const hobbit_commitment *c) { return c->M; }
 const uint8_t *hobbit_commitment_levels_dev(const hobbit_commitment *c) { return c->d_levels; }
 const hobbit_F *hobbit_commitment_tensor_dev(const hobbit_commitment *c) {
+    if (c->half) {                                        // the full linear tensor, materialised once into an allocation of the commitment's own
+        hobbit_commitment *m = const_cast<hobbit_commitment *>(c);
+        if (!m->d_full) {
+            const size_t fbytes = (size_t)m->K * m->cols * m->rows2 * sizeof(F);
+            if (need_device_bytes(m->ctx, fbytes, "commitment_tensor_dev (half commitment)") != 0) return nullptr;
+            if (m->d_full.alloc_bytes(fbytes)) { m->ctx->fail(HOBBIT_ENOMEM, "commitment_tensor_dev: allocation of the full tensor failed"); return nullptr; }
+            if (launch_half_expand(m->ctx, m->d_tensor, m->d_full, m->cols, m->K, m->rows2, m->rows_valid, m->msg_rot) != 0 || m->ctx->sync() != 0) { m->d_full.reset(); return nullptr; }
+        }
+        return reinterpret_cast<const hobbit_F *>(m->d_full.get());
+    }
     if (c->rows_valid < c->rows2 || c->msg_rot) {         // a raw pointer leaves the library: the implicit zeros become real ones and a rotated
         hobbit_commitment *m = const_cast<hobbit_commitment *>(c);      // message half a linear one, once, in place (one drain for both)
         if (launch_zero_rows(m->ctx, m->d_tensor, (size_t)m->K * m->cols, m->rows2, m->rows_valid) != 0 ||
@@ -932,7 +1032,8 @@ int hobbit_commitment_root(hobbit_ctx *ctx, const hobbit_commitment *c, uint8_t 
 int hobbit_commitment_tensor_row(hobbit_ctx *ctx, const hobbit_commitment *c, int chunk, int row, hobbit_F *h_out) {
     if (chunk < 0 || chunk >= c->K || row < 0 || (uint32_t)row >= c->rows2) return ctx->fail(HOBBIT_EINVAL, "tensor_row: index out of range");
     F *tmp; HB_TRY(ctx->workspace((size_t)c->cols * sizeof(F), (void **)&tmp));
-    HB_TRY(launch_tensor_row(ctx, c->d_tensor + (size_t)chunk * c->cols * c->rows2, c->rows2, c->cols, (uint32_t)row, tmp, c->rows_valid, c->msg_rot));
+    if (c->half) HB_TRY(launch_tensor_row_half(ctx, c->d_tensor, (uint32_t)chunk, c->K, c->rows2, c->cols, (uint32_t)row, tmp, c->rows_valid, c->msg_rot));
+    else HB_TRY(launch_tensor_row(ctx, c->d_tensor + (size_t)chunk * c->cols * c->rows2, c->rows2, c->cols, (uint32_t)row, tmp, c->rows_valid, c->msg_rot));
     return hobbit_memcpy_d2h(ctx, h_out, tmp, (size_t)c->cols * sizeof(F));
 }
 int hobbit_commitment_gather(hobbit_ctx *ctx, const hobbit_commitment *c, const uint32_t *h_rows, const uint32_t *h_cols, size_t nq, hobbit_F *h_reply) {
@@ -944,7 +1045,8 @@ int hobbit_commitment_gather(hobbit_ctx *ctx, const hobbit_commitment *c, const 
     F *d_reply = reinterpret_cast<F *>(buf); uint32_t *d_rows = reinterpret_cast<uint32_t *>(buf + rb), *d_cols = d_rows + nq;
     HB_TRY(h2d_staged(ctx, d_rows, h_rows, 4 * nq));
     HB_TRY(h2d_staged(ctx, d_cols, h_cols, 4 * nq));
-    HB_TRY(launch_gather(ctx, c->d_tensor, (size_t)c->cols * c->rows2, c->rows2, c->K, d_rows, d_cols, nq, d_reply, c->rows_valid, c->msg_rot));
+    if (c->half) HB_TRY(launch_gather_half(ctx, c->d_tensor, c->cols, c->rows2, c->K, d_rows, d_cols, nq, d_reply, c->rows_valid, c->msg_rot));
+    else HB_TRY(launch_gather(ctx, c->d_tensor, (size_t)c->cols * c->rows2, c->rows2, c->K, d_rows, d_cols, nq, d_reply, c->rows_valid, c->msg_rot));
     HB_TRY(d2h_staged(ctx, h_reply, d_reply, nq * c->K * sizeof(F)));
     return sc.finish();
 }
@@ -2611,6 +2713,7 @@ struct OpenRun {
     std::vector<F> beta, sv, r1; std::vector<uint32_t> qc, qr; std::vector<uint64_t> Iv; F s2, a; size_t nnz = 0;      // host: beta over the chunk variables, the libc draws, buff2's length
     hobbit_F *Q1, *Q2, *Q3, *Q4, *Q5, *Rr1, *Rr2, *Rr3, *Rr4, *Rr5;                                                    // the output cursors of P1..P5
     F y1 = {}, *y1_pin = nullptr;                                          // y1 and the pinned slot its read-back lands in (y1_p5, finish)
+    bool real_poly = false;                                                // d_poly holds N reals of 8 bytes (hobbit_open_standard_real): the aggregate reads them as such
     ShockPlan plan_c, plan_f;                                              // the libc draws of shockwave_prove(C_c) and (C_f), taken in libc_draws
     // overlapped only: the hand-over of the query answers; shockwave_prove(C_c) on the helper context.  Its thread is started in libc_draws,
     // while the GPU is busy, and parks on sp_cv until start_prove_cc lets it run (sp_go = 1) or the destructor sends it home (-1).
@@ -2670,7 +2773,8 @@ struct OpenRun {
         return 0;
     }
     int aggregate_and_tensor_code() {
-        if (c) HB_TRY(hobbit_aggregate(ctx, d_poly, N, reinterpret_cast<const hobbit_F *>(beta.data()), K, reinterpret_cast<hobbit_F *>(d_aggr)));   // _aggregate axpy (:258-272)
+        if (c && real_poly) HB_TRY(hobbit_aggregate_real(ctx, reinterpret_cast<const uint64_t *>(d_poly), N, reinterpret_cast<const hobbit_F *>(beta.data()), K, reinterpret_cast<hobbit_F *>(d_aggr)));
+        else if (c) HB_TRY(hobbit_aggregate(ctx, d_poly, N, reinterpret_cast<const hobbit_F *>(beta.data()), K, reinterpret_cast<hobbit_F *>(d_aggr)));   // _aggregate axpy (:258-272)
         else HB_TRY(launch_copy(ctx, d_aggr, d_poly, M * sizeof(F)));
         // compute_tensorcode(aggr) (:277): M' = row FFTs (row-major), codeword-major copy, expander encode, parity half back to row-major C
         tr.mark("beta, arena, aggregate");
@@ -2890,10 +2994,11 @@ struct OpenRun {
     }
 };
 static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
-                          bool full) {
+                          bool full, bool real_poly) {
     if ((!c && !dims) || !o || queries <= 0 || queries >= (1 << 20) || (full && (!o->sp_c || !o->sp_f))) return ctx->fail(HOBBIT_EINVAL, "open: bad arguments");
     if (!c && (o->reply || o->paths)) return ctx->fail(HOBBIT_EINVAL, "open_from_aggregate: replies and paths come from the tensor shards, not from here");
     OpenRun r(ctx, d_poly, N, c, h_x, queries, o, full);
+    r.real_poly = real_poly;
     HB_TRY(r.dims_beta_first_draw(dims));
     HB_TRY(r.size_scratch_and_lay_out_arena());
     HB_TRY(r.aggregate_and_tensor_code());
@@ -2917,8 +3022,8 @@ static int open_impl_body(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, con
     return r.finish();
 }
 static int open_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const int *dims, const hobbit_F *h_x, int queries, hobbit_open_out *o,
-                     bool full) {
-    const int rc = open_impl_body(ctx, d_poly, N, c, dims, h_x, queries, o, full);
+                     bool full, bool real_poly = false) {
+    const int rc = open_impl_body(ctx, d_poly, N, c, dims, h_x, queries, o, full, real_poly);
     if (rc) {
         // an error return may leave work queued on the helper contexts' streams (inner commitments, query answers, their staged read-backs
         // into THIS context's arena): drain them before the caller -- or the next call's StageScope -- re-uses those buffers
@@ -2935,6 +3040,11 @@ int hobbit_open_core(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const ho
 int hobbit_open_standard(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const hobbit_F *h_x, int queries, hobbit_open_out *o) {
     if (!c) return ctx->fail(HOBBIT_EINVAL, "open_standard: null commitment");
     return open_impl(ctx, d_poly, N, c, nullptr, h_x, queries, o, true);
+}
+// the same opening with the polynomial as N reals: only the aggregate reads it (k_aggregate_real), every later stage starts from the aggregate
+int hobbit_open_standard_real(hobbit_ctx *ctx, const uint64_t *d_poly, size_t N, const hobbit_commitment *c, const hobbit_F *h_x, int queries, hobbit_open_out *o) {
+    if (!c || !d_poly) return ctx->fail(HOBBIT_EINVAL, "open_standard_real: null commitment or polynomial");
+    return open_impl(ctx, reinterpret_cast<const hobbit_F *>(d_poly), N, c, nullptr, h_x, queries, o, true, true);
 }
 int hobbit_open_from_aggregate(hobbit_ctx *ctx, const hobbit_F *d_aggr, size_t M, int K, int trs, int queries, hobbit_open_out *o) {
     const int dims[2] = {K, trs};

@@ -121,6 +121,7 @@ struct ParitySeg { uint32_t base, count, degree, lvl, off, kind, src, cells; };
 struct DeviceCode {         // finalized code for one message length n
     long long n = 0, len = 0;
     bool small_weights = true;               // all weights real and < 2^32
+    bool real_weights = true;                // no weight with img != 0 (recorded once, by hobbit_graph_finalize)
     std::vector<EncStep> steps;
     mem::Buf<EncStep> d_steps;
     mem::Buf<uint32_t> d_slice_ptr, d_slice_width, d_slice_out;   // per slice: offset, records per output, output ids

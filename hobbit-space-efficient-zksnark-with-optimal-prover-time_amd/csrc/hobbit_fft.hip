@@ -5,6 +5,8 @@
 #include "hobbit_fft_tables.hpp"
 #include "hobbit_kernels.hpp"
 #include "hobbit_rot.hpp"
+#include "hobbit_half.hpp"
+#include "../../include/hobbit_real.h"
 
 namespace hobbit {
 // ============================================================================================
@@ -448,6 +450,110 @@ static int launch_fft_r8(hobbit_ctx *ctx, const F *src, size_t src_ld, uint32_t 
     return ctx->fail(HOBBIT_EINVAL, "fft_r8: logn must be in [6, 11]");
 }
 
+// --------------------------------------------------------------------------------------------
+// The 4096-point row code of a BASE-FIELD row (include/hobbit_real.h): 2048 reals x, zero-padded.  Two consecutive reals are the memory
+// image of one F element z[j] = x[2j] + i x[2j+1], so the row is loaded as 1024 F (16 KiB) and transformed as k_fft_r8<11, true> transforms a
+// zero-padded 2048-point row -- the same passes, tables and lazy sums, one row per workgroup of 256 threads, the radix-4 tail left in LDS.
+// With Z = FFT_2048(z), conj(w) = 1 / w for the roots of unity of order 2^12 | p + 1 gives
+//     E[k] = (Z[k] + conj(Z[-k])) / 2,   O[k] = (Z[k] - conj(Z[-k])) / (2i),   X[k] = E[k] + w^k O[k],   X[2048 - k] = conj(E[k] - w^k O[k]),
+// and X[4096 - k] = conj(X[k]) makes columns 0 .. 2048 the whole row.  The unpacking pass works on the pairs (k, 2048 - k) in LDS: one product
+// per pair, 1/2 = 2^60 as a one-bit rotation.  Canonical arithmetic, canonical results: the bits of k_fft4096<true> on the widened row.
+// TENSOR: row (chunk chunk0 + i, r) of the launch stores X[k] into the commitment's half tensor (hobbit_half.hpp), rotated where rot_mask says so; otherwise
+// row-major, 2049 elements per row.  36 KiB of LDS: four workgroups per CU.
+// --------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t half61(uint64_t x) { return (x >> 1) + ((x & 1) << 60); }      // canonical x / 2: 2^60 = 1/2, and x < p keeps it below p
+__device__ __forceinline__ F fhalf(const F &a) { return fmake(half61(a.re), half61(a.im)); }
+template <bool TENSOR>
+__global__ void __launch_bounds__(256)
+k_fft_real4096(const uint64_t *__restrict__ src, F *__restrict__ dst, const F *__restrict__ tabs, const F *__restrict__ roots, int plus_i, uint32_t trs, uint32_t K,
+               uint32_t rows2, uint32_t rot_mask, uint32_t chunk0, int line_remap) {
+    constexpr uint32_t N = 2048, R = 4, N2 = N / R, OCT = N2 / 8, LDR = N + N / 8;
+    __shared__ F s[LDR];
+    // (k_fft4096's placement for transposed stores: the eight rows that share a 128-byte line of every column go to one XCD, whose L2 merges them)
+    uint32_t row = blockIdx.x;
+    if (line_remap) row = (row & ~63u) + 8 * (row & 7u) + ((row >> 3) & 7u);
+    const uint32_t tid = threadIdx.x;
+    const F *in = reinterpret_cast<const F *>(src + (size_t)row * 2048);
+#pragma unroll
+    for (uint32_t i = 0; i < 1024; i += 256) stF(&s[fft_phys(i + tid)], ldF(in + i + tid));
+    __syncthreads();
+    const uint32_t q = tid / OCT, b = tid % OCT;
+    F a[8];
+    {   // ---- pass 0 of k_fft_r8<11, true>: octet b of sub-sequence q gathers z[R (rev6(b) + OCT rev3(j)) + q], the upper half of the input is zero
+        const uint32_t m = __brev(b) >> 26;
+        a[0] = ldF(&s[fft_phys(R * m + q)]); a[2] = ldF(&s[fft_phys(R * (m + 2 * OCT) + q)]);
+        a[4] = ldF(&s[fft_phys(R * (m + OCT) + q)]); a[6] = ldF(&s[fft_phys(R * (m + 3 * OCT) + q)]);
+        a[1] = a[0]; a[3] = a[2]; a[5] = a[4]; a[7] = a[6];
+        dft8_tail(a, plus_i);
+        __syncthreads();                                            // every input has been read
+        const uint32_t o = fft_phys(q * N2 + 8 * b);
+#pragma unroll
+        for (int t8 = 0; t8 < 8; t8++) stF(&s[o + t8], ffold(a[t8]));
+        __syncthreads();
+    }
+    const F *tw = tabs;
+#pragma unroll
+    for (uint32_t pass = 1; pass < 3; pass++) {
+        const uint32_t h = pass == 1 ? 8u : 64u;
+        const uint32_t k = b & (h - 1), j = b / h, i0 = q * N2 + j * 8 * h + k;
+#pragma unroll
+        for (int t8 = 0; t8 < 8; t8++) a[t8] = ldF(&s[fft_phys(i0 + t8 * h)]);
+#pragma unroll
+        for (int t8 = 1; t8 < 8; t8++) a[t8] = fmul_lz(a[t8], ldF(tw + (t8 - 1) * h + k));
+        HB_DFT8_HEAD(a);
+        dft8_tail(a, plus_i);
+#pragma unroll
+        for (int t8 = 0; t8 < 8; t8++) stF(&s[fft_phys(i0 + t8 * h)], ffold(a[t8]));
+        tw += 7 * h;
+        __syncthreads();
+    }
+    // ---- the radix-4 tail, Z[k + m N/4] = sum_q W_4^(q m) w_2048^(q k) S_q[k], in place: a thread reads and writes the same four slots
+#pragma unroll
+    for (uint32_t c = 0; c < 2; c++) {
+        const uint32_t k = tid + 256 * c;
+        const F y0 = ldF(&s[fft_phys(k)]);
+        const F y1 = fmul_lz(ldF(&s[fft_phys(N2 + k)]), ldF(tw + k));
+        const F y2 = fmul_lz(ldF(&s[fft_phys(2 * N2 + k)]), ldF(tw + N2 + k));
+        const F y3 = fmul_lz(ldF(&s[fft_phys(3 * N2 + k)]), ldF(tw + 2 * N2 + k));
+        const F t0 = faddl(y0, y2), t1 = fsubl<1>(y0, y2), t2 = faddl(y1, y3), t3 = fmul_w4<2>(fsubl<1>(y1, y3), plus_i);
+        stF(&s[fft_phys(k)], fcanon(faddl(t0, t2)));
+        stF(&s[fft_phys(k + N2)], fcanon(faddl(t1, t3)));
+        stF(&s[fft_phys(k + 2 * N2)], fcanon(fsubl<2>(t0, t2)));
+        stF(&s[fft_phys(k + 3 * N2)], fcanon(fsubl<2>(t1, t3)));
+    }
+    __syncthreads();
+    // ---- unpacking on the pairs (k, 2048 - k), k = 0 .. 1024
+    const uint32_t chunk = TENSOR ? chunk0 + row / trs : 0u, r = TENSOR ? row % trs : 0u;
+    auto emit = [&](uint32_t k, const F &v) {
+        if (TENSOR) stF(dst + half_at(chunk, k, r, 4096u, K, rows2, rot_mask), v);
+        else stF(dst + (size_t)row * 2049 + k, v);
+    };
+#pragma unroll
+    for (uint32_t c = 0; c < 5; c++) {
+        const uint32_t k = tid + 256 * c;
+        if (k > 1024) break;                                        // (c == 4: thread 0 alone, the self-paired k = 1024)
+        const F A = ldF(&s[fft_phys(k)]), B = fconj(ldF(&s[fft_phys((N - k) & (N - 1))]));
+        const F S = fadd(A, B), D = fsub(A, B);
+        const F T = fmul(fmake(D.im, D.re ? P61 - D.re : 0), ldF(roots + k));       // w^k (-i D) = 2 w^k O[k]
+        emit(k, fhalf(fadd(S, T)));
+        if (k != 1024) emit(N - k, fconj(fhalf(fsub(S, T))));
+    }
+}
+// tabs: the radix-8 tables of 2048 points, roots: w^k of order 4096 (k < 2048), both forward
+static int launch_fft_real4096(hobbit_ctx *ctx, const uint64_t *src, size_t rows, F *dst, const F *tabs, const F *roots, int plus_i, bool tensor, uint32_t trs,
+                               uint32_t K, uint32_t rot_mask, uint32_t chunk0) {
+    if (!rows) return 0;
+    if (rows >> 31) return ctx->fail(HOBBIT_EINVAL, "fft_real: too many rows");
+    if ((uintptr_t)src & 15) return ctx->fail(HOBBIT_EINVAL, "fft_real: the real rows must be 16-byte aligned");
+    if (tensor) {
+        if (!trs || rows % trs || chunk0 + rows / trs > K || (rot_mask && rot_mask != trs - 1)) return ctx->fail(HOBBIT_EINVAL, "fft_real: bad tensor shape");
+        HB_LAUNCH(ctx, "k_fft_real4096", k_fft_real4096<true>, dim3((unsigned)rows), dim3(256), 0, src, dst, tabs, roots, plus_i, trs, K, 2 * trs, rot_mask, chunk0,
+                  rows % 64 == 0 ? 1 : 0);
+    } else
+        HB_LAUNCH(ctx, "k_fft_real4096_rm", k_fft_real4096<false>, dim3((unsigned)rows), dim3(256), 0, src, dst, tabs, roots, plus_i, 0u, 0u, 0u, 0u, 0u, 0);
+    return 0;
+}
+
 // The same passes for the SECOND half of a long transform (k_fft_cols's job: N-point transforms down the columns of y[n1][k2], N = len / 4096
 // = 32 ... 256, inter-stage twiddle on load, result X[k1 * 4096 + k2]).  A workgroup owns C = 4096 / N adjacent columns; the column index is
 // the fastest thread index, so global loads and stores are C * 16-byte runs and -- with an odd LDS row stride -- the butterflies of the 64 lanes
@@ -802,6 +908,11 @@ int rowcode_4096(hobbit_ctx *ctx, const F *src, size_t src_ld, F *dst, size_t ds
     const R8Set *r8; HB_TRY(r8_set(ctx, false, &r8));
     return launch_fft4096(ctx, src, src_ld, 1, 2048, dst, dst_ld, dst_es, *r8, fmake(1), 0, groups, rows_per_group, src_gs, dst_gs, rot_mask);
 }
+int rowcode_real4096(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, F *dst, bool tensor, uint32_t trs, uint32_t K, uint32_t rot_mask, uint32_t chunk0) {
+    const R8Set *r8; HB_TRY(r8_set(ctx, false, &r8));
+    const F *tabs, *tw; HB_TRY(table(ctx, RADIX8, 11, false, &tabs)); HB_TRY(roots(ctx, 12, false, &tw));
+    return launch_fft_real4096(ctx, src, nrows, dst, tabs, tw, r8->w4_plus_i, tensor, trs, K, rot_mask, chunk0);
+}
 int rowcode_combine(hobbit_ctx *ctx, const F *msg, int logc, uint32_t nrows, F *Y, F *rm) {
     const int lr = logc - 12; const uint32_t R = 1u << lr; const size_t cols = (size_t)1 << logc;
     const R8Set *r8; HB_TRY(r8_set(ctx, false, &r8));
@@ -904,6 +1015,11 @@ int hobbit_fft_batch(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, 
         return fft::any_rows(ctx, d, ld, ld, d, logn, false, (uint32_t)batch);
     }
     return fft::rows(ctx, d, ld, 1u << logn, d, ld, 1, logn, inverse != 0, 1, (uint32_t)batch, 0, 0);
+}
+int hobbit_fft_real_rows(hobbit_ctx *ctx, const uint64_t *d_reals, size_t rows, hobbit_F *d_out) {
+    if (!rows) return 0;
+    if (!d_reals || !d_out) return ctx->fail(HOBBIT_EINVAL, "fft_real_rows: null argument");
+    return fft::rowcode_real4096(ctx, d_reals, rows, reinterpret_cast<F *>(d_out), false, 0, 0, 0, 0);
 }
 int hobbit_fft_any(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, size_t ld, int inverse) {
     if (logn < 1 || logn > 28) return ctx->fail(HOBBIT_EINVAL, "fft_any: logn must be in [1,28]");

@@ -23,6 +23,10 @@ int any_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *ds
 // commitment's rotated message half -- dst_ld == 1, row r of column c at its rotated place.
 int rowcode_4096(hobbit_ctx *ctx, const F *src, size_t src_ld, F *dst, size_t dst_ld, size_t dst_es, uint32_t groups, uint32_t rows_per_group, size_t src_gs,
                  size_t dst_gs, uint32_t rot_mask = 0);
+// The 4096-point row code of `nrows` base-field rows of 2048 reals (include/hobbit_real.h), columns 0 .. 2048.  tensor: rows (chunk, r) of K chunks of
+// trs rows, the first of them row 0 of chunk chunk0, into a commitment's half tensor (hobbit_half.hpp), rotated by rot_mask; otherwise row-major,
+// 2049 elements per row.
+int rowcode_real4096(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, F *dst, bool tensor, uint32_t trs, uint32_t K, uint32_t rot_mask, uint32_t chunk0);
 // The 2^13 .. 2^15-point row code (Elastic_PC opt 2: 32768) of `nrows` contiguous messages of 2^(logc-1) elements: R = 2^(logc-12) strided FFT-4096 per
 // row into Y, then the twiddles and the R-point combine into the row-major rm (both nrows 2^logc elements).
 int rowcode_combine(hobbit_ctx *ctx, const F *msg, int logc, uint32_t nrows, F *Y, F *rm);

@@ -1311,6 +1311,140 @@ int launch_unrotate_msg(hobbit_ctx *ctx, F *tensor, size_t ncols, uint32_t rows2
     HB_LAUNCH(ctx, "k_unrotate_msg", k_unrotate_msg, dim3(grid_for(ncols, 1, 65536)), dim3(1024), lds, tensor, ncols, rows2, rot_mask);
     return 0;
 }
+
+// ============================================================================================
+// The half form of a commitment's tensor (hobbit_half.hpp; include/hobbit_real.h): columns 0 .. cols / 2 of every chunk are in memory, column
+// c > cols / 2 is the conjugate of column cols - c.  Kernels of their own beside k_leaf_chain, k_gather and k_tensor_row, which stay as they are.
+// ============================================================================================
+// the four elements of a leaf group conjugated in place: words 4e + 2, 4e + 3 are the imaginary part of element e
+__device__ __forceinline__ void conj16w(uint32_t m[16]) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const uint64_t im = ((uint64_t)m[4 * e + 3] << 32) | m[4 * e + 2], v = im ? P61 - im : 0;
+        m[4 * e + 2] = (uint32_t)v; m[4 * e + 3] = (uint32_t)(v >> 32);
+    }
+}
+// k_leaf_chain (NL = 1) over a half tensor: the same dense index over all `cols` columns and the zf non-zero groups, the same fill of the zero
+// groups' leaves.  Leaf (j, c) with c > cols / 2 reads the group of column cols - c -- the same contiguous, aligned 64 bytes per chunk, rotated by
+// that column's batch index -- and conjugates it before hashing.
+__global__ void __launch_bounds__(256)
+k_leaf_chain_half(const F *__restrict__ tensor, uint32_t K, uint32_t cols, uint32_t half_trs, uint8_t *__restrict__ leaves, uint32_t zf, ZeroDig zk, uint32_t rot_mask) {
+    const uint32_t stride = gridDim.x * blockDim.x, rows2 = 4 * half_trs;
+    {
+        const size_t fill16 = 2 * (size_t)(half_trs - zf) * cols;
+        uint4 *tail = reinterpret_cast<uint4 *>(leaves + 32 * (size_t)zf * cols);
+        const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;     // stride is even: a thread stores the same half of Z_K every time
+        const uint4 v = (t & 1) ? make_uint4(zk.w[4], zk.w[5], zk.w[6], zk.w[7]) : make_uint4(zk.w[0], zk.w[1], zk.w[2], zk.w[3]);
+        for (size_t u = t; u < fill16; u += stride) tail[u] = v;
+    }
+    const uint32_t total = cols * zf;
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride) {
+        const uint32_t c = g / zf, j = g - c * zf, sc = half_src_col(c, cols);
+        const bool cj = half_is_conj(c, cols);
+        // a column of the main block keeps its place and its rotation from chunk to chunk (hc columns on: a multiple of the rotation's period);
+        // the strip's column of chunk i is batch column K hc + i, with a rotation of its own
+        const bool strip = sc == cols / 2;
+        const F *p0 = tensor + half_at(0, sc, 4 * j, cols, K, rows2, rot_mask);
+        const size_t step = strip ? (size_t)rows2 : (size_t)(cols / 2) * rows2;
+        uint32_t st[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) st[q] = 0;
+        for (uint32_t i = 0; i < K; i++) {
+            uint32_t m[16], h[8];
+            load16w(strip && rot_mask ? tensor + half_at(i, sc, 4 * j, cols, K, rows2, rot_mask) : p0 + (size_t)i * step, m);
+            if (cj) conj16w(m);
+            blake3_compress64(m, h);
+#pragma unroll
+            for (int q = 0; q < 8; q++) { m[q] = h[q]; m[8 + q] = st[q]; }
+            blake3_compress64(m, st);
+        }
+        store8w(leaves + 32 * ((size_t)j * cols + c), st);
+    }
+}
+int launch_leaf_chain_half(hobbit_ctx *ctx, const F *tensor, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from, uint32_t rot_mask) {
+    if (((size_t)cols * half_trs) >> 32) return ctx->fail(HOBBIT_EINVAL, "leaf chain: more than 2^32 leaves");
+    const uint32_t zf = std::min((zero_rows_from + 3) / 4, half_trs);
+    ZeroDig zk = {};
+    if (zf < half_trs) blake3_zero_group_leaf(K, zk.w);
+    HB_LAUNCH(ctx, "k_leaf_chain_half", k_leaf_chain_half, dim3(grid_for((size_t)cols * zf, 256, 4096)), dim3(256), 0, tensor, (uint32_t)K, cols, half_trs, leaves, zf, zk,
+              rot_mask);
+    return 0;
+}
+// one element of the full tensor read from the half one: zero past rows_valid, conjugated past the middle column
+__device__ __forceinline__ F half_load(const F *__restrict__ tensor, uint32_t i, uint32_t c, uint32_t r, uint32_t cols, uint32_t K, uint32_t rows2, uint32_t rows_valid,
+                                       uint32_t rot_mask) {
+    if (r >= rows_valid) return fmake(0);
+    const F v = ldF(tensor + half_at(i, half_src_col(c, cols), r, cols, K, rows2, rot_mask));
+    return half_is_conj(c, cols) ? fconj(v) : v;
+}
+__global__ void k_gather_half(const F *__restrict__ tensor, uint32_t cols, uint32_t rows2, uint32_t K, const uint32_t *__restrict__ rows, const uint32_t *__restrict__ qcols,
+                              size_t nq, F *__restrict__ reply, uint32_t rows_valid, uint32_t rot_mask) {
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (g >= nq * K) return;
+    const size_t q = g / K; const uint32_t i = (uint32_t)(g % K);
+    stF(reply + g, half_load(tensor, i, qcols[q], rows[q], cols, K, rows2, rows_valid, rot_mask));
+}
+int launch_gather_half(hobbit_ctx *ctx, const F *tensor, uint32_t cols, uint32_t rows2, int K, const uint32_t *d_rows, const uint32_t *d_cols, size_t nq, F *d_reply,
+                       uint32_t rows_valid, uint32_t rot_mask) {
+    const size_t total = nq * K;
+    if (!total) return 0;
+    HB_LAUNCH(ctx, "k_gather_half", k_gather_half, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tensor, cols, rows2, (uint32_t)K, d_rows, d_cols, nq, d_reply,
+              rows_valid, rot_mask);
+    return 0;
+}
+__global__ void k_tensor_row_half(const F *__restrict__ tensor, uint32_t chunk, uint32_t K, uint32_t rows2, uint32_t cols, uint32_t row, F *__restrict__ out,
+                                  uint32_t rows_valid, uint32_t rot_mask) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < cols) stF(out + c, half_load(tensor, chunk, c, row, cols, K, rows2, rows_valid, rot_mask));
+}
+int launch_tensor_row_half(hobbit_ctx *ctx, const F *tensor, uint32_t chunk, int K, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid,
+                           uint32_t rot_mask) {
+    HB_LAUNCH(ctx, "k_tensor_row_half", k_tensor_row_half, dim3((cols + 255) / 256), dim3(256), 0, tensor, chunk, (uint32_t)K, rows2, cols, row, d_out, rows_valid, rot_mask);
+    return 0;
+}
+// The mirror that materialises the full linear tensor [K][cols][rows2] from the half one (hobbit_commitment_tensor_dev): one workgroup per
+// full column and pass, reads and writes contiguous along the rows; the implicit zeros become real ones and a rotated message half a linear one.
+__global__ void __launch_bounds__(256)
+k_half_expand(const F *__restrict__ tensor, F *__restrict__ full, uint32_t cols, uint32_t K, uint32_t rows2, uint32_t rows_valid, uint32_t rot_mask) {
+    const size_t ncols = (size_t)K * cols;
+    for (size_t gc = blockIdx.x; gc < ncols; gc += gridDim.x) {
+        const uint32_t i = (uint32_t)(gc / cols), c = (uint32_t)(gc % cols);
+        for (uint32_t r = threadIdx.x; r < rows2; r += blockDim.x) stF(full + gc * rows2 + r, half_load(tensor, i, c, r, cols, K, rows2, rows_valid, rot_mask));
+    }
+}
+int launch_half_expand(hobbit_ctx *ctx, const F *tensor, F *full, uint32_t cols, int K, uint32_t rows2, uint32_t rows_valid, uint32_t rot_mask) {
+    HB_LAUNCH(ctx, "k_half_expand", k_half_expand, dim3(grid_for((size_t)K * cols, 1, 65536)), dim3(256), 0, tensor, full, cols, (uint32_t)K, rows2, rows_valid, rot_mask);
+    return 0;
+}
+// (x, 0) per coefficient: the F form of a real vector
+__global__ void k_widen_real(const uint64_t *__restrict__ x, F *__restrict__ o, size_t n) {
+    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) stF(o + j, fmake(x[j]));
+}
+int launch_widen_real(hobbit_ctx *ctx, const uint64_t *x, F *o, size_t n) {
+    if (!n) return 0;
+    HB_LAUNCH(ctx, "k_widen_real", k_widen_real, dim3(grid_for(n, 256)), dim3(256), 0, x, o, n);
+    return 0;
+}
+// launch_aggregate over a real polynomial: aggr[j] = sum_i beta[i] * poly[i*M + j], each product two F_p products (beta.re x, beta.im x) -- what
+// fmul(beta, (x, 0)) gives, canonical either way -- and half the bytes read.  ACC continues from what aggr holds (slices of 64 chunks).
+template <bool ACC>
+__global__ void k_aggregate_real(const uint64_t *__restrict__ poly, size_t M, int K, AggCoef beta, F *__restrict__ aggr) {
+    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < M; j += (size_t)gridDim.x * blockDim.x) {
+        F acc = ACC ? ldF(aggr + j) : fmake(0);
+        for (int i = 0; i < K; i++) { const uint64_t x = poly[(size_t)i * M + j]; acc = fadd(acc, fmake(mulp(beta.b[i].re, x), mulp(beta.b[i].im, x))); }
+        stF(aggr + j, acc);
+    }
+}
+int launch_aggregate_real(hobbit_ctx *ctx, const uint64_t *poly, size_t M, int K, CHP h_beta, F *aggr) {
+    for (int i0 = 0; i0 < K; i0 += 64) {
+        const int k = K - i0 < 64 ? K - i0 : 64;
+        AggCoef cf;
+        for (int i = 0; i < 64; i++) cf.b[i] = i < k ? h_beta[i0 + i] : fmake(0);
+        if (i0 == 0) HB_LAUNCH(ctx, "k_aggregate_real", k_aggregate_real<false>, dim3(grid_for(M, 256)), dim3(256), 0, poly, M, k, cf, aggr);
+        else HB_LAUNCH(ctx, "k_aggregate_real", k_aggregate_real<true>, dim3(grid_for(M, 256)), dim3(256), 0, poly + (size_t)i0 * M, M, k, cf, aggr);
+    }
+    return 0;
+}
 // multilinear evaluation fold step of evaluate_vector (src/utils.cpp:789-802): v'[j] = (1-r) v[2j] + r v[2j+1]
 __global__ void k_eval_fold(const F *__restrict__ v, F *__restrict__ o, size_t L, F r) {
     for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < L; j += (size_t)gridDim.x * blockDim.x) {

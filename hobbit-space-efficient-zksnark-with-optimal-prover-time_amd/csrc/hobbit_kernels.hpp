@@ -2,6 +2,7 @@
 #pragma once
 #include "hobbit_ctx.hpp"
 #include "hobbit_rot.hpp"
+#include "hobbit_half.hpp"
 
 namespace hobbit {
 // The longest code: hobbit_graph_finalize, the rows-innermost encode, hobbit_parity_commit[_device] / hobbit_parity_open and the long forms of
@@ -66,6 +67,16 @@ int launch_zero_rows(hobbit_ctx *ctx, F *tensor, size_t ncols, uint32_t rows2, u
 int launch_tensor_row(hobbit_ctx *ctx, const F *chunk, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid, uint32_t rot_mask = 0);
 // a rotated message half made linear, in place: rows [0, rot_mask] of each of the ncols columns (hobbit_commitment_tensor_dev)
 int launch_unrotate_msg(hobbit_ctx *ctx, F *tensor, size_t ncols, uint32_t rows2, uint32_t rot_mask);
+// The half form of a commitment's tensor (hobbit_half.hpp): the leaf chain, the gather and the row read over columns 0 .. cols / 2 in memory, the
+// mirror that materialises the full linear tensor [K][cols][rows2], and the real-polynomial forms of the widening copy and the aggregate
+int launch_leaf_chain_half(hobbit_ctx *ctx, const F *tensor, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from, uint32_t rot_mask);
+int launch_gather_half(hobbit_ctx *ctx, const F *tensor, uint32_t cols, uint32_t rows2, int K, const uint32_t *d_rows, const uint32_t *d_cols, size_t nq, F *d_reply,
+                       uint32_t rows_valid, uint32_t rot_mask);
+int launch_tensor_row_half(hobbit_ctx *ctx, const F *tensor, uint32_t chunk, int K, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid,
+                           uint32_t rot_mask);
+int launch_half_expand(hobbit_ctx *ctx, const F *tensor, F *full, uint32_t cols, int K, uint32_t rows2, uint32_t rows_valid, uint32_t rot_mask);
+int launch_widen_real(hobbit_ctx *ctx, const uint64_t *x, F *o, size_t n);
+int launch_aggregate_real(hobbit_ctx *ctx, const uint64_t *poly, size_t M, int K, CHP h_beta, F *aggr);
 int launch_eval_fold(hobbit_ctx *ctx, const F *v, F *o, size_t L, F r);
 int launch_eval_fold2(hobbit_ctx *ctx, const F *v, F *o, size_t L, F r0, F r1);
 int launch_eval_tail(hobbit_ctx *ctx, const F *v, F *o, size_t n, int levels, const F *r);

@@ -14,6 +14,7 @@
 #include "hobbit_dev.hpp"
 #include "hobbit_libcgen.hpp"
 #include "../../include/hobbit_libcgen.h"
+#include "../../include/hobbit_real.h"
 
 using namespace hobbit;
 
@@ -101,6 +102,18 @@ __global__ __launch_bounds__(LANES) void k_libc_randomness(Window w0, const uint
     }
 }
 
+// the same elements as reals: img is 0 in this stream, so 8 bytes per value say everything (include/hobbit_real.h)
+__global__ __launch_bounds__(LANES) void k_libc_randomness_real(Window w0, const uint32_t *__restrict__ tab, uint64_t *__restrict__ out, uint64_t n) {
+    __shared__ uint32_t tile[LANES * PITCH]; __shared__ uint32_t ext[64];
+    wg_draws(w0, tab + TAB_GR, tab + TAB_LANE, blockIdx.x, tile, ext);
+    const uint64_t base = (uint64_t)blockIdx.x * GR_ELEMS;
+    const uint32_t cnt = (uint32_t)(n - base < GR_ELEMS ? n - base : GR_ELEMS);
+    for (uint32_t i = threadIdx.x; i < cnt; i += LANES) {
+        const uint32_t g = i / 100, d = 101 * g;
+        out[base + i] = (uint64_t)tile_at(tile, d) + tile_at(tile, d + 1 + (i - 100 * g));
+    }
+}
+
 // src/expanders.h:20-47: edge e takes target = rand() % R, weight = random()
 __global__ __launch_bounds__(LANES) void k_libc_graph_level(Window w0, const uint32_t *__restrict__ tab, uint32_t R, long long *__restrict__ nbr, F *__restrict__ wt, uint64_t edges) {
     __shared__ uint32_t tile[LANES * PITCH]; __shared__ uint32_t ext[64];
@@ -142,6 +155,12 @@ int launch_randomness(hobbit_ctx *ctx, const uint32_t w[DEG], size_t n, F *d_out
     const uint32_t *tab; uint32_t grid;
     HB_TRY(tables(ctx, &tab)); HB_TRY(grid_of(ctx, n, GR_ELEMS, &grid));
     HB_LAUNCH(ctx, "k_libc_randomness", k_libc_randomness, dim3(grid), dim3(LANES), 0, window_at(w, 0), tab, d_out, (uint64_t)n);
+    return 0;
+}
+int launch_randomness_real(hobbit_ctx *ctx, const uint32_t w[DEG], size_t n, uint64_t *d_out) {
+    const uint32_t *tab; uint32_t grid;
+    HB_TRY(tables(ctx, &tab)); HB_TRY(grid_of(ctx, n, GR_ELEMS, &grid));
+    HB_LAUNCH(ctx, "k_libc_randomness_real", k_libc_randomness_real, dim3(grid), dim3(LANES), 0, window_at(w, 0), tab, d_out, (uint64_t)n);
     return 0;
 }
 int launch_graph_level(hobbit_ctx *ctx, const uint32_t w[DEG], uint64_t first, uint64_t edges, uint32_t R, long long *d_nbr, F *d_w) {
@@ -195,6 +214,18 @@ int hobbit_generate_randomness_dev(hobbit_ctx *ctx, size_t n, hobbit_F *d_out) {
     }
     libcgen::jump(w, (uint64_t)n + (n + 99) / 100, w);
     return libcgen::write_back(w) == 0 ? 0 : ctx->fail(HOBBIT_ESTATE, "generate_randomness_dev: setstate failed");
+}
+int hobbit_generate_randomness_real_dev(hobbit_ctx *ctx, size_t n, uint64_t *d_out) {
+    uint32_t w[DEG];
+    if (libcgen::snapshot(w) != 0) return ctx->fail(HOBBIT_ESTATE, std::string("generate_randomness_real_dev: ") + NOT_TYPE3);
+    if (!n) return 0;
+    if (!d_out) return ctx->fail(HOBBIT_EINVAL, "generate_randomness_real_dev: null output");
+    {
+        libcgen::Guard guard;
+        HB_TRY(launch_randomness_real(ctx, w, n, d_out));
+    }
+    libcgen::jump(w, (uint64_t)n + (n + 99) / 100, w);
+    return libcgen::write_back(w) == 0 ? 0 : ctx->fail(HOBBIT_ESTATE, "generate_randomness_real_dev: setstate failed");
 }
 int hobbit_graph_draw(hobbit_ctx *ctx, long long n, long long *codeword_len) {
     if (n <= 0 || n > (1LL << CODE_MAX_LOG)) return ctx->fail(HOBBIT_EINVAL, "graph_draw: bad n");

@@ -24,10 +24,11 @@ static hobbit_orion *g_or = nullptr;                                // the last 
 static void *g_bds_levels = nullptr;                                // the last commit_brakedown_stream's levels
 static int g_commit_K = 0, g_commit_trs = 0; static size_t g_commit_cols = 0;
 static void *g_poly_dev = nullptr; static size_t g_poly_n = 0;      // device copy of the committed polynomial, kept for open_standard
+static bool g_poly_real = false;                                    // ... held as g_poly_n reals of 8 bytes (commit_standard_real)
 static uint8_t g_commit_root[32];
 // One older commitment stays alive beside the current one: prove_circuit_standard (src/main.cpp:985-1087) commits to the circuit polynomial
 // and to the witness before it opens either.  open_standard finds its commitment by the root of the Commitment_MT it is handed.
-struct CommitRec { hobbit_commitment *c = nullptr; int K = 0, trs = 0; size_t cols = 0; void *poly = nullptr; size_t n = 0; uint8_t root[32]; };
+struct CommitRec { hobbit_commitment *c = nullptr; int K = 0, trs = 0; size_t cols = 0; void *poly = nullptr; size_t n = 0; bool real = false; uint8_t root[32]; };
 static CommitRec g_prev;
 static void free_prev() {
     if (g_prev.c) hobbit_commitment_free(g_prev.c);
@@ -35,8 +36,8 @@ static void free_prev() {
     g_prev = CommitRec();
 }
 static void swap_with_prev() {
-    CommitRec cur; cur.c = g_commit; cur.K = g_commit_K; cur.trs = g_commit_trs; cur.cols = g_commit_cols; cur.poly = g_poly_dev; cur.n = g_poly_n; memcpy(cur.root, g_commit_root, 32);
-    g_commit = g_prev.c; g_commit_K = g_prev.K; g_commit_trs = g_prev.trs; g_commit_cols = g_prev.cols; g_poly_dev = g_prev.poly; g_poly_n = g_prev.n; memcpy(g_commit_root, g_prev.root, 32);
+    CommitRec cur; cur.c = g_commit; cur.K = g_commit_K; cur.trs = g_commit_trs; cur.cols = g_commit_cols; cur.poly = g_poly_dev; cur.n = g_poly_n; cur.real = g_poly_real; memcpy(cur.root, g_commit_root, 32);
+    g_commit = g_prev.c; g_commit_K = g_prev.K; g_commit_trs = g_prev.trs; g_commit_cols = g_prev.cols; g_poly_dev = g_prev.poly; g_poly_n = g_prev.n; g_poly_real = g_prev.real; memcpy(g_commit_root, g_prev.root, 32);
     g_prev = cur;
 }
 // make the commitment whose tree is `MT` the current one (no-op when it already is, or when the caller passes no tree)
@@ -329,7 +330,7 @@ void commit_standard(vector<F> &poly, _hash &comm, vector<vector<_hash>> &MT_has
     hobbit_host_ctx();
     lap("context ready");
     free_prev();
-    if (g_commit) { swap_with_prev(); g_commit = nullptr; g_poly_dev = nullptr; g_poly_n = 0; }
+    if (g_commit) { swap_with_prev(); g_commit = nullptr; g_poly_dev = nullptr; g_poly_n = 0; g_poly_real = false; }
     // the device copy of poly is kept: open_standard receives the same vector and would otherwise pay the PCIe upload again
     HCHK(hobbit_malloc(hobbit_host_ctx(), N * sizeof(F), &g_poly_dev)); g_poly_n = N;
     if (getenv("HOBBIT_HOST_BLOCKING_UPLOAD")) {                    // the round-2 form, for A/B: one blocking copy of the whole vector, then the commit
@@ -464,6 +465,7 @@ static void open_standard_rs(vector<F> &poly, vector<F> &x, vector<vector<_hash>
     ps += MT_ps;
     vt += std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t0).count();
 }
+static void open_lin_on_device(size_t N, vector<F> &x, vector<vector<_hash>> &Commitment_MT, int K, double &vt, double &ps);
 void open_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>> &Commitment_MT, vector<vector<vector<F>>> &_tensor, int K, double &vt, double &ps) {
     (void)_tensor;
     select_commitment(Commitment_MT);
@@ -471,14 +473,20 @@ void open_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>> &Commitme
     const size_t N = poly.size(), M = N / K;
     BUFFER_SPACE = M;
     if (!linear_time) { open_standard_rs(poly, x, Commitment_MT, K, vt, ps); return; }
+    if (!g_poly_dev || g_poly_n != N || g_poly_real || getenv("HOBBIT_HOST_REUPLOAD")) {
+        if (g_poly_dev) hobbit_free(hobbit_host_ctx(), g_poly_dev);
+        HCHK(hobbit_malloc(hobbit_host_ctx(), N * sizeof(F), &g_poly_dev)); g_poly_n = N; g_poly_real = false;
+        HCHK(hobbit_memcpy_h2d(g_ctx, g_poly_dev, poly.data(), N * sizeof(F)));
+    }
+    open_lin_on_device(N, x, Commitment_MT, K, vt, ps);
+}
+// the opening of the current commitment over the device polynomial it kept (F elements, or reals after commit_standard_real), and the
+// reference's proof-size accounting
+static void open_lin_on_device(size_t N, vector<F> &x, vector<vector<_hash>> &Commitment_MT, int K, double &vt, double &ps) {
+    const size_t M = N / K;
     const int queries = 5900; aggregation_queries = queries;
     const int trs = g_commit_trs; const size_t cols = g_commit_cols;
     const int R1 = (int)log2((double)(2 * trs)), logc = (int)log2((double)cols), R3 = R1 + logc, depth = (int)log2((double)M);
-    if (!g_poly_dev || g_poly_n != N || getenv("HOBBIT_HOST_REUPLOAD")) {
-        if (g_poly_dev) hobbit_free(hobbit_host_ctx(), g_poly_dev);
-        HCHK(hobbit_malloc(hobbit_host_ctx(), N * sizeof(F), &g_poly_dev)); g_poly_n = N;
-        HCHK(hobbit_memcpy_h2d(g_ctx, g_poly_dev, poly.data(), N * sizeof(F)));
-    }
     hobbit_host_open_transcript &t = g_open;
     t.queries = queries; t.rounds = R1 + logc + 2 * R3 + logc;
     t.cols.assign(queries, 0); t.rows.assign(queries, 0); t.reply.assign((size_t)queries * K, F(0)); t.paths.assign((size_t)queries * depth * 32, 0);
@@ -486,7 +494,8 @@ void open_standard(vector<F> &poly, vector<F> x, vector<vector<_hash>> &Commitme
     SpBuffers bc(t.sp_c, (size_t)trs * cols, 32), bf(t.sp_f, M, 32);
     hobbit_open_out o{t.cols.data(), t.rows.data(), hF(t.reply.data()), t.paths.data(), hF(t.qpoly.data()), hF(t.r.data()), hF(t.vr.data()), hF(t.fin.data()),
                       hF(t.scalars.data()), t.checks, t.roots, &bc.o, &bf.o};
-    HCHK(hobbit_open_standard(g_ctx, (const hobbit_F *)g_poly_dev, N, g_commit, hF(x.data()), queries, &o));
+    if (g_poly_real) HCHK(hobbit_open_standard_real(g_ctx, (const uint64_t *)g_poly_dev, N, g_commit, hF(x.data()), queries, &o));
+    else HCHK(hobbit_open_standard(g_ctx, (const hobbit_F *)g_poly_dev, N, g_commit, hF(x.data()), queries, &o));
     if (!t.checks[0]) { printf("Error recursion 1\n"); exit(-1); }                         // src/PC_utils.cpp:323-326
     if (!t.checks[1]) { printf("Error recursion 2\n"); exit(-1); }                         // :364-367
     if (!t.checks[2]) { printf("Error in fft\n"); exit(-1); }                              // src/sumcheck.cpp:3016-3019
@@ -1815,6 +1824,57 @@ void test_PC(size_t N, int option, int K) {
     double vt = 0.0, ps = 0.0;
     start = std::chrono::steady_clock::now();
     open_standard(poly, generate_randomness((int)log2((double)poly.size())), MT_hashes, _tensor, K, vt, ps);
+    end = std::chrono::steady_clock::now();
+    double total = commit_time + std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    std::cout << "Total time: " << total << " seconds" << std::endl;
+    printf("%lf,%lf\n", ps, vt);
+}
+
+// ---- base-field polynomials (include/hobbit_real.h) ------------------------------------------------------
+// commit_standard for a polynomial held on the device as N reals of 8 bytes: a half commitment.  The mirror takes the buffer over (it is
+// freed with the commitment) and keeps it for open_standard_real.  MT_hashes as commit_standard returns them; no _tensor is materialised.
+void commit_standard_real(uint64_t *d_poly, size_t N, vector<vector<_hash>> &MT_hashes, int K) {
+    const size_t M = N / K;
+    hobbit_host_ctx();
+    free_prev();
+    if (g_commit) { swap_with_prev(); g_commit = nullptr; }
+    g_poly_dev = d_poly; g_poly_n = N; g_poly_real = true;
+    HCHK(hobbit_commit_standard_real(g_ctx, d_poly, N, K, tensor_row_size, linear_time ? 1 : 0, &g_commit));
+    HCHK(hobbit_sync(g_ctx));
+    g_commit_K = K; g_commit_trs = tensor_row_size; g_commit_cols = 2 * M / tensor_row_size;
+    size_t levels = (size_t)log2((double)M) + 1, off = 0;
+    MT_hashes.resize(levels);
+    const uint8_t *d_lv = (const uint8_t *)hobbit_commitment_levels_dev(g_commit);
+    for (size_t l = 0, sz = M; l < levels; l++, sz /= 2) { MT_hashes[l].resize(sz); HCHK(hobbit_memcpy_d2h(g_ctx, MT_hashes[l].data(), d_lv + 32 * off, 32 * sz)); off += sz; }
+    memcpy(g_commit_root, MT_hashes.back()[0].arr, 32);
+}
+void open_standard_real(size_t N, vector<F> x, vector<vector<_hash>> &Commitment_MT, int K, double &vt, double &ps) {
+    select_commitment(Commitment_MT);
+    if (!g_commit || g_commit_K != K || !g_poly_real || g_poly_n != N) { printf("Error: open_standard_real without a matching commit_standard_real\n"); exit(-1); }
+    BUFFER_SPACE = N / K;
+    open_lin_on_device(N, x, Commitment_MT, K, vt, ps);
+}
+// test_PC option 4 with the polynomial drawn on the device as reals: the same libc draws in the same order, the same root and Ps
+void test_PC_real(size_t N, int K) {
+    uint64_t *d_poly = nullptr;
+    HCHK(hobbit_malloc(hobbit_host_ctx(), N * sizeof(uint64_t), (void **)&d_poly));
+    HCHK(hobbit_generate_randomness_real_dev(g_ctx, N, d_poly));
+    linear_time = true;
+    tensor_row_size = (int)(N / (K * 1ULL << (11)));
+    printf("%d\n", tensor_row_size);
+    expander_init_store(tensor_row_size);
+    vector<vector<_hash>> MT_hashes;
+    auto start = std::chrono::steady_clock::now();
+    commit_standard_real(d_poly, N, MT_hashes, K);
+    auto end = std::chrono::steady_clock::now();
+    double commit_time = std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    std::cout << "Commit time: " << commit_time << " seconds" << std::endl;
+    printf("root ");
+    for (int i = 0; i < 32; i++) printf("%02x", MT_hashes.back()[0].arr[i]);
+    printf("\n");
+    double vt = 0.0, ps = 0.0;
+    start = std::chrono::steady_clock::now();
+    open_standard_real(N, generate_randomness((int)log2((double)N)), MT_hashes, K, vt, ps);
     end = std::chrono::steady_clock::now();
     double total = commit_time + std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
     std::cout << "Total time: " << total << " seconds" << std::endl;

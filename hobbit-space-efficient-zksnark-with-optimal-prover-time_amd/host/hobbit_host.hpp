@@ -20,6 +20,7 @@
 #include "hobbit_longcodes.h"
 #include "hobbit_orion.h"
 #include "hobbit_libcgen.h"
+#include "hobbit_real.h"
 
 using std::vector;
 
@@ -154,6 +155,13 @@ void compute_tensorcode(vector<F> &message, vector<vector<F>> &tensor);
 /* src/Our_PC.hpp:11-15 */
 void commit_standard(vector<F> &poly, _hash &comm, vector<vector<_hash>> &MT_hashes, vector<vector<vector<F>>> &_tensor, int K);
 void test_PC(size_t N, int option, int K);                                          /* options 4, 1 and 3 (Brakedown) */
+/* Base-field polynomials (include/hobbit_real.h): commit_standard / open_standard (linear_time, tensor_row_size set as for commit_standard) for a
+ * polynomial that lives on the device as N reals of 8 bytes.  commit_standard_real takes the device buffer (from hobbit_malloc) over and makes a
+ * half commitment; open_standard_real opens it.  test_PC_real is test_PC's option 4 with the polynomial drawn on the device as reals
+ * (`host/test_pc real <logN> <K>`): the same libc draws in the same order, the same root and Ps. */
+void commit_standard_real(uint64_t *d_poly, size_t N, vector<vector<_hash>> &MT_hashes, int K);
+void open_standard_real(size_t N, vector<F> x, vector<vector<_hash>> &Commitment_MT, int K, double &vt, double &ps);
+void test_PC_real(size_t N, int K);
 /* src/Our_PC.hpp: the Brakedown comparison baseline (src/Our_PC.cpp:197-236, 432-520).  commit_standard_brakedown draws the row code's graphs
  * (expander_init_store(B)) and keeps the encoded matrix on the device; open_brakedown_standard draws r (rows x random()) and the 2900 columns
  * (rand() % 2B), opens, and prints the reference's "PC Open: pt = .., ps = .. KB, vt = .. sec" line. */

@@ -4,6 +4,7 @@
 // baseline: test_PC's last branch, which test_PC itself keeps refusing) and `brakingbase <logN> <K>` (the Braking base baseline: test_PC's
 // option 5, which test_PC itself keeps refusing; shapes outside 4 <= K <= 512, 128 <= N / K <= 2^20 print an error and return 255) and
 // `brakingbase_any <logN> <K>` (the same baseline through include/hobbit_longcodes.h: N / K up to 2^21, which `28 5 128` of PC_tests.sh needs) and
+// `real <logN> <K>` (option 4 with the polynomial drawn on the device as base-field values of 8 bytes and committed as a half commitment) and
 // `orion <logN>` (the Orion baseline: test_PC's option 2, which test_PC itself keeps refusing; logN even in [14, 28], else an error and 255)
 // (src/main.cpp:1176: test_PC(1ULL<<atoi(argv[1]), atoi(argv[2]), atoi(argv[3]))) over the
 // device-backed host mirror.  Build: see __graft_entry__.build_host().
@@ -16,12 +17,18 @@ int main(int argc, char **argv) {
     const bool bbase = argc == 4 && std::string(argv[1]) == "brakingbase";
     const bool bbase_any = argc == 4 && std::string(argv[1]) == "brakingbase_any";
     const bool orion = argc == 3 && std::string(argv[1]) == "orion";
+    const bool real = argc == 4 && std::string(argv[1]) == "real";
     if (argc < 4 && !whir && !orion) {
-        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>   |   %s brakingbase_any <logN> <K>   |   %s orion <logN>\n",
-               argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>   |   %s brakingbase_any <logN> <K>   |   %s orion <logN>   |   %s real <logN> <K>\n",
+               argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 1;
     }
     init_hash();
+    if (real) {                                       // option 4 on a base-field polynomial (include/hobbit_real.h): same root and Ps as `<logN> 4 <K>`
+        const int logn = atoi(argv[2]), K = atoi(argv[3]);
+        if (logn < 1 || logn > 40 || K <= 0 || ((1ULL << logn) / K) % 2048 || (1ULL << logn) / K < 2048 * 4) { printf("Error: real takes N = 2^n and K with N / (2048 K) a multiple of 4\n"); return 255; }
+        test_PC_real(1ULL << logn, K);
+    } else
     if (orion) {                                      // src/Our_PC.cpp:780-793
         const int logn = atoi(argv[2]);
         if (logn < 14 || logn > 28 || (logn & 1)) { printf("Error: Orion takes N = 2^n with n even and 14 <= n <= 28\n"); return 255; }
