@@ -95,6 +95,12 @@ REAL_SYMBOLS = [
 ]
 HOBBIT_EINVAL = -2
 
+# every symbol include/hobbit_elastic_real.h declares (checked by tests/test_elastic_real_cpu.py)
+ELASTIC_REAL_SYMBOLS = [
+    "hobbit_fft_real_rows_any", "hobbit_elastic_begin_real", "hobbit_elastic_push_real", "hobbit_elastic_device_bytes",
+    "hobbit_elastic_open_aggregate_push_real", "hobbit_elastic_open_reply_push_real",
+]
+
 # every symbol include/hobbit_orion.h declares (checked by tests/test_orion.py)
 ORION_SYMBOLS = [
     "hobbit_encode_interleaved_ld", "hobbit_encode_interleaved_ld_order", "hobbit_orion_gather", "hobbit_orion_grid_paths", "hobbit_orion_shape",
@@ -216,7 +222,11 @@ def load_library(path=LIB_PATH):
         "hobbit_widen_real": [V, V, V, S], "hobbit_fft_real_rows": [V, V, S, V], "hobbit_commit_standard_real": [V, V, S, I, I, I, V],
         "hobbit_commit_standard_real_host": [V, V, V, S, I, I, I, V], "hobbit_commitment_is_half": [V], "hobbit_aggregate_real": [V, V, S, V, I, V],
         "hobbit_open_standard_real": [V, V, S, V, V, I, V], "hobbit_generate_randomness_real_dev": [V, S, V],
+        # include/hobbit_elastic_real.h
+        "hobbit_fft_real_rows_any": [V, V, S, I, V], "hobbit_elastic_begin_real": [V, S, I, I, I, V], "hobbit_elastic_push_real": [V, V, V],
+        "hobbit_elastic_device_bytes": [V], "hobbit_elastic_open_aggregate_push_real": [V, V, V], "hobbit_elastic_open_reply_push_real": [V, V, V],
     }
+    lib.hobbit_elastic_device_bytes.restype = c_sz
     lib.hobbit_libc_jump.restype = None
     lib.hobbit_libc_draws_shape.restype = None
     lib.hobbit_orion_free.restype = None
@@ -1554,9 +1564,10 @@ class Hobbit:
         out[:, 0] = np.arange(B, dtype=np.uint64) % np.uint64(1024) + np.uint64(1)
         return out
 
-    def elastic_open(self, N, B, x, queries=700, commit_levels=None, chunk=None, shockwave=True):
+    def elastic_open(self, N, B, x, queries=700, commit_levels=None, chunk=None, shockwave=True, _real=False):
         """Elastic_PC::open, option 1 (src/Elastic_PC.cpp:625-726), prover side.  commit_levels: DeviceBuffer with the commitment tree
         (hobbit_elastic_finish) or None; chunk: DeviceBuffer of the (repeating) read_stream chunk, built here if None."""
+        push_aggr, push_reply = self._elastic_open_pushes(_real)
         x = Fh(x).reshape(-1, 2)
         trs = B >> 11; cols = 4096; K = N // B
         logc = 12; logr = (2 * trs).bit_length() - 1; logt = logr - 1
@@ -1564,12 +1575,12 @@ class Hobbit:
         self._chk(self.lib.hobbit_elastic_open_begin(self.ctx, N, B, trs, _hp(x), queries, ctypes.byref(e)))
         try:
             if chunk is None:
-                chunk = self.to_device(self.read_stream(B))
+                chunk = self.to_device(self.read_stream_real(B) if _real else self.read_stream(B))
             for _ in range(K):
-                self._chk(self.lib.hobbit_elastic_open_aggregate_push(self.ctx, e, chunk.ptr))
+                self._chk(push_aggr(self.ctx, e, chunk.ptr))
             self._chk(self.lib.hobbit_elastic_open_aggregate_finish(self.ctx, e))
             for _ in range(K):
-                self._chk(self.lib.hobbit_elastic_open_reply_push(self.ctx, e, chunk.ptr))
+                self._chk(push_reply(self.ctx, e, chunk.ptr))
             maxr = (2048 * 2 * trs).bit_length() - 1 + logr + (logt + logc) + logc
             depth = (4 * B).bit_length() - 1
             res = dict(cols=np.zeros(queries, np.uint32), rows=np.zeros(queries, np.uint32), rv0=np.zeros(2, np.uint64), reply=np.zeros((queries, K, 2), np.uint64),
@@ -1596,11 +1607,12 @@ class Hobbit:
             res["sp_f"] = self._sp_trim(sp[0], B, 32)
         return res
 
-    def elastic_open2(self, N, B, x, queries=5900, commit_levels=None, chunks=None):
+    def elastic_open2(self, N, B, x, queries=5900, commit_levels=None, chunks=None, _real=False):
         """Elastic_PC::open, option 2 (RS x expander; src/Elastic_PC.cpp:625-726 under linear_time), prover side.  The expander graphs for
         tensor_row_size = B >> 14 must have been uploaded (upload_graphs).  chunks: None = the reference's repeating read_stream chunk; or a
         callable i -> host array (B, 2) / DeviceBuffer, called once per pass and chunk in stream order."""
         x = Fh(x).reshape(-1, 2)
+        push_aggr, push_reply = self._elastic_open_pushes(_real)
         trs = B >> 14; cols = 2 * B // trs; K = N // B
         logc = cols.bit_length() - 1; R1 = (2 * trs).bit_length() - 1; logt = R1 - 1
         e = c_vp()
@@ -1609,18 +1621,18 @@ class Hobbit:
             nc, nr, npad = c_int(), c_int(), c_sz()
             self.lib.hobbit_elastic_open_dims(e, ctypes.byref(nc), ctypes.byref(nr), ctypes.byref(npad))
             nc, nr, npad = nc.value, nr.value, npad.value
-            resident = self.to_device(self.read_stream(B)) if chunks is None else None
+            resident = self.to_device(self.read_stream_real(B) if _real else self.read_stream(B)) if chunks is None else None
 
             def chunk(i):
                 if resident is not None:
                     return resident
                 c = chunks(i)
-                return c if isinstance(c, DeviceBuffer) else self.to_device(Fh(c).reshape(-1, 2))
+                return c if isinstance(c, DeviceBuffer) else self.to_device(self._reals(c) if _real else Fh(c).reshape(-1, 2))
             for i in range(K):
-                self._chk(self.lib.hobbit_elastic_open_aggregate_push(self.ctx, e, chunk(i).ptr))
+                self._chk(push_aggr(self.ctx, e, chunk(i).ptr))
             self._chk(self.lib.hobbit_elastic_open_aggregate_finish(self.ctx, e))
             for i in range(K):
-                self._chk(self.lib.hobbit_elastic_open_reply_push(self.ctx, e, chunk(i).ptr))
+                self._chk(push_reply(self.ctx, e, chunk(i).ptr))
             R3 = npad.bit_length() - 1
             rounds = R1 + logc + R3 + logc
             depth = (4 * B).bit_length() - 1
@@ -1646,6 +1658,70 @@ class Hobbit:
         res["I"] = np.stack([res["cols"], res["rows"]], axis=1)
         res["sp_f"] = self._sp_trim(spf[0], B, 32); res["sp_c"] = self._sp_trim(spc[0], npad, 32)
         return res
+
+    # ---- Elastic_PC on base-field streams (include/hobbit_elastic_real.h): chunks of B canonical values < p, 8 bytes each
+    def _elastic_open_pushes(self, real):
+        if real:
+            return self.lib.hobbit_elastic_open_aggregate_push_real, self.lib.hobbit_elastic_open_reply_push_real
+        return self.lib.hobbit_elastic_open_aggregate_push, self.lib.hobbit_elastic_open_reply_push
+
+    def read_stream_PC_real(self, B):
+        """the real parts of read_stream_PC's default stream (its img is 0 throughout): n = 322322; v[i] = n; n = n*n + i (mod p)"""
+        out = np.zeros(B, np.uint64)
+        n = 322322
+        for i in range(B):
+            out[i] = n
+            n = (n * n + i) % P
+        return out
+
+    def read_stream_real(self, B):
+        """the real parts of read_stream's default stream: v[i] = i % 1024 + 1"""
+        return np.arange(B, dtype=np.uint64) % np.uint64(1024) + np.uint64(1)
+
+    def fft_real_rows_any(self, rows, logL):
+        """rows: (R, L/2) reals, L = 2^logL -> (R, L/2 + 1, 2): columns 0 .. L/2 of the L-point row code of each zero-padded row"""
+        a = np.ascontiguousarray(rows, dtype=np.uint64)
+        h = 1 << (logL - 1)
+        assert a.ndim == 2 and a.shape[1] == h
+        d = self.to_device(a); o = self.alloc(16 * (h + 1) * a.shape[0])
+        self._chk(self.lib.hobbit_fft_real_rows_any(self.ctx, c_vp(d.ptr), c_sz(a.shape[0]), c_int(logL), c_vp(o.ptr)))
+        return self.to_host(o, (a.shape[0], h + 1, 2), np.uint64)
+
+    def elastic_commit_real(self, N, B, opt, gcc_arg_order=1, chunk=None, keep_levels=False, levels="host", chunks=None):
+        """elastic_commit on a base-field stream through half chunk tensors.  chunk: a DeviceBuffer holding the stream's (repeating) chunk of B
+        uint64, read_stream_PC_real(B) if None; chunks: a callable i -> host array of B uint64 / DeviceBuffer, for a stream whose chunks differ."""
+        if opt == 1:
+            lin, trs = 0, B >> 11
+        else:
+            lin, trs = 1, B >> 14
+            self.expander_init_store(trs)
+        e = c_vp()
+        self._chk(self.lib.hobbit_elastic_begin_real(self.ctx, B, trs, lin, gcc_arg_order, ctypes.byref(e)))
+        try:
+            if chunks is None and chunk is None:
+                chunk = self.to_device(self.read_stream_PC_real(B))
+            for i in range(N // B):
+                c = chunk if chunks is None else chunks(i)
+                c = c if isinstance(c, DeviceBuffer) else self.to_device(self._reals(c))
+                self._chk(self.lib.hobbit_elastic_push_real(self.ctx, e, c.ptr))
+            lv = self.alloc(32 * 8 * B)
+            self._chk(self.lib.hobbit_elastic_finish(self.ctx, e, lv.ptr))
+            if levels == "device":
+                root = np.zeros(32, np.uint8)
+                self._chk(self.lib.hobbit_memcpy_d2h(self.ctx, root.ctypes.data, lv.ptr + 32 * (8 * B - 2), 32))
+                return root, lv
+            out = self.to_host(lv, (8 * B - 1, 32), np.uint8)
+        finally:
+            self.lib.hobbit_elastic_free(e)
+        return (out, lv) if keep_levels else out
+
+    def elastic_open_real(self, N, B, x, queries=700, commit_levels=None, chunk=None, shockwave=True):
+        """elastic_open on a base-field stream: both passes take chunks of B uint64 (chunk: a DeviceBuffer, read_stream_real(B) if None)"""
+        return self.elastic_open(N, B, x, queries, commit_levels, chunk, shockwave, _real=True)
+
+    def elastic_open2_real(self, N, B, x, queries=5900, commit_levels=None, chunks=None):
+        """elastic_open2 on a base-field stream; chunks: None or a callable i -> host array of B uint64 / DeviceBuffer"""
+        return self.elastic_open2(N, B, x, queries, commit_levels, chunks, _real=True)
 
     def open_standard_rs(self, poly, c, x, queries=790, want_paths=True, shockwave=True):
         """Our_PC open_standard with linear_time == false (test_PC option 1, src/Our_PC.cpp:604-692), prover side.  poly: host array or

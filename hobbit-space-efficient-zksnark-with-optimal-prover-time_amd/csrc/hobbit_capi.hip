@@ -16,6 +16,7 @@
 #include "hobbit_libcgen.hpp"
 #include "../../include/hobbit_whir.h"
 #include "../../include/hobbit_real.h"
+#include "../../include/hobbit_elastic_real.h"
 
 using namespace hobbit;
 
@@ -1085,6 +1086,7 @@ int hobbit_commitment_path(hobbit_ctx *ctx, const hobbit_commitment *c, size_t c
 struct hobbit_elastic {
     hobbit_ctx *ctx; size_t B; int trs, lin, shift; uint32_t cols, rows2; size_t count;
     mem::Pooled<F> t[4]; mem::Pooled<uint8_t> state;
+    bool real = false;              // hobbit_elastic_begin_real: t[] are half chunk tensors (hobbit_half.hpp), the chunks are base-field values
 };
 int hobbit_elastic_begin(hobbit_ctx *ctx, size_t B, int trs, int linear_time, int gcc_arg_order, hobbit_elastic **out) {
     if (!out) return HOBBIT_EINVAL;
@@ -1102,6 +1104,7 @@ int hobbit_elastic_begin(hobbit_ctx *ctx, size_t B, int trs, int linear_time, in
     return 0;
 }
 int hobbit_elastic_push(hobbit_ctx *ctx, hobbit_elastic *e, const hobbit_F *d_chunk) {
+    if (e->real) return ctx->fail(HOBBIT_ESTATE, "elastic_push: the handle takes base-field chunks (hobbit_elastic_push_real)");
     const int slot = (int)(e->count % 4);
     HB_TRY(tensorcode_chunks(ctx, cF(d_chunk), e->B, 1, e->trs, e->lin, e->t[slot]));   // an all-zero chunk encodes to zeros (:206-226)
     if (slot == 3) HB_TRY(launch_elastic_leaf(ctx, e->t[0], e->t[1], e->t[2], e->t[3], e->rows2, e->cols, e->shift, e->state));
@@ -1111,6 +1114,7 @@ int hobbit_elastic_push(hobbit_ctx *ctx, hobbit_elastic *e, const hobbit_F *d_ch
 // Multi-GPU form of the push: the 4th chunk of a group writes the group's inner digests (4B x 32 B, the reference's leaf order) to
 // d_digests instead of chaining them into the running leaves; the owner of each leaf range chains what it receives (hobbit_chain_digests).
 int hobbit_elastic_push_inner(hobbit_ctx *ctx, hobbit_elastic *e, const hobbit_F *d_chunk, uint8_t *d_digests) {
+    if (e->real) return ctx->fail(HOBBIT_ESTATE, "elastic_push_inner: the handle takes base-field chunks (hobbit_elastic_push_real)");
     const int slot = (int)(e->count % 4);
     HB_TRY(tensorcode_chunks(ctx, cF(d_chunk), e->B, 1, e->trs, e->lin, e->t[slot]));
     if (slot == 3) {
@@ -1125,6 +1129,57 @@ int hobbit_elastic_finish(hobbit_ctx *ctx, hobbit_elastic *e, uint8_t *d_levels)
     return launch_merkle_levels(ctx, d_levels, 4 * e->B, 1);                    // :277-283
 }
 void hobbit_elastic_free(hobbit_elastic *e) { delete e; }
+
+// ---- the streaming commit on base-field chunks (include/hobbit_elastic_real.h) ---------------------------------
+// The handle's four tensors are HALF chunk tensors: columns 0 .. cols / 2, codeword-major (hobbit_half.hpp).  The row code writes them
+// (fft::real_rows_any), the column code runs over cols / 2 + 1 columns, and k_elastic_leaf_half answers the other columns as conjugates.
+// RS x expander: the finalized graphs must have base-field weights, as for hobbit_commit_standard_real.
+static int elastic_real_code(hobbit_ctx *ctx, int trs, int lin, const char *who) {
+    if (!lin) return 0;
+    if (trs > 13 && ctx->code.n != trs) return ctx->fail(HOBBIT_ESTATE, std::string(who) + ": expander graphs for n = trs not finalized");
+    if (trs <= 13 && ctx->code.n != trs) { long long l; HB_TRY(hobbit_graph_finalize(ctx, trs, &l)); }
+    if (!ctx->code.real_weights)
+        return ctx->fail(HOBBIT_EINVAL, std::string(who) + ": a weight of the finalized graphs has img != 0, so column cols - c is not the conjugate of column c");
+    return 0;
+}
+int hobbit_elastic_begin_real(hobbit_ctx *ctx, size_t B, int trs, int linear_time, int gcc_arg_order, hobbit_elastic **out) {
+    if (!out) return HOBBIT_EINVAL;
+    *out = nullptr;
+    if (trs <= 0 || ilog2_exact((size_t)trs) < 0 || B % (size_t)trs || ilog2_exact(B) < 0) return ctx->fail(HOBBIT_EINVAL, "elastic_begin_real: B and trs must be powers of two, trs dividing B");
+    const int logc = ilog2_exact(2 * B / (size_t)trs);
+    if (logc < 3 || logc > 16) return ctx->fail(HOBBIT_EINVAL, "elastic_begin_real: the row code 2B/trs must have 2^3 .. 2^16 points");
+    if (!linear_time && 2 * trs > 4096) return ctx->fail(HOBBIT_EINVAL, "elastic_begin_real: RSxRS needs 2*trs <= 4096");
+    HB_TRY(elastic_real_code(ctx, trs, linear_time, "elastic_begin_real"));
+    Handle<hobbit_elastic, hobbit_elastic_free> e(new hobbit_elastic());
+    e->ctx = ctx; e->B = B; e->trs = trs; e->lin = linear_time; e->shift = gcc_arg_order ? 1 : 0; e->count = 0; e->real = true;
+    e->cols = (uint32_t)(2 * B / trs); e->rows2 = (uint32_t)(2 * trs);
+    bool ok = true;
+    for (int i = 0; i < 4 && ok; i++) ok = ctx->pool_get((size_t)(e->cols / 2 + 1) * e->rows2 * sizeof(F), e->t[i]) == 0;
+    ok = ok && ctx->pool_get(4 * B * 32, e->state) == 0;
+    if (!ok) return ctx->fail(HOBBIT_ENOMEM, "elastic_begin_real: allocation failed");
+    HB_TRY(launch_zero(ctx, e->state, 4 * B * 32));
+    *out = e.release();
+    return 0;
+}
+int hobbit_elastic_push_real(hobbit_ctx *ctx, hobbit_elastic *e, const uint64_t *d_chunk) {
+    if (!e->real) return ctx->fail(HOBBIT_ESTATE, "elastic_push_real: the handle takes F chunks (hobbit_elastic_push)");
+    if (!d_chunk) return ctx->fail(HOBBIT_EINVAL, "elastic_push_real: null chunk");
+    HB_TRY(elastic_real_code(ctx, e->trs, e->lin, "elastic_push_real"));
+    const int slot = (int)(e->count % 4);
+    const uint32_t hcols = e->cols / 2 + 1;
+    F *t = e->t[slot];
+    HB_TRY(fft::real_rows_any(ctx, d_chunk, (size_t)e->trs, ilog2_exact(e->cols), t, true, (uint32_t)e->trs));
+    if (e->lin) HB_TRY(launch_encode(ctx, t, e->rows2, t, e->rows2, e->trs, hcols, 0));
+    else HB_TRY(fft::rows(ctx, t, e->rows2, (uint32_t)e->trs, t, e->rows2, 1, ilog2_exact(e->rows2), false, 1, hcols, 0, 0));
+    if (slot == 3) HB_TRY(launch_elastic_leaf_half(ctx, e->t[0], e->t[1], e->t[2], e->t[3], e->rows2, e->cols, e->shift, e->lin, e->state));
+    e->count++;
+    return 0;
+}
+size_t hobbit_elastic_device_bytes(const hobbit_elastic *e) {
+    size_t b = e->state.bytes();
+    for (int i = 0; i < 4; i++) b += e->t[i].bytes();
+    return b;
+}
 
 // ---- inner PCS commitments of the opening (src/Virgo.cpp:104-178) --------------------------------------
 // rows zero-padded to twice their length and transformed: d_enc row i = FFT(row i of d_poly | zeros)
@@ -1871,6 +1926,12 @@ struct hobbit_elastic_open {
     hobbit_ctx *ctx; size_t N, B, K; int trs, queries; uint32_t cols, rows2;
     std::vector<F> beta; std::vector<uint32_t> qc, qr, ucols, qci; F rv0;
     size_t n_aggr, n_reply; bool committed;
+    enum Form { NONE, FULL, REAL };                         // what a pass has been fed so far: F chunks or base-field chunks (include/hobbit_elastic_real.h), never both
+    Form aggr_form = NONE, reply_form = NONE;
+    int form(Form &pass, Form f, const char *who) {
+        if (pass != NONE && pass != f) return ctx->fail(HOBBIT_ESTATE, std::string(who) + ": F chunks and base-field chunks may not be mixed within one pass");
+        pass = f; return 0;
+    }
     mem::Pooled<F> d_aggr, d_T, d_G, d_reply, d_encf; mem::Pooled<uint8_t> d_lvf; mem::Pooled<uint32_t> d_ucols; mem::Pooled<uint64_t> d_pick; mem::Pooled<int> d_nz;
     // option 2 (linear_time, RS x expander): the "remaining" columns (a queried parity row), the aggregate's row codes M, aux_commit and C_c
     bool lin; std::vector<uint32_t> rem; size_t np;
@@ -2108,6 +2169,7 @@ void hobbit_elastic_open_dims(const hobbit_elastic_open *e, int *ncols, int *nre
 }
 int hobbit_elastic_open_aggregate_push(hobbit_ctx *ctx, hobbit_elastic_open *e, const hobbit_F *d_chunk) {
     if (e->n_aggr >= e->K || e->committed) return ctx->fail(HOBBIT_ESTATE, "elastic_open: more aggregate chunks than N/B");
+    HB_TRY(e->form(e->aggr_form, hobbit_elastic_open::FULL, "elastic_open_aggregate_push"));
     HB_TRY(launch_axpy(ctx, e->d_aggr, cF(d_chunk), e->beta[e->n_aggr], e->B));                             // aggregated_vector[j] += beta1[i]*buff[j] (:330-333)
     e->n_aggr++;
     return 0;
@@ -2136,8 +2198,9 @@ int hobbit_elastic_open_aggregate_finish(hobbit_ctx *ctx, hobbit_elastic_open *e
 }
 int hobbit_elastic_open_reply_push(hobbit_ctx *ctx, hobbit_elastic_open *e, const hobbit_F *d_chunk) {
     if (e->n_reply >= e->K) return ctx->fail(HOBBIT_ESTATE, "elastic_open: more reply chunks than N/B");
+    HB_TRY(e->form(e->reply_form, hobbit_elastic_open::FULL, "elastic_open_reply_push"));
     const size_t i = e->n_reply, half = e->B / (size_t)e->trs; const uint32_t nc = (uint32_t)e->ucols.size();
-    HB_TRY(launch_any_nonzero(ctx, cF(d_chunk), e->B, e->d_nz + i));                                        // an all-zero chunk appends nothing (:510-517)
+    HB_TRY(launch_any_nonzero(ctx, cF(d_chunk), e->B, e->d_nz + i));                                       // an all-zero chunk appends nothing (:510-517)
     if (e->lin) {
         // update_reply_spielman (:431-485): rows RS-encoded, every distinct queried column expander-encoded into its row of d_G (the message half
         // is the column itself); d_pick holds, per reply slot, where the reference AS BUILT reads from (elastic_open_begin_lin)
@@ -2153,6 +2216,34 @@ int hobbit_elastic_open_reply_push(hobbit_ctx *ctx, hobbit_elastic_open *e, cons
     HB_TRY(fft::rows(ctx, cF(d_chunk), half, (uint32_t)half, e->d_T, e->cols, 1, 12, false, 1, (uint32_t)e->trs, 0, 0));
     HB_TRY(launch_gather_cols(ctx, e->d_T, e->cols, (uint32_t)e->trs, e->d_ucols, nc, e->d_G, e->rows2));
     HB_TRY(fft::rows(ctx, e->d_G, e->rows2, (uint32_t)e->trs, e->d_G, e->rows2, 1, ilog2_exact(e->rows2), false, 1, nc, 0, 0));
+    HB_TRY(launch_gather_strided(ctx, e->d_G, e->d_pick, (size_t)e->queries, 1, 1, 0, e->d_reply + i * (size_t)e->queries));
+    e->n_reply++;
+    return 0;
+}
+// The two passes on base-field chunks (include/hobbit_elastic_real.h).  Aggregate: F by F_p, 8 bytes read per coefficient.  Reply: the zero test on
+// reals, the real row code into d_T as trs x (cols / 2 + 1) row-major, the conjugate-aware gather of the distinct queried columns -- before the
+// column code a column c > cols / 2 is the entry-wise conjugate of column cols - c, whatever the column code is -- and from there the pass above.
+int hobbit_elastic_open_aggregate_push_real(hobbit_ctx *ctx, hobbit_elastic_open *e, const uint64_t *d_chunk) {
+    if (e->n_aggr >= e->K || e->committed) return ctx->fail(HOBBIT_ESTATE, "elastic_open: more aggregate chunks than N/B");
+    if (!d_chunk) return ctx->fail(HOBBIT_EINVAL, "elastic_open_aggregate_push_real: null chunk");
+    HB_TRY(e->form(e->aggr_form, hobbit_elastic_open::REAL, "elastic_open_aggregate_push_real"));
+    HB_TRY(launch_axpy_real(ctx, e->d_aggr, d_chunk, e->beta[e->n_aggr], e->B));
+    e->n_aggr++;
+    return 0;
+}
+int hobbit_elastic_open_reply_push_real(hobbit_ctx *ctx, hobbit_elastic_open *e, const uint64_t *d_chunk) {
+    if (e->n_reply >= e->K) return ctx->fail(HOBBIT_ESTATE, "elastic_open: more reply chunks than N/B");
+    if (!d_chunk) return ctx->fail(HOBBIT_EINVAL, "elastic_open_reply_push_real: null chunk");
+    const int logc = ilog2_exact(e->cols);
+    if (logc < 3 || logc > 16) return ctx->fail(HOBBIT_EINVAL, "elastic_open_reply_push_real: the row code must have 2^3 .. 2^16 points");
+    HB_TRY(e->form(e->reply_form, hobbit_elastic_open::REAL, "elastic_open_reply_push_real"));
+    const size_t i = e->n_reply; const uint32_t nc = (uint32_t)e->ucols.size();
+    HB_TRY(launch_any_nonzero_real(ctx, d_chunk, e->B, e->d_nz + i));
+    if (e->lin && ctx->code.n != e->trs) { long long l; HB_TRY(hobbit_graph_finalize(ctx, e->trs, &l)); }
+    HB_TRY(fft::real_rows_any(ctx, d_chunk, (size_t)e->trs, logc, e->d_T, false, 0));
+    HB_TRY(launch_gather_cols_half(ctx, e->d_T, e->cols, (uint32_t)e->trs, e->d_ucols, nc, e->d_G, e->rows2));
+    if (e->lin) HB_TRY(launch_encode(ctx, e->d_G, e->rows2, e->d_G, e->rows2, e->trs, nc, 0));
+    else HB_TRY(fft::rows(ctx, e->d_G, e->rows2, (uint32_t)e->trs, e->d_G, e->rows2, 1, ilog2_exact(e->rows2), false, 1, nc, 0, 0));
     HB_TRY(launch_gather_strided(ctx, e->d_G, e->d_pick, (size_t)e->queries, 1, 1, 0, e->d_reply + i * (size_t)e->queries));
     e->n_reply++;
     return 0;

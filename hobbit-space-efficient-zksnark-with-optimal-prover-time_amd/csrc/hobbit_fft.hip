@@ -7,6 +7,7 @@
 #include "hobbit_rot.hpp"
 #include "hobbit_half.hpp"
 #include "../../include/hobbit_real.h"
+#include "../../include/hobbit_elastic_real.h"
 
 namespace hobbit {
 // ============================================================================================
@@ -554,6 +555,41 @@ static int launch_fft_real4096(hobbit_ctx *ctx, const uint64_t *src, size_t rows
     return 0;
 }
 
+// The unpacking pass of k_fft_real4096 alone, for a real row code of any length L = 2 Lh (include/hobbit_elastic_real.h): Z holds, per row, the
+// Lh-point transform of the row's L/2 reals read as L/4 F elements, zero-padded.  One thread per row and pair (k, Lh - k), k = 0 .. Lh / 2:
+// one product with w^k (w of order L, `roots`), 1/2 as the one-bit rotation, X[k] and X[Lh - k] out; X[L - k] = conj(X[k]) is the rest.
+// TENSOR: the rows are those of ONE chunk and row r stores X[k] at (r, k) of the chunk's half tensor (hobbit_half.hpp); the row index is the
+// fastest thread index, so the stores of a wave are contiguous.  Otherwise row-major, Lh + 1 elements per row, k the fastest index.
+template <bool TENSOR>
+__global__ void __launch_bounds__(256)
+k_real_unpack(const F *__restrict__ Z, F *__restrict__ dst, const F *__restrict__ roots, uint32_t Lh, uint32_t nrows, uint32_t rows2) {
+    const uint32_t np = Lh / 2 + 1;
+    const size_t total = (size_t)nrows * np;
+    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t row = TENSOR ? (uint32_t)(g % nrows) : (uint32_t)(g / np), k = TENSOR ? (uint32_t)(g / nrows) : (uint32_t)(g % np);
+        const F *z = Z + (size_t)row * Lh;
+        const F A = ldF(z + k), B = fconj(ldF(z + ((Lh - k) & (Lh - 1))));
+        const F S = fadd(A, B), D = fsub(A, B);
+        const F T = fmul(fmake(D.im, D.re ? P61 - D.re : 0), ldF(roots + k));       // w^k (-i D) = 2 w^k O[k]
+        const F lo = fhalf(fadd(S, T)), hi = fconj(fhalf(fsub(S, T)));
+        if (TENSOR) {
+            stF(dst + half_chunk_at(row, k, rows2), lo);
+            if (2 * k != Lh) stF(dst + half_chunk_at(row, Lh - k, rows2), hi);
+        } else {
+            stF(dst + (size_t)row * (Lh + 1) + k, lo);
+            if (2 * k != Lh) stF(dst + (size_t)row * (Lh + 1) + Lh - k, hi);
+        }
+    }
+}
+static int launch_real_unpack(hobbit_ctx *ctx, const F *Z, F *dst, const F *roots, uint32_t Lh, uint32_t nrows, bool tensor, uint32_t rows2) {
+    const size_t total = (size_t)nrows * (Lh / 2 + 1);
+    if (!total) return 0;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)1 << 16);
+    if (tensor) HB_LAUNCH(ctx, "k_real_unpack", k_real_unpack<true>, dim3(grid), dim3(256), 0, Z, dst, roots, Lh, nrows, rows2);
+    else HB_LAUNCH(ctx, "k_real_unpack_rm", k_real_unpack<false>, dim3(grid), dim3(256), 0, Z, dst, roots, Lh, nrows, 0u);
+    return 0;
+}
+
 // The same passes for the SECOND half of a long transform (k_fft_cols's job: N-point transforms down the columns of y[n1][k2], N = len / 4096
 // = 32 ... 256, inter-stage twiddle on load, result X[k1 * 4096 + k2]).  A workgroup owns C = 4096 / N adjacent columns; the column index is
 // the fastest thread index, so global loads and stores are C * 16-byte runs and -- with an odd LDS row stride -- the butterflies of the 64 lanes
@@ -997,6 +1033,21 @@ int any_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *ds
     return wide_rows(ctx, dst, logn, inverse, batch);
 }
 
+int real_rows_any(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F *dst, bool tensor, uint32_t trs) {
+    if (logL < 3 || logL > 16) return ctx->fail(HOBBIT_EINVAL, "fft_real_rows_any: logL must be in [3,16]");
+    if (!nrows) return 0;
+    if (nrows >> 20) return ctx->fail(HOBBIT_EINVAL, "fft_real: too many rows");
+    if (tensor && (!trs || nrows != trs)) return ctx->fail(HOBBIT_EINVAL, "fft_real: the tensor form takes the rows of one chunk");
+    if (logL == 12) return rowcode_real4096(ctx, src, nrows, dst, tensor, trs, 1, 0, 0);
+    if ((uintptr_t)src & 15) return ctx->fail(HOBBIT_EINVAL, "fft_real: the real rows must be 16-byte aligned");
+    const size_t Lh = (size_t)1 << (logL - 1);
+    // the packed transform: row r is Lh / 2 F elements, zero-padded to Lh points.  workspace5: the long transform below owns workspace / workspace2
+    F *Z; HB_TRY(ctx->workspace5(nrows * Lh * sizeof(F), (void **)&Z));
+    HB_TRY(any_rows(ctx, reinterpret_cast<const F *>(src), Lh / 2, Lh / 2, Z, logL - 1, false, nrows));
+    const F *tw; HB_TRY(roots(ctx, logL, false, &tw));
+    return launch_real_unpack(ctx, Z, dst, tw, (uint32_t)Lh, (uint32_t)nrows, tensor, 2 * trs);
+}
+
 }  // namespace fft
 }  // namespace hobbit
 
@@ -1020,6 +1071,10 @@ int hobbit_fft_real_rows(hobbit_ctx *ctx, const uint64_t *d_reals, size_t rows, 
     if (!rows) return 0;
     if (!d_reals || !d_out) return ctx->fail(HOBBIT_EINVAL, "fft_real_rows: null argument");
     return fft::rowcode_real4096(ctx, d_reals, rows, reinterpret_cast<F *>(d_out), false, 0, 0, 0, 0);
+}
+int hobbit_fft_real_rows_any(hobbit_ctx *ctx, const uint64_t *d_reals, size_t rows, int logL, hobbit_F *d_out) {
+    if (rows && (!d_reals || !d_out)) return ctx->fail(HOBBIT_EINVAL, "fft_real_rows_any: null argument");
+    return fft::real_rows_any(ctx, d_reals, rows, logL, reinterpret_cast<F *>(d_out), false, 0);
 }
 int hobbit_fft_any(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, size_t ld, int inverse) {
     if (logn < 1 || logn > 28) return ctx->fail(HOBBIT_EINVAL, "fft_any: logn must be in [1,28]");

@@ -27,6 +27,10 @@ int rowcode_4096(hobbit_ctx *ctx, const F *src, size_t src_ld, F *dst, size_t ds
 // trs rows, the first of them row 0 of chunk chunk0, into a commitment's half tensor (hobbit_half.hpp), rotated by rot_mask; otherwise row-major,
 // 2049 elements per row.
 int rowcode_real4096(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, F *dst, bool tensor, uint32_t trs, uint32_t K, uint32_t rot_mask, uint32_t chunk0);
+// The row code of `nrows` base-field rows of L / 2 reals, L = 2^logL, 3 <= logL <= 16 (include/hobbit_elastic_real.h), columns 0 .. L / 2: rowcode_real4096
+// for logL = 12, otherwise the packed L / 2-point transform through any_rows (into workspace5) and k_real_unpack.  tensor: the nrows == trs rows of one
+// chunk into the chunk's half tensor (hobbit_half.hpp: (L / 2 + 1) x 2 trs, codeword-major); otherwise row-major, L / 2 + 1 elements per row.
+int real_rows_any(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F *dst, bool tensor, uint32_t trs);
 // The 2^13 .. 2^15-point row code (Elastic_PC opt 2: 32768) of `nrows` contiguous messages of 2^(logc-1) elements: R = 2^(logc-12) strided FFT-4096 per
 // row into Y, then the twiddles and the R-point combine into the row-major rm (both nrows 2^logc elements).
 int rowcode_combine(hobbit_ctx *ctx, const F *msg, int logc, uint32_t nrows, F *Y, F *rm);

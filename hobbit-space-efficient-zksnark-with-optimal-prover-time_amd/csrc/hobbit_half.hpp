@@ -31,6 +31,19 @@ HB_ROT_HD size_t half_at(uint32_t i, uint32_t sc, uint32_t r, uint32_t cols, uin
     const size_t g = half_col(i, sc, cols, K);
     return g * rows2 + msg_rot_row(r, (uint32_t)g, rot_mask);
 }
+// One chunk's half tensor of the streaming commit (include/hobbit_elastic_real.h): columns 0 .. cols / 2, codeword-major, (cols / 2 + 1) x rows2,
+// the layout above at K = 1, unrotated.  half_ref answers, for entry (r, c) of the full chunk tensor, which stored entry holds it and whether
+// as its conjugate.  RS x expander (linear_time): T(r, cols - c) = conj(T(r, c)).  RS x RS: the column code is a transform of rows2 points, so
+// T(r, cols - c) = conj(T((rows2 - r) mod rows2, c)) -- the conjugate, with the row index negated.
+struct HalfRef { uint32_t row, col; bool conj; };
+HB_ROT_HD HalfRef half_ref(uint32_t r, uint32_t c, uint32_t cols, uint32_t rows2, int linear_time) {
+    if (!half_is_conj(c, cols)) return HalfRef{r, c, false};
+    return HalfRef{linear_time || !r ? r : rows2 - r, cols - c, true};
+}
+// the row of the full entry in column cols - sc that stored entry (row, sc) answers as its conjugate (0 < sc < cols / 2): half_ref's inverse
+HB_ROT_HD uint32_t half_mirror_row(uint32_t row, uint32_t rows2, int linear_time) { return linear_time || !row ? row : rows2 - row; }
+// element offset of stored entry (row, sc) in a chunk's half tensor
+HB_ROT_HD size_t half_chunk_at(uint32_t row, uint32_t sc, uint32_t rows2) { return (size_t)sc * rows2 + row; }
 // conj(a + bi) = a - bi, canonical in and out
 HB_HD F fconj(const F &a) { return fmake(a.re, a.im ? P61 - a.im : 0); }
 

@@ -992,6 +992,66 @@ int launch_elastic_finish(hobbit_ctx *ctx, const uint8_t *state, uint32_t rows2,
     HB_LAUNCH(ctx, "k_elastic_finish", k_elastic_finish, dim3(grid_for((size_t)rows2 * cols, 256, 1 << 16)), dim3(256), 0, state, rows2, cols, leaves);
     return 0;
 }
+// ---- the streaming commit on base-field chunks (include/hobbit_elastic_real.h): k_elastic_leaf over four HALF chunk tensors (hobbit_half.hpp) ----
+// position p + 1 of the full chunk tensor in leaf order p = r cols + c (k_elastic_leaf's `shift`); false past the end
+__device__ __forceinline__ bool elastic_next(uint32_t &r, uint32_t &c, uint32_t rows2, uint32_t cols) {
+    if (c + 1 < cols) { c++; return true; }
+    if (r + 1 < rows2) { r++; c = 0; return true; }
+    return false;
+}
+// entry (r, c) of the full chunk tensor out of its half tensor
+__device__ __forceinline__ F half_ld(const F *__restrict__ t, uint32_t r, uint32_t c, uint32_t cols, uint32_t rows2, int lin) {
+    const HalfRef h = half_ref(r, c, cols, rows2, lin);
+    const F v = ldF(t + half_chunk_at(h.row, h.col, rows2));
+    return h.conj ? fconj(v) : v;
+}
+// st = H( H(a | b | c | d) | st )
+__device__ __forceinline__ void elastic_leaf_update(const F &a, const F &b, const F &c, const F &d, uint8_t *__restrict__ st) {
+    uint32_t m[16], h[8];
+    m[0] = (uint32_t)a.re; m[1] = (uint32_t)(a.re >> 32); m[2] = (uint32_t)a.im; m[3] = (uint32_t)(a.im >> 32);
+    m[4] = (uint32_t)b.re; m[5] = (uint32_t)(b.re >> 32); m[6] = (uint32_t)b.im; m[7] = (uint32_t)(b.im >> 32);
+    m[8] = (uint32_t)c.re; m[9] = (uint32_t)(c.re >> 32); m[10] = (uint32_t)c.im; m[11] = (uint32_t)(c.im >> 32);
+    m[12] = (uint32_t)d.re; m[13] = (uint32_t)(d.re >> 32); m[14] = (uint32_t)d.im; m[15] = (uint32_t)(d.im >> 32);
+    blake3_compress64(m, h);
+#pragma unroll
+    for (int q = 0; q < 8; q++) m[q] = h[q];
+    load8w(st, m + 8);
+    blake3_compress64(m, h);
+    store8w(st, h);
+}
+// One thread per STORED entry (j, sc), sc <= cols / 2: it loads its entries of the last two tensors once and updates leaf (j, sc) and, for
+// 0 < sc < cols / 2, the leaf of the full entry in column cols - sc that (j, sc) answers as its conjugate (half_mirror_row) -- one load, two
+// leaves.  The first two tensors are read per leaf, at the leaf's own position p or with `shift` at p + 1, through half_ref.  The running state is k_elastic_leaf's, codeword-major over the
+// FULL tensor, so k_elastic_finish is the same.  (256, 8): eight waves per SIMD as k_elastic_leaf has, i.e. at most 64 VGPRs.
+__global__ void __launch_bounds__(256, 8)
+k_elastic_leaf_half(const F *__restrict__ t0, const F *__restrict__ t1, const F *__restrict__ t2, const F *__restrict__ t3, uint32_t rows2, uint32_t cols,
+                    int shift, int lin, uint8_t *__restrict__ state) {
+    const uint32_t hc = cols / 2;
+    const size_t T = (size_t)(hc + 1) * rows2;
+    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < T; g += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t sc = (uint32_t)(g / rows2), j = (uint32_t)(g % rows2);
+        const F c = ldF(t2 + g), d = ldF(t3 + g);
+        // the first two tensors at the leaf's own position, or the next one: only c and d stay in registers across the two leaves
+        auto first_two = [&](uint32_t r, uint32_t cc, F &a, F &b) {
+            a = fmake(0); b = fmake(0);
+            if (shift && !elastic_next(r, cc, rows2, cols)) return;
+            a = half_ld(t0, r, cc, cols, rows2, lin); b = half_ld(t1, r, cc, cols, rows2, lin);
+        };
+        F a, b;
+        first_two(j, sc, a, b);
+        elastic_leaf_update(a, b, c, d, state + 32 * g);                                 // (the state index of (j, sc) is sc rows2 + j = g)
+        if (sc > 0 && sc < hc) {
+            const uint32_t cm = cols - sc, jm = half_mirror_row(j, rows2, lin);
+            first_two(jm, cm, a, b);
+            elastic_leaf_update(a, b, fconj(c), fconj(d), state + 32 * ((size_t)cm * rows2 + jm));
+        }
+    }
+}
+int launch_elastic_leaf_half(hobbit_ctx *ctx, const F *t0, const F *t1, const F *t2, const F *t3, uint32_t rows2, uint32_t cols, int shift, int lin, uint8_t *state) {
+    HB_LAUNCH(ctx, "k_elastic_leaf_half", k_elastic_leaf_half, dim3(grid_for((size_t)rows2 * (cols / 2 + 1), 256, 1 << 16)), dim3(256), 0, t0, t1, t2, t3, rows2, cols,
+              shift, lin, state);
+    return 0;
+}
 // shockwave_commit column digests (src/Virgo.cpp:143-151): digest of column c = root of MT_commit_Blake over the
 // k entries enc[0..k)[c] (k/4 leaves of 4 elements, then the tree with the configured parent rule), k <= 64
 __global__ void __launch_bounds__(256)
@@ -2719,6 +2779,40 @@ __global__ void k_gather_cols(const F *__restrict__ T, size_t ld, uint32_t nrows
 int launch_gather_cols(hobbit_ctx *ctx, const F *T, size_t ld, uint32_t nrows, const uint32_t *d_cols, uint32_t ncols, F *G, size_t ldG) {
     if (!ncols || !nrows) return 0;
     HB_LAUNCH(ctx, "k_gather_cols", k_gather_cols, dim3((unsigned)(((size_t)ncols * nrows + 255) / 256)), dim3(256), 0, T, ld, nrows, d_cols, ncols, G, ldG);
+    return 0;
+}
+// k_gather_cols on the row codes of base-field rows kept as columns 0 .. cols / 2 (row-major, cols / 2 + 1 elements per row): before the column
+// code, column c > cols / 2 is the entry-wise conjugate of column cols - c (hobbit_half.hpp)
+__global__ void k_gather_cols_half(const F *__restrict__ T, uint32_t cols, uint32_t nrows, const uint32_t *__restrict__ qcols, uint32_t ncols, F *__restrict__ G, size_t ldG) {
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= (size_t)ncols * nrows) return;
+    const uint32_t c = (uint32_t)(t / nrows), j = (uint32_t)(t % nrows), qc = qcols[c];
+    const F v = ldF(T + (size_t)j * (cols / 2 + 1) + half_src_col(qc, cols));
+    stF(G + (size_t)c * ldG + j, half_is_conj(qc, cols) ? fconj(v) : v);
+}
+int launch_gather_cols_half(hobbit_ctx *ctx, const F *T, uint32_t cols, uint32_t nrows, const uint32_t *d_cols, uint32_t ncols, F *G, size_t ldG) {
+    if (!ncols || !nrows) return 0;
+    HB_LAUNCH(ctx, "k_gather_cols_half", k_gather_cols_half, dim3((unsigned)(((size_t)ncols * nrows + 255) / 256)), dim3(256), 0, T, cols, nrows, d_cols, ncols, G, ldG);
+    return 0;
+}
+// k_axpy and k_any_nonzero over base-field values: y += a * (x, 0), two F_p products per term
+__global__ void k_axpy_real(F *__restrict__ y, const uint64_t *__restrict__ x, F a, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint64_t v = x[i];
+        stF(y + i, fadd(ldF(y + i), fmake(mulp(a.re, v), mulp(a.im, v))));
+    }
+}
+int launch_axpy_real(hobbit_ctx *ctx, F *y, const uint64_t *x, F a, size_t n) {
+    HB_LAUNCH(ctx, "k_axpy_real", k_axpy_real, dim3(grid_for(n, 256)), dim3(256), 0, y, x, a, n);
+    return 0;
+}
+__global__ void k_any_nonzero_real(const uint64_t *__restrict__ v, size_t n, int *__restrict__ flag) {
+    int nz = 0;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) nz |= v[i] != 0;
+    if (__any(nz) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+int launch_any_nonzero_real(hobbit_ctx *ctx, const uint64_t *v, size_t n, int *d_flag) {
+    HB_LAUNCH(ctx, "k_any_nonzero_real", k_any_nonzero_real, dim3(grid_for(n, 256, 1024)), dim3(256), 0, v, n, d_flag);
     return 0;
 }
 // out[cols[i] + j*ld] = vals[i], j < nrows: a column indicator weighted per column (recursive_prover_RS's second beta, src/PC_utils.cpp:489-496)

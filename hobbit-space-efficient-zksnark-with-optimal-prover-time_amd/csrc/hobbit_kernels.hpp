@@ -117,6 +117,11 @@ int launch_gate_sumcheck(hobbit_ctx *ctx, const F *const tabs[6], size_t n, CHP 
 int launch_sumcheck3(hobbit_ctx *ctx, const F *v1, const F *v2, const F *v3, size_t n, F prev_r, MHP h_cpoly, MHP h_r, MHP h_vr, MHP h_final);
 int launch_any_nonzero(hobbit_ctx *ctx, const F *v, size_t n, int *d_flag);
 int launch_gather_cols(hobbit_ctx *ctx, const F *T, size_t ld, uint32_t nrows, const uint32_t *d_cols, uint32_t ncols, F *G, size_t ldG);
+// the streaming commit and opening on base-field chunks (include/hobbit_elastic_real.h)
+int launch_elastic_leaf_half(hobbit_ctx *ctx, const F *t0, const F *t1, const F *t2, const F *t3, uint32_t rows2, uint32_t cols, int shift, int lin, uint8_t *state);
+int launch_gather_cols_half(hobbit_ctx *ctx, const F *T, uint32_t cols, uint32_t nrows, const uint32_t *d_cols, uint32_t ncols, F *G, size_t ldG);
+int launch_axpy_real(hobbit_ctx *ctx, F *y, const uint64_t *x, F a, size_t n);
+int launch_any_nonzero_real(hobbit_ctx *ctx, const uint64_t *v, size_t n, int *d_flag);
 int launch_spread_cols(hobbit_ctx *ctx, const uint32_t *d_cols, const F *d_vals, uint32_t ncols, uint32_t nrows, size_t ld, F *out);
 int launch_seg_prod(hobbit_ctx *ctx, const F *in, uint32_t seg, size_t n_out, F *out);
 int launch_deinterleave(hobbit_ctx *ctx, const F *v, size_t n, F *a, F *b);

@@ -654,6 +654,18 @@ void read_stream_PC(stream_descriptor &fd, F *v, int size) {       // src/witnes
     for (int i = 0; i < size; i++) { v[i] = n; n = n * n + F(i); }
 }
 #endif
+// Base-field streams (include/hobbit_elastic_real.h): the real parts of the two default streams, 8 bytes per value -- their img is 0 throughout --
+// and, while g_real_stream is set (commit_real / open_real), commit and open read, upload and push those instead of the widened elements.
+static bool g_real_stream = false;
+void read_stream_PC_real(stream_descriptor &fd, uint64_t *v, int size) {
+    if (fd.name == "PC_layer" || fd.name == "witness" || fd.name == "circuit") { printf("Error: stream '%s' belongs to the witness generator (out of scope)\n", fd.name.c_str()); exit(-1); }
+    unsigned __int128 n = 322322;
+    for (int i = 0; i < size; i++) { v[i] = (uint64_t)n; n = (n * n + (unsigned)i) % virgo::MODP; }
+}
+void read_stream_real(stream_descriptor &fd, uint64_t *v, int size) {
+    (void)fd;
+    for (int i = 0; i < size; i++) v[i] = (uint64_t)((i % 1024) + 1);
+}
 void init_commitment(bool mod) {                                    // src/Elastic_PC.cpp:728-734
     linear_time = mod;
     tensor_row_size = (int)(BUFFER_SPACE / (1ULL << 11));
@@ -664,10 +676,18 @@ void commit(stream_descriptor fd, _hash &comm, vector<vector<_hash>> &MT_hashes)
     (void)comm; PhaseTimer pt__("commit");
     if (fd.size / BUFFER_SPACE < 4) printf("Decrease buffer size %d\n", (int)(fd.size / BUFFER_SPACE));
     hobbit_elastic *e = nullptr;
-    HCHK(hobbit_elastic_begin(hobbit_host_ctx(), BUFFER_SPACE, tensor_row_size, linear_time ? 1 : 0, 1, &e));
-    vector<F> buff(BUFFER_SPACE);
-    DevBuf d(BUFFER_SPACE * sizeof(F));
+    const bool real = g_real_stream && fd.name != "PC_layer";       // (PC_layer: products taken on the device, they never cross PCIe)
+    if (real) HCHK(hobbit_elastic_begin_real(hobbit_host_ctx(), BUFFER_SPACE, tensor_row_size, linear_time ? 1 : 0, 1, &e));
+    else HCHK(hobbit_elastic_begin(hobbit_host_ctx(), BUFFER_SPACE, tensor_row_size, linear_time ? 1 : 0, 1, &e));
+    vector<F> buff(real ? 0 : BUFFER_SPACE); vector<uint64_t> rbuff(real ? BUFFER_SPACE : 0);
+    DevBuf d(BUFFER_SPACE * (real ? sizeof(uint64_t) : sizeof(F)));
     for (size_t i = 0; i < fd.size / BUFFER_SPACE; i++) {
+        if (real) {
+            TIMED_READ(read_stream_PC_real(fd, rbuff.data(), (int)BUFFER_SPACE));
+            TIMED_UP(HCHK(hobbit_memcpy_h2d(g_ctx, d.p, rbuff.data(), BUFFER_SPACE * sizeof(uint64_t))));
+            HCHK(hobbit_elastic_push_real(g_ctx, e, (const uint64_t *)d.p));
+            continue;
+        }
         if (fd.name == "PC_layer") {
             // read_stream_PC's PC_layer branch (src/witness_stream.cpp:2357-2364): read_mul_tree_layer on the descriptor itself, whose
             // name read_stream does not know -> the product layer fd.layer of the DEFAULT stream; the products are taken on the device
@@ -694,6 +714,11 @@ void read_stream(stream_descriptor &fd, vector<F> &v, int size) {   // src/witne
     for (int i = 0; i < size; i++) v[i] = F((i % 1024) + 1);
 }
 #endif
+// one chunk of read_stream's base-field form, read and uploaded at 8 bytes per value (the opening's two passes under g_real_stream)
+static void real_chunk_up(stream_descriptor &fd, vector<uint64_t> &rbuff, DevBuf &d, size_t B) {
+    TIMED_READ(read_stream_real(fd, rbuff.data(), (int)B));
+    TIMED_UP(HCHK(hobbit_memcpy_h2d(g_ctx, d.p, rbuff.data(), B * sizeof(uint64_t))));
+}
 // src/Elastic_PC.cpp:625-726 under linear_time (RS x expander; test_Elastic_PC option 2): 5900 queries, aggregate()'s expander branch,
 // update_reply_spielman as the reference is built (include/hobbit_hip.h: hobbit_elastic_open_begin_lin), recursive_prover_Spielman_stream
 static void open_linear_time(stream_descriptor fd, vector<F> x, vector<vector<_hash>> &Commitment_MT, double &vt, double &ps) {
@@ -707,9 +732,10 @@ static void open_linear_time(stream_descriptor fd, vector<F> x, vector<vector<_h
     hobbit_host_elastic_transcript &t = g_eopen;
     t.lin = true;
     hobbit_elastic_open_dims(e, &t.ncols, &t.nrem, &t.np);
-    vector<F> buff(B); DevBuf d(B * sizeof(F));
+    vector<F> buff(g_real_stream ? 0 : B); vector<uint64_t> rbuff(g_real_stream ? B : 0); DevBuf d(B * (g_real_stream ? sizeof(uint64_t) : sizeof(F)));
     stream_descriptor fd_a = fd, fd_r = fd;                          // aggregate and compute_aggregation_reply each take the descriptor BY VALUE (:316, :487)
     for (size_t i = 0; i < K; i++) {                                 // aggregate (:327-334)
+        if (g_real_stream) { real_chunk_up(fd_a, rbuff, d, B); HCHK(hobbit_elastic_open_aggregate_push_real(g_ctx, e, (const uint64_t *)d.p)); continue; }
         TIMED_READ(read_stream(fd_a, buff, (int)B));
         TIMED_UP(HCHK(hobbit_memcpy_h2d(g_ctx, d.p, buff.data(), B * sizeof(F))));
         HCHK(hobbit_elastic_open_aggregate_push(g_ctx, e, (const hobbit_F *)d.p));
@@ -717,6 +743,7 @@ static void open_linear_time(stream_descriptor fd, vector<F> x, vector<vector<_h
     HCHK(hobbit_elastic_open_aggregate_finish(g_ctx, e));
     printf("%d\n", (int)((size_t)t.nrem * 2 * (size_t)trs));         // aggregate() prints the flattened aux_commit's size (:408)
     for (size_t i = 0; i < K; i++) {                                 // compute_aggregation_reply (:506-531)
+        if (g_real_stream) { real_chunk_up(fd_r, rbuff, d, B); HCHK(hobbit_elastic_open_reply_push_real(g_ctx, e, (const uint64_t *)d.p)); continue; }
         TIMED_READ(read_stream(fd_r, buff, (int)B));
         TIMED_UP(HCHK(hobbit_memcpy_h2d(g_ctx, d.p, buff.data(), B * sizeof(F))));
         HCHK(hobbit_elastic_open_reply_push(g_ctx, e, (const hobbit_F *)d.p));
@@ -763,15 +790,17 @@ void open(stream_descriptor fd, vector<F> x, vector<vector<_hash>> &Commitment_M
     const int logc = 12, logr = (int)log2((double)(2 * trs)), logt = logr - 1, depth = (int)log2((double)(4 * B));
     hobbit_elastic_open *e = nullptr;
     HCHK(hobbit_elastic_open_begin(hobbit_host_ctx(), fd.size, B, trs, hF(x.data()), queries, &e));
-    vector<F> buff(B); DevBuf d(B * sizeof(F));
+    vector<F> buff(g_real_stream ? 0 : B); vector<uint64_t> rbuff(g_real_stream ? B : 0); DevBuf d(B * (g_real_stream ? sizeof(uint64_t) : sizeof(F)));
     stream_descriptor fd_a = fd, fd_r = fd;                          // aggregate and compute_aggregation_reply each take the descriptor BY VALUE (:316, :487)
     for (size_t i = 0; i < K; i++) {                                 // aggregate (:327-334)
+        if (g_real_stream) { real_chunk_up(fd_a, rbuff, d, B); HCHK(hobbit_elastic_open_aggregate_push_real(g_ctx, e, (const uint64_t *)d.p)); continue; }
         TIMED_READ(read_stream(fd_a, buff, (int)B));
         TIMED_UP(HCHK(hobbit_memcpy_h2d(g_ctx, d.p, buff.data(), B * sizeof(F))));
         HCHK(hobbit_elastic_open_aggregate_push(g_ctx, e, (const hobbit_F *)d.p));
     }
     HCHK(hobbit_elastic_open_aggregate_finish(g_ctx, e));
     for (size_t i = 0; i < K; i++) {                                 // compute_aggregation_reply (:506-531)
+        if (g_real_stream) { real_chunk_up(fd_r, rbuff, d, B); HCHK(hobbit_elastic_open_reply_push_real(g_ctx, e, (const uint64_t *)d.p)); continue; }
         TIMED_READ(read_stream(fd_r, buff, (int)B));
         TIMED_UP(HCHK(hobbit_memcpy_h2d(g_ctx, d.p, buff.data(), B * sizeof(F))));
         HCHK(hobbit_elastic_open_reply_push(g_ctx, e, (const hobbit_F *)d.p));
@@ -848,6 +877,16 @@ void test_Elastic_PC(size_t N, int option) {                        // src/Elast
     elapsed += std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
     if (option == 1) printf("Total prover time : %lf\n", elapsed);                                              // (:759)
     else std::cout << "Total time: " << elapsed << " seconds" << std::endl;                                      // (:783)
+}
+// commit / open / test_Elastic_PC on the base-field form of the default streams: 8 bytes per coefficient over PCIe in all three passes, the
+// same libc draws, the same root, queries, replies and proof size (`host/test_pc elastic_real <logN> <logB> <opt>`, options 1 and 2)
+namespace { struct RealStreamScope { RealStreamScope() { g_real_stream = true; } ~RealStreamScope() { g_real_stream = false; } }; }
+void commit_real(stream_descriptor fd, _hash &comm, vector<vector<_hash>> &MT_hashes) { RealStreamScope s; commit(fd, comm, MT_hashes); }
+void open_real(stream_descriptor fd, vector<F> x, vector<vector<_hash>> &Commitment_MT, double &vt, double &ps) { RealStreamScope s; open(fd, x, Commitment_MT, vt, ps); }
+void test_Elastic_PC_real(size_t N, int option) {
+    if (option != 1 && option != 2) { printf("Error: elastic_real takes options 1 and 2\n"); exit(-1); }
+    RealStreamScope s;
+    test_Elastic_PC(N, option);
 }
 void test_Elastic_PC_commit(size_t N, int option) {                 // commit phase only (kept for callers that time the commit alone)
     _hash comm; vector<vector<_hash>> MT_hashes;

@@ -21,6 +21,7 @@
 #include "hobbit_orion.h"
 #include "hobbit_libcgen.h"
 #include "hobbit_real.h"
+#include "hobbit_elastic_real.h"
 
 using std::vector;
 
@@ -409,6 +410,13 @@ std::vector<uint8_t> hobbit_host_serialize_open(const hobbit_host_open_transcrip
 bool hobbit_host_deserialize_open(const uint8_t *buf, size_t n, hobbit_host_open_transcript &t);
 std::vector<uint8_t> hobbit_host_serialize_rs_open(const hobbit_host_elastic_transcript &t);
 bool hobbit_host_deserialize_rs_open(const uint8_t *buf, size_t n, hobbit_host_elastic_transcript &t);
+/* Elastic_PC on base-field streams (include/hobbit_elastic_real.h): the real parts of the two default streams, 8 bytes per value, and commit /
+ * open / test_Elastic_PC reading, uploading and pushing those (options 1 and 2).  test_Elastic_PC itself keeps widening, as test_PC does. */
+void read_stream_PC_real(stream_descriptor &fd, uint64_t *v, int size);
+void read_stream_real(stream_descriptor &fd, uint64_t *v, int size);
+void commit_real(stream_descriptor fd, _hash &comm, vector<vector<_hash>> &MT_hashes);
+void open_real(stream_descriptor fd, vector<F> x, vector<vector<_hash>> &Commitment_MT, double &vt, double &ps);
+void test_Elastic_PC_real(size_t N, int option);
 void test_Elastic_PC_commit(size_t N, int option);              /* commit phase of test_Elastic_PC (src/Elastic_PC.cpp:736-771) */
 /* src/sumcheck.h:84, src/sumcheck.cpp:1150 : the streaming multiplication-tree prover over read_stream (default stream only) */
 vector<F> prove_multiplication_tree_stream_shallow(stream_descriptor fd, int vectors, int size, F previous_r, int distance, vector<F> prev_x, bool naive, double &vt, double &ps);

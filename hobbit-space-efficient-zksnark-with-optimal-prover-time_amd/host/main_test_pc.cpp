@@ -5,6 +5,8 @@
 // option 5, which test_PC itself keeps refusing; shapes outside 4 <= K <= 512, 128 <= N / K <= 2^20 print an error and return 255) and
 // `brakingbase_any <logN> <K>` (the same baseline through include/hobbit_longcodes.h: N / K up to 2^21, which `28 5 128` of PC_tests.sh needs) and
 // `real <logN> <K>` (option 4 with the polynomial drawn on the device as base-field values of 8 bytes and committed as a half commitment) and
+// `elastic_real <logN> <logB> <opt>` (Elastic_PC options 1 and 2 on the base-field form of the default streams, 8 bytes per value: every line
+// that carries no time equals the line of `elastic <logN> <logB> <opt>`) and
 // `orion <logN>` (the Orion baseline: test_PC's option 2, which test_PC itself keeps refusing; logN even in [14, 28], else an error and 255)
 // (src/main.cpp:1176: test_PC(1ULL<<atoi(argv[1]), atoi(argv[2]), atoi(argv[3]))) over the
 // device-backed host mirror.  Build: see __graft_entry__.build_host().
@@ -19,8 +21,8 @@ int main(int argc, char **argv) {
     const bool orion = argc == 3 && std::string(argv[1]) == "orion";
     const bool real = argc == 4 && std::string(argv[1]) == "real";
     if (argc < 4 && !whir && !orion) {
-        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>   |   %s brakingbase_any <logN> <K>   |   %s orion <logN>   |   %s real <logN> <K>\n",
-               argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+        printf("usage: %s <logN> <4 | 1 | 3> <K>   |   %s elastic <logN> <logB> <opt>   |   %s whir <logN>   |   %s brakingbase <logN> <K>   |   %s brakingbase_any <logN> <K>   |   %s orion <logN>   |   %s real <logN> <K>   |   %s elastic_real <logN> <logB> <1 | 2>\n",
+               argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
         return 1;
     }
     init_hash();
@@ -48,6 +50,12 @@ int main(int argc, char **argv) {
         const int logn = atoi(argv[2]);
         if (logn < 9 || logn > 26) { printf("Error: the standalone WHIR baseline takes 9 <= logN <= 26\n"); return 255; }
         test_whir(1ULL << logn);
+    } else
+    if (std::string(argv[1]) == "elastic_real") {     // include/hobbit_elastic_real.h
+        const int opt = argc > 4 ? atoi(argv[4]) : 1;
+        if (opt != 1 && opt != 2) { printf("Error: elastic_real takes options 1 and 2\n"); return 255; }
+        BUFFER_SPACE = 1ULL << atoi(argv[3]);
+        test_Elastic_PC_real(1ULL << atoi(argv[2]), opt);
     } else
     if (std::string(argv[1]) == "elastic") {          // src/main.cpp:1177-1178: BUFFER_SPACE = 1<<argv[2]; test_Elastic_PC(1<<argv[1], argv[3])
         BUFFER_SPACE = 1ULL << atoi(argv[3]);
