@@ -101,6 +101,11 @@ ELASTIC_REAL_SYMBOLS = [
     "hobbit_elastic_open_aggregate_push_real", "hobbit_elastic_open_reply_push_real",
 ]
 
+# every symbol include/hobbit_real_rs.h declares (checked by tests/test_real_rs_cpu.py)
+REAL_RS_SYMBOLS = [
+    "hobbit_fft_real_rows_len", "hobbit_commit_standard_real_rs", "hobbit_commit_standard_real_rs_host", "hobbit_open_standard_rs_real",
+]
+
 # every symbol include/hobbit_orion.h declares (checked by tests/test_orion.py)
 ORION_SYMBOLS = [
     "hobbit_encode_interleaved_ld", "hobbit_encode_interleaved_ld_order", "hobbit_orion_gather", "hobbit_orion_grid_paths", "hobbit_orion_shape",
@@ -225,6 +230,9 @@ def load_library(path=LIB_PATH):
         # include/hobbit_elastic_real.h
         "hobbit_fft_real_rows_any": [V, V, S, I, V], "hobbit_elastic_begin_real": [V, S, I, I, I, V], "hobbit_elastic_push_real": [V, V, V],
         "hobbit_elastic_device_bytes": [V], "hobbit_elastic_open_aggregate_push_real": [V, V, V], "hobbit_elastic_open_reply_push_real": [V, V, V],
+        # include/hobbit_real_rs.h
+        "hobbit_fft_real_rows_len": [V, V, S, I, V], "hobbit_commit_standard_real_rs": [V, V, S, I, I, V],
+        "hobbit_commit_standard_real_rs_host": [V, V, V, S, I, I, V], "hobbit_open_standard_rs_real": [V, V, S, V, V, I, V],
     }
     lib.hobbit_elastic_device_bytes.restype = c_sz
     lib.hobbit_libc_jump.restype = None
@@ -310,7 +318,7 @@ class Commitment:
         return out
 
     def is_half(self):
-        """made by commit_standard_real: columns 0 .. cols/2 of every chunk in memory (include/hobbit_real.h)"""
+        """made by commit_standard_real or commit_standard_real_rs: columns 0 .. cols/2 of every chunk in memory (include/hobbit_real.h, hobbit_real_rs.h)"""
         return bool(self.hb.lib.hobbit_commitment_is_half(self.h))
 
     def tensor_dev(self):
@@ -1687,6 +1695,38 @@ class Hobbit:
         self._chk(self.lib.hobbit_fft_real_rows_any(self.ctx, c_vp(d.ptr), c_sz(a.shape[0]), c_int(logL), c_vp(o.ptr)))
         return self.to_host(o, (a.shape[0], h + 1, 2), np.uint64)
 
+    def fft_real_rows_len(self, rows, logL):
+        """fft_real_rows_any at 3 <= logL <= 20 (include/hobbit_real_rs.h)"""
+        a = np.ascontiguousarray(rows, dtype=np.uint64)
+        h = 1 << (logL - 1)
+        assert a.ndim == 2 and a.shape[1] == h
+        d = self.to_device(a); o = self.alloc(16 * (h + 1) * a.shape[0])
+        self._chk(self.lib.hobbit_fft_real_rows_len(self.ctx, c_vp(d.ptr), c_sz(a.shape[0]), c_int(logL), c_vp(o.ptr)))
+        return self.to_host(o, (a.shape[0], h + 1, 2), np.uint64)
+
+    def commit_standard_real_rs(self, poly, K, trs, sync=True):
+        """commit_standard(..., lin=0) of a base-field polynomial as a half commitment (include/hobbit_real_rs.h); poly: host array of N uint64 or
+        (DeviceBuffer/ptr, N)"""
+        ptr, N, keep = self._real_ptr(poly)
+        h = c_vp()
+        self._chk(self.lib.hobbit_commit_standard_real_rs(self.ctx, c_vp(ptr), c_sz(N), c_int(K), c_int(trs), ctypes.byref(h)))
+        if sync or keep is not None:
+            self.sync()
+        return Commitment(self, h, N, K, trs)
+
+    def commit_standard_real_rs_host(self, poly, K, trs):
+        """the same from (pageable) host memory at 8 bytes per coefficient.  Returns (Commitment, DeviceBuffer holding the uploaded reals)."""
+        p = self._reals(poly); N = p.shape[0]
+        d = self.alloc(8 * N)
+        h = c_vp()
+        self._chk(self.lib.hobbit_commit_standard_real_rs_host(self.ctx, _hp(p), c_vp(d.ptr), c_sz(N), c_int(K), c_int(trs), ctypes.byref(h)))
+        self.sync()
+        return Commitment(self, h, N, K, trs), d
+
+    def open_standard_rs_real(self, poly, c, x, queries=790, want_paths=True, shockwave=True):
+        """open_standard_rs for a base-field polynomial (host array of N uint64 or (DeviceBuffer/ptr, N)) and its RS x RS commitment, half or full"""
+        return self.open_standard_rs(poly, c, x, queries, want_paths, shockwave, _real=True)
+
     def elastic_commit_real(self, N, B, opt, gcc_arg_order=1, chunk=None, keep_levels=False, levels="host", chunks=None):
         """elastic_commit on a base-field stream through half chunk tensors.  chunk: a DeviceBuffer holding the stream's (repeating) chunk of B
         uint64, read_stream_PC_real(B) if None; chunks: a callable i -> host array of B uint64 / DeviceBuffer, for a stream whose chunks differ."""
@@ -1723,10 +1763,12 @@ class Hobbit:
         """elastic_open2 on a base-field stream; chunks: None or a callable i -> host array of B uint64 / DeviceBuffer"""
         return self.elastic_open2(N, B, x, queries, commit_levels, chunks, _real=True)
 
-    def open_standard_rs(self, poly, c, x, queries=790, want_paths=True, shockwave=True):
+    def open_standard_rs(self, poly, c, x, queries=790, want_paths=True, shockwave=True, _real=False):
         """Our_PC open_standard with linear_time == false (test_PC option 1, src/Our_PC.cpp:604-692), prover side.  poly: host array or
         (DeviceBuffer/ptr, N); c: the Commitment from commit_standard(..., lin=0)."""
-        if isinstance(poly, tuple):
+        if _real:
+            ptr, N, keep = self._real_ptr(poly)
+        elif isinstance(poly, tuple):
             ptr, N = poly; ptr = ptr.ptr if isinstance(ptr, DeviceBuffer) else int(ptr); keep = None
         else:
             p = Fh(poly).reshape(-1, 2); N = p.shape[0]; keep = self.to_device(p); ptr = keep.ptr
@@ -1745,7 +1787,8 @@ class Hobbit:
             _fields_ = [(n, c_vp) for n in names + ("sp_f",)]
         sp = self._sp_buffers(B, 32) if shockwave else None
         o = Out(*([(res[k].ctypes.data if res[k] is not None else None) for k in names] + [ctypes.addressof(sp[1]) if sp else None]))
-        self._chk(self.lib.hobbit_open_standard_rs(self.ctx, c_vp(ptr), c_sz(N), c.h, _hp(x), c_int(queries), ctypes.byref(o)))
+        fn = self.lib.hobbit_open_standard_rs_real if _real else self.lib.hobbit_open_standard_rs
+        self._chk(fn(self.ctx, c_vp(ptr), c_sz(N), c.h, _hp(x), c_int(queries), ctypes.byref(o)))
         nc = int(res["ncols"][0]); np2 = 1 << max(nc - 1, 0).bit_length()
         rounds = (np2 * 2 * trs).bit_length() - 1 + logr + (logt + logc) + logc
         res["poly"] = res["poly"][:rounds]; res["r"] = res["r"][:rounds]

@@ -17,6 +17,7 @@
 #include "../../include/hobbit_whir.h"
 #include "../../include/hobbit_real.h"
 #include "../../include/hobbit_elastic_real.h"
+#include "../../include/hobbit_real_rs.h"
 
 using namespace hobbit;
 
@@ -987,6 +988,61 @@ int hobbit_commit_standard_real_host(hobbit_ctx *ctx, const uint64_t *h_poly, ui
     if (rc) hipStreamSynchronize(ctx->up_stream);                 // nothing of the caller's buffer is still being read on an error return
     return rc;
 }
+// ---- base-field polynomials under RS x RS (include/hobbit_real_rs.h) -----------------------------
+// commit_impl(linear_time = 0) for a real polynomial, as a half commitment.  Rows: the real row code straight into the half layout (fft::rowcode_real_half),
+// all K chunks in one batch where the full form batches them (row codes up to 2^15 points), chunk by chunk beyond; never rotated.  Columns: the
+// rows2-point transform in place over K cols / 2 + K columns, the call tensorcode_chunks makes over K cols.  Leaves: k_leaf_chain_half_rs.
+static int commit_real_rs_impl(hobbit_ctx *ctx, const uint64_t *d_poly, size_t N, int K, int trs, hobbit_commitment **out, Uploader *up) {
+    if (!out) return HOBBIT_EINVAL;
+    *out = nullptr;
+    if (!d_poly) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: null polynomial");
+    if ((uintptr_t)d_poly & 15) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: the polynomial must be 16-byte aligned");
+    if (K <= 0 || N % (size_t)K) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: K must divide N");
+    const size_t M = N / K;
+    if (trs < 4 || trs % 4 || M % (size_t)trs) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: trs must be a multiple of 4 dividing N/K");
+    if (ilog2_exact(M) < 0) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: N/K must be a power of two");
+    const size_t cols = 2 * M / trs, rows2 = 2 * (size_t)trs;
+    const int logc = ilog2_exact(cols), logr = ilog2_exact(rows2);
+    if (logr < 0 || logr > 12) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: the column code needs 2 trs a power of two <= 4096");
+    if (logc < 3 || logc > 20) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: the row code must have 2^3 .. 2^20 points, 8 <= 2 (N/K) / trs <= 2^20");
+    if ((size_t)K * trs >> 20 && logc <= 15) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: more than 2^20 rows in one batch");
+    if (half_ncols((uint32_t)cols, (uint32_t)K) >> 31) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs: more than 2^31 stored columns");
+    Handle<hobbit_commitment, hobbit_commitment_free> c(new hobbit_commitment());
+    c->ctx = ctx; c->N = N; c->M = M; c->K = K; c->trs = trs; c->lin = 0; c->cols = (uint32_t)cols; c->rows2 = (uint32_t)rows2; c->half = true;
+    c->rows_valid = (uint32_t)rows2; c->msg_rot = 0;
+    const size_t hcols = half_ncols((uint32_t)cols, (uint32_t)K);
+    HB_TRY(commit_buffers(ctx, hcols * rows2 * sizeof(F), M, c->d_tensor, c->d_levels));
+    const bool big = (size_t)K * trs * cols * sizeof(F) >= ((size_t)64 << 20);
+    const int pipe = K % 8 == 0 ? 8 : K % 4 == 0 ? 4 : K % 2 == 0 ? 2 : 1, groups = up && big ? pipe : 1, per = K / groups;
+    if (up) { up->groups = groups; up->group_bytes = (size_t)per * M * sizeof(uint64_t); }
+    for (int g = 0; g < groups; g++) {
+        const size_t c0 = (size_t)g * per;
+        if (up) HB_TRY(up->wait(g, ctx->stream));
+        if (logc <= 15) HB_TRY(fft::rowcode_real_half(ctx, d_poly + c0 * M, logc, c->d_tensor, (uint32_t)trs, (uint32_t)K, (uint32_t)per, (uint32_t)c0));
+        else for (int i = 0; i < per; i++)        // (very long rows: one chunk at a time through the long transform, as tensorcode_chunks does)
+            HB_TRY(fft::rowcode_real_half(ctx, d_poly + (c0 + i) * M, logc, c->d_tensor, (uint32_t)trs, (uint32_t)K, 1, (uint32_t)(c0 + i)));
+        if (up) HB_TRY(up->start(g + 1));                 // (host copy + PCIe of the next group, beside this group's kernels)
+    }
+    int r = fft::rows(ctx, c->d_tensor, rows2, (uint32_t)trs, c->d_tensor, rows2, 1, logr, false, 1, (uint32_t)hcols, 0, 0);
+    if (!r) r = launch_leaf_chain_half_rs(ctx, c->d_tensor, K, (uint32_t)cols, (uint32_t)(trs / 2), c->d_levels);
+    if (!r) r = launch_merkle_levels(ctx, c->d_levels, M, 1);
+    if (r) return r;
+    *out = c.release();
+    return 0;
+}
+int hobbit_commit_standard_real_rs(hobbit_ctx *ctx, const uint64_t *d_poly, size_t N, int K, int trs, hobbit_commitment **out) {
+    return commit_real_rs_impl(ctx, d_poly, N, K, trs, out, nullptr);
+}
+int hobbit_commit_standard_real_rs_host(hobbit_ctx *ctx, const uint64_t *h_poly, uint64_t *d_poly, size_t N, int K, int trs, hobbit_commitment **out) {
+    if (!h_poly || !d_poly) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs_host: null polynomial");
+    if (out) *out = nullptr;
+    if ((uintptr_t)d_poly & 15) return ctx->fail(HOBBIT_EINVAL, "commit_standard_real_rs_host: the device polynomial must be 16-byte aligned");
+    HB_TRY(ctx->up_init());
+    Uploader up{ctx, reinterpret_cast<const unsigned char *>(h_poly), reinterpret_cast<unsigned char *>(d_poly), 0, 0};
+    const int rc = commit_real_rs_impl(ctx, d_poly, N, K, trs, out, &up);
+    if (rc) hipStreamSynchronize(ctx->up_stream);                 // nothing of the caller's buffer is still being read on an error return
+    return rc;
+}
 int hobbit_commitment_is_half(const hobbit_commitment *c) { return c && c->half ? 1 : 0; }
 int hobbit_widen_real(hobbit_ctx *ctx, const uint64_t *d_reals, hobbit_F *d_out, size_t n) {
     if (n && (!d_reals || !d_out)) return ctx->fail(HOBBIT_EINVAL, "widen_real: null argument");
@@ -1016,7 +1072,7 @@ const hobbit_F *hobbit_commitment_tensor_dev(const hobbit_commitment *c) {
             const size_t fbytes = (size_t)m->K * m->cols * m->rows2 * sizeof(F);
             if (need_device_bytes(m->ctx, fbytes, "commitment_tensor_dev (half commitment)") != 0) return nullptr;
             if (m->d_full.alloc_bytes(fbytes)) { m->ctx->fail(HOBBIT_ENOMEM, "commitment_tensor_dev: allocation of the full tensor failed"); return nullptr; }
-            if (launch_half_expand(m->ctx, m->d_tensor, m->d_full, m->cols, m->K, m->rows2, m->rows_valid, m->msg_rot) != 0 || m->ctx->sync() != 0) { m->d_full.reset(); return nullptr; }
+            if (launch_half_expand(m->ctx, m->d_tensor, m->d_full, m->cols, m->K, m->rows2, m->rows_valid, m->msg_rot, m->lin) != 0 || m->ctx->sync() != 0) { m->d_full.reset(); return nullptr; }
         }
         return reinterpret_cast<const hobbit_F *>(m->d_full.get());
     }
@@ -1033,7 +1089,7 @@ int hobbit_commitment_root(hobbit_ctx *ctx, const hobbit_commitment *c, uint8_t 
 int hobbit_commitment_tensor_row(hobbit_ctx *ctx, const hobbit_commitment *c, int chunk, int row, hobbit_F *h_out) {
     if (chunk < 0 || chunk >= c->K || row < 0 || (uint32_t)row >= c->rows2) return ctx->fail(HOBBIT_EINVAL, "tensor_row: index out of range");
     F *tmp; HB_TRY(ctx->workspace((size_t)c->cols * sizeof(F), (void **)&tmp));
-    if (c->half) HB_TRY(launch_tensor_row_half(ctx, c->d_tensor, (uint32_t)chunk, c->K, c->rows2, c->cols, (uint32_t)row, tmp, c->rows_valid, c->msg_rot));
+    if (c->half) HB_TRY(launch_tensor_row_half(ctx, c->d_tensor, (uint32_t)chunk, c->K, c->rows2, c->cols, (uint32_t)row, tmp, c->rows_valid, c->msg_rot, c->lin));
     else HB_TRY(launch_tensor_row(ctx, c->d_tensor + (size_t)chunk * c->cols * c->rows2, c->rows2, c->cols, (uint32_t)row, tmp, c->rows_valid, c->msg_rot));
     return hobbit_memcpy_d2h(ctx, h_out, tmp, (size_t)c->cols * sizeof(F));
 }
@@ -1046,7 +1102,7 @@ int hobbit_commitment_gather(hobbit_ctx *ctx, const hobbit_commitment *c, const 
     F *d_reply = reinterpret_cast<F *>(buf); uint32_t *d_rows = reinterpret_cast<uint32_t *>(buf + rb), *d_cols = d_rows + nq;
     HB_TRY(h2d_staged(ctx, d_rows, h_rows, 4 * nq));
     HB_TRY(h2d_staged(ctx, d_cols, h_cols, 4 * nq));
-    if (c->half) HB_TRY(launch_gather_half(ctx, c->d_tensor, c->cols, c->rows2, c->K, d_rows, d_cols, nq, d_reply, c->rows_valid, c->msg_rot));
+    if (c->half) HB_TRY(launch_gather_half(ctx, c->d_tensor, c->cols, c->rows2, c->K, d_rows, d_cols, nq, d_reply, c->rows_valid, c->msg_rot, c->lin));
     else HB_TRY(launch_gather(ctx, c->d_tensor, (size_t)c->cols * c->rows2, c->rows2, c->K, d_rows, d_cols, nq, d_reply, c->rows_valid, c->msg_rot));
     HB_TRY(d2h_staged(ctx, h_reply, d_reply, nq * c->K * sizeof(F)));
     return sc.finish();
@@ -2278,8 +2334,10 @@ int hobbit_elastic_open_finish(hobbit_ctx *ctx, hobbit_elastic_open *e, const ui
 // ---- Our_PC open_standard with linear_time == false (test_PC option 1; the circuit polynomial of prove_circuit_standard): src/Our_PC.cpp:604-692 ----
 // r_v[0], _aggregate (aggregate + C_f, no C_c: :258-276), `queries` (790 in the reference) draws, replies out of the retained tensor, paths,
 // recursive_prover_RS.  Output layout: hobbit_elastic_open_out (reply: queries x K).
-int hobbit_open_standard_rs(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const hobbit_F *h_x, int queries, hobbit_elastic_open_out *o) {
-    if (!c || !o || !h_x || queries <= 0) return ctx->fail(HOBBIT_EINVAL, "open_standard_rs: bad arguments");
+// d_real: the polynomial as N reals of 8 bytes (hobbit_open_standard_rs_real), read by the aggregate alone; otherwise d_poly
+static int open_rs_impl(hobbit_ctx *ctx, const hobbit_F *d_poly, const uint64_t *d_real, size_t N, const hobbit_commitment *c, const hobbit_F *h_x, int queries,
+                        hobbit_elastic_open_out *o) {
+    if (!c || !o || !h_x || queries <= 0 || (!d_poly && !d_real)) return ctx->fail(HOBBIT_EINVAL, "open_standard_rs: bad arguments");
     if (c->lin) return ctx->fail(HOBBIT_EINVAL, "open_standard_rs: the commitment is RS x expander (use hobbit_open_standard)");
     const int K = c->K; const size_t B = c->M, trs = (size_t)c->trs, cols = c->cols, rows2 = c->rows2, nq = (size_t)queries;
     const int logK = ilog2_exact((size_t)K);
@@ -2290,7 +2348,8 @@ int hobbit_open_standard_rs(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, c
     if (ctx->pool_get(B * sizeof(F), d_aggr) || ctx->pool_get(2 * B * sizeof(F), d_encf) || ctx->pool_get(64 * (2 * B / 32), d_lvf) || ctx->pool_get(nq * 4, d_ucols))
         return ctx->fail(HOBBIT_ENOMEM, "open_standard_rs: allocation failed");
     {
-        HB_TRY(launch_aggregate(ctx, cF(d_poly), B, K, beta.data(), d_aggr));                               // _aggregate (:267-272)
+        if (d_real) HB_TRY(launch_aggregate_real(ctx, d_real, B, K, beta.data(), d_aggr));
+        else HB_TRY(launch_aggregate(ctx, cF(d_poly), B, K, beta.data(), d_aggr));                          // _aggregate (:267-272)
         HB_TRY(hobbit_shockwave_commit(ctx, reinterpret_cast<hobbit_F *>(d_aggr.get()), B, 32, reinterpret_cast<hobbit_F *>(d_encf.get()), d_lvf));   // C_f (:274-275)
         std::vector<uint32_t> qc(nq), qr(nq);
         for (size_t q = 0; q < nq; q++) { qc[q] = (uint32_t)(rand() % (long)cols); qr[q] = (uint32_t)(rand() % (long)rows2); }      // (:634-638)
@@ -2306,6 +2365,14 @@ int hobbit_open_standard_rs(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, c
         if (o->paths) HB_TRY(hobbit_commitment_paths(ctx, c, qc.data(), qr.data(), nq, o->paths));          // open_tree_blake(Commitment_MT, I[i], 2B/trs) (:643-645)
         return rs_prover_dev(ctx, d_aggr, B, trs, qc, qr, ucols, d_ucols, d_encf, d_lvf, o);                // (:651-653)
     }
+}
+int hobbit_open_standard_rs(hobbit_ctx *ctx, const hobbit_F *d_poly, size_t N, const hobbit_commitment *c, const hobbit_F *h_x, int queries, hobbit_elastic_open_out *o) {
+    if (!d_poly) return ctx->fail(HOBBIT_EINVAL, "open_standard_rs: bad arguments");
+    return open_rs_impl(ctx, d_poly, nullptr, N, c, h_x, queries, o);
+}
+int hobbit_open_standard_rs_real(hobbit_ctx *ctx, const uint64_t *d_poly, size_t N, const hobbit_commitment *c, const hobbit_F *h_x, int queries, hobbit_elastic_open_out *o) {
+    if (!d_poly) return ctx->fail(HOBBIT_EINVAL, "open_standard_rs_real: null polynomial");
+    return open_rs_impl(ctx, nullptr, d_poly, N, c, h_x, queries, o);
 }
 
 // ---- streaming (space-efficient) provers over a caller-supplied chunk source -------------------------------------------------

@@ -8,6 +8,7 @@
 #include "hobbit_half.hpp"
 #include "../../include/hobbit_real.h"
 #include "../../include/hobbit_elastic_real.h"
+#include "../../include/hobbit_real_rs.h"
 
 namespace hobbit {
 // ============================================================================================
@@ -589,6 +590,32 @@ static int launch_real_unpack(hobbit_ctx *ctx, const F *Z, F *dst, const F *root
     else HB_LAUNCH(ctx, "k_real_unpack_rm", k_real_unpack<false>, dim3(grid), dim3(256), 0, Z, dst, roots, Lh, nrows, 0u);
     return 0;
 }
+// k_real_unpack into a COMMITMENT's half tensor (hobbit_half.hpp; include/hobbit_real_rs.h): Z holds the rows of `nchunks` whole chunks of trs rows, the
+// first of them chunk chunk0 of K, and row r of chunk i stores X[k] at row r of batch column half_col(i, k) -- main block and strip, where
+// k_real_unpack<true> knows one chunk's block alone.  Thread index: r fastest (the stores of a wave are contiguous along the column), then the
+// pair k, then the chunk, so the lines of Z a workgroup touches are those of trs adjacent rows at a few adjacent k.  Unrotated (RS x RS).
+__global__ void __launch_bounds__(256)
+k_real_unpack_half(const F *__restrict__ Z, F *__restrict__ dst, const F *__restrict__ roots, uint32_t Lh, uint32_t trs, uint32_t nchunks, uint32_t chunk0, uint32_t K) {
+    const uint32_t np = Lh / 2 + 1, rows2 = 2 * trs, cols = 2 * Lh;
+    const size_t per = (size_t)trs * np, total = per * nchunks;
+    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < total; g += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t ci = (uint32_t)(g / per), e = (uint32_t)(g - (size_t)ci * per), k = e / trs, r = e - k * trs;
+        const F *z = Z + ((size_t)ci * trs + r) * Lh;
+        const F A = ldF(z + k), B = fconj(ldF(z + ((Lh - k) & (Lh - 1))));
+        const F S = fadd(A, B), D = fsub(A, B);
+        const F T = fmul(fmake(D.im, D.re ? P61 - D.re : 0), ldF(roots + k));       // w^k (-i D) = 2 w^k O[k]
+        stF(dst + half_at(chunk0 + ci, k, r, cols, K, rows2, 0), fhalf(fadd(S, T)));
+        if (2 * k != Lh) stF(dst + half_at(chunk0 + ci, Lh - k, r, cols, K, rows2, 0), fconj(fhalf(fsub(S, T))));
+    }
+}
+static int launch_real_unpack_half(hobbit_ctx *ctx, const F *Z, F *dst, const F *roots, uint32_t Lh, uint32_t trs, uint32_t nchunks, uint32_t chunk0, uint32_t K) {
+    const size_t total = (size_t)trs * (Lh / 2 + 1) * nchunks;
+    if (!total) return 0;
+    if (!trs || chunk0 + (size_t)nchunks > K) return ctx->fail(HOBBIT_EINVAL, "fft_real: bad tensor shape");
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)1 << 16);
+    HB_LAUNCH(ctx, "k_real_unpack_half", k_real_unpack_half, dim3(grid), dim3(256), 0, Z, dst, roots, Lh, trs, nchunks, chunk0, K);
+    return 0;
+}
 
 // The same passes for the SECOND half of a long transform (k_fft_cols's job: N-point transforms down the columns of y[n1][k2], N = len / 4096
 // = 32 ... 256, inter-stage twiddle on load, result X[k1 * 4096 + k2]).  A workgroup owns C = 4096 / N adjacent columns; the column index is
@@ -1033,17 +1060,40 @@ int any_rows(hobbit_ctx *ctx, const F *src, size_t src_ld, size_t src_len, F *ds
     return wide_rows(ctx, dst, logn, inverse, batch);
 }
 
+// the packed transform of `nrows` real rows of Lh reals: row r is Lh / 2 F elements, zero-padded to Lh points, into workspace5 (the long transform owns
+// workspace / workspace2)
+static int real_packed(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F **Z) {
+    const size_t Lh = (size_t)1 << (logL - 1);
+    HB_TRY(ctx->workspace5(nrows * Lh * sizeof(F), (void **)Z));
+    return any_rows(ctx, reinterpret_cast<const F *>(src), Lh / 2, Lh / 2, *Z, logL - 1, false, nrows);
+}
+static int real_rows_impl(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F *dst, bool tensor, uint32_t trs);
 int real_rows_any(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F *dst, bool tensor, uint32_t trs) {
     if (logL < 3 || logL > 16) return ctx->fail(HOBBIT_EINVAL, "fft_real_rows_any: logL must be in [3,16]");
+    return real_rows_impl(ctx, src, nrows, logL, dst, tensor, trs);
+}
+int real_rows_len(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F *dst) {
+    if (logL < 3 || logL > 20) return ctx->fail(HOBBIT_EINVAL, "fft_real_rows_len: logL must be in [3,20]");
+    return real_rows_impl(ctx, src, nrows, logL, dst, false, 0);
+}
+int rowcode_real_half(hobbit_ctx *ctx, const uint64_t *src, int logL, F *dst, uint32_t trs, uint32_t K, uint32_t nchunks, uint32_t chunk0) {
+    if (logL < 3 || logL > 20) return ctx->fail(HOBBIT_EINVAL, "fft_real: the row code of a half commitment has 2^3 .. 2^20 points");
+    if (!trs || !nchunks || chunk0 + (size_t)nchunks > K) return ctx->fail(HOBBIT_EINVAL, "fft_real: bad tensor shape");
+    const size_t nrows = (size_t)nchunks * trs;
+    if (logL == 12) return rowcode_real4096(ctx, src, nrows, dst, true, trs, K, 0, chunk0);
+    if ((uintptr_t)src & 15) return ctx->fail(HOBBIT_EINVAL, "fft_real: the real rows must be 16-byte aligned");
+    F *Z; HB_TRY(real_packed(ctx, src, nrows, logL, &Z));
+    const F *tw; HB_TRY(roots(ctx, logL, false, &tw));
+    return launch_real_unpack_half(ctx, Z, dst, tw, 1u << (logL - 1), trs, nchunks, chunk0, K);
+}
+static int real_rows_impl(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F *dst, bool tensor, uint32_t trs) {
     if (!nrows) return 0;
     if (nrows >> 20) return ctx->fail(HOBBIT_EINVAL, "fft_real: too many rows");
     if (tensor && (!trs || nrows != trs)) return ctx->fail(HOBBIT_EINVAL, "fft_real: the tensor form takes the rows of one chunk");
     if (logL == 12) return rowcode_real4096(ctx, src, nrows, dst, tensor, trs, 1, 0, 0);
     if ((uintptr_t)src & 15) return ctx->fail(HOBBIT_EINVAL, "fft_real: the real rows must be 16-byte aligned");
     const size_t Lh = (size_t)1 << (logL - 1);
-    // the packed transform: row r is Lh / 2 F elements, zero-padded to Lh points.  workspace5: the long transform below owns workspace / workspace2
-    F *Z; HB_TRY(ctx->workspace5(nrows * Lh * sizeof(F), (void **)&Z));
-    HB_TRY(any_rows(ctx, reinterpret_cast<const F *>(src), Lh / 2, Lh / 2, Z, logL - 1, false, nrows));
+    F *Z; HB_TRY(real_packed(ctx, src, nrows, logL, &Z));
     const F *tw; HB_TRY(roots(ctx, logL, false, &tw));
     return launch_real_unpack(ctx, Z, dst, tw, (uint32_t)Lh, (uint32_t)nrows, tensor, 2 * trs);
 }
@@ -1075,6 +1125,10 @@ int hobbit_fft_real_rows(hobbit_ctx *ctx, const uint64_t *d_reals, size_t rows, 
 int hobbit_fft_real_rows_any(hobbit_ctx *ctx, const uint64_t *d_reals, size_t rows, int logL, hobbit_F *d_out) {
     if (rows && (!d_reals || !d_out)) return ctx->fail(HOBBIT_EINVAL, "fft_real_rows_any: null argument");
     return fft::real_rows_any(ctx, d_reals, rows, logL, reinterpret_cast<F *>(d_out), false, 0);
+}
+int hobbit_fft_real_rows_len(hobbit_ctx *ctx, const uint64_t *d_reals, size_t rows, int logL, hobbit_F *d_out) {
+    if (rows && (!d_reals || !d_out)) return ctx->fail(HOBBIT_EINVAL, "fft_real_rows_len: null argument");
+    return fft::real_rows_len(ctx, d_reals, rows, logL, reinterpret_cast<F *>(d_out));
 }
 int hobbit_fft_any(hobbit_ctx *ctx, hobbit_F *d_data, int logn, size_t batch, size_t ld, int inverse) {
     if (logn < 1 || logn > 28) return ctx->fail(HOBBIT_EINVAL, "fft_any: logn must be in [1,28]");

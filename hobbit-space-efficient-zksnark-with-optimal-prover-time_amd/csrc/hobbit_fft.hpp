@@ -31,6 +31,13 @@ int rowcode_real4096(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, F *dst,
 // for logL = 12, otherwise the packed L / 2-point transform through any_rows (into workspace5) and k_real_unpack.  tensor: the nrows == trs rows of one
 // chunk into the chunk's half tensor (hobbit_half.hpp: (L / 2 + 1) x 2 trs, codeword-major); otherwise row-major, L / 2 + 1 elements per row.
 int real_rows_any(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F *dst, bool tensor, uint32_t trs);
+// The same row code at 3 <= logL <= 20 (include/hobbit_real_rs.h), row-major: above 2^16 the packed transform is the long one; the twiddle w^k of order L
+// is read from the ROOTS table of that length.
+int real_rows_len(hobbit_ctx *ctx, const uint64_t *src, size_t nrows, int logL, F *dst);
+// The row code of `nchunks` whole chunks of trs base-field rows (2^(logL-1) reals each, 3 <= logL <= 20), the first of them chunk chunk0 of K, into a
+// COMMITMENT's half tensor (hobbit_half.hpp: main block and strip), unrotated: rowcode_real4096 for logL = 12, otherwise the packed transform of all
+// nchunks trs rows at once (workspace5) and k_real_unpack_half.
+int rowcode_real_half(hobbit_ctx *ctx, const uint64_t *src, int logL, F *dst, uint32_t trs, uint32_t K, uint32_t nchunks, uint32_t chunk0);
 // The 2^13 .. 2^15-point row code (Elastic_PC opt 2: 32768) of `nrows` contiguous messages of 2^(logc-1) elements: R = 2^(logc-12) strided FFT-4096 per
 // row into Y, then the twiddles and the R-point combine into the row-major rm (both nrows 2^logc elements).
 int rowcode_combine(hobbit_ctx *ctx, const F *msg, int logc, uint32_t nrows, F *Y, F *rm);

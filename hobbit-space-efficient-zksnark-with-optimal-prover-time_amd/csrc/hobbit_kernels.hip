@@ -1430,50 +1430,116 @@ int launch_leaf_chain_half(hobbit_ctx *ctx, const F *tensor, int K, uint32_t col
               rot_mask);
     return 0;
 }
-// one element of the full tensor read from the half one: zero past rows_valid, conjugated past the middle column
+// one element of the full tensor read from the half one: zero past rows_valid; column c > cols / 2 is answered through half_ref -- the conjugate of
+// the same row of column cols - c under RS x expander (LIN = 1), of the negated row under RS x RS (LIN = 0, never rotated, every row valid)
+template <int LIN>
 __device__ __forceinline__ F half_load(const F *__restrict__ tensor, uint32_t i, uint32_t c, uint32_t r, uint32_t cols, uint32_t K, uint32_t rows2, uint32_t rows_valid,
                                        uint32_t rot_mask) {
     if (r >= rows_valid) return fmake(0);
-    const F v = ldF(tensor + half_at(i, half_src_col(c, cols), r, cols, K, rows2, rot_mask));
-    return half_is_conj(c, cols) ? fconj(v) : v;
+    const HalfRef h = half_ref(r, c, cols, rows2, LIN);
+    const F v = ldF(tensor + half_at(i, h.col, h.row, cols, K, rows2, rot_mask));
+    return h.conj ? fconj(v) : v;
 }
+template <int LIN>
 __global__ void k_gather_half(const F *__restrict__ tensor, uint32_t cols, uint32_t rows2, uint32_t K, const uint32_t *__restrict__ rows, const uint32_t *__restrict__ qcols,
                               size_t nq, F *__restrict__ reply, uint32_t rows_valid, uint32_t rot_mask) {
     const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (g >= nq * K) return;
     const size_t q = g / K; const uint32_t i = (uint32_t)(g % K);
-    stF(reply + g, half_load(tensor, i, qcols[q], rows[q], cols, K, rows2, rows_valid, rot_mask));
+    stF(reply + g, half_load<LIN>(tensor, i, qcols[q], rows[q], cols, K, rows2, rows_valid, rot_mask));
 }
 int launch_gather_half(hobbit_ctx *ctx, const F *tensor, uint32_t cols, uint32_t rows2, int K, const uint32_t *d_rows, const uint32_t *d_cols, size_t nq, F *d_reply,
-                       uint32_t rows_valid, uint32_t rot_mask) {
+                       uint32_t rows_valid, uint32_t rot_mask, int lin) {
     const size_t total = nq * K;
     if (!total) return 0;
-    HB_LAUNCH(ctx, "k_gather_half", k_gather_half, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tensor, cols, rows2, (uint32_t)K, d_rows, d_cols, nq, d_reply,
-              rows_valid, rot_mask);
+    if (lin) HB_LAUNCH(ctx, "k_gather_half", k_gather_half<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tensor, cols, rows2, (uint32_t)K, d_rows, d_cols, nq, d_reply,
+                       rows_valid, rot_mask);
+    else HB_LAUNCH(ctx, "k_gather_half_rs", k_gather_half<0>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, tensor, cols, rows2, (uint32_t)K, d_rows, d_cols, nq, d_reply,
+                   rows_valid, rot_mask);
     return 0;
 }
+template <int LIN>
 __global__ void k_tensor_row_half(const F *__restrict__ tensor, uint32_t chunk, uint32_t K, uint32_t rows2, uint32_t cols, uint32_t row, F *__restrict__ out,
                                   uint32_t rows_valid, uint32_t rot_mask) {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < cols) stF(out + c, half_load(tensor, chunk, c, row, cols, K, rows2, rows_valid, rot_mask));
+    if (c < cols) stF(out + c, half_load<LIN>(tensor, chunk, c, row, cols, K, rows2, rows_valid, rot_mask));
 }
 int launch_tensor_row_half(hobbit_ctx *ctx, const F *tensor, uint32_t chunk, int K, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid,
-                           uint32_t rot_mask) {
-    HB_LAUNCH(ctx, "k_tensor_row_half", k_tensor_row_half, dim3((cols + 255) / 256), dim3(256), 0, tensor, chunk, (uint32_t)K, rows2, cols, row, d_out, rows_valid, rot_mask);
+                           uint32_t rot_mask, int lin) {
+    if (lin) HB_LAUNCH(ctx, "k_tensor_row_half", k_tensor_row_half<1>, dim3((cols + 255) / 256), dim3(256), 0, tensor, chunk, (uint32_t)K, rows2, cols, row, d_out, rows_valid, rot_mask);
+    else HB_LAUNCH(ctx, "k_tensor_row_half_rs", k_tensor_row_half<0>, dim3((cols + 255) / 256), dim3(256), 0, tensor, chunk, (uint32_t)K, rows2, cols, row, d_out, rows_valid, rot_mask);
     return 0;
 }
 // The mirror that materialises the full linear tensor [K][cols][rows2] from the half one (hobbit_commitment_tensor_dev): one workgroup per
-// full column and pass, reads and writes contiguous along the rows; the implicit zeros become real ones and a rotated message half a linear one.
+// full column and pass, reads and writes contiguous along the rows (RS x RS: the reads of a mirrored column run backwards); the implicit zeros
+// become real ones and a rotated message half a linear one.
+template <int LIN>
 __global__ void __launch_bounds__(256)
 k_half_expand(const F *__restrict__ tensor, F *__restrict__ full, uint32_t cols, uint32_t K, uint32_t rows2, uint32_t rows_valid, uint32_t rot_mask) {
     const size_t ncols = (size_t)K * cols;
     for (size_t gc = blockIdx.x; gc < ncols; gc += gridDim.x) {
         const uint32_t i = (uint32_t)(gc / cols), c = (uint32_t)(gc % cols);
-        for (uint32_t r = threadIdx.x; r < rows2; r += blockDim.x) stF(full + gc * rows2 + r, half_load(tensor, i, c, r, cols, K, rows2, rows_valid, rot_mask));
+        for (uint32_t r = threadIdx.x; r < rows2; r += blockDim.x) stF(full + gc * rows2 + r, half_load<LIN>(tensor, i, c, r, cols, K, rows2, rows_valid, rot_mask));
     }
 }
-int launch_half_expand(hobbit_ctx *ctx, const F *tensor, F *full, uint32_t cols, int K, uint32_t rows2, uint32_t rows_valid, uint32_t rot_mask) {
-    HB_LAUNCH(ctx, "k_half_expand", k_half_expand, dim3(grid_for((size_t)K * cols, 1, 65536)), dim3(256), 0, tensor, full, cols, (uint32_t)K, rows2, rows_valid, rot_mask);
+int launch_half_expand(hobbit_ctx *ctx, const F *tensor, F *full, uint32_t cols, int K, uint32_t rows2, uint32_t rows_valid, uint32_t rot_mask, int lin) {
+    if (lin) HB_LAUNCH(ctx, "k_half_expand", k_half_expand<1>, dim3(grid_for((size_t)K * cols, 1, 65536)), dim3(256), 0, tensor, full, cols, (uint32_t)K, rows2, rows_valid, rot_mask);
+    else HB_LAUNCH(ctx, "k_half_expand_rs", k_half_expand<0>, dim3(grid_for((size_t)K * cols, 1, 65536)), dim3(256), 0, tensor, full, cols, (uint32_t)K, rows2, rows_valid, rot_mask);
+    return 0;
+}
+// the 16 words a mirrored leaf hashes, from its stored group's 16 words m and the next group's first element n4
+__device__ __forceinline__ void leaf_rs_mirror_words(const uint32_t m[16], const uint4 &n4, uint32_t w[16]) {
+    w[0] = n4.x; w[1] = n4.y; w[2] = n4.z; w[3] = n4.w;
+#pragma unroll
+    for (int q = 0; q < 4; q++) { w[4 + q] = m[12 + q]; w[8 + q] = m[8 + q]; w[12 + q] = m[4 + q]; }
+    conj16w(w);
+}
+// st = H( H(m) | st ); m is consumed
+__device__ __forceinline__ void leaf_chain_step(uint32_t m[16], uint32_t st[8]) {
+    uint32_t h[8];
+    blake3_compress64(m, h);
+#pragma unroll
+    for (int q = 0; q < 8; q++) { m[q] = h[q]; m[8 + q] = st[q]; }
+    blake3_compress64(m, st);
+}
+// The leaf chain over an RS x RS half tensor (include/hobbit_real_rs.h; DESIGN.md section 4, "Base-field polynomials under RS x RS").  The column
+// code is a transform of rows2 points, so T(r, cols - c) = conj(T((rows2 - r) mod rows2, c)): leaf (j', cols - sc) hashes the conjugates of stored
+// rows (rows2 - 4 j' - e) mod rows2, e = 0 .. 3, of column sc.  With G = rows2 / 4 groups and g = G - 1 - j' these are row 4 (g + 1) mod rows2 --
+// the first row of the NEXT group, wrapping to row 0 -- and then rows 4g + 3, 4g + 2, 4g + 1.  One thread owns stored group (g, sc), sc <= cols / 2:
+// per chunk it loads its 64 bytes and that one element beyond them and updates two chains, leaf (g, sc) and, for 0 < sc < cols / 2, leaf
+// (G - 1 - g, cols - sc): 80 bytes per two leaves.  g is the fastest thread index; there are no zero groups (RS x RS fills all rows2 rows) and no rotation.
+// 82 VGPRs, no scratch (forcing eight waves spilled 80 bytes); the per-leaf form -- one thread per leaf, 57 VGPRs -- measured 0.36 ms slower at
+// (2^28, 32, 128) and was not kept.
+__global__ void __launch_bounds__(256)
+k_leaf_chain_half_rs(const F *__restrict__ tensor, uint32_t K, uint32_t cols, uint32_t G, uint8_t *__restrict__ leaves) {
+    const uint32_t stride = gridDim.x * blockDim.x, rows2 = 4 * G, hc = cols / 2;
+    const uint32_t total = (hc + 1) * G;
+    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+        const uint32_t sc = t / G, g = t - sc * G;
+        const bool strip = sc == hc, two = sc > 0 && sc < hc;
+        const F *p0 = tensor + half_col(0, sc, cols, K) * rows2;
+        const size_t step = strip ? (size_t)rows2 : (size_t)hc * rows2;
+        const uint32_t nx = (4 * g + 4) & (rows2 - 1);
+        uint32_t st[8], sm[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) st[q] = sm[q] = 0;
+        for (uint32_t i = 0; i < K; i++) {
+            const F *col = p0 + (size_t)i * step;
+            uint32_t m[16], w[16];
+            load16w(col + 4 * g, m);
+            if (two) leaf_rs_mirror_words(m, *reinterpret_cast<const uint4 *>(col + nx), w);
+            leaf_chain_step(m, st);
+            if (two) leaf_chain_step(w, sm);
+        }
+        store8w(leaves + 32 * ((size_t)g * cols + sc), st);
+        if (two) store8w(leaves + 32 * ((size_t)(G - 1 - g) * cols + (cols - sc)), sm);
+    }
+}
+int launch_leaf_chain_half_rs(hobbit_ctx *ctx, const F *tensor, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves) {
+    if (((size_t)cols * half_trs) >> 32) return ctx->fail(HOBBIT_EINVAL, "leaf chain: more than 2^32 leaves");
+    if (!half_trs || (half_trs & (half_trs - 1))) return ctx->fail(HOBBIT_EINVAL, "leaf chain (RS x RS half form): 2 trs must be a power of two");
+    HB_LAUNCH(ctx, "k_leaf_chain_half_rs", k_leaf_chain_half_rs, dim3(grid_for((size_t)(cols / 2 + 1) * half_trs, 256, 4096)), dim3(256), 0, tensor, (uint32_t)K, cols, half_trs,
+              leaves);
     return 0;
 }
 // (x, 0) per coefficient: the F form of a real vector

@@ -70,11 +70,14 @@ int launch_unrotate_msg(hobbit_ctx *ctx, F *tensor, size_t ncols, uint32_t rows2
 // The half form of a commitment's tensor (hobbit_half.hpp): the leaf chain, the gather and the row read over columns 0 .. cols / 2 in memory, the
 // mirror that materialises the full linear tensor [K][cols][rows2], and the real-polynomial forms of the widening copy and the aggregate
 int launch_leaf_chain_half(hobbit_ctx *ctx, const F *tensor, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves, uint32_t zero_rows_from, uint32_t rot_mask);
+// lin: the commitment's column code -- 1 RS x expander (column cols - c is the conjugate of column c, row for row), 0 RS x RS (of the negated row)
 int launch_gather_half(hobbit_ctx *ctx, const F *tensor, uint32_t cols, uint32_t rows2, int K, const uint32_t *d_rows, const uint32_t *d_cols, size_t nq, F *d_reply,
-                       uint32_t rows_valid, uint32_t rot_mask);
+                       uint32_t rows_valid, uint32_t rot_mask, int lin = 1);
 int launch_tensor_row_half(hobbit_ctx *ctx, const F *tensor, uint32_t chunk, int K, uint32_t rows2, uint32_t cols, uint32_t row, F *d_out, uint32_t rows_valid,
-                           uint32_t rot_mask);
-int launch_half_expand(hobbit_ctx *ctx, const F *tensor, F *full, uint32_t cols, int K, uint32_t rows2, uint32_t rows_valid, uint32_t rot_mask);
+                           uint32_t rot_mask, int lin = 1);
+int launch_half_expand(hobbit_ctx *ctx, const F *tensor, F *full, uint32_t cols, int K, uint32_t rows2, uint32_t rows_valid, uint32_t rot_mask, int lin = 1);
+// the leaf chain over an RS x RS half tensor (include/hobbit_real_rs.h): one thread per stored group, two leaves; half_trs = rows2 / 4 groups, a power of two
+int launch_leaf_chain_half_rs(hobbit_ctx *ctx, const F *tensor, int K, uint32_t cols, uint32_t half_trs, uint8_t *leaves);
 int launch_widen_real(hobbit_ctx *ctx, const uint64_t *x, F *o, size_t n);
 int launch_aggregate_real(hobbit_ctx *ctx, const uint64_t *poly, size_t M, int K, CHP h_beta, F *aggr);
 int launch_eval_fold(hobbit_ctx *ctx, const F *v, F *o, size_t L, F r);

@@ -429,16 +429,23 @@ static hobbit_host_elastic_transcript g_eopen;
 hobbit_host_elastic_transcript &hobbit_host_last_elastic_open() { return g_eopen; }
 // open_standard's linear_time == false branch (src/Our_PC.cpp:609-611, 651-652: 790 queries, recursive_prover_RS); the messages land in
 // hobbit_host_last_elastic_open() (same transcript shape as Elastic_PC::open option 1, replies queries x K)
+static void open_rs_on_device(size_t N, vector<F> &x, vector<vector<_hash>> &Commitment_MT, int K, double &vt, double &ps);
 static void open_standard_rs(vector<F> &poly, vector<F> &x, vector<vector<_hash>> &Commitment_MT, int K, double &vt, double &ps) {
-    const size_t N = poly.size(), M = N / K;
+    const size_t N = poly.size();
+    if (!g_poly_dev || g_poly_n != N || g_poly_real || getenv("HOBBIT_HOST_REUPLOAD")) {
+        if (g_poly_dev) hobbit_free(hobbit_host_ctx(), g_poly_dev);
+        HCHK(hobbit_malloc(hobbit_host_ctx(), N * sizeof(F), &g_poly_dev)); g_poly_n = N; g_poly_real = false;
+        HCHK(hobbit_memcpy_h2d(g_ctx, g_poly_dev, poly.data(), N * sizeof(F)));
+    }
+    open_rs_on_device(N, x, Commitment_MT, K, vt, ps);
+}
+// the RS x RS opening of the current commitment over the device polynomial it kept (F elements, or reals after commit_standard_real), and the
+// reference's proof-size accounting
+static void open_rs_on_device(size_t N, vector<F> &x, vector<vector<_hash>> &Commitment_MT, int K, double &vt, double &ps) {
+    const size_t M = N / K;
     const int queries = 790; aggregation_queries = queries;
     const int trs = g_commit_trs; const size_t cols = g_commit_cols;
     const int logc = (int)log2((double)cols), logr = (int)log2((double)(2 * trs)), logt = logr - 1, depth = (int)log2((double)M);
-    if (!g_poly_dev || g_poly_n != N || getenv("HOBBIT_HOST_REUPLOAD")) {
-        if (g_poly_dev) hobbit_free(hobbit_host_ctx(), g_poly_dev);
-        HCHK(hobbit_malloc(hobbit_host_ctx(), N * sizeof(F), &g_poly_dev)); g_poly_n = N;
-        HCHK(hobbit_memcpy_h2d(g_ctx, g_poly_dev, poly.data(), N * sizeof(F)));
-    }
     hobbit_host_elastic_transcript &t = g_eopen;
     const int maxr = 11 + logr + logr + (logt + logc) + logc;
     t.queries = queries; t.cols.assign(queries, 0); t.rows.assign(queries, 0); t.reply.assign((size_t)queries * K, F(0)); t.paths.assign((size_t)queries * depth * 32, 0);
@@ -446,7 +453,8 @@ static void open_standard_rs(vector<F> &poly, vector<F> &x, vector<vector<_hash>
     SpBuffers bf(t.sp_f, M, 32);
     hobbit_elastic_open_out o{t.cols.data(), t.rows.data(), hF(&t.rv0), hF(t.reply.data()), &t.reply_len, t.paths.data(), t.cf_root, &t.ncols,
                               hF(t.qpoly.data()), hF(t.r.data()), hF(t.vr.data()), hF(t.fin.data()), t.checks, hF(t.rx.data()), &bf.o};
-    HCHK(hobbit_open_standard_rs(g_ctx, (const hobbit_F *)g_poly_dev, N, g_commit, hF(x.data()), queries, &o));
+    if (g_poly_real) HCHK(hobbit_open_standard_rs_real(g_ctx, (const uint64_t *)g_poly_dev, N, g_commit, hF(x.data()), queries, &o));
+    else HCHK(hobbit_open_standard_rs(g_ctx, (const hobbit_F *)g_poly_dev, N, g_commit, hF(x.data()), queries, &o));
     if (!t.checks[0] || !t.checks[1]) { printf("Error in fft\n"); exit(-1); }                                   // src/sumcheck.cpp:3016-3019
     if (t.sp_f.iters && !(t.sp_f.wchecks[0] && t.sp_f.wchecks[1])) { printf("Error in final verification step\n"); exit(-1); }
     printf(">>OK\n");
@@ -1878,7 +1886,8 @@ void commit_standard_real(uint64_t *d_poly, size_t N, vector<vector<_hash>> &MT_
     free_prev();
     if (g_commit) { swap_with_prev(); g_commit = nullptr; }
     g_poly_dev = d_poly; g_poly_n = N; g_poly_real = true;
-    HCHK(hobbit_commit_standard_real(g_ctx, d_poly, N, K, tensor_row_size, linear_time ? 1 : 0, &g_commit));
+    if (linear_time) HCHK(hobbit_commit_standard_real(g_ctx, d_poly, N, K, tensor_row_size, 1, &g_commit));
+    else HCHK(hobbit_commit_standard_real_rs(g_ctx, d_poly, N, K, tensor_row_size, &g_commit));              // RS x RS (include/hobbit_real_rs.h)
     HCHK(hobbit_sync(g_ctx));
     g_commit_K = K; g_commit_trs = tensor_row_size; g_commit_cols = 2 * M / tensor_row_size;
     size_t levels = (size_t)log2((double)M) + 1, off = 0;
@@ -1891,6 +1900,7 @@ void open_standard_real(size_t N, vector<F> x, vector<vector<_hash>> &Commitment
     select_commitment(Commitment_MT);
     if (!g_commit || g_commit_K != K || !g_poly_real || g_poly_n != N) { printf("Error: open_standard_real without a matching commit_standard_real\n"); exit(-1); }
     BUFFER_SPACE = N / K;
+    if (!linear_time) { open_rs_on_device(N, x, Commitment_MT, K, vt, ps); return; }
     open_lin_on_device(N, x, Commitment_MT, K, vt, ps);
 }
 // test_PC option 4 with the polynomial drawn on the device as reals: the same libc draws in the same order, the same root and Ps
@@ -1902,6 +1912,30 @@ void test_PC_real(size_t N, int K) {
     tensor_row_size = (int)(N / (K * 1ULL << (11)));
     printf("%d\n", tensor_row_size);
     expander_init_store(tensor_row_size);
+    vector<vector<_hash>> MT_hashes;
+    auto start = std::chrono::steady_clock::now();
+    commit_standard_real(d_poly, N, MT_hashes, K);
+    auto end = std::chrono::steady_clock::now();
+    double commit_time = std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    std::cout << "Commit time: " << commit_time << " seconds" << std::endl;
+    printf("root ");
+    for (int i = 0; i < 32; i++) printf("%02x", MT_hashes.back()[0].arr[i]);
+    printf("\n");
+    double vt = 0.0, ps = 0.0;
+    start = std::chrono::steady_clock::now();
+    open_standard_real(N, generate_randomness((int)log2((double)N)), MT_hashes, K, vt, ps);
+    end = std::chrono::steady_clock::now();
+    double total = commit_time + std::chrono::duration_cast<std::chrono::duration<double>>(end - start).count();
+    std::cout << "Total time: " << total << " seconds" << std::endl;
+    printf("%lf,%lf\n", ps, vt);
+}
+// test_PC option 1 (RS x RS, tensor_row_size = 128) with the polynomial drawn on the device as reals (include/hobbit_real_rs.h): the same libc
+// draws in the same order, the same lines
+void test_PC_real_rs(size_t N, int K) {
+    uint64_t *d_poly = nullptr;
+    HCHK(hobbit_malloc(hobbit_host_ctx(), N * sizeof(uint64_t), (void **)&d_poly));
+    HCHK(hobbit_generate_randomness_real_dev(g_ctx, N, d_poly));
+    linear_time = false; tensor_row_size = 128;
     vector<vector<_hash>> MT_hashes;
     auto start = std::chrono::steady_clock::now();
     commit_standard_real(d_poly, N, MT_hashes, K);

@@ -22,6 +22,7 @@
 #include "hobbit_libcgen.h"
 #include "hobbit_real.h"
 #include "hobbit_elastic_real.h"
+#include "hobbit_real_rs.h"
 
 using std::vector;
 
@@ -163,6 +164,9 @@ void test_PC(size_t N, int option, int K);                                      
 void commit_standard_real(uint64_t *d_poly, size_t N, vector<vector<_hash>> &MT_hashes, int K);
 void open_standard_real(size_t N, vector<F> x, vector<vector<_hash>> &Commitment_MT, int K, double &vt, double &ps);
 void test_PC_real(size_t N, int K);
+/* test_PC's option 1 (RS x RS, tensor_row_size 128) the same way (include/hobbit_real_rs.h): commit_standard_real / open_standard_real route to the
+ * RS x RS calls when linear_time is false. */
+void test_PC_real_rs(size_t N, int K);
 /* src/Our_PC.hpp: the Brakedown comparison baseline (src/Our_PC.cpp:197-236, 432-520).  commit_standard_brakedown draws the row code's graphs
  * (expander_init_store(B)) and keeps the encoded matrix on the device; open_brakedown_standard draws r (rows x random()) and the 2900 columns
  * (rand() % 2B), opens, and prints the reference's "PC Open: pt = .., ps = .. KB, vt = .. sec" line. */
